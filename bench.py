@@ -8,6 +8,12 @@ HBM when the timed region starts.  Model = config/transformer/pretrain/fometa-hk
 (d_model 512, 8 heads, d_inner 2048, 2 enc / 4 dec, odim 367, dropout 0.1), random-init weights.
 
     python bench.py [--gpus N --steps K --warmup W]          # N>1 via torch.distributed.run, one rank per GPU
+    python bench.py --full                                   # + every other leg (see below)
+    python bench.py --dump-outputs DIR                       # + what the timed region computed, as DIR/*.npy
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  --full adds the
+legs that take runs of their own: long_run, single_task_fomaml / single_task_train, mixed_lengths, matrix, meta_step,
+roofline + kernel_ms_per_step, e2e_pretrain / e2e_train and cpu_baseline (the --no-* switches leave single legs out of it).
 
 N ranks = N groups of independent accent-tasks (FOMAML shards tasks over GPUs; the inner step has no exchange),
 so scaling is "weak": value = N * tasks_per_gpu * B * K / max-over-ranks time.  The meta-gradient all-reduce of
@@ -213,14 +219,60 @@ def cpu_baseline(cfg, B, T, D, steps=6):
             "sample": f"{steps} timed + 1 warm-up inner steps, B={B} x T={T} x D={D}, same model/config, fp32 torch CPU oracle, dropout 0"}
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20       # --dump-outputs writes at most this much (float32 samples of the large arrays)
+DUMP_SAMPLE_MAX = 1 << 19              # elements kept of one large array
+
+
+def sample_index(n, m, seed):
+    """m fixed, seeded positions out of n: one uniformly drawn position in each of m equal strata (sorted, covers the whole array)"""
+    rng = np.random.RandomState(seed)
+    lo = np.arange(m, dtype=np.int64) * n // m
+    hi = np.append(lo[1:], n)
+    return lo + (rng.random_sample(m) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(tasks, out_dir):
+    """What the timed region's last inner step left a caller, per task slot k: slot{k}_stats (loss, n_correct, n_total, grad_norm of
+    that step; float64), slot{k}_logits ([B, L, odim] of its forward), slot{k}_params / slot{k}_momentum (weights and momentum after its
+    SGD step) and slot{k}_grads (its clipped gradient).  Arrays above the per-array share of DUMP_BUDGET_BYTES are written as the
+    elements at sample_index(numel, share, seed) of the flattened array, the same positions from run to run."""
+    arrays = {}
+    for k, t in enumerate(tasks):
+        with torch.cuda.stream(t.stream):
+            st = t.eng.read_stats()
+            logits, _ = t.eng.last_logits()
+            arrays[f"slot{k}_stats"] = torch.tensor([st["loss"], st["n_correct"], st["n_total"], st["grad_norm"]], dtype=torch.float64)
+            arrays[f"slot{k}_logits"] = logits.contiguous()
+            arrays[f"slot{k}_params"] = t.eng.params
+            arrays[f"slot{k}_momentum"] = t.mom
+            arrays[f"slot{k}_grads"] = t.eng.grads
+    share = min(DUMP_SAMPLE_MAX, DUMP_BUDGET_BYTES // 4 // len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.reshape(-1)
+        if a.numel() > share:
+            seed = 1 if name.endswith("_logits") else 0         # params, momentum and grads of a slot: the same positions
+            a = a[torch.from_numpy(sample_index(a.numel(), share, seed)).to(a.device)]
+        v = a.cpu().numpy()
+        v = v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        total += v.nbytes
+    assert total <= 64 * 2 ** 20, total
+    log(f"outputs of the last timed step: {len(arrays)} arrays, {total / 2 ** 20:.1f} MB -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=120, help="timed steps per task slot (120 x 6.5 ms = 0.8 s: a 30-step region read 3 % below the 6 s long_run leg of the same process)")
+    ap.add_argument("--steps", type=int, default=120, help="timed steps per task slot (120 x 6.5 ms = 0.8 s: a 30-step region read 3 %% below the 6 s long_run leg of the same process)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=16, help="utterances per inner step per GPU (16 = what the shipped half_batch_ilen rule yields at 1000 frames)")
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--idim", type=int, default=80)
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline region (long_run, single_task_*, mixed_lengths, matrix, "
+                    "meta_step, roofline, e2e_*, cpu_baseline); the --no-* switches below leave single legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write what its last step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=16, help="utterances per step of the CPU baseline leg (same B as the GPU leg by default)")
@@ -315,8 +367,9 @@ def main():
     class Task:                                                  # one accent-task slot: replica + stream + resident batch
         def __init__(self, k, cfg=cfg, sd0=sd0, B=B, T=T, D=D):
             self.eng = MasrEngine(cfg, ODIM, label_smoothing=0.2, device=dev)
+            self.sd0, self.seed = sd0, 531 + rank * 64 + k
             self.eng.load_state_dict(sd0)
-            self.eng.set_seed(531 + rank * 64 + k)
+            self.eng.set_seed(self.seed)
             self.eng.set_concurrency(K)
             xs, self.il, self.ys, self.ol = synth_batch(B, T, D, seed=rank * 64 + k)   # numpy seed 0 + task index
             self.xs = xs.to(dev)
@@ -329,6 +382,14 @@ def main():
             self.eng.run_batch(self.xs, self.il, self.ys, self.ol, train=True)
             self.eng.clip_sgd_step(self.mom, 5.0, lr, 0.9, True, first_step=(self.i == 0))
             self.i += 1
+
+        def reset(self):
+            """back to the state the slot was created in: initial weights, zero momentum, dropout stream at its start"""
+            with torch.cuda.stream(self.stream):
+                self.eng.load_state_dict(self.sd0)
+                self.mom.zero_()
+            self.eng.set_seed(self.seed)
+            self.i = 0
 
     tasks = [Task(k) for k in range(K)]
     eng = tasks[0].eng
@@ -421,12 +482,19 @@ def main():
     stagger = 0.0
     if K > 1 and not args.no_stagger and single_first is not None:
         stagger = single_first["ms_per_step"] * 1e-3 / K         # spread the K task phases over one single-task step
+    if single_first is not None:
+        # (the one-task leg above, which the stagger of a plain run needs too, ran a timing-dependent number of steps on slot 0: the headline
+        # region starts every slot from its initial state, so that what it computes depends on the arguments alone)
+        tasks[0].reset()
     dt = timed(tasks, args.steps, args.warmup, stagger)
     st = eng.read_stats()
     assert np.isfinite(st["loss"]) and np.isfinite(st["grad_norm"]), st
     log(f"timed region: {dt:.3f} s for {args.steps} steps x {K} task(s); loss {st['loss']:.4f}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tasks, args.dump_outputs)
+    full = args.full                                             # everything below the headline region runs only with --full
     long_run = None
-    if args.long_seconds > 0:
+    if full and args.long_seconds > 0:
         # the driver's K-step region is ~0.2 s (clock ramp and jitter are a visible part of it): the same measurement over >= 2 s
         nlong = max(args.steps, int(1.1 * args.long_seconds / (dt / args.steps)) + 1)      # (+10 %: the short region includes the ramp)
         with ClockSampler(local) as clk:
@@ -434,7 +502,9 @@ def main():
         long_run = {"steps": nlong, "seconds": dtl, "value": world * K * B * nlong / dtl, "ms_per_step": dtl / nlong * 1e3,
                     "clocks_under_load": clk.summary()}
         log(f"long run: {dtl:.2f} s for {nlong} steps -> {long_run['value']:.1f} utt/s; clocks {long_run['clocks_under_load']}")
-    if K > 1 and args.single_seconds > 0:
+    if not full:
+        single = None                                            # (the one-task leg of a plain run only sized the stagger)
+    elif K > 1 and args.single_seconds > 0:
         with ClockSampler(local) as clk1:
             single = time_single(tasks, B, F_step, args.single_seconds)      # warm clocks: right behind the long run
         single["clocks_under_load"] = clk1.summary()
@@ -447,7 +517,7 @@ def main():
     # utterances of a batch share one length (what the reference's BucketSampler yields) and the half-batch rule applies
     # above 512 frames (B/1 or B*2 utterances, batch_size 32 of the shipped configs = 2 * B here)
     mixed = None
-    if not args.no_mixed:
+    if full and not args.no_mixed:
         rng = np.random.RandomState(1234 + rank)
         pools = []
         for t in tasks:
@@ -480,7 +550,7 @@ def main():
     # ---- SURVEY 8(d) matrix: the same K-task measurement at the shipped idim 83, at B = 32 (the reference's full-batch rule below 512
     # frames; not the headline shape) and on the 4e2d / E256 / H4 geometry -- one number each, short regions
     matrix = None
-    if not args.no_matrix:
+    if full and not args.no_matrix:
         matrix = {}
         nmx = max(6, args.steps // 3)
         for name, over, Bm, Dm in (("idim83", {}, B, 83), ("batch32", {}, 2 * B, D),
@@ -510,7 +580,7 @@ def main():
     # sum / n_tasks and the replicated Noam-Adam step.  Timed with and without the exchange: the difference is the part
     # of the all-reduce that is NOT hidden.  (The metric itself counts inner steps, which have no exchange.)
     meta = None
-    if not args.no_meta_step:
+    if full and not args.no_meta_step:
       try:
           from masr_amd.parallel import TaskSharder
           sharder = TaskSharder.from_env() if dist is not None else TaskSharder()
@@ -671,7 +741,7 @@ def main():
     roof = None
     prof_all = None
     nprof = 5
-    if rank == 0 and not args.no_profile:
+    if full and rank == 0 and not args.no_profile:
         eng.set_concurrency(1)
         eng.profile(True)
         for i in range(nprof):
@@ -791,7 +861,7 @@ def main():
         out = {
             "metric": "inner-step utterances/sec (10s x 80-dim fbank)", "value": value, "unit": "utt/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": full,
             "config": {"workload": "pretrain.py --algo fomaml inner step (run_batch + clip 5 + SGD nesterov), "
                                    "config/transformer/pretrain/fometa-hkust.yaml geometry, synthetic 10s x %d-dim fbank" % D,
                        "batch_per_task": B, "tasks_per_gpu": K, "frames": T, "idim": D, "dropout": cfg["dropout"],
@@ -813,7 +883,7 @@ def main():
             out["kernel_ms_per_step"] = {k: v[0] / nprof for k, v in prof_all.items()}
         if meta:
             out["meta_step"] = meta
-        if not args.no_e2e and world == 1 and dist is None:
+        if full and not args.no_e2e and world == 1 and dist is None:
             # the product loop end to end (not part of `value`, whose inputs are resident in HBM): a child process, because this one
             # holds K engines and the loop wants the same streams; synthetic shards of the bench shape on local disk
             import subprocess
@@ -846,7 +916,7 @@ def main():
                         log(f"end-to-end train.py ({opt_name}): {res['utt_per_s']:.0f} utt/s")
                     except Exception as ex:
                         out["e2e_train"][opt_name] = {"error": f"{type(ex).__name__}: {ex}"}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             log("cpu baseline (oracle on host cores) ...")
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_batch, T, D, args.cpu_steps)
             log("cpu baseline done")

@@ -1192,10 +1192,11 @@ def gen_hkust_fullsize_goldens():
 
 
 def gen_metric_goldens():
-    """Metric.batch_cal_er (src/monitor/metric.py:36-87) on seeded logits with the reference's sentencepiece model."""
+    """Metric.batch_cal_er (src/monitor/metric.py:36-87) on seeded logits with the toy sentencepiece model (tests/golden/toy_spm.*,
+    oracle/make_toy_spm.py): the test replays it from the repository alone."""
     from src.monitor.metric import Metric
-    units = ['<s>'] + [l.rstrip().split(' ')[0] for l in open(REF / "data" / "valid_train_en_unigram150_units.txt")] + ['</s>']
-    m = Metric(str(REF / "data" / "valid_train_en_unigram150.model"), units, 0, len(units) - 1)
+    units = ['<s>'] + [l.rstrip().split(' ')[0] for l in open(OUT / "toy_spm_units.txt")] + ['</s>']
+    m = Metric(str(OUT / "toy_spm.model"), units, 0, len(units) - 1)
     g = torch.Generator().manual_seed(21)
     B, L = 6, 12
     gold = torch.full((B, L), -1, dtype=torch.int64)

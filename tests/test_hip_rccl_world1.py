@@ -82,7 +82,7 @@ def test_bench_collective_legs_through_rccl_with_one_rank(tmp_path):
     of the timed region and the meta-step legs with their all-reduces (per round on the side stream; one per wave of task slots) run
     through RCCL with one rank -- what the driver's multi-GPU bench will execute first, minus the other ranks."""
     import json
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--tasks-per-gpu", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--tasks-per-gpu", "2", "--no-cpu-baseline",
                         "--long-seconds", "0", "--meta-steps", "2", "--no-matrix", "--no-mixed", "--no-e2e"], cwd=tmp_path, env=_env(MASR_FORCE_COLLECTIVE="1"),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -156,16 +156,13 @@ def test_levenshtein():
         assert levenshtein(a, b) == dp(a, b)
 
 
-SPM = Path("/root/reference/data/valid_train_en_unigram150.model")
-
-
-@pytest.mark.skipif(not SPM.exists(), reason="needs the reference's sentencepiece model (build container only)")
 def test_metric_matches_reference(golden_dir):
-    """eval metric path: teacher-forced argmax -> trim -> DecodePieces -> Levenshtein."""
+    """eval metric path: teacher-forced argmax -> trim -> DecodePieces -> Levenshtein, with the toy
+    sentencepiece model the reference's Metric ran on when tests/golden/metric.npz was made."""
     from masr_amd.monitor.metric import Metric
     g = np.load(golden_dir / "metric.npz")
-    units = ['<s>'] + [l.rstrip().split(' ')[0] for l in open(SPM.parent / "valid_train_en_unigram150_units.txt")] + ['</s>']
-    m = Metric(SPM, units, 0, len(units) - 1)
+    units = ['<s>'] + [l.rstrip().split(' ')[0] for l in open(golden_dir / "toy_spm_units.txt")] + ['</s>']
+    m = Metric(golden_dir / "toy_spm.model", units, 0, len(units) - 1)
     pred_ids, gold = torch.from_numpy(g["pred_ids"]), torch.from_numpy(g["gold"])
     logits = torch.nn.functional.one_hot(pred_ids, 367).float()
     assert abs(m.batch_cal_er(logits, gold, ['att'], ['cer'])['att_cer'] - float(g["cer"])) < 1e-9
