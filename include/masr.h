@@ -211,6 +211,19 @@ const float* masr_stats_device(masr_model* m);
 int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 int masr_recog_full(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 
+/* Beam search over the KV-cached decoder step (no LM, no CTC: the scores are sums of fp32 log_softmax of the decoder's logits).
+ * Per utterance b: enc_len = floor(ilens[b] / 4); maxlen = enc_len if max_step_ratio <= 0, else max(1, floor(max_step_ratio * enc_len)),
+ * capped at the 3000 rows of pe; minlen = floor(min_step_ratio * enc_len); Lmax = max over b of maxlen.  1 <= K <= 64.
+ * At every step the K best extensions (score descending, parent rank ascending, token ascending) of the live hypotheses are kept;
+ * those that end in <eos> (excluded while a hypothesis has fewer than minlen tokens) are set aside as ended; an utterance stops when
+ * nothing runs any more or its best ended score is >= its best running one; after maxlen steps the running ones end as they are.
+ * Result (device): tokens int32 [B][Lmax] (the best ended hypothesis without sos / eos, -1 behind it), lens int32 [B], scores fp32 [B].
+ * K = 1 is the greedy decode of masr_recog trimmed at its first <eos>.  Needs a workspace of masr_beam_workspace_bytes(B, T, K, Lmax)
+ * bound with masr_bind; the decode step is captured as its own hipGraph (the cache of masr_recog is not touched). */
+int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
+int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                    int32_t* tokens, int32_t* lens, float* scores, void* stream);
+
 /* Levenshtein distance of two id sequences (host-side; replaces the `editdistance` extension the reference's metric
  * imports, src/monitor/metric.py:4,66,87).  Returns the distance, < 0 on bad arguments. */
 int64_t masr_edit_distance(const int32_t* a, int na, const int32_t* b, int nb);

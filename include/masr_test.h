@@ -29,6 +29,10 @@ int masr_test_attention_dropout(const uint16_t* q, const uint16_t* k, const uint
 /* the NT GEMM with any combination of its fused epilogue stages (tools/bench_gemm_epi.py: what each stage costs per launch) */
 int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, const float* bias, int relu,
                        float drop_p, const float* residual, const uint16_t* mask, float* C32, uint16_t* C16, void* stream);
+/* the decode's few-row GEMM (decode.hip skinny_gemm_kernel, the launch of every decoder Linear of masr_recog / masr_recog_beam):
+ * C[M][N] = epi(A[M][K] W[N][K]^T) with bias, ReLU, fp32 residual [M][N], fp32 and/or bf16 output (tools/bench_beam.py: against the NT GEMM) */
+int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,
+                          const float* residual, float* C32, uint16_t* C16, void* stream);
 /* the operand-shadow pass of masr_refresh on ONE Linear weight: W fp32 [N][K] at P + src (P 16-byte aligned, src any dword offset >= 4 with at
  * least four floats of P behind the tensor -- in the flat parameter buffer the shadowed tensors are neither first nor last) -> k16 bf16 [N][K]
  * and its transpose t16 bf16 [K][ldt] (ldt >= N; the pads of a row stay untouched) */

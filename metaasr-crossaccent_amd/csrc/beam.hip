@@ -1,0 +1,220 @@
+// Beam-search decoding for MyTransformer (engine.hip: masr_recog_beam).  The decoder step of the greedy decode (decode.hip) runs
+// on R = B*K rows, row r = hypothesis r % K of utterance r / K; these kernels are the per-step glue around it.
+//
+// Per step t (read from the device scalar step[0], so the launch sequence is parameter-identical for every step and is replayed
+// as a hipGraph):
+//   beam_embed_step   row r: the embedding of its last token + pe[t-1]; its self-attention slot table (key j of row r lives in
+//                     cache row tab[r][j]) = its parent's table of the previous step, and tab[r][t-1] = r (the slot this step writes)
+//   ... decoder layers + fp32 logits (engine.hip) ...
+//   beam_row_topk     one wave per live row: fp32 log-softmax and the row's K best tokens (logit descending, token ascending)
+//   beam_select       one wave per utterance: K-way merge of the K sorted row lists -> the K best candidates (score descending,
+//                     parent rank ascending, then the row order above), ended / running bookkeeping, finished flag, step ticket
+// beam_backtrace runs once after the last step.
+//
+// Order of candidates.  Within one parent the score is fl(ps + fl(fl(z - mx) - log s)), a monotone function of the logit z, so the
+// row order (z descending, token ascending) is also score order there; a score tie inside one row that the rounding made out of two
+// different logits is decided by the logit.  Hence K = 1 picks exactly the greedy arg-max (first maximal logit).
+#include "kernels.h"
+
+namespace {
+
+constexpr float NEG_INF = -__builtin_inff();
+
+__device__ __forceinline__ uint32_t ord_f32(float v) {             // monotone float -> uint32 (larger float, larger key)
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), o, 64) << 32) |
+                                     (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+__global__ void beam_init_kernel(BeamArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) { a.step[0] = 1; a.step[1] = 0; }
+    if (i < a.R) a.score[i] = (i % a.K == 0) ? 0.f : NEG_INF;     // at t = 1 only row 0 of each utterance is live
+    if (i < a.B) { a.fin[i] = 0; a.best_score[i] = NEG_INF; a.best_len[i] = 0; a.best_row[i] = i * a.K; }
+}
+
+// grid R, 256 threads
+__global__ __launch_bounds__(256) void beam_embed_step_kernel(BeamArgs a, const float* __restrict__ table, const float* __restrict__ pe,
+                                                             float* __restrict__ y32, bf16* __restrict__ y16, int E) {
+    const int r = blockIdx.x, st = *a.step, u0 = (r / a.K) * a.K;
+    int tok = a.sos, par = r;
+    if (st > 1) {
+        tok = a.tok_hist[(long)(st - 2) * a.R + r];
+        par = a.par_hist[(long)(st - 2) * a.R + r];
+        // rows of a finished utterance are not written any more; keep their reads in bounds (their results are never used)
+        if (tok < 0 || tok >= a.C) tok = a.sos;
+        if (par < u0 || par >= u0 + a.K) par = r;
+    }
+    for (int e = threadIdx.x; e < E; e += 256) {
+        const float v = table[(long)tok * E + e] + pe[(long)(st - 1) * E + e];
+        y32[(long)r * E + e] = v;
+        y16[(long)r * E + e] = (bf16)v;
+    }
+    int* cur = a.tab + (long)(st & 1) * a.R * a.Lmax + (long)r * a.Lmax;
+    const int* prev = a.tab + (long)((st - 1) & 1) * a.R * a.Lmax + (long)par * a.Lmax;
+    for (int j = threadIdx.x; j < st - 1; j += 256) cur[j] = prev[j];
+    if (threadIdx.x == 0) cur[st - 1] = r;
+}
+
+// grid ceil(R / 4), 256 threads: one wave per row.  list_tok / list_score [R][K]: the row's K best extensions, token -1 past the end
+__global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const int u = r / a.K, st = *a.step;
+    if (a.fin[u]) return;
+    const float ps = a.score[r];
+    int* lt = a.list_tok + (long)r * a.K;
+    float* ls = a.list_score + (long)r * a.K;
+    if (ps == NEG_INF) {                                         // dead row: an empty list
+        for (int i = lane; i < a.K; i += 64) { lt[i] = -1; ls[i] = NEG_INF; }
+        return;
+    }
+    const float* z = logits + (long)r * ld;
+    const int no_eos = (st - 1) < a.minlen[u];                   // the hypothesis has st - 1 tokens
+    float mx = NEG_INF;
+    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
+    s = wave_sum(s);
+    const float lse = __logf(s);
+    // K rounds of "largest key below the previous one"; key = (ordered logit, inverted token): unique per token
+    unsigned long long prev = ~0ull;
+    for (int i = 0; i < a.K; ++i) {
+        unsigned long long best = 0;
+        for (int c = lane; c < a.C; c += 64) {
+            if (no_eos && c == a.eos) continue;
+            const unsigned long long key = ((unsigned long long)ord_f32(z[c]) << 32) | (uint32_t)(0x7fffffff - c);
+            if (key < prev && key > best) best = key;
+        }
+        best = wave_max_u64(best);
+        if (lane == 0) {
+            if (best == 0) { lt[i] = -1; ls[i] = NEG_INF; }
+            else {
+                const int c = 0x7fffffff - (int)(uint32_t)best;
+                lt[i] = c; ls[i] = ps + ((z[c] - mx) - lse);
+            }
+        }
+        prev = best;
+        if (best == 0) {                                         // fewer than K tokens: pad the rest of the list
+            for (int k = i + 1 + lane; k < a.K; k += 64) { lt[k] = -1; ls[k] = NEG_INF; }
+            break;
+        }
+    }
+}
+
+// grid B, 64 threads (one wave; lane k = parent rank k)
+__global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
+    __shared__ float s_score[64];
+    __shared__ int s_tok[64], s_par[64];
+    const int u = blockIdx.x, lane = threadIdx.x, K = a.K, st = *a.step;
+    if (!a.fin[u]) {
+        const int r0 = u * K;
+        // K-way merge: lane k's head is the best untaken entry of row r0 + k.  key = (ordered score, 63 - parent, 63 - list position)
+        int h = 0;
+        auto head_key = [&]() -> unsigned long long {
+            if (lane >= K || h >= K) return 0ull;
+            const float sc = a.list_score[(long)(r0 + lane) * K + h];
+            if (a.list_tok[(long)(r0 + lane) * K + h] < 0 || sc == NEG_INF) return 0ull;
+            return ((unsigned long long)ord_f32(sc) << 32) | (uint32_t)(((63 - lane) << 6) | (63 - h));
+        };
+        unsigned long long key = head_key();
+        int n = 0;
+        for (; n < K; ++n) {
+            const unsigned long long top = wave_max_u64(key);
+            if (top == 0) break;
+            const int k = 63 - (int)((top >> 6) & 63);
+            if (lane == k) {
+                s_score[n] = a.list_score[(long)(r0 + k) * K + h];
+                s_tok[n] = a.list_tok[(long)(r0 + k) * K + h];
+                s_par[n] = r0 + k;
+                ++h;
+                key = head_key();
+            }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            float bs = a.best_score[u]; int bl = a.best_len[u], br = a.best_row[u];
+            const int maxlen = a.maxlen[u];
+            int j = 0; float run_best = NEG_INF;
+            for (int i = 0; i < n; ++i) {                        // rank order: strict '>' keeps the earlier step, then the lower rank
+                const float sc = s_score[i];
+                if (s_tok[i] == a.eos) {                         // ended: the parent's tokens, without eos
+                    if (sc > bs) { bs = sc; bl = st - 1; br = s_par[i]; }
+                    continue;
+                }
+                const int row = r0 + j++;
+                a.tok_hist[(long)(st - 1) * a.R + row] = s_tok[i];
+                a.par_hist[(long)(st - 1) * a.R + row] = s_par[i];
+                a.score[row] = sc;
+                if (run_best == NEG_INF) run_best = sc;
+                if (st >= maxlen && sc > bs) { bs = sc; bl = st; br = row; }     // the last step: running hypotheses end as they are
+            }
+            for (int k = j; k < K; ++k) {                        // the beam shrank: dead rows
+                a.tok_hist[(long)(st - 1) * a.R + r0 + k] = a.sos;
+                a.par_hist[(long)(st - 1) * a.R + r0 + k] = r0 + k;
+                a.score[r0 + k] = NEG_INF;
+            }
+            a.best_score[u] = bs; a.best_len[u] = bl; a.best_row[u] = br;
+            // log-probabilities are <= 0: no running hypothesis can overtake an ended one that is at least as good
+            if (j == 0 || st >= maxlen || bs >= run_best) a.fin[u] = 1;
+        }
+    }
+    if (lane == 0) {
+        // the last utterance to finish advances the step (every block has read step[0] before taking its ticket)
+        __threadfence();
+        if (atomicAdd(a.step + 1, 1) == a.B - 1) { a.step[1] = 0; a.step[0] = st + 1; }
+    }
+}
+
+// grid B, 64 threads: tokens [B][Lmax] (-1 past the end), lens [B], scores [B] of the best ended hypothesis
+__global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
+    const int u = blockIdx.x;
+    const int n = a.best_len[u];
+    int* out = tokens + (long)u * a.Lmax;
+    for (int i = threadIdx.x; i < a.Lmax; i += 64) if (i >= n) out[i] = -1;
+    if (threadIdx.x == 0) {
+        int row = a.best_row[u];
+        for (int s = n; s >= 1; --s) {                           // tok_hist[s-1][row] = token s of the hypothesis in row `row` after step s
+            out[s - 1] = a.tok_hist[(long)(s - 1) * a.R + row];
+            row = a.par_hist[(long)(s - 1) * a.R + row];
+        }
+        lens[u] = n;
+        scores[u] = a.best_score[u];
+    }
+}
+
+}  // namespace
+
+#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : (mk_set_error(__func__, "launch failed"), -1))
+
+int mk_beam_init(const BeamArgs& a, hipStream_t s) {
+    const int n = a.R > a.B ? a.R : a.B;
+    hipLaunchKernelGGL(beam_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s) {
+    hipLaunchKernelGGL(beam_embed_step_kernel, dim3(a.R), dim3(256), 0, s, a, table, pe, y32, y16, E);
+    return LAUNCH_OK();
+}
+int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_t s) {
+    hipLaunchKernelGGL(beam_row_topk_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, logits, ld);
+    return LAUNCH_OK();
+}
+int mk_beam_select(const BeamArgs& a, hipStream_t s) {
+    if (a.K < 1 || a.K > 64) { mk_set_error("mk_beam_select", "beam size must be in [1, 64]"); return -1; }
+    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(64), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
+    hipLaunchKernelGGL(beam_backtrace_kernel, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores);
+    return LAUNCH_OK();
+}

@@ -61,9 +61,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
     __shared__ float s_o[4][HD];
     constexpr int CH = HD / 8, G = 256 / CH, GW = 64 / CH;   // column chunks, key groups per workgroup / per wave
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int klen = a.step ? *a.step : a.klens[b];
-    const bf16* __restrict__ kc = a.k + (long)b * a.kv_batch_stride + h * HD;
-    const bf16* __restrict__ vc = a.v + (long)b * a.kv_batch_stride + h * HD;
+    const int ub = a.rows_per_utt > 1 ? b / a.rows_per_utt : b;         // cache row / klens index (beam: the utterance of row b)
+    const int klen = a.step ? *a.step : a.klens[ub];
+    const bf16* __restrict__ kc = a.k + (long)ub * a.kv_batch_stride + h * HD;
+    const bf16* __restrict__ vc = a.v + (long)ub * a.kv_batch_stride + h * HD;
+    const int* __restrict__ srow = a.src ? a.src + (klen & 1) * a.src_flip + (long)b * a.ld_src : nullptr;
     const bf16* kn = a.knew ? a.knew + (long)b * a.ldnew + h * HD : nullptr;
     const bf16* vn = a.knew ? a.vnew + (long)b * a.ldnew + h * HD : nullptr;
     if (kn && tid < HD) {                                    // append (read back only by later launches)
@@ -78,7 +80,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
 #pragma unroll
         for (int c = 0; c < CH; ++c) qv[c] = ld8(qp + 8 * c);
         for (int j = tid; j < klen; j += 256) {
-            const bf16* kr = (kn && j == klen - 1) ? kn : kc + (long)j * a.ldk;
+            const bf16* kr = (kn && j == klen - 1) ? kn
+                           : (srow ? a.k + (long)srow[j] * a.kv_batch_stride + h * HD : kc) + (long)j * a.ldk;
             bf16x8 kv[CH];
 #pragma unroll
             for (int c = 0; c < CH; ++c) kv[c] = ld8(kr + 8 * c);
@@ -107,7 +110,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     for (int j = g; j < klen; j += G) {
-        const bf16* vr = (vn && j == klen - 1) ? vn : vc + (long)j * a.ldk;
+        const bf16* vr = (vn && j == klen - 1) ? vn
+                       : (srow ? a.v + (long)srow[j] * a.kv_batch_stride + h * HD : vc) + (long)j * a.ldk;
         const bf16x8 vv = ld8(vr + 8 * c);
         const float p = sS[j];
 #pragma unroll

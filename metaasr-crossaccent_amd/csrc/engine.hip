@@ -81,6 +81,7 @@ struct Acts {
 }  // namespace
 
 constexpr int KSPLIT_MAX = 8;
+constexpr int MASR_PE_ROWS = 3000;                         // rows of the positional-encoding table (masr_bind)
 struct masr_model {
     masr_config cfg;
     int E, H, hd, Fi, NE, ND, C, Cp, D, Dp, F;
@@ -121,6 +122,9 @@ struct masr_model {
     // cached hipGraph of one incremental decode step (masr_recog)
     hipGraphExec_t dec_exec = nullptr; hipGraph_t dec_graph = nullptr; hipEvent_t dec_done = nullptr;
     int dec_key[3] = {0, 0, 0}; const void* dec_key_ptr[3] = {nullptr, nullptr, nullptr};
+    // cached hipGraph of one beam-search step (masr_recog_beam), keyed on its own shape: the greedy graph above is left alone
+    hipGraphExec_t beam_exec = nullptr; hipGraph_t beam_graph = nullptr; hipEvent_t beam_done = nullptr;
+    int beam_key[4] = {0, 0, 0, 0}; const void* beam_key_ptr[2] = {nullptr, nullptr};
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[MASR_PROF_N]; int prof_used[MASR_PROF_N] = {0};
@@ -537,6 +541,9 @@ void masr_destroy(masr_model* m) {
     if (m->dec_done) { hipEventSynchronize(m->dec_done); hipEventDestroy(m->dec_done); }
     if (m->dec_exec) hipGraphExecDestroy(m->dec_exec);
     if (m->dec_graph) hipGraphDestroy(m->dec_graph);
+    if (m->beam_done) { hipEventSynchronize(m->beam_done); hipEventDestroy(m->beam_done); }
+    if (m->beam_exec) hipGraphExecDestroy(m->beam_exec);
+    if (m->beam_graph) hipGraphDestroy(m->beam_graph);
     for (auto& sg : m->step_graphs) { hipGraphExecDestroy(sg.e); hipGraphDestroy(sg.g); }
     for (auto& e : m->stage_ev) if (e) hipEventDestroy(e);
     for (auto& v : m->prof_ev) for (auto& p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -1091,24 +1098,26 @@ int masr_copy(float* dst, const float* src, int64_t n, void* stream) {
     return 0;
 }
 
-// One incremental decode step (the newest target position of every utterance) -- SURVEY 8(f).1.  Every launch below has
-// step-independent arguments; the step itself lives in *a.step_dev, so the sequence is captured once and replayed.
-static int decode_step(Ctx& c, int* out) {
+// The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
+// a.y32[0] / a.y16[0], output a.y32[ND].  Self-attention keys/values of earlier positions live in d.qkv ([rows][slots][3E]);
+// src (beam) maps row r's key j to the cache row that holds it; cross-attention row r reads utterance r / rows_per_utt.
+struct DecStepGeom { int rows, slots, rows_per_utt; bf16* step_qkv; const int* src; long src_flip; };
+static int decode_layers(Ctx& c, const DecStepGeom& gm) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
-    const int E = m->E, Fi = m->Fi, B = a.B;
+    const int E = m->E, Fi = m->Fi, B = gm.rows;
     auto lin = [&](const bf16* x, long ldx, const bf16* wk, int N, int K, const float* bias) {
         SkinnyArgs g{}; g.A = x; g.lda = ldx; g.W = wk; g.ldw = K; g.M = B; g.N = N; g.K = K; g.bias = bias; return g;
     };
     auto att = [&]() { AttnDecodeArgs t{}; t.B = B; t.H = m->H; t.hd = m->hd; t.ldo = E; return t; };
-    CK(mk_recog_embed_step(a.step_dev, out, P + m->embed_w, m->pe, a.y32[0], a.y16[0], B, E, 0, s));
     for (int l = 0; l < m->ND; ++l) {
         DecAct& d = a.dec[l]; const DecL& w = m->dec[l];
         // causal self-attention: keys/values of earlier positions live in d.qkv ([B][Ldec][3E], the layout of the full decode)
-        SkinnyArgs g = lin(a.y16[l], E, w.sa.in.k16, 3 * E, E, P + w.sa.in.b); g.C16 = a.step_qkv; g.ldc16 = 3 * E;
+        SkinnyArgs g = lin(a.y16[l], E, w.sa.in.k16, 3 * E, E, P + w.sa.in.b); g.C16 = gm.step_qkv; g.ldc16 = 3 * E;
         CK(mk_skinny_gemm(g, s));
         AttnDecodeArgs t = att();
-        t.q = a.step_qkv; t.ldq = 3 * E; t.k = d.qkv + E; t.v = d.qkv + 2 * E; t.ldk = 3 * E; t.kv_batch_stride = (long)a.L * 3 * E;
-        t.knew = a.step_qkv + E; t.vnew = a.step_qkv + 2 * E; t.ldnew = 3 * E; t.step = a.step_dev; t.o = d.ao; t.Tk_cap = a.L;
+        t.q = gm.step_qkv; t.ldq = 3 * E; t.k = d.qkv + E; t.v = d.qkv + 2 * E; t.ldk = 3 * E; t.kv_batch_stride = (long)gm.slots * 3 * E;
+        t.knew = gm.step_qkv + E; t.vnew = gm.step_qkv + 2 * E; t.ldnew = 3 * E; t.step = a.step_dev; t.o = d.ao; t.Tk_cap = gm.slots;
+        t.src = gm.src; t.ld_src = gm.slots; t.src_flip = gm.src_flip;
         CK(mk_attn_decode(t, s));
         g = lin(d.ao, E, w.sa.out.k16, E, E, P + w.sa.out.b); g.residual = a.y32[l]; g.ldres = E; g.C32 = d.s1; g.ldc = E;
         CK(mk_skinny_gemm(g, s));
@@ -1118,7 +1127,7 @@ static int decode_step(Ctx& c, int* out) {
         CK(mk_skinny_gemm(g, s));
         t = att();
         t.q = d.q; t.ldq = E; t.k = d.kv; t.v = d.kv + E; t.ldk = m->NK; t.kv_batch_stride = (long)a.Tp * m->NK;
-        t.klens = a.enc_lens; t.o = d.co; t.Tk_cap = a.Tp;
+        t.klens = a.enc_lens; t.o = d.co; t.Tk_cap = a.Tp; t.rows_per_utt = gm.rows_per_utt;
         CK(mk_attn_decode(t, s));
         g = lin(d.co, E, w.ca.out.k16, E, E, P + w.ca.out.b); g.residual = d.y1_32; g.ldres = E; g.C32 = d.s2; g.ldc = E;
         CK(mk_skinny_gemm(g, s));
@@ -1129,16 +1138,44 @@ static int decode_step(Ctx& c, int* out) {
         CK(mk_skinny_gemm(g, s));
         CK(ln_fwd(c, w.n3, d.s3, a.y32[l + 1], a.y16[l + 1], d.m3, d.r3, B));
     }
-    // the last projection in fp32 on the master weights (an arg-max follows: mk_logits_f32); layer 0's pre-LayerNorm sum is free by now
+    // the last projection in fp32 on the master weights (a selection follows: mk_logits_f32); layer 0's pre-LayerNorm sum is free by now
     float* yf32 = a.dec[0].s1;
     CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], yf32, nullptr, a.mdf, a.rdf, B));
     CK(mk_logits_f32(yf32, P + m->ct.w, P + m->ct.b, a.logits, m->Cp, B, m->C, E, s));
+    return 0;
+}
+
+// One incremental decode step (the newest target position of every utterance) -- SURVEY 8(f).1.  Every launch below has
+// step-independent arguments; the step itself lives in *a.step_dev, so the sequence is captured once and replayed.
+static int decode_step(Ctx& c, int* out) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
+    const int E = m->E, B = a.B;
+    CK(mk_recog_embed_step(a.step_dev, out, P + m->embed_w, m->pe, a.y32[0], a.y16[0], B, E, 0, s));
+    CK(decode_layers(c, DecStepGeom{B, a.L, 1, a.step_qkv, nullptr, 0}));
     CK(mk_recog_argmax_step(a.step_dev, a.logits, m->Cp, out, B, m->C, s));       // also advances *step_dev
     return 0;
 }
 
 // shared front half of the two decoders: argument checks, activation plan, enc_lens upload, encoder
-static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out) {
+// beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
+// rows, and the beam state follows the activations in the same arena
+struct BeamPlan { int K, Lmax; BeamArgs* args; bf16** step_qkv; };
+static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp) {
+    const int R = B * bp.K, L = bp.Lmax;
+    BeamArgs& a = *bp.args;
+    a = BeamArgs{};
+    a.B = B; a.K = bp.K; a.R = R; a.Lmax = L; a.C = m->C; a.sos = 0; a.eos = m->C - 1;
+    *bp.step_qkv = ar.get<bf16>((int64_t)R * 3 * m->E);
+    a.tab = ar.get<int>(2 * (int64_t)R * L);
+    a.tok_hist = ar.get<int>((int64_t)L * R); a.par_hist = ar.get<int>((int64_t)L * R);
+    a.score = ar.get<float>(R);
+    a.list_tok = ar.get<int>((int64_t)R * bp.K); a.list_score = ar.get<float>((int64_t)R * bp.K);
+    int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
+    a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
+}
+
+static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
+                         const BeamPlan* beam = nullptr) {
     if (!m->P) { mk_set_error("masr_recog", "not bound"); return -1; }
     if (B <= 0 || T < 4) { mk_set_error("masr_recog", "need B >= 1 and T >= 4"); return -1; }
     int Ldec = 0;
@@ -1147,8 +1184,13 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
         if ((int)(ilens[b] / 4) > Ldec) Ldec = (int)(ilens[b] / 4);
     }
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    plan_acts(m, ar, m->acts, B, T, Ldec, false);
-    if (ar.off > m->ws_bytes) { mk_set_error("masr_recog", "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"); return -2; }
+    plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : Ldec, false);
+    if (beam) plan_beam(m, ar, B, *beam);
+    if (ar.off > m->ws_bytes) {
+        mk_set_error("masr_recog", beam ? "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))"
+                                        : "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))");
+        return -2;
+    }
     Acts& a = m->acts; m->have_acts = true;
     const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
     HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
@@ -1216,6 +1258,88 @@ int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int 
         for (int step = 1; step <= Ldec; ++step) HIP_CHECK_RET(hipGraphLaunch(m->dec_exec, s));
         HIP_CHECK_RET(hipEventRecord(m->dec_done, s));
     }
+    m->have_acts = false;
+    return 0;
+}
+
+int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
+    Arena ar{nullptr, 0, 0};
+    Acts a; BeamArgs ba; bf16* sq;
+    plan_acts(m, ar, a, B, T, K * Lmax, false);
+    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq});
+    return m->persist_bytes + ar.off + 4096;
+}
+
+// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.
+static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
+    CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
+    CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
+    CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
+    CK(mk_beam_select(ba, s));                                  // also advances *step_dev
+    return 0;
+}
+
+int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
+    // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters) and replayed
+    // Lmax times -- utterances that finish earlier idle through the remaining replays.
+    if (!m) { mk_set_error("masr_recog_beam", "null model"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error("masr_recog_beam", "beam size K must be in [1, 64]"); return -1; }
+    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error("masr_recog_beam", "null pointer"); return -1; }
+    if (B <= 0) { mk_set_error("masr_recog_beam", "need B >= 1"); return -1; }
+    std::vector<int> mx_len(B), mn_len(B);
+    int Lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error("masr_recog_beam", "ilens must be in [4, T]"); return -1; }
+        const int enc = (int)(ilens[b] / 4);
+        int ml = max_step_ratio <= 0.f ? enc : std::max(1, (int)std::floor((double)max_step_ratio * enc));
+        mx_len[b] = std::min(ml, MASR_PE_ROWS);
+        mn_len[b] = std::max(0, (int)std::floor((double)min_step_ratio * enc));
+        Lmax = std::max(Lmax, mx_len[b]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    BeamArgs ba; bf16* step_qkv = nullptr;
+    const BeamPlan bp{K, Lmax, &ba, &step_qkv};
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, &bp); if (rc) return rc; }
+    Acts& a = m->acts;
+    ba.step = a.step_dev;
+    {   // per-utterance maxlen / minlen through the next staging slot (the one behind recog_prepare's enc_lens)
+        const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
+        HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
+        int* h = m->h_stage + (int64_t)slot * m->stage_ints;
+        for (int b = 0; b < B; ++b) { h[b] = mx_len[b]; h[B + b] = mn_len[b]; }
+        HIP_CHECK_RET(hipMemcpyAsync(const_cast<int*>(ba.maxlen), h, sizeof(int) * 2 * (size_t)B, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
+    }
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(project_memory_kv(c));
+    CK(mk_beam_init(ba, s));
+    const bool use_graph = s != nullptr && !m->prof && !getenv("MASR_RECOG_NO_GRAPH");
+    if (!use_graph) {
+        for (int step = 1; step <= Lmax; ++step) CK(beam_step(c, ba, step_qkv));
+    } else {
+        const int key[4] = {B, T, K, Lmax}; const void* kp[2] = {m->ws, m->P};
+        const bool hit = m->beam_exec && !memcmp(key, m->beam_key, sizeof key) && !memcmp(kp, m->beam_key_ptr, sizeof kp);
+        if (!hit) {
+            if (m->beam_done) HIP_CHECK_RET(hipEventSynchronize(m->beam_done));    // no replay of the old graph in flight
+            else HIP_CHECK_RET(hipEventCreateWithFlags(&m->beam_done, hipEventDisableTiming));
+            if (m->beam_exec) { hipGraphExecDestroy(m->beam_exec); m->beam_exec = nullptr; }
+            if (m->beam_graph) { hipGraphDestroy(m->beam_graph); m->beam_graph = nullptr; }
+            HIP_CHECK_RET(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            const int rc = beam_step(c, ba, step_qkv);
+            const hipError_t e = hipStreamEndCapture(s, &m->beam_graph);
+            if (rc || e != hipSuccess) { mk_set_error("masr_recog_beam", "stream capture of the beam step failed"); return -1; }
+            HIP_CHECK_RET(hipGraphInstantiate(&m->beam_exec, m->beam_graph, nullptr, nullptr, 0));
+            memcpy(m->beam_key, key, sizeof key); memcpy(m->beam_key_ptr, kp, sizeof kp);
+        }
+        for (int step = 1; step <= Lmax; ++step) HIP_CHECK_RET(hipGraphLaunch(m->beam_exec, s));
+        HIP_CHECK_RET(hipEventRecord(m->beam_done, s));
+    }
+    CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
 }
@@ -1312,6 +1436,13 @@ int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_
     g.drop_p = drop_p; g.seed = 1; g.site = 2; g.residual = residual; g.ldres = N; g.mask = (const bf16*)mask; g.ldmask = N;
     g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
     return mk_gemm(g, (hipStream_t)stream);
+}
+int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,
+                          const float* residual, float* C32, uint16_t* C16, void* stream) {
+    SkinnyArgs g{};
+    g.A = (const bf16*)A; g.lda = lda; g.W = (const bf16*)W; g.ldw = ldw; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
+    g.residual = residual; g.ldres = N; g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
+    return mk_skinny_gemm(g, (hipStream_t)stream);
 }
 int masr_test_linear_shadows(const float* P, int64_t src, int N, int K, int ldt, uint16_t* k16, uint16_t* t16, void* stream) {
     if (N <= 0 || K <= 0 || ldt < N || src < 4) { mk_set_error("masr_test_linear_shadows", "N, K > 0, ldt >= N, src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }

@@ -131,6 +131,12 @@ struct AttnDecodeArgs {
     const int* klens;                          // [B] valid keys (cross-attention) when step == null
     bf16* o; long ldo;
     int B, H, hd, Tk_cap;                      // Tk_cap bounds the key count (sizes the LDS score row)
+    // beam search (beam.hip).  rows_per_utt > 1: query row b reads the cross-attention cache / klens of utterance b / rows_per_utt.
+    // src != null (self-attention): cached key/value j of row b lives in cache row src[(klen & 1) * src_flip + b * ld_src + j]
+    // (the slot table of the step, double-buffered by step parity); the newest row is still appended to b's own cache row.
+    // Greedy passes 0 / null: same loads, same arithmetic.
+    int rows_per_utt;
+    const int* src; long ld_src, src_flip;
 };
 int mk_attn_decode(const AttnDecodeArgs& a, hipStream_t s);
 int mk_recog_embed_step(const int* step, const int* out, const float* table, const float* pe, float* y32, bf16* y16, int B, int E, int sos,
@@ -140,6 +146,25 @@ int mk_recog_argmax_step(int* step, const float* logits, long ld, int* out, int 
 int mk_recog_step_set(int* step, int value, int inc, hipStream_t s);     // inc ? *step += 1 : *step = value
 // logits[r][c] = bias[c] + <y32[r], W32[c]> in fp32 on the master weights (the decode's last projection: an arg-max follows)
 int mk_logits_f32(const float* y32, const float* W32, const float* bias, float* logits, long ld, int rows, int C, int E, hipStream_t s);
+
+// ---------------------------------------------------------------- beam search (beam.hip)
+// device state of one beam decode: R = B*K hypothesis rows (row r = rank r % K of utterance r / K), Lmax steps at most
+struct BeamArgs {
+    int* step;                                 // [2]: current step t (1-based), ticket counter
+    int B, K, R, Lmax, C, sos, eos;
+    const int *maxlen, *minlen;                // [B] per utterance
+    int* tab;                                  // [2][R][Lmax] self-attention slot tables (step parity)
+    int *tok_hist, *par_hist;                  // [Lmax][R]: token / parent row of the running hypothesis in row r after step t
+    float* score;                              // [R] running scores (-inf = dead row)
+    int* list_tok; float* list_score;          // [R][K] each row's K best extensions of the step
+    int* fin;                                  // [B] utterance finished
+    float* best_score; int *best_len, *best_row;   // [B] best ended hypothesis: score, token count, row at step best_len
+};
+int mk_beam_init(const BeamArgs& a, hipStream_t s);
+int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s);
+int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
+int mk_beam_select(const BeamArgs& a, hipStream_t s);                    // also advances step[0] once all B utterances are done
+int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
 
 // ---------------------------------------------------------------- row ops (rowops.hip)
 int mk_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y32, bf16* y16,

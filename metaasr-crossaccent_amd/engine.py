@@ -116,7 +116,9 @@ class MasrEngine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _ensure_ws(self, B, T, L):
-        need = int(self._l.masr_workspace_bytes(self.h, B, T, L))
+        self._ensure_ws_bytes(int(self._l.masr_workspace_bytes(self.h, B, T, L)))
+
+    def _ensure_ws_bytes(self, need):
         if self.ws is None or self.ws.numel() < need:
             torch.cuda.synchronize(self.device)
             self.ws = None
@@ -218,6 +220,42 @@ class MasrEngine:
         check(fn(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, _ptr(out), self.stream()), "masr_recog")
         self._last_x = xs
         return out.to(torch.int64)
+
+    @staticmethod
+    def beam_lengths(ilens, min_step_ratio=0.0, max_step_ratio=1.0):
+        """per-utterance (maxlen, minlen) of masr_recog_beam, computed as the library does (the ratios as fp32)"""
+        rmax, rmin = float(np.float32(max_step_ratio)), float(np.float32(min_step_ratio))
+        out = []
+        for n in ilens:
+            enc = int(n) // 4
+            ml = enc if rmax <= 0 else max(1, math.floor(rmax * enc))
+            out.append((min(ml, 3000), max(0, math.floor(rmin * enc))))
+        return out
+
+    def recog_beam(self, xs: torch.Tensor, ilens, beam_size: int, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
+        """beam search (masr_recog_beam): returns (list of B token lists without sos / eos, fp32 scores [B] on the host).
+        K = beam_size in [1, 64]; an utterance's result does not depend on the rest of its batch."""
+        K = int(beam_size)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
+        need = int(self._l.masr_beam_workspace_bytes(self.h, B, T, K, Lmax))
+        check(need if need < 0 else 0, "masr_beam_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        tok = torch.empty(B, Lmax, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, dtype=torch.float32, device=self.device)
+        check(self._l.masr_recog_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
+                                      _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam")
+        self._last_x = xs
+        tok, lens = tok.cpu(), lens.cpu()
+        return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
 
     def read_stats(self):
         out = (C.c_float * 4)()

@@ -100,3 +100,8 @@ class MyTransformer:
         """greedy decode (:143-176): encoder once, max(enc_lens) full re-decodes, arg-max of every position -> [Ldec, B]"""
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog(xs_pad, ilens)
+
+    def beam_decode(self, xs_pad, ilens, beam_size, min_step_ratio=0.0, max_step_ratio=1.0):
+        """beam search (masr_recog_beam; the reference has none for this model): (B token lists without sos / eos, scores [B])"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam(xs_pad, ilens, beam_size, min_step_ratio, max_step_ratio)

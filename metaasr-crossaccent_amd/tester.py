@@ -1,7 +1,9 @@
 """Tester: greedy decoding of the test shard into `<log_dir>/<decode_suffix>/best-hyp` (reference: src/tester.py:18-273).
 Line format "<ref ids> TAB <hyp ids>" (space separated), `trim` = cut at the first </s> after position 0 -- unchanged, so
 translate.py / score.sh of the reference run on these files as they are.  Only the transformer + greedy path exists in
-the reference for this model (beam search raises NotImplementedError there, tester.py:121-124)."""
+the reference for this model (beam search raises NotImplementedError there, tester.py:121-124); `--decode_mode beam` with the
+transformer runs this project's GPU beam search (masr_recog_beam) with the config's solver.beam_decode block and writes the
+best hypothesis of each utterance in the same line format."""
 from pathlib import Path
 from shutil import rmtree
 
@@ -98,10 +100,39 @@ class Tester:
         with open(Path(self.decode_dir, 'best-hyp'), 'a') as fout:
             fout.write("{}\t{}\n".format(" ".join(str(i) for i in y), " ".join(str(i) for i in hyp)))
 
+    def batch_beam_decode(self, xs, ilens, ys, olens):
+        hyps, _ = self.asr_model.beam_decode(xs, ilens, self.beam_size, self.min_step_ratio, self.max_step_ratio)
+        for hyp, y in zip(hyps, ys):
+            self.write_hyp(y.tolist(), hyp)
+        return True
+
+    def _beam_settings(self):
+        if self.decode_mode == 'lm_beam':
+            raise NotImplementedError("lm_beam: this project has no language model to fuse")
+        if self.model_name == 'blstm':
+            raise NotImplementedError("beam: beam search is only implemented for the transformer (the reference's BLSTM beam "
+                                      "decoder is dead code, DESIGN 9); use --decode_mode greedy")
+        bd = self.config.get('solver', {}).get('beam_decode')
+        if not isinstance(bd, dict) or 'beam_size' not in bd:
+            raise ValueError("decode_mode 'beam' needs a solver.beam_decode block with at least beam_size in the config")
+        self.beam_size = int(bd['beam_size'])
+        if not 1 <= self.beam_size <= 64:
+            raise ValueError(f"solver.beam_decode.beam_size must be in [1, 64], got {self.beam_size}")
+        self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
+        self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
+        if 'att_w' in bd:
+            logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: this model has no CTC head to weigh against the attention decoder")
+
     def exec(self):
+        if self.decode_mode not in ('greedy', 'beam', 'lm_beam'):
+            raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
+        decode = self.batch_greedy_decode
         if self.decode_mode != 'greedy':
-            raise NotImplementedError(f"{self.decode_mode} haven't supported yet")      # as the reference (tester.py:121-124)
-        logger.notice(f"Start greedy decoding: {len(self.eval_set)} batches of <= {self.batch_size}")
+            self._beam_settings()
+            decode = self.batch_beam_decode
+            logger.notice(f"Start beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
+        else:
+            logger.notice(f"Start greedy decoding: {len(self.eval_set)} batches of <= {self.batch_size}")
         # --resume: prev_decode_step counts the LINES (utterances) already in best-hyp.  The reference's batch path does not
         # skip at all (tester.py:149-152: a resumed batch decode appends everything again); its per-utterance path skips
         # by step.  Here whole batches are skipped while all their utterances are already written; a partially written
@@ -114,6 +145,6 @@ class Tester:
                 seen += n
                 continue
             self._skip_lines = done - seen if seen < done else 0
-            self.batch_greedy_decode(*self.eval_set.materialize(idxs))
+            decode(*self.eval_set.materialize(idxs))
             seen += n
         self._skip_lines = 0
