@@ -39,6 +39,14 @@ const char* masr_last_error(void);
 
 /* MyTransformer.__init__ (mono_transformer_torch.py:37-104): builds the parameter table only. */
 masr_model* masr_create(const masr_config* cfg);
+/* Extension (the reference's transformer trains on the decoder's CE alone): joint CTC/attention training, ESPnet's `mtlalpha`
+ * (YAML asr_model.ctc_weight).  ctc_weight == 0 is exactly masr_create.  0 < w < 1 adds the head ctc.ctc_lo = Linear(d_model -> odim)
+ * over the encoder memory (the output of encoder.norm, no dropout), appended behind every other parameter (ctc.ctc_lo.weight
+ * [odim][d_model], ctc.ctc_lo.bias [odim]), and masr_run_batch's loss becomes (1 - w) * CE + w * CTC, the CTC term
+ * nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) of log_softmax(head logits) with targets y (no sos / eos), input lengths
+ * floor(ilens / 4).  Stats are unchanged in layout: out[0] = the joint loss, out[1] / out[2] the decoder's.  Labels must be shorter than
+ * 1024 tokens, odim <= 4096.  A w outside [0, 1) returns null. */
+masr_model* masr_create_ctc(const masr_config* cfg, float ctc_weight);
 void masr_destroy(masr_model* m);
 
 /* Flat fp32 parameter buffer layout = the reference state_dict order without
@@ -47,7 +55,8 @@ int64_t masr_param_numel(const masr_model* m);
 int masr_param_count(const masr_model* m);
 int masr_param_info(const masr_model* m, int idx, char* name, int name_cap, int64_t shape[4], int* ndim, int64_t* offset);
 
-/* workspace needed for a batch of B utterances x T frames with L = max(olen)+1 target positions */
+/* workspace needed for a batch of B utterances x T frames with L = max(olen)+1 target positions (with a CTC head: its logits, gradient
+ * operand and lattice work buffer included) */
 int64_t masr_workspace_bytes(const masr_model* m, int B, int T, int L);
 /* params/grads: fp32 [masr_param_numel]; pe: fp32 [3000][d_model] (PositionalEncoding buffer, :16-28) */
 int masr_bind(masr_model* m, float* params, float* grads, const float* pe, void* workspace, int64_t ws_bytes);

@@ -20,6 +20,7 @@ _SIGS = {
     "masr_version": (C.c_int, []),
     "masr_last_error": (C.c_char_p, []),
     "masr_create": (vp, [C.POINTER(MasrConfig)]),
+    "masr_create_ctc": (vp, [C.POINTER(MasrConfig), f32]),
     "masr_destroy": (None, [vp]),
     "masr_param_numel": (i64, [vp]),
     "masr_param_count": (i32, [vp]),

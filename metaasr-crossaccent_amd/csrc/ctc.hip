@@ -34,8 +34,10 @@ __device__ __forceinline__ float lae(float a, float b) {          // log(exp a +
 //                      parallel, so this part fills the chip; class posteriors summed by owner threads in a fixed order as before
 //                      (bit-reproducible), the blank states by wave sums folded in wave order
 // Lengths are vetted by both (see ctc_mark).
-struct CtcGeo { int T, B, C, blank, Spad; long st_t, st_b; };
-__device__ __forceinline__ long ctc_at(const CtcGeo& g, int t, int b) { return ((long)t * g.st_t + (long)b * g.st_b) * g.C; }
+// ld: row stride of the logits (C on the BLSTM path; the padded vocabulary width of the transformer's CTC head)
+struct CtcGeo { int T, B, C, blank, Spad; long st_t, st_b, ld; };
+__device__ __forceinline__ long ctc_row(const CtcGeo& g, int t, int b) { return (long)t * g.st_t + (long)b * g.st_b; }
+__device__ __forceinline__ long ctc_at(const CtcGeo& g, int t, int b) { return ctc_row(g, t, b) * g.ld; }
 
 // log-softmax normaliser of every frame: one wave per frame, grid (ceil(T / 4), B)
 __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ logits, const int* __restrict__ in_len, CtcGeo g, float* __restrict__ work) {
@@ -167,18 +169,21 @@ __global__ __launch_bounds__(256) void ctc_sweep_kernel(const float* __restrict_
     }
 }
 
+// OutT = float: the BLSTM path's fp32 gradient, rows of C.  OutT = bf16 (the transformer's joint objective): the gradient times
+// `wscale` (the CTC weight) as the bf16 operand of the head's backward GEMMs, rows of ldg >= C with the pad columns zeroed
+template <typename OutT>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__ logits, const int* __restrict__ targets,
                                                        const int* __restrict__ tgt_off, const int* __restrict__ in_len,
-                                                       const int* __restrict__ tgt_len, CtcGeo g, float* __restrict__ grad,
-                                                       const float* __restrict__ work) {
+                                                       const int* __restrict__ tgt_len, CtcGeo g, OutT* __restrict__ grad, long ldg,
+                                                       float wscale, const float* __restrict__ work) {
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = g.T, B = g.B, C = g.C, blank = g.blank, Spad = g.Spad;
     const int Tb = in_len[b], Lb = tgt_len[b], S = 2 * Lb + 1;
-    float* gr = grad + ctc_at(g, t, b);
+    OutT* gr = grad + ctc_row(g, t, b) * ldg;
     const float ll = work[2L * B * T * Spad + 2L * B * T + b];
     const bool bad = Tb < 0 || Tb > T || Lb < 0 || S > Spad;
     if (bad || t >= Tb || ll == NINF || ll != ll) {                            // padded frame, refused or infeasible utterance: zero row
-        for (int c = tid; c < C; c += 256) gr[c] = 0.f;
+        for (int c = tid; c < ldg; c += 256) gr[c] = (OutT)0.f;
         return;
     }
     const int* tg = targets + tgt_off[b];
@@ -216,13 +221,26 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
     if (tid == 0) acc[blank] = (red[0] + red[1]) + (red[2] + red[3]);
     __syncthreads();
     const float gscale = 1.f / ((float)(Lb > 0 ? Lb : 1) * (float)B);
-    for (int c = tid; c < C; c += 256) gr[c] = (__expf(z[c] - lse) - acc[c]) * gscale;
+    if constexpr (sizeof(OutT) == sizeof(float)) {
+        for (int c = tid; c < C; c += 256) gr[c] = (__expf(z[c] - lse) - acc[c]) * gscale;
+    } else {
+        for (int c = tid; c < ldg; c += 256) gr[c] = (OutT)(c < C ? ((__expf(z[c] - lse) - acc[c]) * gscale) * wscale : 0.f);
+    }
 }
 __global__ void ctc_mean_kernel(const float* __restrict__ nll, const int* __restrict__ tgt_len, int B, float* __restrict__ out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         float s = 0.f;
         for (int b = 0; b < B; ++b) s += nll[b] / (float)(tgt_len[b] > 0 ? tgt_len[b] : 1);
         out[0] = s / B;
+    }
+}
+// the joint objective of the transformer: stats[0] holds the decoder's label-smoothed CE (ls_ce_reduce); it becomes
+// att_w * CE + w * CTC, the CTC term reduced exactly as ctc_mean_kernel does
+__global__ void ctc_mix_kernel(const float* __restrict__ nll, const int* __restrict__ tgt_len, int B, float att_w, float w, float* __restrict__ stats) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += nll[b] / (float)(tgt_len[b] > 0 ? tgt_len[b] : 1);
+        stats[0] = att_w * stats[0] + w * (s / B);
     }
 }
 }  // namespace
@@ -247,10 +265,23 @@ int mk_ctc_loss(const float* logits, const int* targets, const int* tgt_off, con
                   int B, int C, int blank, float* nll, float* loss_out, float* grad, float* work, int maxS, hipStream_t s, int batch_first) {
     if (maxS > MAXS || C > 4096) { mk_set_error("mk_ctc_loss", "lattice wider than 2048 states or > 4096 classes"); return -1; }
     if (T <= 0 || B <= 0 || C <= 0 || maxS < 1 || blank < 0 || blank >= C) { mk_set_error("mk_ctc_loss", "T, B, C, maxS must be positive and 0 <= blank < C"); return -1; }
-    const CtcGeo g{T, B, C, blank, (maxS + 3) / 4 * 4, batch_first ? 1L : (long)B, batch_first ? (long)T : 1L};
+    const CtcGeo g{T, B, C, blank, (maxS + 3) / 4 * 4, batch_first ? 1L : (long)B, batch_first ? (long)T : 1L, (long)C};
     hipLaunchKernelGGL(ctc_lse_kernel, dim3((T + 3) / 4, B), dim3(256), 0, s, logits, in_len, g, work);
     hipLaunchKernelGGL(ctc_sweep_kernel, dim3(B, 2), dim3(256), 0, s, logits, targets, tgt_off, in_len, tgt_len, g, nll, work);
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(256), 0, s, logits, targets, tgt_off, in_len, tgt_len, g, grad, work);
+    hipLaunchKernelGGL(ctc_grad_kernel<float>, dim3(T, B), dim3(256), 0, s, logits, targets, tgt_off, in_len, tgt_len, g, grad, (long)C, 1.f, work);
     hipLaunchKernelGGL(ctc_mean_kernel, dim3(1), dim3(64), 0, s, nll, tgt_len, B, loss_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int mk_ctc_loss_joint(const float* logits, long ld, const int* targets, const int* tgt_off, const int* in_len, const int* tgt_len, int T, int B,
+                      int C, float* nll, bf16* grad16, float w, float* stats, float* work, int maxS, hipStream_t s) {
+    if (maxS > MAXS || C > 4096) { mk_set_error("mk_ctc_loss_joint", "lattice wider than 2048 states or > 4096 classes"); return -1; }
+    if (T <= 0 || B <= 0 || C <= 0 || maxS < 1 || ld < C || (grad16 && (ld & 7))) { mk_set_error("mk_ctc_loss_joint", "bad geometry"); return -1; }
+    const CtcGeo g{T, B, C, 0, (maxS + 3) / 4 * 4, 1L, (long)T, ld};                         // batch-first rows [B][T] (the encoder memory)
+    hipLaunchKernelGGL(ctc_lse_kernel, dim3((T + 3) / 4, B), dim3(256), 0, s, logits, in_len, g, work);
+    hipLaunchKernelGGL(ctc_sweep_kernel, dim3(B, 2), dim3(256), 0, s, logits, targets, tgt_off, in_len, tgt_len, g, nll, work);
+    if (grad16)                                                                                 // (evaluation: no backward)
+        hipLaunchKernelGGL(ctc_grad_kernel<bf16>, dim3(T, B), dim3(256), 0, s, logits, targets, tgt_off, in_len, tgt_len, g, grad16, ld, w, work);
+    hipLaunchKernelGGL(ctc_mix_kernel, dim3(1), dim3(64), 0, s, nll, tgt_len, B, 1.f - w, w, stats);
+    if (hipGetLastError() != hipSuccess) { mk_set_error("mk_ctc_loss_joint", "launch failed"); return -1; }
+    return 0;
 }

@@ -76,6 +76,10 @@ struct Acts {
     float* slab; int64_t slab_floats;
     float *cw_slab[3], *c1_slab;                           // partial slabs of the conv weight gradients: each its own, all folded by ONE launch at the end of the pass
     float* ln_slab; int64_t ln_slab_floats;                // one region per LayerNorm backward (grouped reduce)
+    // joint CTC/attention objective (masr_create_ctc; null otherwise): the head's fp32 logits [rows_e][Cp] over the encoder memory, w * their
+    // CTC gradient as the bf16 operand of the head's backward [rows_e][Cp] (training only), per-utterance nll [B], the lattice's work buffer,
+    // and the targets' offsets | lengths into `gold` [2][B] (behind tok_start, in the same upload)
+    float *ctc_logits = nullptr, *ctc_nll = nullptr, *ctc_work = nullptr; bf16* ctc_d16 = nullptr; int* ctc_tgt = nullptr; int ctc_maxS = 0;
 };
 
 }  // namespace
@@ -86,7 +90,9 @@ struct masr_model {
     masr_config cfg;
     int E, H, hd, Fi, NE, ND, C, Cp, D, Dp, F;
     std::vector<PInfo> params; int64_t nparams = 0;
-    Conv conv[4]; Lin v2e, ct; int64_t embed_w; std::vector<EncL> enc; Norm enc_norm; std::vector<DecL> dec; Norm dec_norm;
+    Conv conv[4]; Lin v2e, ct; int64_t embed_w;
+    std::vector<EncL> enc; Norm enc_norm; std::vector<DecL> dec; Norm dec_norm;
+    float ctc_w = 0.f; Lin ctc{};                          // joint CTC/attention objective (masr_create_ctc): weight, head ctc.ctc_lo [odim][E] (0: no head)
     float *P = nullptr, *G = nullptr; const float* pe = nullptr;
     char* ws = nullptr; int64_t ws_bytes = 0, persist_bytes = 0;
     bf16 *v2e_k = nullptr;                    // permuted vgg2enc weight (NHWC feature order)
@@ -181,17 +187,21 @@ void plan_persistent(masr_model* m, Arena& ar) {
     m->kv_k16 = ar.get<bf16>((int64_t)m->NK * m->E); m->kvT = ar.get<bf16>((int64_t)m->E * m->NK); m->kv_bias = ar.get<float>(m->NK);
     m->stats = ar.get<float>(64);
     m->conv_sched = ar.get<unsigned>(64);
+    if (m->ctc_w > 0.f) { m->ctc.k16 = ar.get<bf16>((int64_t)m->Cp * m->E); m->ctc.t16 = ar.get<bf16>((int64_t)m->E * m->Cp); }   // (pads zeroed in masr_bind)
 }
 
 // ------------------------------------------------------------------ activation plan
-void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, bool train) {
+// ctc: the joint objective's branch (hybrid models; masr_run_batch only -- the decoders do not plan it)
+void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, bool train, bool ctc = false) {
     const int E = m->E, Fi = m->Fi, H = m->H;
     a.B = B; a.T = T; a.D = m->D; a.H2 = T / 2; a.W2 = m->D / 2; a.Tp = a.H2 / 2; a.Dp = a.W2 / 2; a.L = L;
     a.rows_e = B * a.Tp; a.rows_d = B * L;
     const int64_t re = a.rows_e, rd = a.rows_d;
-    a.tok_in = ar.get<int>(3 * rd + B + 8 + m->C + 1); a.gold = a.tok_in + rd; a.enc_lens = a.gold + rd;   // one block: one H2D copy per step
+    const bool hybrid = m->ctc_w > 0.f;
+    a.tok_in = ar.get<int>(3 * rd + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0)); a.gold = a.tok_in + rd; a.enc_lens = a.gold + rd;   // one block: one H2D copy per step
     a.meta = reinterpret_cast<uint32_t*>(a.enc_lens + B);
     a.tok_order = a.enc_lens + B + 8; a.tok_start = a.tok_order + rd;
+    a.ctc_tgt = hybrid ? a.tok_start + m->C + 1 : nullptr;
     a.step_dev = ar.get<int>(4);
     a.step_qkv = ar.get<bf16>((int64_t)B * 3 * E);
     const int64_t P1 = (int64_t)B * T * m->D, P2 = (int64_t)B * a.H2 * a.W2;
@@ -255,6 +265,14 @@ void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, boo
             g.gf = ar.get<bf16>(rd * Fi); g.gq = ar.get<bf16>(rd * E); g.gqkv = ar.get<bf16>(rd * 3 * E);
         }
         a.dp2 = ar.get<bf16>(re * m->F); a.da3 = ar.get<bf16>(P2 * 128); a.dp1 = ar.get<bf16>(P2 * 64);
+    }
+    a.ctc_logits = a.ctc_nll = a.ctc_work = nullptr; a.ctc_d16 = nullptr; a.ctc_maxS = 0;
+    if (hybrid && ctc) {                                       // (behind everything else: the plain model's plan is unchanged)
+        a.ctc_maxS = 2 * (L - 1) + 1;                           // 2 max(olen) + 1 lattice states
+        a.ctc_logits = ar.get<float>(re * m->Cp);
+        a.ctc_nll = ar.get<float>(B);
+        a.ctc_work = ar.get<float>(mk_ctc_work_floats(a.Tp, B, a.ctc_maxS));
+        a.ctc_d16 = train ? ar.get<bf16>(re * m->Cp) : nullptr;
     }
 }
 
@@ -532,6 +550,20 @@ masr_model* masr_create(const masr_config* cfg) {
     return m;
 }
 
+masr_model* masr_create_ctc(const masr_config* cfg, float ctc_weight) {
+    if (!(ctc_weight >= 0.f && ctc_weight < 1.f)) { mk_set_error("masr_create_ctc", "ctc_weight must lie in [0, 1)"); return nullptr; }
+    masr_model* m = masr_create(cfg);
+    if (!m || ctc_weight == 0.f) return m;
+    if (m->C > 4096) { mk_set_error("masr_create_ctc", "the CTC lattice supports odim <= 4096"); masr_destroy(m); return nullptr; }
+    // the head goes behind every parameter of the plain model (its offsets, and those of the persistent region, stay put)
+    m->ctc_w = ctc_weight;
+    m->ctc = add_linear(m, "ctc.ctc_lo", m->C, m->E);
+    Arena ar{nullptr, 0, 0};
+    plan_persistent(m, ar);
+    m->persist_bytes = ar.off;
+    return m;
+}
+
 void masr_destroy(masr_model* m) {
     if (!m) return;
     if (m->h_stage) hipHostFree(m->h_stage);
@@ -564,7 +596,7 @@ int masr_param_info(const masr_model* m, int idx, char* name, int cap, int64_t s
 int64_t masr_workspace_bytes(const masr_model* m, int B, int T, int L) {
     Arena ar{nullptr, 0, 0};
     Acts a;
-    plan_acts(m, ar, a, B, T, L, true);
+    plan_acts(m, ar, a, B, T, L, true, true);
     return m->persist_bytes + ar.off + 4096;
 }
 
@@ -605,11 +637,16 @@ int masr_bind(masr_model* m, float* params, float* grads, const float* pe, void*
             job(SH_LINEAR, d.ca.in.w + (long)E * E, 2 * E, E, m->NK, 0, 0, m->kv_k16 + (long)l * 2 * E * E, m->kvT + (long)l * 2 * E);   // key|value thirds
             job(SH_COPY32, d.ca.in.b + E, 2 * E, 0, 0, 0, 0, m->kv_bias + (long)l * 2 * E, nullptr);
         }
+        if (m->ctc_w > 0.f) job(SH_LINEAR, m->ctc.w, m->C, E, m->Cp, 0, 0, m->ctc.k16, m->ctc.t16);     // CTC head (pads zero, as char_trans)
     }
     // pads of the char_trans shadows must be zero (rows/cols >= odim); the refresh kernels only write the odim part
     HIP_CHECK_RET(hipMemset(m->conv_sched, 0, sizeof(unsigned) * 64));   // tile counters of the streaming conv (re-armed by the kernel itself)
     HIP_CHECK_RET(hipMemset(m->ct.k16, 0, sizeof(bf16) * (size_t)m->Cp * m->E));
     HIP_CHECK_RET(hipMemset(m->ct.t16, 0, sizeof(bf16) * (size_t)m->E * m->Cp));
+    if (m->ctc_w > 0.f) {
+        HIP_CHECK_RET(hipMemset(m->ctc.k16, 0, sizeof(bf16) * (size_t)m->Cp * m->E));
+        HIP_CHECK_RET(hipMemset(m->ctc.t16, 0, sizeof(bf16) * (size_t)m->E * m->Cp));
+    }
     m->have_acts = false;
     return 0;
 }
@@ -793,6 +830,26 @@ static int memory_kv_bwd(Ctx& c) {
     return 0;
 }
 
+// the CTC head of the joint objective (masr_create_ctc): fp32 logits of the encoder memory's bf16 operand, the lattice over them with the
+// targets read from `gold`, and stats[0] = (1 - w) CE + w CTC.  Training: w * d CTC / d logits as the bf16 operand of ctc_backward
+static int ctc_forward(Ctx& c) {
+    masr_model* m = c.m; Acts& a = m->acts;
+    GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
+    g.C32 = a.ctc_logits; g.ldc = m->Cp;
+    CK(gemm(c, g));
+    Prof p(m, MASR_PROF_MISC, c.s);
+    return mk_ctc_loss_joint(a.ctc_logits, m->Cp, a.gold, a.ctc_tgt, a.enc_lens, a.ctc_tgt + a.B, a.Tp, a.B, m->C, a.ctc_nll,
+                             c.train ? a.ctc_d16 : nullptr, m->ctc_w, m->stats, a.ctc_work, a.ctc_maxS, c.s);
+}
+// its backward: weight / bias gradients join the grouped encoder-row launch, d(memory) is added into dmem32 (behind memory_kv_bwd)
+static int ctc_backward(Ctx& c) {
+    masr_model* m = c.m; Acts& a = m->acts;
+    CK(lin_wgrad(c, a.ctc_d16, m->Cp, a.mem16, m->E, a.rows_e, m->C, m->E, m->G + m->ctc.w, m->G + m->ctc.b, true));
+    GemmArgs g = lin_dgrad_args(a.ctc_d16, m->Cp, m->ctc.t16, m->Cp, a.rows_e, m->Cp, m->E);
+    g.C32 = a.dmem32; g.ldc = m->E; g.accumulate = 1;
+    return gemm(c, g);
+}
+
 static int backward(Ctx& c, const float* xs) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; float* G = m->G;
     const int E = m->E, L = a.L, B = a.B;
@@ -820,6 +877,7 @@ static int backward(Ctx& c, const float* xs) {
                           a.gao_d, dg.gqkv, nullptr, a.delta_d, gcur, nullptr, 0, d.site[0], false, l > 0 ? &ks : nullptr));
     }
     CK(memory_kv_bwd(c));
+    if (m->ctc_w > 0.f) CK(ctc_backward(c));
     float* g_dec_in = gcur;                                  // d(decoder input): consumed by embed_bwd after the split-K combine
     // ---- encoder
     gcur = a.ge_b; gs = a.ge_a;
@@ -891,10 +949,13 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
     for (int b = 0; b < B; ++b) { if (olens[b] > maxo) maxo = (int)olens[b]; ntot += olens[b] + 1; }
     const int L = maxo + 1;
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    plan_acts(m, ar, m->acts, B, T, L, train);
+    plan_acts(m, ar, m->acts, B, T, L, train, true);
     if (ar.off > m->ws_bytes) { mk_set_error("masr_run_batch", "workspace too small (see masr_workspace_bytes)"); return -2; }
     Acts& a = m->acts; m->have_acts = true;
-    const int64_t stage_n = (int64_t)3 * B * L + B + 8 + m->C + 1;        // tok_in | gold | enc_lens | meta | tok_order | tok_start
+    const bool hybrid = m->ctc_w > 0.f;
+    if (hybrid && 2 * maxo + 1 > 2048) { mk_set_error("masr_run_batch", "CTC objective: labels longer than 1023 tokens"); return -1; }
+    // tok_in | gold | enc_lens | meta | tok_order | tok_start (| CTC target offsets | lengths)
+    const int64_t stage_n = (int64_t)3 * B * L + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0);
     if (stage_n > m->stage_ints) {
         // the pinned staging ring grows with the batch (B * L) and the vocabulary (C): drain the copies in flight, then re-allocate
         for (auto& ev : m->stage_ev) HIP_CHECK_RET(hipEventSynchronize(ev));
@@ -943,6 +1004,12 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
         for (int b = 0; b < B; ++b) for (int l = 0; l <= (int)olens[b]; ++l) h_order[h_start[h_in[b * L + l]]++] = b * L + l;
         for (int v = V; v > 0; --v) h_start[v] = h_start[v - 1];
         h_start[0] = 0;
+        if (hybrid) {
+            // CTC targets: the labels of utterance b are the first olens[b] entries of its gold row (behind them: eos, then -1).  Every
+            // 2 olen + 1 fits the lattice the work buffer holds (2 max olen + 1); olen > enc_len is left to zero_infinity
+            int* h_ctc = h_start + V + 1;
+            for (int b = 0; b < B; ++b) { h_ctc[b] = b * L; h_ctc[B + b] = (int)olens[b]; }
+        }
     }
     HIP_CHECK_RET(hipMemcpyAsync(a.tok_in, h, sizeof(int) * (size_t)stage_n, hipMemcpyHostToDevice, s));   // tok_in | gold | enc_lens | meta | tok_order | tok_start
     HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
@@ -953,7 +1020,8 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
         CK(forward_decoder(cc));
         { Prof p(m, MASR_PROF_MISC, s);
           CK(mk_ls_ce(a.logits, m->Cp, a.gold, a.rows_d, m->C, m->cfg.label_smoothing, inv_ntot, a.dlogits, a.row_loss, a.row_correct,
-                      m->stats, s, cc.inv_ptr)); }
+                      m->stats, s, cc.inv_ptr, 1.f - m->ctc_w)); }
+        if (hybrid) CK(ctc_forward(cc));
         if (train) CK(backward(cc, xs));
         return 0;
     };

@@ -222,8 +222,10 @@ int mk_colsum(const bf16* x, long ld, float* out, float* slab, int rows, int col
 long mk_colsum_slab_floats(int rows, int cols);
 // label-smoothed CE: logits fp32 [rows][ld]; gold int [rows] (-1 ignored); writes dlogits bf16 [rows][ld]
 // stats[0] = loss (already / n_total), stats[1] = n_correct, stats[2] = n_total
+// grad_w: factor of the gradient alone (the joint CTC/attention objective's 1 - w; 1 = the plain CE, the same bits)
 int mk_ls_ce(const float* logits, long ld, const int* gold, int rows, int C, float eps, float inv_ntotal,
-               bf16* dlogits, float* row_loss, int* row_correct, float* stats, hipStream_t s, const float* inv_ntotal_ptr = nullptr);
+               bf16* dlogits, float* row_loss, int* row_correct, float* stats, hipStream_t s, const float* inv_ntotal_ptr = nullptr,
+               float grad_w = 1.f);
 
 // ---------------------------------------------------------------- flat optimiser ops (optim.hip)
 int mk_sumsq(const float* x, long n, float* slab, float* out_norm, hipStream_t s);       // out_norm[0] = sqrt(sum x^2)
@@ -328,3 +330,8 @@ int mk_ctc_loss(const float* logits, const int* targets, const int* tgt_off, con
                   int maxS, hipStream_t s, int batch_first = 0);      // batch_first: logits / grad are [B][T][C]
 int mk_ctc_status(const float* work, int T, int B, int maxS, hipStream_t s);     // > 0: (index + 1) of an utterance the CTC launch on `work` refused (bad lengths)
 long mk_ctc_work_floats(int T, int B, int maxS);
+// the transformer's joint CTC/attention objective (engine.hip): logits fp32 [B][T][ld] of the CTC head over the encoder memory, blank 0.
+// stats[0] (the decoder's CE, mk_ls_ce) becomes (1 - w) CE + w CTC; grad16 (null: forward only) = w * d CTC / d logits as bf16 [B][T][ld],
+// pad columns C .. ld zero.  Lengths are vetted on the host by the caller (no mk_ctc_status on this path).
+int mk_ctc_loss_joint(const float* logits, long ld, const int* targets, const int* tgt_off, const int* in_len, const int* tgt_len, int T, int B,
+                      int C, float* nll /*[B]*/, bf16* grad16, float w, float* stats, float* work, int maxS, hipStream_t s);

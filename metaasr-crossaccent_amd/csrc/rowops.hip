@@ -316,8 +316,9 @@ __global__ __launch_bounds__(256) void recog_argmax_kernel(const float* __restri
 __global__ __launch_bounds__(256) void ls_ce_kernel(const float* __restrict__ logits, long ld, const int* __restrict__ gold,
                                                     int rows, int C, float eps, float inv_ntotal,
                                                     bf16* __restrict__ dlogits, float* __restrict__ row_loss,
-                                                    int* __restrict__ row_correct, const float* __restrict__ inv_ptr) {
+                                                    int* __restrict__ row_correct, const float* __restrict__ inv_ptr, float grad_w) {
     if (inv_ptr) inv_ntotal = *inv_ptr;                       // replayed step: 1 / n_total of THIS batch lives on the device
+    const float gscale = inv_ntotal * grad_w;                 // (grad_w = 1: exactly inv_ntotal)
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float* z = logits + (long)row * ld;
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(256) void ls_ce_kernel(const float* __restrict__ lo
         float v = 0.f;
         if (valid && c < C) {
             const float p = __expf(z[c] - lse);
-            v = (qsum * p - (c == g ? on : off)) * inv_ntotal;
+            v = (qsum * p - (c == g ? on : off)) * gscale;
         }
         d[c] = (bf16)v;
     }
@@ -498,8 +499,9 @@ int mk_colsum(const bf16* x, long ld, float* out, float* slab, int rows, int col
     return LAUNCH_OK();
 }
 int mk_ls_ce(const float* logits, long ld, const int* gold, int rows, int C, float eps, float inv_ntotal, bf16* dlogits,
-               float* row_loss, int* row_correct, float* stats, hipStream_t s, const float* inv_ptr) {
-    hipLaunchKernelGGL(ls_ce_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, ld, gold, rows, C, eps, inv_ntotal, dlogits, row_loss, row_correct, inv_ptr);
+               float* row_loss, int* row_correct, float* stats, hipStream_t s, const float* inv_ptr, float grad_w) {
+    hipLaunchKernelGGL(ls_ce_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, ld, gold, rows, C, eps, inv_ntotal, dlogits, row_loss, row_correct, inv_ptr,
+                       grad_w);
     hipLaunchKernelGGL(ls_ce_reduce, dim3(1), dim3(256), 0, s, row_loss, row_correct, rows, inv_ntotal, stats, inv_ptr);
     return LAUNCH_OK();
 }

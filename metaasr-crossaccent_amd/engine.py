@@ -17,6 +17,15 @@ from . import _cabi
 from ._cabi import MasrConfig, check, lib
 
 MASR_TRAIN, MASR_EVAL = 1, 0
+CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
+
+
+def ctc_weight_of(model_para: dict) -> float:
+    """asr_model.ctc_weight (absent = 0: the plain model), validated: 0 <= w < 1"""
+    w = float(model_para.get('ctc_weight', 0.0) or 0.0)
+    if not 0.0 <= w < 1.0:
+        raise ValueError(f"asr_model.ctc_weight must lie in [0, 1), got {w}")
+    return w
 
 
 def sinusoid_pe(max_len: int, E: int) -> torch.Tensor:
@@ -75,6 +84,7 @@ class MasrEngine:
         self.device = torch.device(device)
         self.model_para = model_para
         self.odim = odim
+        self.ctc_weight = ctc_weight_of(model_para)      # joint CTC/attention objective: loss = (1 - w) CE + w CTC (include/masr.h masr_create_ctc)
         self.cfg = MasrConfig(
             idim=model_para["idim"], odim=odim, d_model=model_para["d_model"], nheads=model_para["nheads"],
             d_inner=model_para["d_inner"], enc_layers=model_para["encoder"]["nlayers"],
@@ -82,9 +92,9 @@ class MasrEngine:
             dropout=float(model_para.get("dropout", 0.0)), pos_dropout=float(model_para.get("pos_dropout", 0.0)),
             label_smoothing=float(label_smoothing))
         self._l = lib()
-        self.h = self._l.masr_create(C.byref(self.cfg))
+        self.h = self._l.masr_create_ctc(C.byref(self.cfg), self.ctc_weight)
         if not self.h:
-            raise _cabi.MasrError("masr_create: " + self._l.masr_last_error().decode())
+            raise _cabi.MasrError("masr_create_ctc: " + self._l.masr_last_error().decode())
         self.numel = int(self._l.masr_param_numel(self.h))
         self.tied = bool(self.cfg.tie_weights)
         with torch.cuda.device(self.device):
@@ -144,8 +154,20 @@ class MasrEngine:
         return sd
 
     def load_state_dict(self, sd, flat=None):
+        """strict, except that a checkpoint without the CTC head loads into a hybrid model (the head keeps what it holds, i.e. its
+        fresh initialisation); a checkpoint WITH the head does not load into a plain model"""
         dst = self.params if flat is None else flat
+        extra = [k for k in CTC_HEAD if k in sd and k not in self.table]
+        if extra:
+            raise RuntimeError(f"the checkpoint holds the CTC head {', '.join(extra)} but this model has none (asr_model.ctc_weight is 0): "
+                               "set ctc_weight to load it")
+        kept = [k for k in CTC_HEAD if k in self.table and k not in sd]
+        if kept:
+            from .monitor import logger
+            logger.notice(f"the checkpoint has no CTC head: {', '.join(kept)} keep their fresh initialisation")
         for n, (off, shape) in self.table.items():
+            if n in kept:
+                continue
             t = sd[n]
             dst[off:off + t.numel()].copy_(t.detach().reshape(-1).to(torch.float32))
         if flat is None:

@@ -11,7 +11,11 @@ from .engine import MasrEngine
 def reference_init_state_dict(model_para, odim):
     """Initial weights identical to the reference's for the same torch seed: replays the reference's RNG consumption
     (module construction order of mono_transformer_torch.py:49-104, then xavier_uniform_ over parameters() with
-    dim > 1, :106-109) with throw-away torch.nn modules on the host.  Pinned by tests/golden/init.npz."""
+    dim > 1, :106-109) with throw-away torch.nn modules on the host.  Pinned by tests/golden/init.npz.
+    asr_model.ctc_weight > 0 (the joint objective; no counterpart in the reference): the CTC head ctc.ctc_lo is built AFTER that whole
+    sequence -- nn.Linear(E, odim), then xavier_uniform_ on its weight (its bias keeps Linear's init) -- so every other tensor is the
+    same for the same seed, and its two tensors follow the rest of the state_dict."""
+    from .engine import ctc_weight_of
     import warnings
     from torch import nn
     p = model_para
@@ -42,6 +46,10 @@ def reference_init_state_dict(model_para, odim):
     for mname, mod in mods.items():
         for n, t in mod.state_dict().items():
             sd[f"{mname}.{n}"] = t.detach()
+    if ctc_weight_of(p) > 0.0:
+        ctc_lo = nn.Linear(E, odim)
+        nn.init.xavier_uniform_(ctc_lo.weight)
+        sd["ctc.ctc_lo.weight"], sd["ctc.ctc_lo.bias"] = ctc_lo.weight.detach(), ctc_lo.bias.detach()
     return sd
 
 

@@ -9,6 +9,7 @@ from shutil import rmtree
 
 import torch
 
+from .engine import CTC_HEAD
 from .io.dataset import get_loader
 from .marcos import *  # noqa: F401,F403
 from .monitor import logger
@@ -180,7 +181,11 @@ class MonoASRInterface(TrainInterface):
             self.dashboard.set_step(self.global_step)
         elif self.paras.pretrain:
             cur = eng.state_dict()
-            cur.update(self.filter_model(torch.load(self.pretrain_model_path)))
+            pre = self.filter_model(torch.load(self.pretrain_model_path))
+            kept = [k for k in CTC_HEAD if k in eng.table and k not in pre]
+            if kept:                                                     # (a hybrid model from a plain snapshot, or 'ctc' not in pretrain_module)
+                logger.notice(f"the pretrained model gives no CTC head: {', '.join(kept)} keep their fresh initialisation")
+            cur.update(pre)
             eng.load_state_dict(cur)
             freeze = self.config['solver'].get('freeze_module')
             if freeze:

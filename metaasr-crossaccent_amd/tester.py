@@ -121,7 +121,11 @@ class Tester:
         self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
         self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
         if 'att_w' in bd:
-            logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: this model has no CTC head to weigh against the attention decoder")
+            if self.asr_model.engine.ctc_weight > 0.0:
+                logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: joint CTC/attention decoding is not built, this model's CTC head "
+                              "is used in training only and the beam runs on the attention decoder alone")
+            else:
+                logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: this model has no CTC head to weigh against the attention decoder")
 
     def exec(self):
         if self.decode_mode not in ('greedy', 'beam', 'lm_beam'):
