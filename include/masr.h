@@ -220,7 +220,7 @@ const float* masr_stats_device(masr_model* m);
 int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 int masr_recog_full(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 
-/* Beam search over the KV-cached decoder step (no LM, no CTC: the scores are sums of fp32 log_softmax of the decoder's logits).
+/* Beam search over the KV-cached decoder step (no LM, no CTC -- see masr_recog_beam_ctc: the scores are sums of fp32 log_softmax of the decoder's logits).
  * Per utterance b: enc_len = floor(ilens[b] / 4); maxlen = enc_len if max_step_ratio <= 0, else max(1, floor(max_step_ratio * enc_len)),
  * capped at the 3000 rows of pe; minlen = floor(min_step_ratio * enc_len); Lmax = max over b of maxlen.  1 <= K <= 64.
  * At every step the K best extensions (score descending, parent rank ascending, token ascending) of the live hypotheses are kept;
@@ -232,6 +232,19 @@ int masr_recog_full(masr_model* m, const float* xs, const int64_t* ilens, int B,
 int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
 int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
                     int32_t* tokens, int32_t* lens, float* scores, void* stream);
+
+/* Joint CTC/attention beam search (hybrid models of masr_create_ctc; ESPnet's ctc_weight decoding, Watanabe et al. 2017).  The search of
+ * masr_recog_beam with the CTC head's one-pass prefix score psi over the encoder memory (log_softmax of the head, blank 0, T_b = enc_len frames):
+ * each live hypothesis keeps its P = min(floor(3K/2), eligible) best tokens by attention logit (blank never, eos from minlen tokens on), and a
+ * candidate scores s(h+c) = s(h) + att_w * lp_att(c | h) + ctc_w * (psi(h+c) - psi(h)) in fp32; psi(h+eos) is the full CTC log-probability
+ * of h.  The K best candidates (joint score descending, parent rank ascending, logit descending, token ascending) are kept; a candidate
+ * scoring -inf is never kept nor ended.  Stop rule, minlen / maxlen and the result layout as masr_recog_beam; scores are joint scores, and an
+ * utterance where nothing ended gets the empty hypothesis with score -inf.  Needs ctc_w > 0 and att_w >= 0 (both finite), a CTC head, the
+ * bounds of masr_recog_beam and a workspace of masr_beam_ctc_workspace_bytes(B, T, K, Lmax) (it holds [2][B*K][T/4][P] CTC states of
+ * 8 bytes).  The step is captured as its own hipGraph. */
+int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
+int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                        float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
 /* Levenshtein distance of two id sequences (host-side; replaces the `editdistance` extension the reference's metric
  * imports, src/monitor/metric.py:4,66,87).  Returns the distance, < 0 on bad arguments. */

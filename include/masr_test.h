@@ -33,6 +33,17 @@ int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_
  * C[M][N] = epi(A[M][K] W[N][K]^T) with bias, ReLU, fp32 residual [M][N], fp32 and/or bf16 output (tools/bench_beam.py: against the NT GEMM) */
 int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,
                           const float* residual, float* C32, uint16_t* C16, void* stream);
+/* the joint beam's CTC prefix-score kernel (beam.hip beam_ctc_prefix_kernel, the per-step launch of masr_recog_beam_ctc) alone, on one
+ * hypothesis row over T frames: lp fp32 [C][T] (x_t(c), frame-contiguous per class; blank 0, eos C - 1); the parent as (last, parent, psi_par,
+ * score): last = -1 for the empty hypothesis (its state and psi 0 come from the decode's init kernel; parent / psi_par are ignored), else its
+ * last token, with its state parent fp32 [T][2] (r^n_t, r^b_t) and prefix score psi_par; n (1..96) pre-beam candidates cand int32 [n]
+ * (1 .. C-1, or -1 = none) with their attention log-probs att_lp fp32 [n].  Out: the row's list as the decode step leaves it -- list_tok /
+ * list_score / list_psi / list_slot [n] sorted by joint score s + att_w lp + ctc_w (psi - psi_par) (descending, then candidate index), -1 /
+ * -inf behind the finite ones -- and the candidates' states out_state fp32 [T][n][2] (columns of eos and of -1: zero).  All arrays on
+ * the device; synchronises the stream. */
+int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                         const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
+                         int32_t* list_slot, float* out_state, void* stream);
 /* the operand-shadow pass of masr_refresh on ONE Linear weight: W fp32 [N][K] at P + src (P 16-byte aligned, src any dword offset >= 4 with at
  * least four floats of P behind the tensor -- in the flat parameter buffer the shadowed tensors are neither first nor last) -> k16 bf16 [N][K]
  * and its transpose t16 bf16 [K][ldt] (ldt >= N; the pads of a row stay untouched) */

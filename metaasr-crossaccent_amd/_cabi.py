@@ -68,6 +68,8 @@ _SIGS = {
     "masr_recog_full": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "masr_beam_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
+    "masr_beam_ctc_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
+    "masr_recog_beam_ctc": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_edit_distance": (i64, [vp, i32, vp, i32]),
     "masr_blstm_create": (vp, [vp]),
     "masr_blstm_destroy": (None, [vp]),
@@ -101,6 +103,7 @@ _SIGS = {
     "masr_test_attention_dropout": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_gemm_epi": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp]),
     "masr_test_skinny_gemm": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
+    "masr_test_ctc_prefix": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "masr_test_linear_shadows": (i32, [vp, i64, i32, i32, i32, vp, vp, vp]),
     "masr_test_conv1_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "masr_test_conv3x3": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),

@@ -111,31 +111,39 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamArgs a, const fl
     }
 }
 
-// grid B, 64 threads (one wave; lane k = parent rank k)
+// grid B, 64 threads (one wave; lane k = parent rank k).  JOINT (masr_recog_beam_ctc): the row lists are P long, sorted by joint score,
+// and a kept candidate also takes its prefix score and the place of its CTC state
+template <bool JOINT>
 __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
+    constexpr int HB = JOINT ? 7 : 6;                            // bits of the list position in the merge key (P <= 96, K <= 64)
     __shared__ float s_score[64];
     __shared__ int s_tok[64], s_par[64];
+    __shared__ float s_psi[JOINT ? 64 : 1];
+    __shared__ int s_slot[JOINT ? 64 : 1];
     const int u = blockIdx.x, lane = threadIdx.x, K = a.K, st = *a.step;
+    const int W = JOINT ? a.P : K;                               // list length
     if (!a.fin[u]) {
         const int r0 = u * K;
-        // K-way merge: lane k's head is the best untaken entry of row r0 + k.  key = (ordered score, 63 - parent, 63 - list position)
+        // K-way merge: lane k's head is the best untaken entry of row r0 + k.  key = (ordered score, 63 - parent, max - list position)
         int h = 0;
         auto head_key = [&]() -> unsigned long long {
-            if (lane >= K || h >= K) return 0ull;
-            const float sc = a.list_score[(long)(r0 + lane) * K + h];
-            if (a.list_tok[(long)(r0 + lane) * K + h] < 0 || sc == NEG_INF) return 0ull;
-            return ((unsigned long long)ord_f32(sc) << 32) | (uint32_t)(((63 - lane) << 6) | (63 - h));
+            if (lane >= K || h >= W) return 0ull;
+            const float sc = a.list_score[(long)(r0 + lane) * W + h];
+            if (a.list_tok[(long)(r0 + lane) * W + h] < 0 || sc == NEG_INF) return 0ull;
+            return ((unsigned long long)ord_f32(sc) << 32) | (uint32_t)(((63 - lane) << HB) | ((1 << HB) - 1 - h));
         };
         unsigned long long key = head_key();
         int n = 0;
         for (; n < K; ++n) {
             const unsigned long long top = wave_max_u64(key);
             if (top == 0) break;
-            const int k = 63 - (int)((top >> 6) & 63);
+            const int k = 63 - (int)((top >> HB) & 63);
             if (lane == k) {
-                s_score[n] = a.list_score[(long)(r0 + k) * K + h];
-                s_tok[n] = a.list_tok[(long)(r0 + k) * K + h];
+                const long e = (long)(r0 + k) * W + h;
+                s_score[n] = a.list_score[e];
+                s_tok[n] = a.list_tok[e];
                 s_par[n] = r0 + k;
+                if constexpr (JOINT) { s_psi[n] = a.list_psi[e]; s_slot[n] = a.list_slot[e]; }
                 ++h;
                 key = head_key();
             }
@@ -155,6 +163,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
                 a.tok_hist[(long)(st - 1) * a.R + row] = s_tok[i];
                 a.par_hist[(long)(st - 1) * a.R + row] = s_par[i];
                 a.score[row] = sc;
+                if constexpr (JOINT) { a.psi[row] = s_psi[i]; a.src[row] = s_par[i] * a.P + s_slot[i]; }
                 if (run_best == NEG_INF) run_best = sc;
                 if (st >= maxlen && sc > bs) { bs = sc; bl = st; br = row; }     // the last step: running hypotheses end as they are
             }
@@ -173,6 +182,166 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
         __threadfence();
         if (atomicAdd(a.step + 1, 1) == a.B - 1) { a.step[1] = 0; a.step[0] = st + 1; }
     }
+}
+
+// ---------------------------------------------------------------- joint CTC/attention decoding (masr_recog_beam_ctc)
+// The one-pass CTC prefix score (Watanabe et al. 2017; ESPnet's CTCPrefixScore).  x_t(c) = a.ctc_lp[u][c][t], blank 0, eos C - 1.
+// State of hypothesis h at frame t < T_b: (r^n_t, r^b_t).  Extension by c (not blank, not eos), phi_t = logaddexp(r^n_t(h), r^b_t(h)),
+// or r^b_t(h) when c is h's last token:
+//   r^n_0 = x_0(c) if h is empty else -inf,  r^b_0 = -inf
+//   r^n_t = logaddexp(r^n_{t-1}, phi_{t-1}) + x_t(c),  r^b_t = logaddexp(r^n_{t-1}, r^b_{t-1}) + x_t(blank)
+//   psi(h+c) = logsumexp(r^n_0, phi_{t-1} + x_t(c) for 1 <= t < T_b);  psi(h+eos) = phi_{T_b-1} (no plain-phi exception)
+// Joint score s(h+c) = s(h) + att_w * lp_att(c | h) + ctc_w * (psi(h+c) - psi(h)), fp32 in that order (no contraction).
+
+__device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e^b); -inf + -inf = -inf, never NaN
+    const float m = fmaxf(a, b);
+    if (m == NEG_INF) return NEG_INF;
+    return m + __logf(1.f + __expf(fminf(a, b) - m));
+}
+
+// grid ceil(B*Tp / 4), 256 threads: one wave per frame row b*Tp + t of the head's fp32 logits -> lp[b][c][t] (frames t < T_b only)
+__global__ __launch_bounds__(256) void beam_ctc_logsoftmax_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B * a.Tp) return;
+    const int b = row / a.Tp, t = row % a.Tp;
+    if (t >= a.enc_lens[b]) return;
+    const float* z = logits + (long)row * ld;
+    float mx = NEG_INF;
+    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
+    s = wave_sum(s);
+    const float lse = __logf(s);
+    float* out = const_cast<float*>(a.ctc_lp) + (long)b * a.C * a.Tp + t;
+    for (int c = lane; c < a.C; c += 64) out[(long)c * a.Tp] = (z[c] - mx) - lse;
+}
+
+// grid B, 64 threads, after beam_init_kernel: the empty hypothesis (r^n = -inf, r^b_t = x_0(blank) + ... + x_t(blank), psi 0) in
+// parity 0, row u*K, slot 0; every row's psi / src point there
+__global__ __launch_bounds__(64) void beam_ctc_init_kernel(BeamArgs a) {
+    const int u = blockIdx.x;
+    for (int k = threadIdx.x; k < a.K; k += 64) { const int r = u * a.K + k; a.psi[r] = 0.f; a.src[r] = (u * a.K) * a.P; }
+    if (threadIdx.x == 0) {
+        const float* xb = a.ctc_lp + (long)u * a.C * a.Tp;        // class 0 = blank
+        float2* st = a.ctc_state + (long)(u * a.K) * a.Tp * a.P;
+        float acc = 0.f;
+        for (int t = 0; t < a.enc_lens[u]; ++t) { acc += xb[t]; st[(long)t * a.P] = make_float2(NEG_INF, acc); }
+    }
+}
+
+// grid ceil(R / 4), 256 threads: one wave per live row.  pre_tok / pre_lp [R][P]: the row's P best tokens by logit (logit descending,
+// token ascending; blank never, eos once the hypothesis has minlen tokens), each with its fp32 attention log-prob; token -1 past the end
+__global__ __launch_bounds__(256) void beam_ctc_prebeam_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const int u = r / a.K, st = *a.step;
+    if (a.fin[u] || a.score[r] == NEG_INF) return;               // (the prefix kernel gives a dead row its empty list)
+    int* pt = a.pre_tok + (long)r * a.P;
+    float* pl = a.pre_lp + (long)r * a.P;
+    const float* z = logits + (long)r * ld;
+    const int no_eos = (st - 1) < a.minlen[u];
+    float mx = NEG_INF;
+    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
+    s = wave_sum(s);
+    const float lse = __logf(s);
+    unsigned long long prev = ~0ull;
+    for (int i = 0; i < a.P; ++i) {
+        unsigned long long best = 0;
+        for (int c = lane; c < a.C; c += 64) {
+            if (c == 0 || (no_eos && c == a.eos)) continue;
+            const unsigned long long key = ((unsigned long long)ord_f32(z[c]) << 32) | (uint32_t)(0x7fffffff - c);
+            if (key < prev && key > best) best = key;
+        }
+        best = wave_max_u64(best);
+        if (lane == 0) {
+            const int c = 0x7fffffff - (int)(uint32_t)best;
+            pt[i] = best ? c : -1;
+            pl[i] = best ? (z[c] - mx) - lse : NEG_INF;
+        }
+        prev = best;
+        if (best == 0) {
+            for (int k = i + 1 + lane; k < a.P; k += 64) { pt[k] = -1; pl[k] = NEG_INF; }
+            break;
+        }
+    }
+}
+
+// grid R, 128 threads: thread i runs the chain of the row's pre-beam candidate i (i < P <= 96), serial over the T_b frames.  The parent's
+// phi_t, r^b_t and x_t(blank) are staged in LDS by chunks of CTC_CH frames (every chain of the row shares them); the candidate's
+// (r^n_t, r^b_t) go to ctc_state[st & 1][r][t][i], so a wave's stores at one frame are contiguous.  Then the row's candidates are
+// sorted by (joint score descending, pre-beam position ascending) into list_tok / list_score / list_psi / list_slot.
+constexpr int CTC_CH = 256;
+__global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
+    __shared__ float s_phi[CTC_CH], s_rbp[CTC_CH], s_xb[CTC_CH];
+    __shared__ unsigned long long s_key[128];
+    const int r = blockIdx.x, i = threadIdx.x, u = r / a.K, P = a.P;
+    if (a.fin[u]) return;
+    const long lo = (long)r * P;
+    const float ps = a.score[r];
+    if (ps == NEG_INF) {                                         // dead row: an empty list
+        if (i < P) { a.list_tok[lo + i] = -1; a.list_score[lo + i] = NEG_INF; }
+        return;
+    }
+    const int st = *a.step, Tb = a.enc_lens[u], sp = a.src[r];
+    const int last = st > 1 ? a.tok_hist[(long)(st - 2) * a.R + r] : -1;
+    const long plane = (long)a.R * a.Tp * P;
+    const float2* prev = a.ctc_state + ((st - 1) & 1) * plane + (long)(sp / P) * a.Tp * P + sp % P;   // parent state, frame t at [t * P]
+    float2* cur = a.ctc_state + (st & 1) * plane + (long)r * a.Tp * P + i;
+    const float* lp = a.ctc_lp + (long)u * a.C * a.Tp;
+    const int c = i < P ? a.pre_tok[lo + i] : -1;
+    const bool chain = c > 0 && c != a.eos, rep = c == last;
+    const float* xc = lp + (long)(chain ? c : 0) * a.Tp;
+    float rn = NEG_INF, rb = NEG_INF, psi = NEG_INF, ph = NEG_INF;       // ph = phi_{t-1} as this candidate sees it
+    for (int t0 = 0; t0 < Tb; t0 += CTC_CH) {
+        const int n = min(CTC_CH, Tb - t0);
+        __syncthreads();                                         // the previous chunk is consumed
+        for (int t = i; t < n; t += 128) {
+            const float2 v = prev[(long)(t0 + t) * P];
+            s_phi[t] = log_add(v.x, v.y); s_rbp[t] = v.y; s_xb[t] = lp[t0 + t];
+        }
+        __syncthreads();
+        if (chain) {
+            int t = 0;
+            if (t0 == 0) {
+                rn = st == 1 ? xc[0] : NEG_INF;                  // (step 1: the parent is the empty hypothesis)
+                psi = rn;
+                cur[0] = make_float2(rn, rb);
+                ph = rep ? s_rbp[0] : s_phi[0];
+                t = 1;
+            }
+            for (; t < n; ++t) {
+                const float x = xc[t0 + t];
+                const float rn1 = log_add(rn, ph) + x;
+                rb = log_add(rn, rb) + s_xb[t];
+                psi = log_add(psi, ph + x);
+                rn = rn1;
+                cur[(long)(t0 + t) * P] = make_float2(rn, rb);
+                ph = rep ? s_rbp[t] : s_phi[t];
+            }
+        }
+        if (c == a.eos && t0 + n == Tb) psi = s_phi[n - 1];      // the parent's full CTC log-probability
+    }
+    unsigned long long key = 0;
+    float js = NEG_INF;
+    if (c > 0 && psi != NEG_INF) {
+        const float d = __fsub_rn(psi, a.psi[r]);
+        js = __fadd_rn(__fadd_rn(ps, __fmul_rn(a.att_w, a.pre_lp[lo + i])), __fmul_rn(a.ctc_w, d));
+        if (js != NEG_INF) key = ((unsigned long long)ord_f32(js) << 32) | (uint32_t)(127 - i);
+    }
+    s_key[i] = key;
+    const int nv = __syncthreads_count(key != 0);
+    // the nv finite candidates take positions [0, nv) by rank; every position in [nv, P) is padded by its own thread, whatever that
+    // thread's candidate was (ranks are < nv: the two kinds of store never meet).  No position keeps a previous step's entry.
+    if (key) {
+        int rank = 0;
+        for (int j = 0; j < P; ++j) rank += s_key[j] > key;
+        a.list_tok[lo + rank] = c; a.list_score[lo + rank] = js; a.list_psi[lo + rank] = psi; a.list_slot[lo + rank] = i;
+    }
+    if (i < P && i >= nv) { a.list_tok[lo + i] = -1; a.list_score[lo + i] = NEG_INF; }
 }
 
 // grid B, 64 threads: tokens [B][Lmax] (-1 past the end), lens [B], scores [B] of the best ended hypothesis
@@ -211,10 +380,33 @@ int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_
 }
 int mk_beam_select(const BeamArgs& a, hipStream_t s) {
     if (a.K < 1 || a.K > 64) { mk_set_error("mk_beam_select", "beam size must be in [1, 64]"); return -1; }
-    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(beam_select_kernel<false>, dim3(a.B), dim3(64), 0, s, a);
     return LAUNCH_OK();
 }
 int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
     hipLaunchKernelGGL(beam_backtrace_kernel, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores);
+    return LAUNCH_OK();
+}
+
+int mk_beam_ctc_logsoftmax(const BeamArgs& a, const float* logits, long ld, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_logsoftmax_kernel, dim3((a.B * a.Tp + 3) / 4), dim3(256), 0, s, a, logits, ld);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_init_kernel, dim3(a.B), dim3(64), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s) {
+    hipLaunchKernelGGL(beam_ctc_prebeam_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, logits, ld);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s) {
+    if (a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_prefix", "pre-beam width must be in [1, 96]"); return -1; }
+    hipLaunchKernelGGL(beam_ctc_prefix_kernel, dim3(a.R), dim3(128), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s) {
+    if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_select", "need 1 <= K <= 64, 1 <= P <= 96"); return -1; }
+    hipLaunchKernelGGL(beam_select_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
     return LAUNCH_OK();
 }

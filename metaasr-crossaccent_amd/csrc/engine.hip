@@ -131,6 +131,9 @@ struct masr_model {
     // cached hipGraph of one beam-search step (masr_recog_beam), keyed on its own shape: the greedy graph above is left alone
     hipGraphExec_t beam_exec = nullptr; hipGraph_t beam_graph = nullptr; hipEvent_t beam_done = nullptr;
     int beam_key[4] = {0, 0, 0, 0}; const void* beam_key_ptr[2] = {nullptr, nullptr};
+    // cached hipGraph of one joint CTC/attention beam step (masr_recog_beam_ctc), keyed on its shape and the two weights
+    hipGraphExec_t bj_exec = nullptr; hipGraph_t bj_graph = nullptr; hipEvent_t bj_done = nullptr;
+    int bj_key[6] = {0, 0, 0, 0, 0, 0}; const void* bj_key_ptr[2] = {nullptr, nullptr};
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[MASR_PROF_N]; int prof_used[MASR_PROF_N] = {0};
@@ -576,6 +579,9 @@ void masr_destroy(masr_model* m) {
     if (m->beam_done) { hipEventSynchronize(m->beam_done); hipEventDestroy(m->beam_done); }
     if (m->beam_exec) hipGraphExecDestroy(m->beam_exec);
     if (m->beam_graph) hipGraphDestroy(m->beam_graph);
+    if (m->bj_done) { hipEventSynchronize(m->bj_done); hipEventDestroy(m->bj_done); }
+    if (m->bj_exec) hipGraphExecDestroy(m->bj_exec);
+    if (m->bj_graph) hipGraphDestroy(m->bj_graph);
     for (auto& sg : m->step_graphs) { hipGraphExecDestroy(sg.e); hipGraphDestroy(sg.g); }
     for (auto& e : m->stage_ev) if (e) hipEventDestroy(e);
     for (auto& v : m->prof_ev) for (auto& p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -1227,9 +1233,11 @@ static int decode_step(Ctx& c, int* out) {
 // shared front half of the two decoders: argument checks, activation plan, enc_lens upload, encoder
 // beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
 // rows, and the beam state follows the activations in the same arena
-struct BeamPlan { int K, Lmax; BeamArgs* args; bf16** step_qkv; };
+// joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
+// log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
+struct BeamPlan { int K, Lmax; BeamArgs* args; bf16** step_qkv; int P = 0, Tp = 0; float** ctc_logits = nullptr; };
 static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp) {
-    const int R = B * bp.K, L = bp.Lmax;
+    const int R = B * bp.K, L = bp.Lmax, W = bp.P ? bp.P : bp.K;
     BeamArgs& a = *bp.args;
     a = BeamArgs{};
     a.B = B; a.K = bp.K; a.R = R; a.Lmax = L; a.C = m->C; a.sos = 0; a.eos = m->C - 1;
@@ -1237,9 +1245,18 @@ static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp)
     a.tab = ar.get<int>(2 * (int64_t)R * L);
     a.tok_hist = ar.get<int>((int64_t)L * R); a.par_hist = ar.get<int>((int64_t)L * R);
     a.score = ar.get<float>(R);
-    a.list_tok = ar.get<int>((int64_t)R * bp.K); a.list_score = ar.get<float>((int64_t)R * bp.K);
+    a.list_tok = ar.get<int>((int64_t)R * W); a.list_score = ar.get<float>((int64_t)R * W);
     int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
     a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
+    if (!bp.P) return;
+    const int P = bp.P, Tp = bp.Tp;
+    a.P = P; a.Tp = Tp;
+    *bp.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    a.ctc_lp = ar.get<float>((int64_t)B * m->C * Tp);
+    a.ctc_state = ar.get<float2>(2 * (int64_t)R * Tp * P);
+    a.psi = ar.get<float>(R); a.src = ar.get<int>(R);
+    a.pre_tok = ar.get<int>((int64_t)R * P); a.pre_lp = ar.get<float>((int64_t)R * P);
+    a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
 }
 
 static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
@@ -1255,8 +1272,9 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
     plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : Ldec, false);
     if (beam) plan_beam(m, ar, B, *beam);
     if (ar.off > m->ws_bytes) {
-        mk_set_error("masr_recog", beam ? "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))"
-                                        : "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))");
+        mk_set_error("masr_recog", !beam ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : beam->P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
+                                             : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
         return -2;
     }
     Acts& a = m->acts; m->have_acts = true;
@@ -1339,29 +1357,48 @@ int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int 
     return m->persist_bytes + ar.off + 4096;
 }
 
-// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.
+static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
+
+int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_ctc_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error("masr_beam_ctc_workspace_bytes", "the model has no CTC head (masr_create_ctc)"); return -1; }
+    Arena ar{nullptr, 0, 0};
+    Acts a; BeamArgs ba; bf16* sq; float* cl;
+    plan_acts(m, ar, a, B, T, K * Lmax, false);
+    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq, beam_prebeam_width(K), T / 4, &cl});
+    return m->persist_bytes + ar.off + 4096;
+}
+
+// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
+// CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.
 static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
     CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
+    if (ba.P) {
+        CK(mk_beam_ctc_prebeam(ba, a.logits, m->Cp, s));
+        CK(mk_beam_ctc_prefix(ba, s));
+        CK(mk_beam_ctc_select(ba, s));                          // also advances *step_dev
+        return 0;
+    }
     CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
     CK(mk_beam_select(ba, s));                                  // also advances *step_dev
     return 0;
 }
 
-int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
-                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+// masr_recog_beam (wts == null) and masr_recog_beam_ctc (wts = {att_w, ctc_w}): the same decode, each with its own cached step graph
+static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                           const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn) {
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters) and replayed
     // Lmax times -- utterances that finish earlier idle through the remaining replays.
-    if (!m) { mk_set_error("masr_recog_beam", "null model"); return -1; }
-    if (K < 1 || K > 64) { mk_set_error("masr_recog_beam", "beam size K must be in [1, 64]"); return -1; }
-    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error("masr_recog_beam", "null pointer"); return -1; }
-    if (B <= 0) { mk_set_error("masr_recog_beam", "need B >= 1"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
+    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B <= 0) { mk_set_error(fn, "need B >= 1"); return -1; }
     std::vector<int> mx_len(B), mn_len(B);
     int Lmax = 0;
     for (int b = 0; b < B; ++b) {
-        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error("masr_recog_beam", "ilens must be in [4, T]"); return -1; }
+        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error(fn, "ilens must be in [4, T]"); return -1; }
         const int enc = (int)(ilens[b] / 4);
         int ml = max_step_ratio <= 0.f ? enc : std::max(1, (int)std::floor((double)max_step_ratio * enc));
         mx_len[b] = std::min(ml, MASR_PE_ROWS);
@@ -1369,8 +1406,8 @@ int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B,
         Lmax = std::max(Lmax, mx_len[b]);
     }
     hipStream_t s = (hipStream_t)stream;
-    BeamArgs ba; bf16* step_qkv = nullptr;
-    const BeamPlan bp{K, Lmax, &ba, &step_qkv};
+    BeamArgs ba; bf16* step_qkv = nullptr; float* ctc_logits = nullptr;
+    const BeamPlan bp{K, Lmax, &ba, &step_qkv, wts ? beam_prebeam_width(K) : 0, T / 4, &ctc_logits};
     int Ldec = 0;
     { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, &bp); if (rc) return rc; }
     Acts& a = m->acts;
@@ -1386,30 +1423,65 @@ int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B,
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     CK(project_memory_kv(c));
     CK(mk_beam_init(ba, s));
+    if (wts) {
+        // once per decode: the CTC head over the memory (training's GEMM: bf16 operands, fp32 logits), its log-softmax per frame, the
+        // empty hypothesis's state
+        ba.att_w = wts[0]; ba.ctc_w = wts[1]; ba.enc_lens = a.enc_lens;
+        GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
+        g.C32 = ctc_logits; g.ldc = m->Cp;
+        CK(gemm(c, g));
+        CK(mk_beam_ctc_logsoftmax(ba, ctc_logits, m->Cp, s));
+        CK(mk_beam_ctc_init(ba, s));
+    }
     const bool use_graph = s != nullptr && !m->prof && !getenv("MASR_RECOG_NO_GRAPH");
     if (!use_graph) {
         for (int step = 1; step <= Lmax; ++step) CK(beam_step(c, ba, step_qkv));
     } else {
-        const int key[4] = {B, T, K, Lmax}; const void* kp[2] = {m->ws, m->P};
-        const bool hit = m->beam_exec && !memcmp(key, m->beam_key, sizeof key) && !memcmp(kp, m->beam_key_ptr, sizeof kp);
+        hipGraphExec_t& exec = wts ? m->bj_exec : m->beam_exec;
+        hipGraph_t& graph = wts ? m->bj_graph : m->beam_graph;
+        hipEvent_t& done = wts ? m->bj_done : m->beam_done;
+        int* gkey = wts ? m->bj_key : m->beam_key;
+        const void** gkey_ptr = wts ? m->bj_key_ptr : m->beam_key_ptr;
+        int key[6] = {B, T, K, Lmax, 0, 0}; const void* kp[2] = {m->ws, m->P};
+        if (wts) { memcpy(key + 4, wts, 2 * sizeof(float)); }
+        const size_t nkey = (wts ? 6 : 4) * sizeof(int);
+        const bool hit = exec && !memcmp(key, gkey, nkey) && !memcmp(kp, gkey_ptr, sizeof kp);
         if (!hit) {
-            if (m->beam_done) HIP_CHECK_RET(hipEventSynchronize(m->beam_done));    // no replay of the old graph in flight
-            else HIP_CHECK_RET(hipEventCreateWithFlags(&m->beam_done, hipEventDisableTiming));
-            if (m->beam_exec) { hipGraphExecDestroy(m->beam_exec); m->beam_exec = nullptr; }
-            if (m->beam_graph) { hipGraphDestroy(m->beam_graph); m->beam_graph = nullptr; }
+            if (done) HIP_CHECK_RET(hipEventSynchronize(done));    // no replay of the old graph in flight
+            else HIP_CHECK_RET(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+            if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+            if (graph) { hipGraphDestroy(graph); graph = nullptr; }
             HIP_CHECK_RET(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             const int rc = beam_step(c, ba, step_qkv);
-            const hipError_t e = hipStreamEndCapture(s, &m->beam_graph);
-            if (rc || e != hipSuccess) { mk_set_error("masr_recog_beam", "stream capture of the beam step failed"); return -1; }
-            HIP_CHECK_RET(hipGraphInstantiate(&m->beam_exec, m->beam_graph, nullptr, nullptr, 0));
-            memcpy(m->beam_key, key, sizeof key); memcpy(m->beam_key_ptr, kp, sizeof kp);
+            const hipError_t e = hipStreamEndCapture(s, &graph);
+            if (rc || e != hipSuccess) { mk_set_error(fn, "stream capture of the beam step failed"); return -1; }
+            HIP_CHECK_RET(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            memcpy(gkey, key, nkey); memcpy(gkey_ptr, kp, sizeof kp);
         }
-        for (int step = 1; step <= Lmax; ++step) HIP_CHECK_RET(hipGraphLaunch(m->beam_exec, s));
-        HIP_CHECK_RET(hipEventRecord(m->beam_done, s));
+        for (int step = 1; step <= Lmax; ++step) HIP_CHECK_RET(hipGraphLaunch(exec, s));
+        HIP_CHECK_RET(hipEventRecord(done, s));
     }
     CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
+}
+
+int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    if (!m) { mk_set_error("masr_recog_beam", "null model"); return -1; }
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, "masr_recog_beam");
+}
+
+int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                        float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // joint CTC/attention beam (beam.hip): the attention beam's search with the CTC prefix score of the head's log-probs
+    const char* fn = "masr_recog_beam_ctc";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
+    if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
+    const float wts[2] = {att_w, ctc_w};
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn);
 }
 
 // Levenshtein distance of two id sequences (host code; the reference's metric imports the `editdistance` C extension,
@@ -1511,6 +1583,53 @@ int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int
     g.A = (const bf16*)A; g.lda = lda; g.W = (const bf16*)W; g.ldw = ldw; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
     g.residual = residual; g.ldres = N; g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
     return mk_skinny_gemm(g, (hipStream_t)stream);
+}
+int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                         const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
+                         int32_t* list_slot, float* out_state, void* stream) {
+    const char* fn = "masr_test_ctc_prefix";
+    if (!lp || !cand || !att_lp || !list_tok || !list_score || !list_psi || !list_slot || !out_state || (last >= 0 && !parent)) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (C < 2 || T < 1 || n < 1 || n > 96 || last < -1 || last >= C) { mk_set_error(fn, "need C >= 2, T >= 1, 1 <= n <= 96, -1 <= last < C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hc(n);
+    HIP_CHECK_RET(hipMemcpyAsync(hc.data(), cand, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    for (int v : hc) if (v == 0 || v < -1 || v >= C) { mk_set_error(fn, "candidates must lie in 1 .. C-1 or be -1"); return -1; }
+    // one utterance, one row (B = K = R = 1), P = n; step 1 reads the empty state of parity 0, step 2 the given parent in parity 1
+    const int st = last < 0 ? 1 : 2;
+    const size_t plane = (size_t)T * n;
+    char* w = nullptr;
+    HIP_CHECK_RET(hipMalloc(&w, 256 + 2 * plane * sizeof(float2)));
+    if (hipMemsetAsync(w, 0, 256 + 2 * plane * sizeof(float2), s) != hipSuccess) { hipFree(w); mk_set_error(fn, "memset failed"); return -1; }
+    int* ints = reinterpret_cast<int*>(w);                  // step[2] | fin | enc_len | tok_hist | src
+    float* flts = reinterpret_cast<float*>(w + 64);         // score | psi
+    const int h_ints[6] = {st, 0, 0, T, last, 0};
+    const float h_flts[2] = {score, psi_par};
+    BeamArgs a{};
+    a.step = ints; a.fin = ints + 2; a.enc_lens = ints + 3; a.tok_hist = ints + 4; a.src = ints + 5;
+    a.score = flts; a.psi = flts + 1;
+    a.B = 1; a.K = 1; a.R = 1; a.Lmax = st; a.C = C; a.sos = 0; a.eos = C - 1;
+    a.P = n; a.Tp = T; a.att_w = att_w; a.ctc_w = ctc_w;
+    a.ctc_lp = lp; a.ctc_state = reinterpret_cast<float2*>(w + 256);
+    a.pre_tok = const_cast<int*>(cand); a.pre_lp = const_cast<float*>(att_lp);
+    a.list_tok = list_tok; a.list_score = list_score; a.list_psi = list_psi; a.list_slot = list_slot;
+    int rc = 0;
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(ints, h_ints, sizeof h_ints, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(flts, h_flts, sizeof h_flts, hipMemcpyHostToDevice, s));
+        if (last < 0) CK(mk_beam_ctc_init(a, s));            // (writes psi 0 and src 0: the empty hypothesis)
+        else HIP_CHECK_RET(hipMemcpy2DAsync(a.ctc_state + plane, (size_t)n * sizeof(float2), parent, sizeof(float2), sizeof(float2), T,
+                                            hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_ctc_prefix(a, s));
+        HIP_CHECK_RET(hipMemcpyAsync(out_state, a.ctc_state + (st & 1) * plane, plane * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    rc = run();
+    hipFree(w);
+    return rc;
 }
 int masr_test_linear_shadows(const float* P, int64_t src, int N, int K, int ldt, uint16_t* k16, uint16_t* t16, void* stream) {
     if (N <= 0 || K <= 0 || ldt < N || src < 4) { mk_set_error("masr_test_linear_shadows", "N, K > 0, ldt >= N, src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }

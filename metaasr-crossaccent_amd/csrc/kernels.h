@@ -159,12 +159,30 @@ struct BeamArgs {
     int* list_tok; float* list_score;          // [R][K] each row's K best extensions of the step
     int* fin;                                  // [B] utterance finished
     float* best_score; int *best_len, *best_row;   // [B] best ended hypothesis: score, token count, row at step best_len
+    // joint CTC/attention decode (masr_recog_beam_ctc; P = 0 and null otherwise).  list_tok / list_score are then [R][P] and hold each
+    // row's candidates sorted by joint score
+    int P, Tp;                                 // pre-beam width floor(3K/2), frame stride of the CTC arrays
+    float att_w, ctc_w;
+    const int* enc_lens;                       // [B] CTC frames T_b
+    const float* ctc_lp;                       // [B][C][Tp] fp32 log_softmax of the CTC head (frame-contiguous per class)
+    float2* ctc_state;                         // [2][R][Tp][P] (r^n, r^b) of row r's candidate i at frame t, step parity
+    float* psi;                                // [R] CTC prefix score of the row's hypothesis
+    int* src;                                  // [R] its CTC state: parent row * P + candidate slot of the previous step
+    int* pre_tok; float* pre_lp;               // [R][P] pre-beam: the P best tokens by logit, their attention log-probs
+    int* list_slot; float* list_psi;           // [R][P] beside list_tok / list_score: the candidate's chain slot and prefix score
 };
 int mk_beam_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s);
 int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
 int mk_beam_select(const BeamArgs& a, hipStream_t s);                    // also advances step[0] once all B utterances are done
 int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
+// joint CTC/attention beam (beam.hip): logits [B*Tp][ld] of the CTC head -> a.ctc_lp; the empty hypothesis's CTC state (after mk_beam_init);
+// per step the pre-beam, the prefix scores with the row sort, and the joint select (in place of mk_beam_row_topk / mk_beam_select)
+int mk_beam_ctc_logsoftmax(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
+int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s);
+int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
+int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
+int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s);                // also advances step[0]
 
 // ---------------------------------------------------------------- row ops (rowops.hip)
 int mk_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y32, bf16* y16,

@@ -254,27 +254,37 @@ class MasrEngine:
             out.append((min(ml, 3000), max(0, math.floor(rmin * enc))))
         return out
 
-    def recog_beam(self, xs: torch.Tensor, ilens, beam_size: int, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
+    def recog_beam(self, xs: torch.Tensor, ilens, beam_size: int, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0,
+                   att_weight: float = 1.0, ctc_weight: float = 0.0):
         """beam search (masr_recog_beam): returns (list of B token lists without sos / eos, fp32 scores [B] on the host).
-        K = beam_size in [1, 64]; an utterance's result does not depend on the rest of its batch."""
+        K = beam_size in [1, 64]; an utterance's result does not depend on the rest of its batch.  ctc_weight != 0 runs the joint
+        CTC/attention search (masr_recog_beam_ctc: needs a hybrid model, ctc_weight > 0, att_weight >= 0); with ctc_weight == 0 the
+        attention decoder alone decides and att_weight is not used."""
         K = int(beam_size)
         if not 1 <= K <= 64:
             raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        joint = float(ctc_weight) != 0.0
         if xs.device != self.device:
             xs = xs.to(self.device, non_blocking=True)
         xs = xs.contiguous().float()
         B, T, D = xs.shape
         il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
         Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
-        need = int(self._l.masr_beam_workspace_bytes(self.h, B, T, K, Lmax))
-        check(need if need < 0 else 0, "masr_beam_workspace_bytes")
+        ws_fn = "masr_beam_ctc_workspace_bytes" if joint else "masr_beam_workspace_bytes"
+        need = int(getattr(self._l, ws_fn)(self.h, B, T, K, Lmax))
+        check(need if need < 0 else 0, ws_fn)
         self._ensure_ws_bytes(need)
         self.refresh()
         tok = torch.empty(B, Lmax, dtype=torch.int32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
         scores = torch.empty(B, dtype=torch.float32, device=self.device)
-        check(self._l.masr_recog_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
-                                      _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam")
+        if joint:
+            check(self._l.masr_recog_beam_ctc(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
+                                              float(att_weight), float(ctc_weight), _ptr(tok), _ptr(lens), _ptr(scores), self.stream()),
+                  "masr_recog_beam_ctc")
+        else:
+            check(self._l.masr_recog_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
+                                          _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam")
         self._last_x = xs
         tok, lens = tok.cpu(), lens.cpu()
         return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()

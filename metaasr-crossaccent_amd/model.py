@@ -109,7 +109,8 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog(xs_pad, ilens)
 
-    def beam_decode(self, xs_pad, ilens, beam_size, min_step_ratio=0.0, max_step_ratio=1.0):
-        """beam search (masr_recog_beam; the reference has none for this model): (B token lists without sos / eos, scores [B])"""
+    def beam_decode(self, xs_pad, ilens, beam_size, min_step_ratio=0.0, max_step_ratio=1.0, att_weight=1.0, ctc_weight=0.0):
+        """beam search (masr_recog_beam, or masr_recog_beam_ctc when ctc_weight != 0; the reference has none for this model):
+        (B token lists without sos / eos, scores [B])"""
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
-        return self.engine.recog_beam(xs_pad, ilens, beam_size, min_step_ratio, max_step_ratio)
+        return self.engine.recog_beam(xs_pad, ilens, beam_size, min_step_ratio, max_step_ratio, att_weight, ctc_weight)

@@ -3,7 +3,11 @@ Line format "<ref ids> TAB <hyp ids>" (space separated), `trim` = cut at the fir
 translate.py / score.sh of the reference run on these files as they are.  Only the transformer + greedy path exists in
 the reference for this model (beam search raises NotImplementedError there, tester.py:121-124); `--decode_mode beam` with the
 transformer runs this project's GPU beam search (masr_recog_beam) with the config's solver.beam_decode block and writes the
-best hypothesis of each utterance in the same line format."""
+best hypothesis of each utterance in the same line format.  On a hybrid model (asr_model.ctc_weight > 0) a block with ctc_w > 0 runs
+the joint CTC/attention search (masr_recog_beam_ctc) with att_w (default 1 - ctc_w) and ctc_w.  The weights are checked on every model,
+hybrid or plain, before anything is decoded: a negative or non-finite ctc_w or att_w raises ValueError, and so does ctc_w > 1 without an
+att_w (the default 1 - ctc_w is then negative).  A plain model with valid weights decodes as before and logs that they are ignored."""
+import math
 from pathlib import Path
 from shutil import rmtree
 
@@ -101,7 +105,8 @@ class Tester:
             fout.write("{}\t{}\n".format(" ".join(str(i) for i in y), " ".join(str(i) for i in hyp)))
 
     def batch_beam_decode(self, xs, ilens, ys, olens):
-        hyps, _ = self.asr_model.beam_decode(xs, ilens, self.beam_size, self.min_step_ratio, self.max_step_ratio)
+        hyps, _ = self.asr_model.beam_decode(xs, ilens, self.beam_size, self.min_step_ratio, self.max_step_ratio,
+                                             self.att_weight, self.ctc_weight)
         for hyp, y in zip(hyps, ys):
             self.write_hyp(y.tolist(), hyp)
         return True
@@ -120,12 +125,28 @@ class Tester:
             raise ValueError(f"solver.beam_decode.beam_size must be in [1, 64], got {self.beam_size}")
         self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
         self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
-        if 'att_w' in bd:
-            if self.asr_model.engine.ctc_weight > 0.0:
-                logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: joint CTC/attention decoding is not built, this model's CTC head "
-                              "is used in training only and the beam runs on the attention decoder alone")
-            else:
+        ctc_w = self._weight(bd, 'ctc_w', 0.0)
+        att_w = self._weight(bd, 'att_w', 1.0 - ctc_w)
+        self.att_weight, self.ctc_weight = 1.0, 0.0                 # attention decoder alone (masr_recog_beam)
+        if self.asr_model.engine.ctc_weight > 0.0:
+            if ctc_w > 0.0:
+                self.att_weight, self.ctc_weight = att_w, ctc_w
+                logger.notice(f"Joint CTC/attention beam decoding: att_w = {att_w}, ctc_w = {ctc_w}")
+            elif 'att_w' in bd:
+                logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: beam_decode.ctc_w is absent or 0, so the beam runs on the "
+                              "attention decoder alone and this model's CTC head is not used")
+        else:
+            if ctc_w > 0.0:
+                logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
+            if 'att_w' in bd:
                 logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: this model has no CTC head to weigh against the attention decoder")
+
+    @staticmethod
+    def _weight(bd, key, default):
+        w = float(bd.get(key, default))
+        if not math.isfinite(w) or w < 0.0:
+            raise ValueError(f"solver.beam_decode.{key} must be finite and >= 0, got {bd.get(key, default)}")
+        return w
 
     def exec(self):
         if self.decode_mode not in ('greedy', 'beam', 'lm_beam'):
