@@ -44,6 +44,29 @@ int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int
 int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
                          const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
                          int32_t* list_slot, float* out_state, void* stream);
+/* the decode's one-query attention (decode.hip attn_decode_kernel, every self- and cross-attention of masr_recog / masr_recog_beam) with
+ * every field of its launch: q [B][ldq], head h at column h*hd; cache k / v + b*kv_batch_stride + j*ldk + h*hd; the key count is the
+ * device scalar *step (self-attention: knew / vnew [B][ldnew] are the newest row, appended to the cache at slot *step - 1) or klens [B]
+ * (cross-attention; rows_per_utt > 1: row b reads cache row / klens entry b / rows_per_utt); src (with step only): key j of row b lives in
+ * cache row src[(klen & 1) * src_flip + b * ld_src + j].  o bf16 [B][ldo].  Reads the key counts and the src entries back first and
+ * refuses a key count outside [1, Tk_cap] or a src entry outside the cache rows; synchronises the stream. */
+int masr_test_attn_decode(const uint16_t* q, int64_t ldq, const uint16_t* k, const uint16_t* v, int64_t ldk, int64_t kv_batch_stride,
+                          const uint16_t* knew, const uint16_t* vnew, int64_t ldnew, const int32_t* step, const int32_t* klens, uint16_t* o,
+                          int64_t ldo, int B, int H, int hd, int Tk_cap, int rows_per_utt, const int32_t* src, int64_t ld_src, int64_t src_flip,
+                          void* stream);
+/* the greedy decode's fp32 last projection (decode.hip logits_f32_kernel): z [rows][ld] = bias [C] + y32 [rows][E] W32 [C][E]^T; 16-byte
+ * loads when y32 and W32 are both 16-byte aligned, 4-byte loads otherwise */
+int masr_test_logits_f32(const float* y32, const float* W32, const float* bias, float* z, int64_t ld, int rows, int C, int E, void* stream);
+/* the greedy decode's arg-max (decode.hip recog_argmax_step_kernel): out[(step[0] - 1) * B + b] = first maximal index of logits [b][:C]
+ * (0 when no value is above -inf); the last row to finish sets step = {step[0] + 1, 0}.  step int32 [2] on the device */
+int masr_test_recog_argmax_step(int32_t* step, const float* logits, int64_t ld, int32_t* out, int B, int C, void* stream);
+/* one step t of the beam search's glue (beam.hip beam_row_topk_kernel + beam_select_kernel<false>) on R = B*K rows of caller-given fp32
+ * logits [R][ld].  In: minlen / maxlen [B].  In and out: score [R], fin [B], best_score / best_len / best_row [B], and row t-1 of the
+ * token / parent history tok_hist_row / par_hist_row [R] (the entries the step does not write keep the caller's values).  Out: the rows'
+ * lists list_tok / list_score [R][K] and the step pair step_out int32 [2].  All arrays on the device; synchronises the stream. */
+int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int32_t* minlen, const int32_t* maxlen, const float* logits,
+                        int64_t ld, float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* list_tok,
+                        float* list_score, int32_t* tok_hist_row, int32_t* par_hist_row, int32_t* step_out, void* stream);
 /* the operand-shadow pass of masr_refresh on ONE Linear weight: W fp32 [N][K] at P + src (P 16-byte aligned, src any dword offset >= 4 with at
  * least four floats of P behind the tensor -- in the flat parameter buffer the shadowed tensors are neither first nor last) -> k16 bf16 [N][K]
  * and its transpose t16 bf16 [K][ldt] (ldt >= N; the pads of a row stay untouched) */

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void recog_argmax_step_kernel(int* step, const
     __shared__ float smx[4]; __shared__ int sam[4];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* z = logits + (long)b * ld;
-    float mx = -3.4e38f; int am = 0x7fffffff;
+    float mx = -INFINITY; int am = 0x7fffffff;             // (not -3.4e38f: a row whose only finite value is -FLT_MAX must return its index)
     for (int c = threadIdx.x; c < C; c += 256) { const float v = z[c]; if (v > mx) { mx = v; am = c; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

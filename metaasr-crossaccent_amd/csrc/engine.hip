@@ -1631,6 +1631,85 @@ int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* p
     hipFree(w);
     return rc;
 }
+int masr_test_attn_decode(const uint16_t* q, int64_t ldq, const uint16_t* k, const uint16_t* v, int64_t ldk, int64_t kv_batch_stride,
+                          const uint16_t* knew, const uint16_t* vnew, int64_t ldnew, const int32_t* step, const int32_t* klens, uint16_t* o,
+                          int64_t ldo, int B, int H, int hd, int Tk_cap, int rows_per_utt, const int32_t* src, int64_t ld_src, int64_t src_flip,
+                          void* stream) {
+    const char* fn = "masr_test_attn_decode";
+    if (!q || !k || !v || !o || !step == !klens || !knew != !vnew || (src && !step)) {
+        mk_set_error(fn, "null pointer (exactly one of step / klens; knew and vnew together; src with step only)"); return -1;
+    }
+    if (B < 1 || H < 1 || Tk_cap < 1 || rows_per_utt < 0 || (src && (ld_src < 0 || src_flip < 0))) { mk_set_error(fn, "bad sizes"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    // the rows of the key/value cache the launch can address: row b reads cache row b, or b / rows_per_utt
+    const int ncache = rows_per_utt > 1 ? (B + rows_per_utt - 1) / rows_per_utt : B;
+    std::vector<int> kl(ncache);
+    if (step) HIP_CHECK_RET(hipMemcpyAsync(kl.data(), step, sizeof(int), hipMemcpyDeviceToHost, s));
+    else HIP_CHECK_RET(hipMemcpyAsync(kl.data(), klens, sizeof(int) * ncache, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if (step) std::fill(kl.begin(), kl.end(), kl[0]);
+    for (int n : kl) if (n < 1 || n > Tk_cap) { mk_set_error(fn, "key count outside [1, Tk_cap]"); return -1; }
+    if (src) {                                               // every slot-table entry the launch reads must name a cache row
+        std::vector<int> row;
+        for (int b = 0; b < B; ++b) {
+            const int n = kl[rows_per_utt > 1 ? b / rows_per_utt : b];
+            row.resize(n);
+            HIP_CHECK_RET(hipMemcpy(row.data(), src + (n & 1) * src_flip + (long)b * ld_src, sizeof(int) * n, hipMemcpyDeviceToHost));
+            for (int j = 0; j < n - (knew ? 1 : 0); ++j) if (row[j] < 0 || row[j] >= ncache) { mk_set_error(fn, "src entry outside the cache rows"); return -1; }
+        }
+    }
+    AttnDecodeArgs a{};
+    a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldk = ldk; a.kv_batch_stride = kv_batch_stride;
+    a.knew = (const bf16*)knew; a.vnew = (const bf16*)vnew; a.ldnew = ldnew; a.step = step; a.klens = klens; a.o = (bf16*)o; a.ldo = ldo;
+    a.B = B; a.H = H; a.hd = hd; a.Tk_cap = Tk_cap; a.rows_per_utt = rows_per_utt; a.src = src; a.ld_src = ld_src; a.src_flip = src_flip;
+    return mk_attn_decode(a, s);
+}
+int masr_test_logits_f32(const float* y32, const float* W32, const float* bias, float* z, int64_t ld, int rows, int C, int E, void* stream) {
+    if (!y32 || !W32 || !bias || !z || C < 1 || ld < C) { mk_set_error("masr_test_logits_f32", "null pointer, C < 1 or ld < C"); return -1; }
+    return mk_logits_f32(y32, W32, bias, z, ld, rows, C, E, (hipStream_t)stream);
+}
+int masr_test_recog_argmax_step(int32_t* step, const float* logits, int64_t ld, int32_t* out, int B, int C, void* stream) {
+    if (!step || !logits || !out || B < 1 || C < 1 || ld < C) { mk_set_error("masr_test_recog_argmax_step", "null pointer, B < 1, C < 1 or ld < C"); return -1; }
+    return mk_recog_argmax_step(step, logits, ld, out, B, C, (hipStream_t)stream);
+}
+int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int32_t* minlen, const int32_t* maxlen, const float* logits,
+                        int64_t ld, float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* list_tok,
+                        float* list_score, int32_t* tok_hist_row, int32_t* par_hist_row, int32_t* step_out, void* stream) {
+    const char* fn = "masr_test_beam_step";
+    if (!minlen || !maxlen || !logits || !score || !fin || !best_score || !best_len || !best_row || !list_tok || !list_score ||
+        !tok_hist_row || !par_hist_row || !step_out) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
+    if (B < 1 || C < 1 || t < 1 || ld < C || sos < 0 || sos >= C || eos < 0 || eos >= C) { mk_set_error(fn, "need B, C, t >= 1, ld >= C, sos / eos < C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    const size_t hist = (size_t)t * R * sizeof(int);
+    int* w = nullptr;                                        // step[2] | tok_hist [t][R] | par_hist [t][R]
+    HIP_CHECK_RET(hipMalloc(&w, 64 + 2 * hist));
+    int* tok_hist = w + 16;
+    int* par_hist = tok_hist + (size_t)t * R;
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = sos; a.eos = eos; a.maxlen = maxlen; a.minlen = minlen;
+    a.tok_hist = tok_hist; a.par_hist = par_hist; a.score = score; a.list_tok = list_tok; a.list_score = list_score; a.fin = fin;
+    a.best_score = best_score; a.best_len = best_len; a.best_row = best_row;
+    auto run = [&]() -> int {                                // row t-1 of the history starts as the caller's, so untouched entries show
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_row_topk(a, logits, ld, s));
+        CK(mk_beam_select(a, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
 int masr_test_linear_shadows(const float* P, int64_t src, int N, int K, int ldt, uint16_t* k16, uint16_t* t16, void* stream) {
     if (N <= 0 || K <= 0 || ldt < N || src < 4) { mk_set_error("masr_test_linear_shadows", "N, K > 0, ldt >= N, src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }
     ShadowJobs jobs{};
