@@ -67,6 +67,32 @@ int masr_test_recog_argmax_step(int32_t* step, const float* logits, int64_t ld, 
 int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int32_t* minlen, const int32_t* maxlen, const float* logits,
                         int64_t ld, float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* list_tok,
                         float* list_score, int32_t* tok_hist_row, int32_t* par_hist_row, int32_t* step_out, void* stream);
+/* ---- the training step's row kernels alone (tests/test_hip_train_row_kernels.py).  Each entry vets on the host what the kernel would index
+ * with, fills the launcher's arguments and calls it; all arrays on the device.
+ * The loss head (rowops.hip ls_ce_kernel + ls_ce_reduce, mk_ls_ce): logits fp32 [rows][ld], gold int32 [rows] (a class, or -1 = not counted) ->
+ * dlogits bf16 [rows][ld] (pad columns C .. ld and rows with gold -1: zero), row_loss fp32 [rows], row_correct int32 [rows], stats fp32 [3] =
+ * {loss sum * inv_ntotal, number correct, n_total}.  inv_ntotal_ptr (optional, device): read instead of the by-value inv_ntotal, as a replayed
+ * step graph does.  grad_w scales dlogits only.  Reads gold back first and refuses ld < C, rows < 1 and a gold value outside [-1, C). */
+int masr_test_ls_ce(const float* logits, int64_t ld, const int32_t* gold, int rows, int C, float eps, float inv_ntotal, const float* inv_ntotal_ptr,
+                    float grad_w, uint16_t* dlogits, float* row_loss, int32_t* row_correct, float* stats, void* stream);
+/* embedding + positional encoding + positional dropout (rowops.hip embed_fwd_kernel): tok int32 [B][L], table fp32 [V][E], pe fp32 [>= L][E] ->
+ * y32 / y16 [B][L][E] = (table[tok] + pe[l]) * keep-scale of element (b L + l) E + e at `site`; seed_ptr (optional, device) is read instead of
+ * seed.  Refuses a token outside [0, V). */
+int masr_test_embed_fwd(const int32_t* tok, const float* table, const float* pe, float* y32, uint16_t* y16, int B, int L, int E, int V, float drop_p,
+                        uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream);
+/* its backward (folds.h embed_bwd_body): dtable [V][E] (+)= the sum over the positions i that hold token v of dy [n][E] row i times the keep-scale
+ * of element i E + col.  Takes the tokens tok int32 [n] and groups the positions by token on the host with the helper masr_run_batch uses.
+ * Refuses a token outside [0, V) and E % 64 != 0; synchronises the stream. */
+int masr_test_embed_bwd(const int32_t* tok, int n, const float* dy, float* dtable, int V, int E, int accumulate, float drop_p, uint32_t seed,
+                        uint32_t site, const uint32_t* seed_ptr, void* stream);
+/* y bf16 [n] = bf16(x [n] * keep-scale of element i at `site`) (rowops.hip cast_dropout_kernel: the encoder output gradient on its way to the VGG) */
+int masr_test_cast_dropout(const float* x, uint16_t* y, int64_t n, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream);
+/* vgg2enc's weight gradient from the engine's feature order back to the reference's (folds.h vgg2enc_unpermute_body):
+ * dw [E][C][Dp] <- g [E][Dp][C] */
+int masr_test_vgg2enc_grad_unpermute(const float* g, float* dw, int E, int C, int Dp, void* stream);
+/* the arg-max of the full-sequence greedy decode (rowops.hip recog_argmax_kernel): out int32 [L][B], out[l][b] = first maximal index of logits fp32 [b L + l][:C]
+ * (row stride ld; 0 when no value is above -inf) */
+int masr_test_recog_argmax(const float* logits, int64_t ld, int32_t* out, int B, int L, int C, void* stream);
 /* the operand-shadow pass of masr_refresh on ONE Linear weight: W fp32 [N][K] at P + src (P 16-byte aligned, src any dword offset >= 4 with at
  * least four floats of P behind the tensor -- in the flat parameter buffer the shadowed tensors are neither first nor last) -> k16 bf16 [N][K]
  * and its transpose t16 bf16 [K][ldt] (ldt >= N; the pads of a row stay untouched) */

@@ -108,6 +108,12 @@ _SIGS = {
     "masr_test_logits_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "masr_test_recog_argmax_step": (i32, [vp, vp, i64, vp, i32, i32, vp]),
     "masr_test_beam_step": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_ls_ce": (i32, [vp, i64, vp, i32, i32, f32, f32, vp, f32, vp, vp, vp, vp, vp]),
+    "masr_test_embed_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp, vp]),
+    "masr_test_embed_bwd": (i32, [vp, i32, vp, vp, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp, vp]),
+    "masr_test_cast_dropout": (i32, [vp, vp, i64, f32, C.c_uint32, C.c_uint32, vp, vp]),
+    "masr_test_vgg2enc_grad_unpermute": (i32, [vp, vp, i32, i32, i32, vp]),
+    "masr_test_recog_argmax": (i32, [vp, i64, vp, i32, i32, i32, vp]),
     "masr_test_linear_shadows": (i32, [vp, i64, i32, i32, i32, vp, vp, vp]),
     "masr_test_conv1_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "masr_test_conv3x3": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),

@@ -945,6 +945,20 @@ static int backward(Ctx& c, const float* xs) {
     return 0;
 }
 
+// The positions of tok [B][L] grouped by token id for the embedding backward (mk_embed_bwd): order[start[v] .. start[v + 1]) = the positions
+// b * L + l that hold token v, ascending (a stable counting sort); start has V + 1 entries.  Of row b the positions 0 .. olens[b] count (all L
+// when olens is null).  Every token must lie in [0, V).
+static void group_positions_by_token(const int* tok, int B, int L, const int64_t* olens, int V, int* order, int* start) {
+    auto cnt = [&](int b) { return olens ? (int)olens[b] + 1 : L; };
+    for (int v = 0; v <= V; ++v) start[v] = 0;
+    for (int b = 0; b < B; ++b) for (int l = 0; l < cnt(b); ++l) start[tok[b * L + l] + 1]++;
+    for (int v = 0; v < V; ++v) start[v + 1] += start[v];
+    // (fill with a running cursor kept in the start array itself, then shift it back)
+    for (int b = 0; b < B; ++b) for (int l = 0; l < cnt(b); ++l) order[start[tok[b * L + l]]++] = b * L + l;
+    for (int v = V; v > 0; --v) start[v] = start[v - 1];
+    start[0] = 0;
+}
+
 int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const int64_t* ys_flat, const int64_t* olens, int B, int T,
                    int flags, void* stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -1003,13 +1017,7 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
         // that a single workgroup column would sum for nothing.
         int* h_order = h_len + B + 8; int* h_start = h_order + (int64_t)B * L;
         const int V = m->C;
-        for (int v = 0; v <= V; ++v) h_start[v] = 0;
-        for (int b = 0; b < B; ++b) for (int l = 0; l <= (int)olens[b]; ++l) h_start[h_in[b * L + l] + 1]++;
-        for (int v = 0; v < V; ++v) h_start[v + 1] += h_start[v];
-        // (fill with a running cursor kept in the start array itself, then shift it back)
-        for (int b = 0; b < B; ++b) for (int l = 0; l <= (int)olens[b]; ++l) h_order[h_start[h_in[b * L + l]]++] = b * L + l;
-        for (int v = V; v > 0; --v) h_start[v] = h_start[v - 1];
-        h_start[0] = 0;
+        group_positions_by_token(h_in, B, L, olens, V, h_order, h_start);
         if (hybrid) {
             // CTC targets: the labels of utterance b are the first olens[b] entries of its gold row (behind them: eos, then -1).  Every
             // 2 olen + 1 fits the lattice the work buffer holds (2 max olen + 1); olen > enc_len is left to zero_infinity
@@ -1709,6 +1717,73 @@ int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int3
     const int rc = run();
     hipFree(w);
     return rc;
+}
+// ---- the training step's row kernels alone (tests/test_hip_train_row_kernels.py): each entry vets what the kernel would index with, fills the
+// launcher's arguments and calls it
+static int test_read_ints(const int32_t* dev, size_t n, std::vector<int>& host, hipStream_t s) {
+    host.resize(n);
+    HIP_CHECK_RET(hipMemcpyAsync(host.data(), dev, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_ls_ce(const float* logits, int64_t ld, const int32_t* gold, int rows, int C, float eps, float inv_ntotal, const float* inv_ntotal_ptr,
+                    float grad_w, uint16_t* dlogits, float* row_loss, int32_t* row_correct, float* stats, void* stream) {
+    const char* fn = "masr_test_ls_ce";
+    if (!logits || !gold || !dlogits || !row_loss || !row_correct || !stats) { mk_set_error(fn, "null pointer"); return -1; }
+    if (rows < 1 || C < 1 || ld < C) { mk_set_error(fn, "need rows >= 1, C >= 1, ld >= C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hg;
+    CK(test_read_ints(gold, (size_t)rows, hg, s));
+    for (int g : hg) if (g < -1 || g >= C) { mk_set_error(fn, "gold must lie in [0, C) or be -1"); return -1; }
+    return mk_ls_ce(logits, ld, gold, rows, C, eps, inv_ntotal, (bf16*)dlogits, row_loss, row_correct, stats, s, inv_ntotal_ptr, grad_w);
+}
+int masr_test_embed_fwd(const int32_t* tok, const float* table, const float* pe, float* y32, uint16_t* y16, int B, int L, int E, int V, float drop_p,
+                        uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    const char* fn = "masr_test_embed_fwd";
+    if (!tok || !table || !pe || !y32 || !y16) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B < 1 || L < 1 || E < 1 || V < 1 || !(drop_p >= 0.f && drop_p < 1.f)) { mk_set_error(fn, "need B, L, E, V >= 1 and 0 <= drop_p < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ht;
+    CK(test_read_ints(tok, (size_t)B * L, ht, s));
+    for (int t : ht) if (t < 0 || t >= V) { mk_set_error(fn, "token outside [0, V)"); return -1; }
+    return mk_embed_fwd(tok, table, pe, y32, (bf16*)y16, B, L, E, drop_p, seed, site, s, seed_ptr);
+}
+int masr_test_embed_bwd(const int32_t* tok, int n, const float* dy, float* dtable, int V, int E, int accumulate, float drop_p, uint32_t seed,
+                        uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    const char* fn = "masr_test_embed_bwd";
+    if (!tok || !dy || !dtable) { mk_set_error(fn, "null pointer"); return -1; }
+    if (n < 1 || V < 1 || E < 1 || !(drop_p >= 0.f && drop_p < 1.f)) { mk_set_error(fn, "need n, V, E >= 1 and 0 <= drop_p < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ht;
+    CK(test_read_ints(tok, (size_t)n, ht, s));
+    for (int t : ht) if (t < 0 || t >= V) { mk_set_error(fn, "token outside [0, V)"); return -1; }
+    std::vector<int> sorted((size_t)n + V + 1);                // order [n] | start [V + 1], as masr_run_batch stages them
+    group_positions_by_token(ht.data(), 1, n, nullptr, V, sorted.data(), sorted.data() + n);
+    int* d = nullptr;
+    HIP_CHECK_RET(hipMalloc(&d, sizeof(int) * sorted.size()));
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(d, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice, s));
+        CK(mk_embed_bwd(d, d + n, dy, dtable, V, E, accumulate, drop_p, seed, site, s, seed_ptr));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(d);
+    return rc;
+}
+int masr_test_cast_dropout(const float* x, uint16_t* y, int64_t n, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    if (!x || !y || n < 1 || n > 0x7fffffffL || !(drop_p >= 0.f && drop_p < 1.f)) {
+        mk_set_error("masr_test_cast_dropout", "null pointer, n outside [1, 2^31) or drop_p outside [0, 1)"); return -1;
+    }
+    return mk_cast_dropout(x, (bf16*)y, (long)n, drop_p, seed, site, (hipStream_t)stream, seed_ptr);
+}
+int masr_test_vgg2enc_grad_unpermute(const float* g, float* dw, int E, int C, int Dp, void* stream) {
+    if (!g || !dw || E < 1 || C < 1 || Dp < 1) { mk_set_error("masr_test_vgg2enc_grad_unpermute", "null pointer or E, C, Dp < 1"); return -1; }
+    return mk_vgg2enc_grad_unpermute(g, dw, E, C, Dp, (hipStream_t)stream);
+}
+int masr_test_recog_argmax(const float* logits, int64_t ld, int32_t* out, int B, int L, int C, void* stream) {
+    if (!logits || !out || B < 1 || L < 1 || C < 1 || ld < C) { mk_set_error("masr_test_recog_argmax", "null pointer, B, L, C < 1 or ld < C"); return -1; }
+    return mk_recog_argmax(logits, ld, out, B, L, C, (hipStream_t)stream);
 }
 int masr_test_linear_shadows(const float* P, int64_t src, int N, int K, int ldt, uint16_t* k16, uint16_t* t16, void* stream) {
     if (N <= 0 || K <= 0 || ldt < N || src < 4) { mk_set_error("masr_test_linear_shadows", "N, K > 0, ldt >= N, src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }

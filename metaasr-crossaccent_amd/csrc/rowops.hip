@@ -294,12 +294,13 @@ __global__ void recog_build_tok_kernel(int* __restrict__ tok, const int* __restr
     const int b = i / L, l = i % L;
     tok[i] = l == 0 ? sos : out[(l - 1) * B + b];
 }
-// out[l][b] = argmax_c logits[b*L + l][c]  (first maximal index, as torch.argmax); one wave per row
+// out[l][b] = argmax_c logits[b*L + l][c]  (first maximal index, as torch.argmax; 0 for a row with nothing above -inf, as
+// recog_argmax_step_kernel); one wave per row
 __global__ __launch_bounds__(256) void recog_argmax_kernel(const float* __restrict__ logits, long ld, int* __restrict__ out, int B, int L, int C) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= B * L) return;
     const float* z = logits + (long)row * ld;
-    float mx = -3.4e38f; int am = 0;
+    float mx = -INFINITY; int am = 0;                        // (not -3.4e38f: a row whose only value above -inf is -FLT_MAX must return its index)
     for (int c = lane; c < C; c += 64) { const float v = z[c]; if (v > mx) { mx = v; am = c; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(256) void ls_ce_kernel(const float* __restrict__ lo
     if (row >= rows) return;
     const float* z = logits + (long)row * ld;
     const int g = gold[row];
-    float mx = -3.4e38f; int amax = 0;
+    float mx = -INFINITY; int amax = 0;                      // (as recog_argmax_kernel)
     for (int c = lane; c < C; c += 64) { const float v = z[c]; if (v > mx) { mx = v; amax = c; } }
     // wave arg-max, ties -> lowest index (torch max(1) returns the first maximal index on CPU)
 #pragma unroll
@@ -343,7 +344,8 @@ __global__ __launch_bounds__(256) void ls_ce_kernel(const float* __restrict__ lo
         if (valid) {
             const float sum_logp = sz - C * lse;                         // sum_c logp_c
             const float lg = z[g] - lse;
-            loss = -((on - off) * lg + off * sum_logp);
+            // eps == 0: the gold term alone -- 0 * sum_logp would be NaN for a row that holds a -inf logit, where plain CE is finite
+            loss = off > 0.f ? -((on - off) * lg + off * sum_logp) : -lg;
         }
         row_loss[row] = loss;
         row_correct[row] = (valid && amax == g) ? 1 : 0;
