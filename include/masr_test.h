@@ -137,7 +137,7 @@ int64_t masr_test_conv3x3_wgrad_slab_floats(int B, int H, int W, int CIN, int CO
  * engine's merged launch -- members [0, first_members) reduce over `rows` rows and are dispatched first, the others over the first rows_rest. */
 int masr_test_wgrad_grouped(const uint16_t* dy, int64_t lddy, const uint16_t* x, int64_t ldx, float* dW, float* db, float* dW2, float* db2,
                             int rows, int N, int K, void* stream);
-/* the k-split GEMM + summing LayerNorm pair of the decoder (engine.hip ffn_fwd / ln_fwd, ffn_bwd / ln_bwd): forward when x == NULL, backward otherwise */
+/* the k-split GEMM + summing LayerNorm pair of the decoder (train.hip ffn_fwd / ffn_bwd / ln_bwd, engine_internal.h ln_fwd): forward when x == NULL, backward otherwise */
 int masr_test_ksplit_ln(const uint16_t* A, const uint16_t* B, int rows, int E, int K, int split, const float* bias, const float* residual, float drop_p,
                         uint32_t seed, uint32_t site, float* part, const float* gamma, const float* beta, float* sum_out, float* y32, uint16_t* y16,
                         float* mean, float* rstd, const float* x, float* dx32, uint16_t* dx16, float* slab, void* stream);

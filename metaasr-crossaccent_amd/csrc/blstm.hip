@@ -3,7 +3,7 @@
 //   1->128->128 pool(ceil) ->256->256 pool(ceil), then RNNP = L x {packed BLSTM(enc_dim), Linear(2 enc_dim -> proj), tanh},
 //   pad frames zeroed) + Linear head, and BLSTMTrainer.run_batch (src/blstm_trainer.py:55-85): targets [sos]+y+[eos] with
 //   sos = eos = odim-1, log_softmax + nn.CTCLoss(blank 0, mean, zero_infinity), backward.
-// Same memory model as engine.hip: one flat fp32 parameter / gradient buffer in the reference's state_dict order, bf16
+// Same memory model as engine.hip (PInfo, Arena: host_util.h): one flat fp32 parameter / gradient buffer in the reference's state_dict order, bf16
 // operand shadows, a bump-allocated activation arena, every kernel on the caller's stream.  Time sub-sampling between layers
 // (encoder.sample_rate, RNNP.forward encoder.py:118-121): layer i's LSTM runs on Ts[i] frames per utterance, its output keeps
 // every sub[i]-th frame before the projection, enc_lens -> (enc_lens + 1) / sub[i].  Dropout 0 per layer (a no-op in the
@@ -15,19 +15,10 @@
 #include "../../include/masr.h"
 #include "../../include/masr_test.h"
 #include "kernels.h"
+#include "host_util.h"
 
 namespace {
 
-struct PInfo { std::string name; int64_t shape[4]; int ndim; int64_t off; int64_t numel; };
-struct Arena {
-    char* base; int64_t cap, off;
-    template <class T> T* get(int64_t n) {
-        const int64_t bytes = (n * (int64_t)sizeof(T) + 255) & ~(int64_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += bytes;
-        return p;
-    }
-};
 struct ConvP { int64_t w, b; int CO, CI; bf16 *k16, *d16; };
 struct LstmDir { int64_t wih, whh, bih, bhh; bf16 *wih16, *wihT16, *whh16, *whhT16; float* bias; };
 struct Layer { LstmDir d[2]; int64_t btw, btb; int K, N; bf16 *bt16, *btT16; };       // K = LSTM input width, N = projection width
@@ -64,8 +55,6 @@ struct masr_blstm {
 };
 
 namespace {
-
-#define CK(expr) do { if ((expr) != 0) return -1; } while (0)
 
 int64_t add_param(masr_blstm* m, const std::string& name, std::initializer_list<int64_t> shape) {
     PInfo p; p.name = name; p.ndim = (int)shape.size(); p.numel = 1;

@@ -348,7 +348,7 @@ int mk_ctc_loss(const float* logits, const int* targets, const int* tgt_off, con
                   int maxS, hipStream_t s, int batch_first = 0);      // batch_first: logits / grad are [B][T][C]
 int mk_ctc_status(const float* work, int T, int B, int maxS, hipStream_t s);     // > 0: (index + 1) of an utterance the CTC launch on `work` refused (bad lengths)
 long mk_ctc_work_floats(int T, int B, int maxS);
-// the transformer's joint CTC/attention objective (engine.hip): logits fp32 [B][T][ld] of the CTC head over the encoder memory, blank 0.
+// the transformer's joint CTC/attention objective (train.hip ctc_forward): logits fp32 [B][T][ld] of the CTC head over the encoder memory, blank 0.
 // stats[0] (the decoder's CE, mk_ls_ce) becomes (1 - w) CE + w CTC; grad16 (null: forward only) = w * d CTC / d logits as bf16 [B][T][ld],
 // pad columns C .. ld zero.  Lengths are vetted on the host by the caller (no mk_ctc_status on this path).
 int mk_ctc_loss_joint(const float* logits, long ld, const int* targets, const int* tgt_off, const int* in_len, const int* tgt_len, int T, int B,

@@ -1,0 +1,311 @@
+// libmasr engine, the decoders (MyTransformer.recog, mono_transformer_torch.py:143-176, and the beam searches of beam.hip): the
+// literal whole-prefix re-decode, the KV-cached greedy decode, the attention beam and the joint CTC/attention beam.  Each of the
+// last three captures the launch sequence of ONE step into a hipGraph of its own and replays it once per step (run_steps).
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include <algorithm>
+
+#include "engine_internal.h"
+
+// The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
+// a.y32[0] / a.y16[0], output a.y32[ND].  Self-attention keys/values of earlier positions live in d.qkv ([rows][slots][3E]);
+// src (beam) maps row r's key j to the cache row that holds it; cross-attention row r reads utterance r / rows_per_utt.
+struct DecStepGeom { int rows, slots, rows_per_utt; bf16* step_qkv; const int* src; long src_flip; };
+static int decode_layers(Ctx& c, const DecStepGeom& gm) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
+    const int E = m->E, Fi = m->Fi, B = gm.rows;
+    auto lin = [&](const bf16* x, long ldx, const bf16* wk, int N, int K, const float* bias) {
+        SkinnyArgs g{}; g.A = x; g.lda = ldx; g.W = wk; g.ldw = K; g.M = B; g.N = N; g.K = K; g.bias = bias; return g;
+    };
+    auto att = [&]() { AttnDecodeArgs t{}; t.B = B; t.H = m->H; t.hd = m->hd; t.ldo = E; return t; };
+    for (int l = 0; l < m->ND; ++l) {
+        DecAct& d = a.dec[l]; const DecL& w = m->dec[l];
+        // causal self-attention: keys/values of earlier positions live in d.qkv ([B][Ldec][3E], the layout of the full decode)
+        SkinnyArgs g = lin(a.y16[l], E, w.sa.in.k16, 3 * E, E, P + w.sa.in.b); g.C16 = gm.step_qkv; g.ldc16 = 3 * E;
+        CK(mk_skinny_gemm(g, s));
+        AttnDecodeArgs t = att();
+        t.q = gm.step_qkv; t.ldq = 3 * E; t.k = d.qkv + E; t.v = d.qkv + 2 * E; t.ldk = 3 * E; t.kv_batch_stride = (long)gm.slots * 3 * E;
+        t.knew = gm.step_qkv + E; t.vnew = gm.step_qkv + 2 * E; t.ldnew = 3 * E; t.step = a.step_dev; t.o = d.ao; t.Tk_cap = gm.slots;
+        t.src = gm.src; t.ld_src = gm.slots; t.src_flip = gm.src_flip;
+        CK(mk_attn_decode(t, s));
+        g = lin(d.ao, E, w.sa.out.k16, E, E, P + w.sa.out.b); g.residual = a.y32[l]; g.ldres = E; g.C32 = d.s1; g.ldc = E;
+        CK(mk_skinny_gemm(g, s));
+        CK(ln_fwd(c, w.n1, d.s1, d.y1_32, d.y1_16, d.m1, d.r1, B));
+        // cross-attention over the encoder memory: d.kv was projected once, before the first step
+        g = lin(d.y1_16, E, w.ca.q_k16, E, E, P + w.ca.in.b); g.C16 = d.q; g.ldc16 = E;
+        CK(mk_skinny_gemm(g, s));
+        t = att();
+        t.q = d.q; t.ldq = E; t.k = d.kv; t.v = d.kv + E; t.ldk = m->NK; t.kv_batch_stride = (long)a.Tp * m->NK;
+        t.klens = a.enc_lens; t.o = d.co; t.Tk_cap = a.Tp; t.rows_per_utt = gm.rows_per_utt;
+        CK(mk_attn_decode(t, s));
+        g = lin(d.co, E, w.ca.out.k16, E, E, P + w.ca.out.b); g.residual = d.y1_32; g.ldres = E; g.C32 = d.s2; g.ldc = E;
+        CK(mk_skinny_gemm(g, s));
+        CK(ln_fwd(c, w.n2, d.s2, d.y2_32, d.y2_16, d.m2, d.r2, B));
+        g = lin(d.y2_16, E, w.l1.k16, Fi, E, P + w.l1.b); g.relu = 1; g.C16 = d.f; g.ldc16 = Fi;
+        CK(mk_skinny_gemm(g, s));
+        g = lin(d.f, Fi, w.l2.k16, E, Fi, P + w.l2.b); g.residual = d.y2_32; g.ldres = E; g.C32 = d.s3; g.ldc = E;
+        CK(mk_skinny_gemm(g, s));
+        CK(ln_fwd(c, w.n3, d.s3, a.y32[l + 1], a.y16[l + 1], d.m3, d.r3, B));
+    }
+    // the last projection in fp32 on the master weights (a selection follows: mk_logits_f32); layer 0's pre-LayerNorm sum is free by now
+    float* yf32 = a.dec[0].s1;
+    CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], yf32, nullptr, a.mdf, a.rdf, B));
+    CK(mk_logits_f32(yf32, P + m->ct.w, P + m->ct.b, a.logits, m->Cp, B, m->C, E, s));
+    return 0;
+}
+
+// One incremental decode step (the newest target position of every utterance) -- SURVEY 8(f).1.  Every launch below has
+// step-independent arguments; the step itself lives in *a.step_dev, so the sequence is captured once and replayed.
+static int decode_step(Ctx& c, int* out) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
+    const int E = m->E, B = a.B;
+    CK(mk_recog_embed_step(a.step_dev, out, P + m->embed_w, m->pe, a.y32[0], a.y16[0], B, E, 0, s));
+    CK(decode_layers(c, DecStepGeom{B, a.L, 1, a.step_qkv, nullptr, 0}));
+    CK(mk_recog_argmax_step(a.step_dev, a.logits, m->Cp, out, B, m->C, s));       // also advances *step_dev
+    return 0;
+}
+
+// `n` decode steps on stream s; step() enqueues the launches of one.  Direct launches on the legacy NULL stream, while profiling, or with
+// MASR_RECOG_NO_GRAPH set (read on every call).  Otherwise the step is captured once per key (key: shape, key_ptr: the buffers its launches
+// were given) into `gc` and replayed n times; a new key waits for the last replay of the old graph before that is destroyed.
+template <class Step>
+static int run_steps(masr_model* m, DecodeGraph& gc, const int (&key)[6], const void* const (&key_ptr)[3], int n, hipStream_t s, const char* fn,
+                     const char* capture_err, Step step) {
+    const bool use_graph = s != nullptr && !m->prof && !getenv("MASR_RECOG_NO_GRAPH");
+    if (!use_graph) {
+        for (int i = 0; i < n; ++i) CK(step());
+        return 0;
+    }
+    const bool hit = gc.exec && !memcmp(key, gc.key, sizeof key) && !memcmp(key_ptr, gc.key_ptr, sizeof key_ptr);
+    if (!hit) {
+        if (gc.done) HIP_CHECK_RET(hipEventSynchronize(gc.done));      // no replay of the old graph in flight
+        else HIP_CHECK_RET(hipEventCreateWithFlags(&gc.done, hipEventDisableTiming));
+        if (gc.exec) { hipGraphExecDestroy(gc.exec); gc.exec = nullptr; }
+        if (gc.graph) { hipGraphDestroy(gc.graph); gc.graph = nullptr; }
+        HIP_CHECK_RET(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int rc = step();
+        const hipError_t e = hipStreamEndCapture(s, &gc.graph);
+        if (rc || e != hipSuccess) { mk_set_error(fn, capture_err); return -1; }
+        HIP_CHECK_RET(hipGraphInstantiate(&gc.exec, gc.graph, nullptr, nullptr, 0));
+        memcpy(gc.key, key, sizeof key); memcpy(gc.key_ptr, key_ptr, sizeof key_ptr);
+    }
+    for (int i = 0; i < n; ++i) HIP_CHECK_RET(hipGraphLaunch(gc.exec, s));
+    HIP_CHECK_RET(hipEventRecord(gc.done, s));
+    return 0;
+}
+
+// shared front half of the two decoders: argument checks, activation plan, enc_lens upload, encoder
+// beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
+// rows, and the beam state follows the activations in the same arena
+// joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
+// log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
+struct BeamPlan { int K, Lmax; BeamArgs* args; bf16** step_qkv; int P = 0, Tp = 0; float** ctc_logits = nullptr; };
+static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp) {
+    const int R = B * bp.K, L = bp.Lmax, W = bp.P ? bp.P : bp.K;
+    BeamArgs& a = *bp.args;
+    a = BeamArgs{};
+    a.B = B; a.K = bp.K; a.R = R; a.Lmax = L; a.C = m->C; a.sos = 0; a.eos = m->C - 1;
+    *bp.step_qkv = ar.get<bf16>((int64_t)R * 3 * m->E);
+    a.tab = ar.get<int>(2 * (int64_t)R * L);
+    a.tok_hist = ar.get<int>((int64_t)L * R); a.par_hist = ar.get<int>((int64_t)L * R);
+    a.score = ar.get<float>(R);
+    a.list_tok = ar.get<int>((int64_t)R * W); a.list_score = ar.get<float>((int64_t)R * W);
+    int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
+    a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
+    if (!bp.P) return;
+    const int P = bp.P, Tp = bp.Tp;
+    a.P = P; a.Tp = Tp;
+    *bp.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    a.ctc_lp = ar.get<float>((int64_t)B * m->C * Tp);
+    a.ctc_state = ar.get<float2>(2 * (int64_t)R * Tp * P);
+    a.psi = ar.get<float>(R); a.src = ar.get<int>(R);
+    a.pre_tok = ar.get<int>((int64_t)R * P); a.pre_lp = ar.get<float>((int64_t)R * P);
+    a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
+}
+
+static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
+                         const BeamPlan* beam = nullptr) {
+    if (!m->P) { mk_set_error("masr_recog", "not bound"); return -1; }
+    if (B <= 0 || T < 4) { mk_set_error("masr_recog", "need B >= 1 and T >= 4"); return -1; }
+    int Ldec = 0;
+    for (int b = 0; b < B; ++b) {
+        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error("masr_recog", "ilens must be in [4, T]"); return -1; }
+        if ((int)(ilens[b] / 4) > Ldec) Ldec = (int)(ilens[b] / 4);
+    }
+    Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : Ldec, false);
+    if (beam) plan_beam(m, ar, B, *beam);
+    if (ar.off > m->ws_bytes) {
+        mk_set_error("masr_recog", !beam ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : beam->P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
+                                             : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
+        return -2;
+    }
+    Acts& a = m->acts; m->have_acts = true;
+    const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
+    HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
+    int* h_len = m->h_stage + (int64_t)slot * m->stage_ints;
+    for (int b = 0; b < B; ++b) h_len[b] = (int)(ilens[b] / 4);
+    HIP_CHECK_RET(hipMemcpyAsync(a.enc_lens, h_len, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(forward_encoder(c, xs));
+    *Ldec_out = Ldec;
+    return 0;
+}
+
+extern "C" {
+
+int masr_recog_full(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream) {
+    // MyTransformer.recog (mono_transformer_torch.py:143-176) literally: the encoder runs once; then, for step = 1 .. max(enc_lens),
+    // the WHOLE prefix [sos, out_0 .. out_{step-2}] is decoded again (no KV cache, exactly as the reference) and every
+    // position's arg-max becomes the new `out`.  The result after the last step is out[Ldec][B].
+    hipStream_t s = (hipStream_t)stream;
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec); if (rc) return rc; }
+    Acts& a = m->acts;
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(project_memory_kv(c));                               // (the memory does not change between steps)
+    for (int step = 1; step <= Ldec; ++step) {
+        a.L = step; a.rows_d = B * step;
+        CK(mk_recog_build_tok(a.tok_in, out, B, step, 0, s));
+        CK(forward_decoder(c, false, true));
+        CK(mk_recog_argmax(a.logits, m->Cp, out, B, step, m->C, s));
+    }
+    m->have_acts = false;                                   // logits/gold views are not meaningful after a decode
+    return 0;
+}
+
+int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream) {
+    // Same token sequences as masr_recog_full with O(L) instead of O(L^2) decoder work: the target mask is causal, so the
+    // re-decode of earlier positions reproduces what is already in `out`; only the newest position is computed per step,
+    // against cached self-attention keys/values and encoder-memory keys/values projected once.  The per-step launch
+    // sequence is captured into a hipGraph and replayed Ldec times (run_steps).
+    hipStream_t s = (hipStream_t)stream;
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec); if (rc) return rc; }
+    Acts& a = m->acts;
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(project_memory_kv(c));
+    CK(mk_recog_step_set(a.step_dev, 1, 0, s));
+    const int key[6] = {B, T, Ldec, 0, 0, 0}; const void* const kp[3] = {m->ws, m->P, out};
+    CK(run_steps(m, m->greedy_graph, key, kp, Ldec, s, "masr_recog", "stream capture of the decode step failed", [&] { return decode_step(c, out); }));
+    m->have_acts = false;
+    return 0;
+}
+
+int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
+    Arena ar{nullptr, 0, 0};
+    Acts a; BeamArgs ba; bf16* sq;
+    plan_acts(m, ar, a, B, T, K * Lmax, false);
+    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq});
+    return m->persist_bytes + ar.off + 4096;
+}
+
+static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
+
+int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_ctc_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error("masr_beam_ctc_workspace_bytes", "the model has no CTC head (masr_create_ctc)"); return -1; }
+    Arena ar{nullptr, 0, 0};
+    Acts a; BeamArgs ba; bf16* sq; float* cl;
+    plan_acts(m, ar, a, B, T, K * Lmax, false);
+    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq, beam_prebeam_width(K), T / 4, &cl});
+    return m->persist_bytes + ar.off + 4096;
+}
+
+// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
+// CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.
+static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
+    CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
+    CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
+    if (ba.P) {
+        CK(mk_beam_ctc_prebeam(ba, a.logits, m->Cp, s));
+        CK(mk_beam_ctc_prefix(ba, s));
+        CK(mk_beam_ctc_select(ba, s));                          // also advances *step_dev
+        return 0;
+    }
+    CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
+    CK(mk_beam_select(ba, s));                                  // also advances *step_dev
+    return 0;
+}
+
+// masr_recog_beam (wts == null) and masr_recog_beam_ctc (wts = {att_w, ctc_w}): the same decode, each with its own cached step graph
+static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                           const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn) {
+    // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
+    // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
+    // weights) and replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
+    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B <= 0) { mk_set_error(fn, "need B >= 1"); return -1; }
+    std::vector<int> mx_len(B), mn_len(B);
+    int Lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error(fn, "ilens must be in [4, T]"); return -1; }
+        const int enc = (int)(ilens[b] / 4);
+        int ml = max_step_ratio <= 0.f ? enc : std::max(1, (int)std::floor((double)max_step_ratio * enc));
+        mx_len[b] = std::min(ml, MASR_PE_ROWS);
+        mn_len[b] = std::max(0, (int)std::floor((double)min_step_ratio * enc));
+        Lmax = std::max(Lmax, mx_len[b]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    BeamArgs ba; bf16* step_qkv = nullptr; float* ctc_logits = nullptr;
+    const BeamPlan bp{K, Lmax, &ba, &step_qkv, wts ? beam_prebeam_width(K) : 0, T / 4, &ctc_logits};
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, &bp); if (rc) return rc; }
+    Acts& a = m->acts;
+    ba.step = a.step_dev;
+    {   // per-utterance maxlen / minlen through the next staging slot (the one behind recog_prepare's enc_lens)
+        const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
+        HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
+        int* h = m->h_stage + (int64_t)slot * m->stage_ints;
+        for (int b = 0; b < B; ++b) { h[b] = mx_len[b]; h[B + b] = mn_len[b]; }
+        HIP_CHECK_RET(hipMemcpyAsync(const_cast<int*>(ba.maxlen), h, sizeof(int) * 2 * (size_t)B, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
+    }
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(project_memory_kv(c));
+    CK(mk_beam_init(ba, s));
+    if (wts) {
+        // once per decode: the CTC head over the memory (training's GEMM: bf16 operands, fp32 logits), its log-softmax per frame, the
+        // empty hypothesis's state
+        ba.att_w = wts[0]; ba.ctc_w = wts[1]; ba.enc_lens = a.enc_lens;
+        GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
+        g.C32 = ctc_logits; g.ldc = m->Cp;
+        CK(gemm(c, g));
+        CK(mk_beam_ctc_logsoftmax(ba, ctc_logits, m->Cp, s));
+        CK(mk_beam_ctc_init(ba, s));
+    }
+    int key[6] = {B, T, K, Lmax, 0, 0}; const void* const kp[3] = {m->ws, m->P, nullptr};
+    if (wts) memcpy(key + 4, wts, 2 * sizeof(float));
+    CK(run_steps(m, wts ? m->joint_graph : m->beam_graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
+                 [&] { return beam_step(c, ba, step_qkv); }));
+    CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
+    m->have_acts = false;
+    return 0;
+}
+
+int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    if (!m) { mk_set_error("masr_recog_beam", "null model"); return -1; }
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, "masr_recog_beam");
+}
+
+int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                        float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // joint CTC/attention beam (beam.hip): the attention beam's search with the CTC prefix score of the head's log-probs
+    const char* fn = "masr_recog_beam_ctc";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
+    if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
+    const float wts[2] = {att_w, ctc_w};
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn);
+}
+
+}  // extern "C"

@@ -1,0 +1,389 @@
+// libmasr: the standalone kernel entry points of include/masr_test.h (parity tests, probes).  Each fills a launcher's argument
+// struct from plain pointers and calls it; none touches a masr_model.
+#include <algorithm>
+#include <vector>
+
+#include "../../include/masr_test.h"
+#include "kernels.h"
+#include "host_util.h"
+
+extern "C" {
+
+int masr_test_gemm(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, int reduction_major, const float* bias,
+                   int relu, float* C32, int64_t ldc, void* stream) {
+    GemmArgs g = gemm_args();
+    g.A = (const bf16*)A; g.lda = lda; g.B = (const bf16*)B; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.reduction_major = reduction_major;
+    g.bias = bias; g.relu = relu; g.C32 = C32; g.ldc = ldc;
+    return mk_gemm(g, (hipStream_t)stream);
+}
+int masr_test_dropout_mask(uint32_t seed, uint32_t site, int64_t n, float p, float* out, void* stream) {
+    return mk_dropout_mask(out, n, p, seed, site, (hipStream_t)stream);
+}
+int masr_test_gemm_dropout(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, float drop_p, uint32_t seed,
+                           uint32_t site, float* C32, int64_t ldc, void* stream) {
+    GemmArgs g = gemm_args();
+    g.A = (const bf16*)A; g.lda = lda; g.B = (const bf16*)B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+    g.drop_p = drop_p; g.seed = seed; g.site = site; g.C32 = C32; g.ldc = ldc;
+    return mk_gemm(g, (hipStream_t)stream);
+}
+int masr_test_attention_dropout(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, float* lse, int B, int H, int Tq, int Tk,
+                                int hd, float drop_p, uint32_t seed, uint32_t site, void* stream) {
+    const long E = (long)H * hd;
+    AttnArgs a{};
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldq = a.ldk = a.ldv = E; a.o = (bf16*)o; a.ldo = E; a.lse = lse;
+    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.drop_p = drop_p; a.seed = seed; a.site = site;
+    return mk_attn_fwd(a, (hipStream_t)stream);
+}
+int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, const float* bias, int relu,
+                       float drop_p, const float* residual, const uint16_t* mask, float* C32, uint16_t* C16, void* stream) {
+    GemmArgs g = gemm_args();
+    g.A = (const bf16*)A; g.lda = lda; g.B = (const bf16*)B; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
+    g.drop_p = drop_p; g.seed = 1; g.site = 2; g.residual = residual; g.ldres = N; g.mask = (const bf16*)mask; g.ldmask = N;
+    g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
+    return mk_gemm(g, (hipStream_t)stream);
+}
+int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,
+                          const float* residual, float* C32, uint16_t* C16, void* stream) {
+    SkinnyArgs g{};
+    g.A = (const bf16*)A; g.lda = lda; g.W = (const bf16*)W; g.ldw = ldw; g.M = M; g.N = N; g.K = K; g.bias = bias; g.relu = relu;
+    g.residual = residual; g.ldres = N; g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
+    return mk_skinny_gemm(g, (hipStream_t)stream);
+}
+int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                         const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
+                         int32_t* list_slot, float* out_state, void* stream) {
+    const char* fn = "masr_test_ctc_prefix";
+    if (!lp || !cand || !att_lp || !list_tok || !list_score || !list_psi || !list_slot || !out_state || (last >= 0 && !parent)) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (C < 2 || T < 1 || n < 1 || n > 96 || last < -1 || last >= C) { mk_set_error(fn, "need C >= 2, T >= 1, 1 <= n <= 96, -1 <= last < C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hc(n);
+    HIP_CHECK_RET(hipMemcpyAsync(hc.data(), cand, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    for (int v : hc) if (v == 0 || v < -1 || v >= C) { mk_set_error(fn, "candidates must lie in 1 .. C-1 or be -1"); return -1; }
+    // one utterance, one row (B = K = R = 1), P = n; step 1 reads the empty state of parity 0, step 2 the given parent in parity 1
+    const int st = last < 0 ? 1 : 2;
+    const size_t plane = (size_t)T * n;
+    char* w = nullptr;
+    HIP_CHECK_RET(hipMalloc(&w, 256 + 2 * plane * sizeof(float2)));
+    if (hipMemsetAsync(w, 0, 256 + 2 * plane * sizeof(float2), s) != hipSuccess) { hipFree(w); mk_set_error(fn, "memset failed"); return -1; }
+    int* ints = reinterpret_cast<int*>(w);                  // step[2] | fin | enc_len | tok_hist | src
+    float* flts = reinterpret_cast<float*>(w + 64);         // score | psi
+    const int h_ints[6] = {st, 0, 0, T, last, 0};
+    const float h_flts[2] = {score, psi_par};
+    BeamArgs a{};
+    a.step = ints; a.fin = ints + 2; a.enc_lens = ints + 3; a.tok_hist = ints + 4; a.src = ints + 5;
+    a.score = flts; a.psi = flts + 1;
+    a.B = 1; a.K = 1; a.R = 1; a.Lmax = st; a.C = C; a.sos = 0; a.eos = C - 1;
+    a.P = n; a.Tp = T; a.att_w = att_w; a.ctc_w = ctc_w;
+    a.ctc_lp = lp; a.ctc_state = reinterpret_cast<float2*>(w + 256);
+    a.pre_tok = const_cast<int*>(cand); a.pre_lp = const_cast<float*>(att_lp);
+    a.list_tok = list_tok; a.list_score = list_score; a.list_psi = list_psi; a.list_slot = list_slot;
+    int rc = 0;
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(ints, h_ints, sizeof h_ints, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(flts, h_flts, sizeof h_flts, hipMemcpyHostToDevice, s));
+        if (last < 0) CK(mk_beam_ctc_init(a, s));            // (writes psi 0 and src 0: the empty hypothesis)
+        else HIP_CHECK_RET(hipMemcpy2DAsync(a.ctc_state + plane, (size_t)n * sizeof(float2), parent, sizeof(float2), sizeof(float2), T,
+                                            hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_ctc_prefix(a, s));
+        HIP_CHECK_RET(hipMemcpyAsync(out_state, a.ctc_state + (st & 1) * plane, plane * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    rc = run();
+    hipFree(w);
+    return rc;
+}
+int masr_test_attn_decode(const uint16_t* q, int64_t ldq, const uint16_t* k, const uint16_t* v, int64_t ldk, int64_t kv_batch_stride,
+                          const uint16_t* knew, const uint16_t* vnew, int64_t ldnew, const int32_t* step, const int32_t* klens, uint16_t* o,
+                          int64_t ldo, int B, int H, int hd, int Tk_cap, int rows_per_utt, const int32_t* src, int64_t ld_src, int64_t src_flip,
+                          void* stream) {
+    const char* fn = "masr_test_attn_decode";
+    if (!q || !k || !v || !o || !step == !klens || !knew != !vnew || (src && !step)) {
+        mk_set_error(fn, "null pointer (exactly one of step / klens; knew and vnew together; src with step only)"); return -1;
+    }
+    if (B < 1 || H < 1 || Tk_cap < 1 || rows_per_utt < 0 || (src && (ld_src < 0 || src_flip < 0))) { mk_set_error(fn, "bad sizes"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    // the rows of the key/value cache the launch can address: row b reads cache row b, or b / rows_per_utt
+    const int ncache = rows_per_utt > 1 ? (B + rows_per_utt - 1) / rows_per_utt : B;
+    std::vector<int> kl(ncache);
+    if (step) HIP_CHECK_RET(hipMemcpyAsync(kl.data(), step, sizeof(int), hipMemcpyDeviceToHost, s));
+    else HIP_CHECK_RET(hipMemcpyAsync(kl.data(), klens, sizeof(int) * ncache, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if (step) std::fill(kl.begin(), kl.end(), kl[0]);
+    for (int n : kl) if (n < 1 || n > Tk_cap) { mk_set_error(fn, "key count outside [1, Tk_cap]"); return -1; }
+    if (src) {                                               // every slot-table entry the launch reads must name a cache row
+        std::vector<int> row;
+        for (int b = 0; b < B; ++b) {
+            const int n = kl[rows_per_utt > 1 ? b / rows_per_utt : b];
+            row.resize(n);
+            HIP_CHECK_RET(hipMemcpy(row.data(), src + (n & 1) * src_flip + (long)b * ld_src, sizeof(int) * n, hipMemcpyDeviceToHost));
+            for (int j = 0; j < n - (knew ? 1 : 0); ++j) if (row[j] < 0 || row[j] >= ncache) { mk_set_error(fn, "src entry outside the cache rows"); return -1; }
+        }
+    }
+    AttnDecodeArgs a{};
+    a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldk = ldk; a.kv_batch_stride = kv_batch_stride;
+    a.knew = (const bf16*)knew; a.vnew = (const bf16*)vnew; a.ldnew = ldnew; a.step = step; a.klens = klens; a.o = (bf16*)o; a.ldo = ldo;
+    a.B = B; a.H = H; a.hd = hd; a.Tk_cap = Tk_cap; a.rows_per_utt = rows_per_utt; a.src = src; a.ld_src = ld_src; a.src_flip = src_flip;
+    return mk_attn_decode(a, s);
+}
+int masr_test_logits_f32(const float* y32, const float* W32, const float* bias, float* z, int64_t ld, int rows, int C, int E, void* stream) {
+    if (!y32 || !W32 || !bias || !z || C < 1 || ld < C) { mk_set_error("masr_test_logits_f32", "null pointer, C < 1 or ld < C"); return -1; }
+    return mk_logits_f32(y32, W32, bias, z, ld, rows, C, E, (hipStream_t)stream);
+}
+int masr_test_recog_argmax_step(int32_t* step, const float* logits, int64_t ld, int32_t* out, int B, int C, void* stream) {
+    if (!step || !logits || !out || B < 1 || C < 1 || ld < C) { mk_set_error("masr_test_recog_argmax_step", "null pointer, B < 1, C < 1 or ld < C"); return -1; }
+    return mk_recog_argmax_step(step, logits, ld, out, B, C, (hipStream_t)stream);
+}
+int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int32_t* minlen, const int32_t* maxlen, const float* logits,
+                        int64_t ld, float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* list_tok,
+                        float* list_score, int32_t* tok_hist_row, int32_t* par_hist_row, int32_t* step_out, void* stream) {
+    const char* fn = "masr_test_beam_step";
+    if (!minlen || !maxlen || !logits || !score || !fin || !best_score || !best_len || !best_row || !list_tok || !list_score ||
+        !tok_hist_row || !par_hist_row || !step_out) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
+    if (B < 1 || C < 1 || t < 1 || ld < C || sos < 0 || sos >= C || eos < 0 || eos >= C) { mk_set_error(fn, "need B, C, t >= 1, ld >= C, sos / eos < C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    const size_t hist = (size_t)t * R * sizeof(int);
+    int* w = nullptr;                                        // step[2] | tok_hist [t][R] | par_hist [t][R]
+    HIP_CHECK_RET(hipMalloc(&w, 64 + 2 * hist));
+    int* tok_hist = w + 16;
+    int* par_hist = tok_hist + (size_t)t * R;
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = sos; a.eos = eos; a.maxlen = maxlen; a.minlen = minlen;
+    a.tok_hist = tok_hist; a.par_hist = par_hist; a.score = score; a.list_tok = list_tok; a.list_score = list_score; a.fin = fin;
+    a.best_score = best_score; a.best_len = best_len; a.best_row = best_row;
+    auto run = [&]() -> int {                                // row t-1 of the history starts as the caller's, so untouched entries show
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_row_topk(a, logits, ld, s));
+        CK(mk_beam_select(a, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+// ---- the training step's row kernels alone (tests/test_hip_train_row_kernels.py): each entry vets what the kernel would index with, fills the
+// launcher's arguments and calls it
+static int test_read_ints(const int32_t* dev, size_t n, std::vector<int>& host, hipStream_t s) {
+    host.resize(n);
+    HIP_CHECK_RET(hipMemcpyAsync(host.data(), dev, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_ls_ce(const float* logits, int64_t ld, const int32_t* gold, int rows, int C, float eps, float inv_ntotal, const float* inv_ntotal_ptr,
+                    float grad_w, uint16_t* dlogits, float* row_loss, int32_t* row_correct, float* stats, void* stream) {
+    const char* fn = "masr_test_ls_ce";
+    if (!logits || !gold || !dlogits || !row_loss || !row_correct || !stats) { mk_set_error(fn, "null pointer"); return -1; }
+    if (rows < 1 || C < 1 || ld < C) { mk_set_error(fn, "need rows >= 1, C >= 1, ld >= C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hg;
+    CK(test_read_ints(gold, (size_t)rows, hg, s));
+    for (int g : hg) if (g < -1 || g >= C) { mk_set_error(fn, "gold must lie in [0, C) or be -1"); return -1; }
+    return mk_ls_ce(logits, ld, gold, rows, C, eps, inv_ntotal, (bf16*)dlogits, row_loss, row_correct, stats, s, inv_ntotal_ptr, grad_w);
+}
+int masr_test_embed_fwd(const int32_t* tok, const float* table, const float* pe, float* y32, uint16_t* y16, int B, int L, int E, int V, float drop_p,
+                        uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    const char* fn = "masr_test_embed_fwd";
+    if (!tok || !table || !pe || !y32 || !y16) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B < 1 || L < 1 || E < 1 || V < 1 || !(drop_p >= 0.f && drop_p < 1.f)) { mk_set_error(fn, "need B, L, E, V >= 1 and 0 <= drop_p < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ht;
+    CK(test_read_ints(tok, (size_t)B * L, ht, s));
+    for (int t : ht) if (t < 0 || t >= V) { mk_set_error(fn, "token outside [0, V)"); return -1; }
+    return mk_embed_fwd(tok, table, pe, y32, (bf16*)y16, B, L, E, drop_p, seed, site, s, seed_ptr);
+}
+int masr_test_embed_bwd(const int32_t* tok, int n, const float* dy, float* dtable, int V, int E, int accumulate, float drop_p, uint32_t seed,
+                        uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    const char* fn = "masr_test_embed_bwd";
+    if (!tok || !dy || !dtable) { mk_set_error(fn, "null pointer"); return -1; }
+    if (n < 1 || V < 1 || E < 1 || !(drop_p >= 0.f && drop_p < 1.f)) { mk_set_error(fn, "need n, V, E >= 1 and 0 <= drop_p < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ht;
+    CK(test_read_ints(tok, (size_t)n, ht, s));
+    for (int t : ht) if (t < 0 || t >= V) { mk_set_error(fn, "token outside [0, V)"); return -1; }
+    std::vector<int> sorted((size_t)n + V + 1);                // order [n] | start [V + 1], as masr_run_batch stages them
+    group_positions_by_token(ht.data(), 1, n, nullptr, V, sorted.data(), sorted.data() + n);
+    int* d = nullptr;
+    HIP_CHECK_RET(hipMalloc(&d, sizeof(int) * sorted.size()));
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(d, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice, s));
+        CK(mk_embed_bwd(d, d + n, dy, dtable, V, E, accumulate, drop_p, seed, site, s, seed_ptr));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(d);
+    return rc;
+}
+int masr_test_cast_dropout(const float* x, uint16_t* y, int64_t n, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_ptr, void* stream) {
+    if (!x || !y || n < 1 || n > 0x7fffffffL || !(drop_p >= 0.f && drop_p < 1.f)) {
+        mk_set_error("masr_test_cast_dropout", "null pointer, n outside [1, 2^31) or drop_p outside [0, 1)"); return -1;
+    }
+    return mk_cast_dropout(x, (bf16*)y, (long)n, drop_p, seed, site, (hipStream_t)stream, seed_ptr);
+}
+int masr_test_vgg2enc_grad_unpermute(const float* g, float* dw, int E, int C, int Dp, void* stream) {
+    if (!g || !dw || E < 1 || C < 1 || Dp < 1) { mk_set_error("masr_test_vgg2enc_grad_unpermute", "null pointer or E, C, Dp < 1"); return -1; }
+    return mk_vgg2enc_grad_unpermute(g, dw, E, C, Dp, (hipStream_t)stream);
+}
+int masr_test_recog_argmax(const float* logits, int64_t ld, int32_t* out, int B, int L, int C, void* stream) {
+    if (!logits || !out || B < 1 || L < 1 || C < 1 || ld < C) { mk_set_error("masr_test_recog_argmax", "null pointer, B, L, C < 1 or ld < C"); return -1; }
+    return mk_recog_argmax(logits, ld, out, B, L, C, (hipStream_t)stream);
+}
+int masr_test_linear_shadows(const float* P, int64_t src, int N, int K, int ldt, uint16_t* k16, uint16_t* t16, void* stream) {
+    if (N <= 0 || K <= 0 || ldt < N || src < 4) { mk_set_error("masr_test_linear_shadows", "N, K > 0, ldt >= N, src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }
+    ShadowJobs jobs{};
+    jobs.n = 1;
+    jobs.d[0] = ShadowDesc{src, SH_LINEAR, N, K, ldt, 0, 0, 0};
+    jobs.blocks = mk_shadow_blocks(jobs.d[0]);
+    jobs.p[0] = (bf16*)k16; jobs.p[1] = (bf16*)t16;
+    return mk_all_shadows(P, jobs, (hipStream_t)stream);
+}
+int masr_test_conv1_fwd(const float* x, const float* w, const float* bias, uint16_t* out, uint64_t* relu_bits, int B, int H, int W, void* stream) {
+    return mk_conv1_fwd(x, w, bias, (bf16*)out, B, H, W, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(relu_bits));
+}
+int masr_test_conv3x3(const uint16_t* in, const uint16_t* wk, const float* bias, int relu, uint16_t* out, int B, int H, int W, int CIN,
+                      int COUT, void* stream) {
+    ConvArgs a{}; a.in = (const bf16*)in; a.wk = (const bf16*)wk; a.bias = bias; a.relu = relu; a.out = (bf16*)out;
+    a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3(a, (hipStream_t)stream);
+}
+int masr_test_conv3x3_ex(const uint16_t* in, const uint16_t* wk, const float* bias, int relu, const uint16_t* mask, uint16_t* out,
+                         uint16_t* pool_out, int B, int H, int W, int CIN, int COUT, void* stream) {
+    ConvArgs a{}; a.in = (const bf16*)in; a.wk = (const bf16*)wk; a.bias = bias; a.relu = relu; a.mask = (const bf16*)mask; a.out = (bf16*)out;
+    a.pool_out = (bf16*)pool_out; a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3(a, (hipStream_t)stream);
+}
+int masr_test_conv3x3_sign_bits(const uint16_t* in, const uint16_t* wk, const float* bias, int relu, const uint16_t* mask, const uint32_t* mask_bits,
+                                uint16_t* out, uint32_t* out_sign_bits, int B, int H, int W, int CIN, int COUT, void* stream) {
+    ConvArgs a{}; a.in = (const bf16*)in; a.wk = (const bf16*)wk; a.bias = bias; a.relu = relu; a.mask = (const bf16*)mask;
+    a.mask_bits = (const unsigned long long*)mask_bits; a.out = (bf16*)out; a.out_sign_bits = (unsigned long long*)out_sign_bits;
+    a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3(a, (hipStream_t)stream);
+}
+int masr_test_conv3x3_pool_idx(const uint16_t* in, const uint16_t* wk, const float* bias, uint16_t* out, uint16_t* pool_out, uint8_t* pool_idx,
+                               int drop_out, int B, int H, int W, int CIN, int COUT, void* stream) {
+    ConvArgs a{}; a.in = (const bf16*)in; a.wk = (const bf16*)wk; a.bias = bias; a.relu = 1; a.out = (bf16*)out;
+    a.pool_out = (bf16*)pool_out; a.pool_idx = pool_idx; a.out_optional = drop_out; a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3(a, (hipStream_t)stream);
+}
+int masr_test_conv3x3_dgrad_pooled(const uint16_t* dy, const uint16_t* dy_pooled, const uint8_t* pool_idx, const uint16_t* wk, const uint32_t* mask_bits,
+                                   uint16_t* out, int B, int H, int W, void* stream) {
+    ConvArgs a{}; a.in = (const bf16*)dy; a.in_pooled = (const bf16*)dy_pooled; a.in_idx = pool_idx; a.wk = (const bf16*)wk;
+    a.mask = (const bf16*)out; a.mask_bits = (const unsigned long long*)mask_bits; a.out = (bf16*)out;      // (mask: any non-null pointer -- the sign words are what is read)
+    a.B = B; a.H = H; a.W = W; a.CIN = 128; a.COUT = 128;
+    return mk_conv3x3(a, (hipStream_t)stream);
+}
+int64_t masr_test_conv1_wgrad_fused_slab_floats(int B, int H, int W) { return mk_conv1_wgrad_fused_slab_floats(B, H, W); }
+int masr_test_conv1_wgrad_fused(const uint16_t* dy, const uint16_t* dy_pooled, const uint8_t* pool_idx, const uint16_t* wk, const uint64_t* mask_bits,
+                                const float* x1, float* slab, int64_t slab_floats, float* dw1, float* db1, int B, int H, int W, void* stream) {
+    if (slab_floats < mk_conv1_wgrad_fused_slab_floats(B, H, W)) { mk_set_error("masr_test_conv1_wgrad_fused", "slab too small"); return -1; }
+    ConvArgs a{}; a.in = (const bf16*)dy; a.in_pooled = (const bf16*)dy_pooled; a.in_idx = pool_idx; a.wk = (const bf16*)wk;
+    a.mask = (const bf16*)wk; a.mask_bits = (const unsigned long long*)mask_bits; a.x1 = x1; a.w1_slab = slab;
+    a.B = B; a.H = H; a.W = W; a.CIN = 64; a.COUT = 64;
+    CK(mk_conv3x3(a, (hipStream_t)stream));
+    return mk_conv1_wgrad_fused_reduce(slab, B, H, W, dw1, db1, (hipStream_t)stream);
+}
+int64_t masr_test_conv3x3_wgrad_slab_floats(int B, int H, int W, int CIN, int COUT) { return mk_conv3x3_wgrad_slab_floats(B, H, W, CIN, COUT); }
+int masr_test_conv3x3_wgrad(const uint16_t* in, const uint16_t* dy, float* dw, float* slab, int64_t slab_floats, int B, int H, int W, int CIN,
+                            int COUT, void* stream) {
+    if (slab_floats < mk_conv3x3_wgrad_slab_floats(B, H, W, CIN, COUT)) { mk_set_error("masr_test_conv3x3_wgrad", "slab too small"); return -1; }
+    ConvWgradArgs a{}; a.in = (const bf16*)in; a.dy = (const bf16*)dy; a.dw = dw; a.slab = slab; a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3_wgrad(a, (hipStream_t)stream);
+}
+int64_t masr_test_layernorm_slab_floats(int rows, int E) { return mk_layernorm_bwd_slab_floats(rows, E); }
+int masr_test_layernorm(const float* x, const float* gamma, const float* beta, const float* dy, float* y, uint16_t* y16, float* mean,
+                        float* rstd, float* dx, uint16_t* dx16, float* dgamma, float* dbeta, float* slab, int rows, int E, float drop_p,
+                        uint32_t seed, uint32_t site, void* stream) {
+    if (mk_layernorm_fwd(x, gamma, beta, y, (bf16*)y16, mean, rstd, rows, E, (hipStream_t)stream)) return -1;
+    return mk_layernorm_bwd(dy, x, gamma, mean, rstd, dx, (bf16*)dx16, drop_p, seed, site, dgamma, dbeta, slab, rows, E, (hipStream_t)stream, nullptr);
+}
+int masr_test_ksplit_ln(const uint16_t* A, const uint16_t* B, int rows, int E, int K, int split, const float* bias, const float* residual, float drop_p,
+                        uint32_t seed, uint32_t site, float* part, const float* gamma, const float* beta, float* sum_out, float* y32, uint16_t* y16,
+                        float* mean, float* rstd, const float* x, float* dx32, uint16_t* dx16, float* slab, void* stream) {
+    // the engine's k-split pair (ffn_fwd + ln_fwd / ffn_bwd + ln_bwd): C = A [rows, K] . B [E, K]^T as `split` fp32 partial products in `part`,
+    // then the LayerNorm that sums them.  x == null: forward (row = sum + bias, dropout, + residual -> sum_out, y32 / y16, mean, rstd);
+    // x given: backward (dy = sum + residual; mean / rstd are inputs; dx32 / dx16 and the [ceil(rows / 4)][2][E] partials of dgamma / dbeta in slab)
+    GemmArgs g = gemm_args();
+    g.A = (const bf16*)A; g.lda = K; g.B = (const bf16*)B; g.ldb = K; g.M = rows; g.N = E; g.K = K;
+    g.C32 = part; g.ldc = E; g.split_k = split; g.split_stride = (long)rows * E;
+    CK(mk_gemm(g, (hipStream_t)stream));
+    if (!x) {
+        const LnSumArgs sm{part, (long)rows * E, split, bias, residual, drop_p, seed, site, nullptr, sum_out};
+        return mk_layernorm_fwd_sum(sm, gamma, beta, y32, (bf16*)y16, mean, rstd, rows, E, (hipStream_t)stream);
+    }
+    const LnSumArgs sm{part, (long)rows * E, split, nullptr, residual, 0.f, 0u, 0u, nullptr, nullptr};
+    return mk_layernorm_bwd_sum(sm, x, gamma, mean, rstd, dx32, (bf16*)dx16, drop_p, seed, site, slab, rows, E, (hipStream_t)stream, nullptr);
+}
+int masr_test_wgrad_grouped(const uint16_t* dy, int64_t lddy, const uint16_t* x, int64_t ldx, float* dW, float* db, float* dW2, float* db2,
+                            int rows, int N, int K, void* stream) {
+    // two members over the same operands (the second one optional): exercises the descriptor walk of the grouped grid
+    WgradGroup grp{};
+    grp.n = dW2 ? 2 : 1;
+    for (int i = 0; i < grp.n; ++i) {
+        WgradDesc& d = grp.p[i];
+        d.dy = (const bf16*)dy; d.x = (const bf16*)x; d.dW = i ? dW2 : dW; d.db = i ? db2 : db; d.lddy = (int)lddy; d.ldx = (int)ldx; d.rows = rows; d.N = N; d.K = K;
+    }
+    return mk_gemm_wgrad_grouped(grp, (hipStream_t)stream);
+}
+int masr_test_wgrad_grouped_n(const uint16_t* dy, int64_t lddy, const uint16_t* x, int64_t ldx, float* dW, int64_t member_stride, int members,
+                              int first_members, int rows, int rows_rest, int N, int K, void* stream) {
+    // `members` group members over the SAME operands (member i writes dW + i * member_stride; 0 = all into one buffer): what the grouped
+    // launch costs when every panel is resident in L2 / the Infinity Cache (tools/wgrad_probe.py).  first_members > 0: the two-segment
+    // tile list of the engine's merged launch -- members [0, first_members) reduce over `rows` rows and are dispatched first, the rest
+    // over the first `rows_rest` rows
+    WgradGroup grp{};
+    grp.n = members < WGRAD_GROUP_MAX ? members : WGRAD_GROUP_MAX;
+    for (int i = 0; i < grp.n; ++i) {
+        WgradDesc& d = grp.p[i];
+        d.dy = (const bf16*)dy; d.x = (const bf16*)x; d.dW = dW + (int64_t)i * member_stride; d.db = nullptr; d.lddy = (int)lddy; d.ldx = (int)ldx;
+        d.rows = (first_members > 0 && i >= first_members) ? rows_rest : rows; d.N = N; d.K = K;
+    }
+    return mk_gemm_wgrad_grouped(grp, (hipStream_t)stream, first_members);
+}
+int masr_test_conv3x3_wgrad_pooled(const uint16_t* in, const uint16_t* dy_pooled, const uint8_t* pool_idx, float* dw, float* db, float* slab,
+                                   int64_t slab_floats, int B, int H, int W, int CIN, int COUT, void* stream) {
+    if (slab_floats < mk_conv3x3_wgrad_slab_floats(B, H, W, CIN, COUT)) { mk_set_error("masr_test_conv3x3_wgrad_pooled", "slab too small"); return -1; }
+    ConvWgradArgs a{}; a.in = (const bf16*)in; a.dy_pooled = (const bf16*)dy_pooled; a.pool_idx = pool_idx; a.dw = dw; a.db = db; a.slab = slab;
+    a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
+    return mk_conv3x3_wgrad(a, (hipStream_t)stream);
+}
+int masr_test_attention_dropout_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o, uint16_t* dq, uint16_t* dk,
+                                    uint16_t* dv, float* lse, const int32_t* klens, int B, int H, int Tq, int Tk, int hd, int causal, float drop_p,
+                                    uint32_t seed, uint32_t site, void* stream) {
+    const long E = (long)H * hd;
+    AttnArgs a{};
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldq = a.ldk = a.ldv = E; a.o = (bf16*)o; a.ldo = E; a.lse = lse;
+    a.klens = klens; a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal; a.drop_p = drop_p; a.seed = seed; a.site = site;
+    CK(mk_attn_fwd(a, (hipStream_t)stream));
+    a.dout = (const bf16*)dout; a.lddo = E; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lddq = a.lddk = a.lddv = E;
+    return mk_attn_bwd(a, (hipStream_t)stream);
+}
+int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o, uint16_t* dq, uint16_t* dk,
+                        uint16_t* dv, float* lse, float* delta, const int32_t* klens, int B, int H, int Tq, int Tk, int hd, int causal,
+                        void* stream) {
+    const long E = (long)H * hd;
+    AttnArgs a{};
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldq = a.ldk = a.ldv = E; a.o = (bf16*)o; a.ldo = E; a.lse = lse;
+    a.klens = klens; a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal;
+    CK(mk_attn_fwd(a, (hipStream_t)stream));
+    if (dout) {
+        a.dout = (const bf16*)dout; a.lddo = E; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lddq = a.lddk = a.lddv = E; a.delta = delta;
+        CK(mk_attn_bwd(a, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -128,7 +128,7 @@ def test_beam_batch_independence_and_graph_replay(eng):
     xs, il, _, _ = synth_batch(31, [64, 40, 52, 33, 60], [3] * 5)   # ragged: maxlen 16, 10, 13, 8, 15
     K = 6
     t1, s1 = eng.recog_beam(xs, il, K)
-    t2, s2 = eng.recog_beam(xs, il, K)                      # replays the cached graph
+    t2, s2 = eng.recog_beam(xs, il, K)                      # again (direct launches on this stream; graphs: test_hip_decode_graphs.py)
     assert t1 == t2 and torch.equal(s1, s2)
     perm = [3, 0, 4, 2, 1]
     tp, sp = eng.recog_beam(xs[perm], il[perm], K)

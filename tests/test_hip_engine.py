@@ -391,7 +391,7 @@ def test_eight_encoder_layers_build_and_step():
 
 @pytest.mark.parametrize("dropout", [0.0, 0.1])
 def test_ksplit_gemms_with_the_combine_inside_the_layernorm(dropout):
-    """engine.hip ksplit_of: at the hkust geometry the decoder's FFN second layer (K = 2048), its first layer's dgrad and the packed q/k/v dgrad
+    """train.hip ksplit_of: at the hkust geometry the decoder's FFN second layer (K = 2048), its first layer's dgrad and the packed q/k/v dgrad
     (K = 1536) run k-split, and the LayerNorm (backward) behind each sums the fp32 partial products and applies the GEMM's epilogue (bias, dropout
     with the GEMM's element index, residual).  The pair itself is checked number by number in test_hip_kernels.py
     (test_ksplit_gemm_summed_by_the_layernorm) and on a one-decoder-layer model below (test_ksplit_one_decoder_layer_is_tight); here the whole
@@ -497,7 +497,7 @@ def test_task_slot_hint_never_changes_bits(ksplit):
 
 @pytest.mark.parametrize("cfg_name", ["tiny", "hkust"])
 def test_merged_weight_gradient_launch_equals_two_launches(cfg_name):
-    """engine.hip flush_wgrads: the decoder-row weight gradients ride in the encoder rows' launch (two-segment tile list, long tiles
+    """train.hip flush_wgrads: the decoder-row weight gradients ride in the encoder rows' launch (two-segment tile list, long tiles
     dispatched first).  Against the two separate launches (masr_set_split_wgrad_launches): every gradient of a training step bit for bit."""
     cfg = dict(TINY if cfg_name == "tiny" else HKUST)
     sd = ref_cpu.deterministic_state_dict(cfg, ODIM, seed=6)

@@ -119,7 +119,7 @@ def test_joint_batch_independence_and_graph_replay(tiny):
     xs, il, _, _ = synth_batch(31, [64, 40, 52, 33, 60], [3] * 5)
     K, w = 6, dict(att_weight=0.5, ctc_weight=0.5)
     t1, s1 = e.recog_beam(xs, il, K, **w)
-    t2, s2 = e.recog_beam(xs, il, K, **w)                      # replays the cached graph
+    t2, s2 = e.recog_beam(xs, il, K, **w)                      # again (direct launches on this stream; graphs: test_hip_decode_graphs.py)
     assert t1 == t2 and torch.equal(s1, s2)
     perm = [3, 0, 4, 2, 1]
     tp, sp = e.recog_beam(xs[perm], il[perm], K, **w)

@@ -493,7 +493,7 @@ def test_layernorm_fwd_bwd(L, rows, E):
                                                   (3, 256, 4096, 8, 0.1)])
 def test_ksplit_gemm_summed_by_the_layernorm(L, rows, E, K, split, drop):
     """The decoder's few-row GEMMs with a long reduction run k-split, and the LayerNorm behind them sums the fp32 partial products
-    (engine.hip ffn_fwd / ln_fwd, ffn_bwd / ln_bwd, attn_block_bwd; rowops.hip LnSumArgs).  Forward: sum + bias, dropout at the GEMM's element
+    (train.hip gemm_or_ksplit: ffn_fwd, ffn_bwd, attn_block_fwd / _bwd, with ln_fwd / ln_bwd behind them; rowops.hip LnSumArgs).  Forward: sum + bias, dropout at the GEMM's element
     index, + residual, LayerNorm -- against mk_gemm's own epilogue followed by the plain LayerNorm (same numbers up to fp32 summation order)
     and against torch.  Backward: dy = sum + residual gradient."""
     g = torch.Generator(device="cuda").manual_seed(rows + K)
@@ -612,7 +612,7 @@ def test_attention_dropout_forward_backward(L, B_, H, Tq, Tk, hd, causal, masked
 
 def test_dropout_keep_rate_and_scale_per_site():
     """nn.Dropout semantics at every site of the engine (PE dropout 1 / 100, attention probabilities, attention out-proj,
-    FFN inner, FFN out: sites 1.. and 100.. in csrc/engine.hip): an element is kept with probability 1 - p and scaled by
+    FFN inner, FFN out: sites 1.. and 100.. in csrc/train.hip): an element is kept with probability 1 - p and scaled by
     1/(1-p); masks of different sites, seeds and elements are independent.  The mask is a stateless hash of (seed, site,
     index): checked through the hash itself, through the GEMM epilogue and through the attention-probability path."""
     L = _cabi.lib()
