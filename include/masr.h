@@ -246,6 +246,14 @@ int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, 
 int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
                         float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
+/* CTC prefix beam search on the CTC head alone (hybrid models of masr_create_ctc): the encoder and the head GEMM of
+ * masr_recog_beam_ctc, then masr_ctc_beam_search (below) on the head's fp32 logits with blank 0, eos = odim - 1, Tp = T / 4 and
+ * enc_len = floor(ilens[b] / 4).  Result (device): tokens int32 [B][nbest][T/4], lens int32 [B][nbest], scores fp32 [B][nbest].  A model
+ * without a CTC head returns -1.  Needs a workspace of masr_ctc_beam_workspace_bytes(B, T, K) bound with masr_bind. */
+int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K);
+int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
+                        float* scores, void* stream);
+
 /* Levenshtein distance of two id sequences (host-side; replaces the `editdistance` extension the reference's metric
  * imports, src/monitor/metric.py:4,66,87).  Returns the distance, < 0 on bad arguments. */
 int64_t masr_edit_distance(const int32_t* a, int na, const int32_t* b, int nb);
@@ -338,6 +346,24 @@ int masr_ctc_status(const float* work, int T, int B, int maxS, void* stream);
 int masr_ctc_loss(const float* logits, const int32_t* targets, const int32_t* tgt_off, const int32_t* in_len,
                   const int32_t* tgt_len, int T, int B, int C, int blank, float* nll, float* loss, float* grad,
                   float* work, int maxS, void* stream);
+
+/* CTC prefix beam search with merging (Hannun et al. 2014) over a CTC output layer, model-free like masr_ctc_loss.
+ * logits: device fp32, the row of utterance b, frame t at logits + (b * Tp + t) * ld (ld >= C); enc_lens: device int32 [B], each clamped to
+ * [0, Tp] by the kernels; frames past it are never read.  x_t = fp32 log_softmax of the row.  Classes `blank` and `eos` (-1 = none) are
+ * never emitted.  The beam holds at most K distinct prefixes with (p_b, p_nb) in log space, from the empty prefix (0, -inf).  Per frame, with
+ * S_t the P = min(K, emittable classes) best emittable classes by (x_t descending, class ascending), every entry h in rank order gives
+ *   stay:      p_b' = logaddexp(p_b, p_nb) + x_t(blank),  p_nb' = p_nb + x_t(last(h))  (-inf for the empty prefix)
+ *   h + c:     p_b' = -inf,  p_nb' = (c == last(h) ? p_b : logaddexp(p_b, p_nb)) + x_t(c)        for c in S_t
+ * and an extension h + c that is itself an entry h' of the beam is no candidate: its p_nb' is log-added to p_nb' of stay(h').  A candidate
+ * scores logaddexp(p_b', p_nb'); the K best by (score descending, parent rank ascending, stay before extensions, position in S_t
+ * ascending) are kept, -inf candidates never.  All of it fp32 in this order.  Prefix identity is (length, 64-bit hash), see DESIGN 5.3.
+ * Result (device): the final beam in rank order, tokens int32 [B][nbest][Tp] (-1 behind each list), lens int32 [B][nbest], scores fp32
+ * [B][nbest]; slots beyond the live entries have lens -1 and score -inf; enc_len 0 gives the empty prefix with score 0.
+ * -1 (text in masr_last_error()) unless 1 <= K <= 64, 1 <= nbest <= K, 2 <= C <= 4096, 0 <= blank < C, eos in {-1} or [0, C) and != blank,
+ * B >= 1, Tp >= 1, work_bytes >= masr_ctc_beam_work_bytes(B, Tp, C, K), and no pointer is null. */
+int64_t masr_ctc_beam_work_bytes(int B, int Tp, int C, int K);
+int masr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                         void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
 /* device timing (HIP events on the launch stream) for bench.py's roofline block: one slot per conv launch of the VGG
  * front-end (each is ONE launch per step, so slot time / launches = that kernel's average duration) and one per kernel

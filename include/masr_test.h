@@ -161,6 +161,10 @@ int masr_test_attention_dropout_bwd(const uint16_t* q, const uint16_t* k, const 
 int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o,
                         uint16_t* dq, uint16_t* dk, uint16_t* dv, float* lse, float* delta, const int32_t* klens,
                         int B, int H, int Tq, int Tk, int hd, int causal, void* stream);
+/* where the last masr_recog_ctc_beam call with this B, T, K left the inputs of its masr_ctc_beam_search in the bound workspace: the CTC
+ * head's fp32 logits (row of utterance b, frame t at logits + (b * (T / 4) + t) * ld, C = odim valid columns) and enc_lens int32 [B].
+ * Valid until the next call that uses the workspace. */
+int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,8 @@ _SIGS = {
     "masr_recog_beam": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
     "masr_beam_ctc_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_ctc": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
+    "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "masr_edit_distance": (i64, [vp, i32, vp, i32]),
     "masr_blstm_create": (vp, [vp]),
     "masr_blstm_destroy": (None, [vp]),
@@ -94,6 +96,8 @@ _SIGS = {
     "masr_ctc_work_floats": (i64, [i32, i32, i32]),
     "masr_ctc_status": (i32, [vp, i32, i32, i32, vp]),
     "masr_ctc_loss": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "masr_ctc_beam_work_bytes": (i64, [i32, i32, i32, i32]),
+    "masr_ctc_beam_search": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "masr_profile_enable": (i32, [vp, i32]),
     "masr_profile_read": (i32, [vp, C.POINTER(f32), C.POINTER(i32)]),
     "masr_test_blstm_stall": (None, [vp, i32]),          # include/masr_test.h from here on
@@ -104,6 +108,7 @@ _SIGS = {
     "masr_test_gemm_epi": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp]),
     "masr_test_skinny_gemm": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "masr_test_ctc_prefix": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "masr_test_ctc_beam_logits": (i32, [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp)]),
     "masr_test_attn_decode": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
     "masr_test_logits_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "masr_test_recog_argmax_step": (i32, [vp, vp, i64, vp, i32, i32, vp]),
@@ -159,6 +164,14 @@ def lib():
 
 class MasrError(RuntimeError):
     pass
+
+
+def nbest_lists(tok, lens, scores):
+    """device results of masr_ctc_beam_search (tokens [B][N][Tp], lens [B][N], scores [B][N] torch tensors) -> per utterance
+    [(token list, score), ...] without the slots beyond the live entries (lens -1)"""
+    tok, lens, scores = tok.cpu(), lens.cpu(), scores.cpu()
+    return [[(tok[b, i, :int(lens[b, i])].tolist(), float(scores[b, i])) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
+            for b in range(lens.size(0))]
 
 
 def check(rc, what=""):

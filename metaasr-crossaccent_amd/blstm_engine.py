@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import check, lib
+from ._cabi import check, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -138,6 +138,28 @@ class BlstmEngine:
         check(self._l.masr_blstm_check(self.h, self.stream()), "masr_blstm_check")
         return self.last_logits()
 
+    def ctc_beam(self, xs, ilens, K, nbest=1, blank=0):
+        """CTC prefix beam search over the head's output (masr_ctc_beam_search; `blank` and eos = odim - 1 are never emitted): the
+        forward with its check, then the search on last_logits() with a work tensor of this engine's own.  Returns per utterance a list
+        of at most nbest (token list, score), best first."""
+        K, N = int(K), int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {K}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        logits, lens = self.forward(xs, ilens)                 # (runs masr_blstm_check)
+        B, Tp, Cc = logits.shape
+        need = int(self._l.masr_ctc_beam_work_bytes(B, Tp, Cc, K))
+        check(need if need < 0 else 0, "masr_ctc_beam_work_bytes")
+        if getattr(self, "_beam_work", None) is None or self._beam_work.numel() < need:
+            self._beam_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        tok = torch.empty(B, N, Tp, dtype=torch.int32, device=self.device)
+        ln = torch.empty(B, N, dtype=torch.int32, device=self.device)
+        sc = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self._l.masr_ctc_beam_search(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, _ptr(self._beam_work),
+                                           self._beam_work.numel(), _ptr(tok), _ptr(ln), _ptr(sc), self.stream()), "masr_ctc_beam_search")
+        return nbest_lists(tok, ln, sc)
+
     def set_resident_recurrence(self, on: bool):
         """the LSTM recurrence as one launch per layer and pass (include/masr.h masr_blstm_set_resident_recurrence); default on"""
         self._l.masr_blstm_set_resident_recurrence(self.h, int(bool(on)))
@@ -236,6 +258,16 @@ class MonoBLSTM:
         return logits, lens.to(torch.int64)
 
     greedy_decode = __call__                                  # mono_blstm.py:63-64
+
+    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
+        """CTC prefix beam search on the head (BlstmEngine.ctc_beam; the reference's own beam decoder is dead code).
+        Each utterance is run alone, cut to its own length.  The VGG front end does not mask padded frames (as in the reference: behind
+        the first conv they hold relu(bias), which the next convs read at the utterance's last frames), so in a padded batch an
+        utterance's logits depend on the batch's length; alone, its hypotheses are a function of the utterance, whatever the batch size."""
+        out = []
+        for b, n in enumerate(torch.as_tensor(ilens).tolist()):
+            out += self.engine.ctc_beam(xs_pad[b:b + 1, :int(n)], [int(n)], beam_size, nbest, blank=self.blank_id)
+        return out
 
     def train(self):
         self.training = True

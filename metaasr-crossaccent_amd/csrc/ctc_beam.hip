@@ -1,0 +1,252 @@
+// CTC prefix beam search over a CTC output layer alone (masr_ctc_beam_search; Hannun et al. 2014, with merging).
+//
+//   ctc_beam_frames   one wave per valid frame row (b, t < enc_len): the row's log-sum-exp, x_t(blank) and S_t = its P best emittable
+//                     classes (logit descending, class ascending -- x_t is monotone in the logit) with their log-probs
+//   ctc_beam_sweep    one workgroup per utterance, serial over its frames: beam and candidates in LDS, one back-pointer record per kept
+//                     entry and frame in the work buffer; its tail walks the records of the final beam and writes the N-best list
+//
+// x_t(c) = logit - lse with lse = max + log(sum exp(logit - max)), the same expression in both kernels, so a class scores the same whether
+// it is read from S_t or gathered as a prefix's last token.  All beam arithmetic is fp32 in the written order.
+//
+// Prefix identity is (length, 64-bit rolling hash of the tokens): an entry carries its own hash and the hash of the prefix without its last
+// token, so "h + c is the beam entry h'" is  len(h') == len(h) + 1, parent_hash(h') == hash(h), last(h') == c.  Two different prefixes of
+// one beam with equal length and equal hash would be merged wrongly (DESIGN 5.3 has the odds).
+#include "kernels.h"
+
+namespace {
+
+constexpr float NEG_INF = -__builtin_inff();
+constexpr int SW_THREADS = 256, SW_WAVES = SW_THREADS / 64, KMAX = 64;
+constexpr unsigned long long HASH_EMPTY = 0xcbf29ce484222325ull;
+
+__device__ __forceinline__ uint32_t ord_f32(float v) {             // monotone float -> uint32 (larger float, larger key)
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), o, 64) << 32) |
+                                     (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e^b); -inf + -inf = -inf, never NaN
+    const float m = fmaxf(a, b);
+    if (m == NEG_INF) return NEG_INF;
+    return m + __logf(1.f + __expf(fminf(a, b) - m));
+}
+__device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) {
+    h = (h ^ (unsigned long long)(c + 1)) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+}
+__device__ __forceinline__ int clamp_len(int n, int Tp) { return n < 0 ? 0 : (n > Tp ? Tp : n); }
+
+// grid ceil(B*Tp / 4), 256 threads: one wave per frame row b*Tp + t
+__global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long)a.B * a.Tp) return;
+    const int b = (int)(row / a.Tp), t = (int)(row % a.Tp);
+    if (t >= clamp_len(a.enc_lens[b], a.Tp)) return;
+    const float* z = a.logits + row * a.ld;
+    float mx = NEG_INF;
+    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
+    s = wave_sum(s);
+    const float lse = mx + __logf(s);
+    if (lane == 0) { a.lse[row] = lse; a.xb[row] = z[a.blank] - lse; }
+    int* sc = a.s_cls + row * a.P;
+    float* sl = a.s_lp + row * a.P;
+    // P rounds of "largest key below the previous one"; key = (ordered logit, inverted class): unique per class
+    unsigned long long prev = ~0ull;
+    for (int i = 0; i < a.P; ++i) {
+        unsigned long long best = 0;
+        for (int c = lane; c < a.C; c += 64) {
+            if (c == a.blank || c == a.eos) continue;
+            const unsigned long long key = ((unsigned long long)ord_f32(z[c] + 0.f) << 32) | (uint32_t)(0x7fffffff - c);   // (-0 orders as +0)
+            if (key < prev && key > best) best = key;
+        }
+        best = wave_max_u64(best);
+        if (lane == 0) {
+            const int c = 0x7fffffff - (int)(uint32_t)best;
+            sc[i] = best ? c : -1;
+            sl[i] = best ? z[c] - lse : NEG_INF;
+        }
+        prev = best;
+        if (best == 0) {                                         // (NaN rows only: P never exceeds the emittable classes)
+            for (int k = i + 1 + lane; k < a.P; k += 64) { sc[k] = -1; sl[k] = NEG_INF; }
+            break;
+        }
+    }
+}
+
+// grid B, 256 threads.  Candidate index of frame t: parent rank k, then stay (0) or position j in S_t (1 + j): idx = k * (P + 1) + ...,
+// so "score descending, index ascending" is the selection order of DESIGN 5.3.  s_sc holds each candidate's ordered score, 0 = not a
+// candidate (-inf, or an extension merged into a stay).
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs a, int nbest, int* __restrict__ tokens, int* __restrict__ lens,
+                                                                    float* __restrict__ scores) {
+    __shared__ float s_pb[2][KMAX], s_pnb[2][KMAX];
+    __shared__ int s_last[2][KMAX], s_len[2][KMAX];
+    __shared__ unsigned long long s_hash[2][KMAX], s_phash[2][KMAX];
+    __shared__ float s_tot[KMAX], s_stay_pb[KMAX], s_stay_pnb[KMAX], s_xl[KMAX];
+    __shared__ int s_cls[KMAX], s_win[KMAX];
+    __shared__ uint32_t s_sc[KMAX * (KMAX + 1)];
+    __shared__ unsigned long long s_wmax[2][SW_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int K = a.K, P = a.P, P1 = P + 1, Tp = a.Tp;
+    const int Tb = clamp_len(a.enc_lens[b], Tp);
+    int cur = 0, n = 1;
+    if (tid == 0) {
+        s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_hash[0][0] = HASH_EMPTY; s_phash[0][0] = 0;
+    }
+    __syncthreads();
+    for (int t = 0; t < Tb; ++t) {
+        const long row = (long)b * Tp + t;
+        const int nxt = cur ^ 1;
+        // the frame's token set, and every entry's not-extended candidate
+        if (tid < P) { s_cls[tid] = a.s_cls[row * P + tid]; s_xl[tid] = a.s_lp[row * P + tid]; }
+        if (tid < n) {
+            const float pb = s_pb[cur][tid], pnb = s_pnb[cur][tid];
+            const int last = s_last[cur][tid];
+            const float tot = log_add(pb, pnb);
+            s_tot[tid] = tot;
+            s_stay_pb[tid] = tot + a.xb[row];
+            s_stay_pnb[tid] = last < 0 ? NEG_INF : pnb + (a.logits[row * a.ld + last] - a.lse[row]);
+        }
+        __syncthreads();
+        const int ncand = n * P1;
+        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+            const int k = idx / P1, j = idx % P1 - 1;
+            if (j < 0) continue;
+            const float v = (s_cls[j] == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+            s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
+        }
+        __syncthreads();
+        // merge: the extension of k that is the beam entry k2 adds to k2's stay (at most one k per k2)
+        for (int p = tid; p < n * n; p += SW_THREADS) {
+            const int k = p / n, k2 = p % n;
+            if (s_len[cur][k2] != s_len[cur][k] + 1 || s_phash[cur][k2] != s_hash[cur][k]) continue;
+            const int c = s_last[cur][k2];
+            for (int j = 0; j < P; ++j) {
+                if (s_cls[j] != c) continue;
+                const float v = (c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+                s_stay_pnb[k2] = log_add(s_stay_pnb[k2], v);
+                s_sc[k * P1 + 1 + j] = 0u;
+                break;
+            }
+        }
+        __syncthreads();
+        if (tid < n) {
+            const float v = log_add(s_stay_pb[tid], s_stay_pnb[tid]);
+            s_sc[tid * P1] = v == NEG_INF ? 0u : ord_f32(v);
+        }
+        __syncthreads();
+        // the K best: arg-max rounds; a thread rescans its own candidates (idx = tid mod 256) only after it gave the winner
+        unsigned long long mine = 0;
+        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+            const unsigned long long key = ((unsigned long long)s_sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+            if (s_sc[idx] && key > mine) mine = key;
+        }
+        int kept = 0;
+        for (int r = 0; r < K; ++r) {
+            const unsigned long long wm = wave_max_u64(mine);
+            if (lane == 0) s_wmax[r & 1][wave] = wm;
+            __syncthreads();
+            unsigned long long best = s_wmax[r & 1][0];
+#pragma unroll
+            for (int w = 1; w < SW_WAVES; ++w) { const unsigned long long v = s_wmax[r & 1][w]; best = v > best ? v : best; }
+            if (best == 0) break;                                // uniform: nothing but -inf candidates is left
+            const int win = (int)(0xffffffffu - (uint32_t)best);
+            if (tid == 0) s_win[r] = win;
+            if (win % SW_THREADS == tid) {
+                s_sc[win] = 0u;
+                mine = 0;
+                for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+                    const unsigned long long key = ((unsigned long long)s_sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+                    if (s_sc[idx] && key > mine) mine = key;
+                }
+            }
+            kept = r + 1;
+        }
+        __syncthreads();
+        // the next beam, in rank order, and its back-pointer records: parent slot | (emitted class + 1) << 8  (0 = stay)
+        if (tid < kept) {
+            const int win = s_win[tid], k = win / P1, j = win % P1 - 1;
+            int rec = k;
+            if (j < 0) {
+                s_pb[nxt][tid] = s_stay_pb[k]; s_pnb[nxt][tid] = s_stay_pnb[k];
+                s_last[nxt][tid] = s_last[cur][k]; s_len[nxt][tid] = s_len[cur][k];
+                s_hash[nxt][tid] = s_hash[cur][k]; s_phash[nxt][tid] = s_phash[cur][k];
+            } else {
+                const int c = s_cls[j];
+                s_pb[nxt][tid] = NEG_INF;
+                s_pnb[nxt][tid] = (c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+                s_last[nxt][tid] = c; s_len[nxt][tid] = s_len[cur][k] + 1;
+                s_hash[nxt][tid] = hash_push(s_hash[cur][k], c); s_phash[nxt][tid] = s_hash[cur][k];
+                rec |= (c + 1) << 8;
+            }
+            a.rec[row * K + tid] = rec;
+        }
+        __syncthreads();
+        cur = nxt; n = kept;
+    }
+    // N-best list of the final beam: each live slot walks its records backwards (a prefix of len tokens meets exactly len emitting
+    // records on the way); everything behind a list's length is -1
+    int* out = tokens + (long)b * nbest * Tp;
+    if (tid < nbest) {
+        const bool live = tid < n;
+        int pos = live ? s_len[cur][tid] : 0, slot = tid;
+        s_win[tid] = pos;
+        lens[b * nbest + tid] = live ? pos : -1;
+        scores[b * nbest + tid] = live ? log_add(s_pb[cur][tid], s_pnb[cur][tid]) : NEG_INF;
+        for (int t = Tb - 1; t >= 0 && pos > 0; --t) {
+            const int rec = a.rec[((long)b * Tp + t) * K + slot];
+            if (rec >> 8) out[(long)tid * Tp + --pos] = (rec >> 8) - 1;
+            slot = rec & 0xff;
+        }
+    }
+    __syncthreads();
+    for (long i = tid; i < (long)nbest * Tp; i += SW_THREADS) if ((int)(i % Tp) >= s_win[i / Tp]) out[i] = -1;
+}
+
+long align256(long v) { return (v + 255) & ~255l; }
+int beam_width(int C, int K, int eos) { const int e = C - 1 - (eos >= 0 ? 1 : 0); return K < e ? K : e; }
+
+}  // namespace
+
+int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K) {
+    if (B < 1 || Tp < 1 || C < 2 || C > 4096 || K < 1 || K > 64) { mk_set_error("mk_ctc_beam_work_bytes", "need B >= 1, Tp >= 1, 2 <= C <= 4096, 1 <= K <= 64"); return -1; }
+    const long rows = (long)B * Tp, P = K < C - 1 ? K : C - 1;     // (sized for eos = -1, the wider token set)
+    return 2 * align256(4 * rows) + 2 * align256(4 * rows * P) + align256(4 * rows * K);
+}
+
+int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos, void* work,
+                       int64_t work_bytes, int* tokens, int* lens, float* scores, hipStream_t s) {
+    const char* fn = "mk_ctc_beam_search";
+    if (!logits || !enc_lens || !work || !tokens || !lens || !scores) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B < 1 || Tp < 1) { mk_set_error(fn, "need B >= 1 and Tp >= 1"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
+    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
+    if (C < 2 || C > 4096 || ld < C) { mk_set_error(fn, "need 2 <= C <= 4096 and ld >= C"); return -1; }
+    if (blank < 0 || blank >= C) { mk_set_error(fn, "blank must be in [0, C)"); return -1; }
+    if (eos < -1 || eos >= C || eos == blank) { mk_set_error(fn, "eos must be -1 or a class in [0, C) other than blank"); return -1; }
+    if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) { mk_set_error(fn, "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned"); return -1; }
+    CtcBeamArgs a{};
+    a.logits = logits; a.ld = ld; a.enc_lens = enc_lens;
+    a.B = B; a.Tp = Tp; a.C = C; a.K = K; a.P = beam_width(C, K, eos); a.blank = blank; a.eos = eos;
+    const long rows = (long)B * Tp, Pmax = K < C - 1 ? K : C - 1;
+    char* w = (char*)work;
+    a.lse = (float*)w; w += align256(4 * rows);
+    a.xb = (float*)w; w += align256(4 * rows);
+    a.s_cls = (int*)w; w += align256(4 * rows * Pmax);
+    a.s_lp = (float*)w; w += align256(4 * rows * Pmax);
+    a.rec = (int*)w;
+    hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ctc_beam_sweep_kernel, dim3(B), dim3(SW_THREADS), 0, s, a, nbest, tokens, lens, scores);
+    if (hipGetLastError() != hipSuccess) { mk_set_error(fn, "launch failed"); return -1; }
+    return 0;
+}

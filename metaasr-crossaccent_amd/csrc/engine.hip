@@ -487,6 +487,11 @@ int masr_ctc_loss(const float* logits, const int32_t* targets, const int32_t* tg
                   int B, int C, int blank, float* nll, float* loss, float* grad, float* work, int maxS, void* stream) {
     return mk_ctc_loss(logits, targets, tgt_off, in_len, tgt_len, T, B, C, blank, nll, loss, grad, work, maxS, (hipStream_t)stream);
 }
+int64_t masr_ctc_beam_work_bytes(int B, int Tp, int C, int K) { return mk_ctc_beam_work_bytes(B, Tp, C, K); }
+int masr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                         void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    return mk_ctc_beam_search(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, (hipStream_t)stream);
+}
 
 int masr_profile_enable(masr_model* m, int on) {
     m->prof = on != 0;

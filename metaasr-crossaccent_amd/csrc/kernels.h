@@ -184,6 +184,21 @@ int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStre
 int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
 int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s);                // also advances step[0]
 
+// ---------------------------------------------------------------- CTC prefix beam search (ctc_beam.hip)
+// logits: row of utterance b, frame t at logits + (b*Tp + t)*ld.  P = min(K, emittable classes).  The arrays below are carved from the work buffer.
+struct CtcBeamArgs {
+    const float* logits; long ld;
+    const int* enc_lens;                       // [B] valid frames (clamped to [0, Tp] by the kernels)
+    int B, Tp, C, K, P, blank, eos;            // eos -1 = none
+    float *lse, *xb;                           // [B*Tp] log-sum-exp of the row, x_t(blank)
+    int* s_cls; float* s_lp;                   // [B*Tp][P] the frame's token set S_t and its log-probs
+    int* rec;                                  // [B*Tp][K] back-pointers: parent slot | (emitted class + 1) << 8, 0 in the high part = stay
+};
+int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K);
+// tokens int32 [B][nbest][Tp] (-1 behind each list), lens int32 [B][nbest] (-1 = no entry), scores fp32 [B][nbest] (-inf = no entry)
+int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos, void* work,
+                       int64_t work_bytes, int* tokens, int* lens, float* scores, hipStream_t s);
+
 // ---------------------------------------------------------------- row ops (rowops.hip)
 int mk_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y32, bf16* y16,
                        float* mean, float* rstd, int rows, int E, hipStream_t s);

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "engine_internal.h"
+#include "../../include/masr_test.h"
 
 // The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
 // a.y32[0] / a.y16[0], output a.y32[ND].  Self-attention keys/values of earlier positions live in d.qkv ([rows][slots][3E]);
@@ -125,8 +126,18 @@ static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp)
     a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
 }
 
+// CTC-only beam (masr_recog_ctc_beam): no decoder rows beyond one per utterance; the head's logits [B*Tp][Cp] and the search's work buffer
+// follow the activations
+struct CtcBeamPlan { int K; float** logits; void** work; int64_t* work_bytes; };
+static void plan_ctc_beam(const masr_model* m, Arena& ar, int B, int T, const CtcBeamPlan& cp) {
+    const int Tp = T / 4;
+    *cp.logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    *cp.work_bytes = mk_ctc_beam_work_bytes(B, Tp, m->C, cp.K);
+    *cp.work = ar.get<char>(*cp.work_bytes);
+}
+
 static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
-                         const BeamPlan* beam = nullptr) {
+                         const BeamPlan* beam = nullptr, const CtcBeamPlan* ctc = nullptr) {
     if (!m->P) { mk_set_error("masr_recog", "not bound"); return -1; }
     if (B <= 0 || T < 4) { mk_set_error("masr_recog", "need B >= 1 and T >= 4"); return -1; }
     int Ldec = 0;
@@ -135,10 +146,12 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
         if ((int)(ilens[b] / 4) > Ldec) Ldec = (int)(ilens[b] / 4);
     }
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : Ldec, false);
+    plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : ctc ? 1 : Ldec, false);
     if (beam) plan_beam(m, ar, B, *beam);
+    if (ctc) plan_ctc_beam(m, ar, B, T, *ctc);
     if (ar.off > m->ws_bytes) {
-        mk_set_error("masr_recog", !beam ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+        mk_set_error("masr_recog", ctc ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
+                                   : !beam ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
                                    : beam->P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
                                              : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
         return -2;
@@ -203,6 +216,15 @@ int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int 
     plan_acts(m, ar, a, B, T, K * Lmax, false);
     plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq});
     return m->persist_bytes + ar.off + 4096;
+}
+
+// once per decode, shared by masr_recog_beam_ctc and masr_recog_ctc_beam: the CTC head over the encoder memory (training's GEMM: bf16
+// operands, fp32 logits [B*Tp][Cp])
+static int ctc_head_logits(Ctx& c, float* ctc_logits) {
+    masr_model* m = c.m; Acts& a = m->acts;
+    GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
+    g.C32 = ctc_logits; g.ldc = m->Cp;
+    return gemm(c, g);
 }
 
 static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
@@ -272,12 +294,9 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     CK(project_memory_kv(c));
     CK(mk_beam_init(ba, s));
     if (wts) {
-        // once per decode: the CTC head over the memory (training's GEMM: bf16 operands, fp32 logits), its log-softmax per frame, the
-        // empty hypothesis's state
+        // once per decode: the CTC head over the memory, its log-softmax per frame, the empty hypothesis's state
         ba.att_w = wts[0]; ba.ctc_w = wts[1]; ba.enc_lens = a.enc_lens;
-        GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
-        g.C32 = ctc_logits; g.ldc = m->Cp;
-        CK(gemm(c, g));
+        CK(ctc_head_logits(c, ctc_logits));
         CK(mk_beam_ctc_logsoftmax(ba, ctc_logits, m->Cp, s));
         CK(mk_beam_ctc_init(ba, s));
     }
@@ -306,6 +325,54 @@ int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, in
     if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
     const float wts[2] = {att_w, ctc_w};
     return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn);
+}
+
+int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
+    const char* fn = "masr_ctc_beam_workspace_bytes";
+    if (!m || B <= 0 || T < 4 || K < 1 || K > 64) { mk_set_error(fn, "need B >= 1, T >= 4, 1 <= K <= 64"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    Arena ar{nullptr, 0, 0};
+    Acts a; float* cl; void* w; int64_t wb;
+    plan_acts(m, ar, a, B, T, 1, false);
+    plan_ctc_beam(m, ar, B, T, CtcBeamPlan{K, &cl, &w, &wb});
+    return m->persist_bytes + ar.off + 4096;
+}
+
+int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
+                        float* scores, void* stream) {
+    // CTC prefix beam search on the head alone (ctc_beam.hip): one encoder pass, the head GEMM, one sweep over the T/4 frames
+    const char* fn = "masr_recog_ctc_beam";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
+    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
+    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error(fn, "null pointer"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    float* ctc_logits = nullptr; void* work = nullptr; int64_t work_bytes = 0;
+    const CtcBeamPlan cp{K, &ctc_logits, &work, &work_bytes};
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, nullptr, &cp); if (rc) return rc; }
+    Acts& a = m->acts;
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(ctc_head_logits(c, ctc_logits));
+    CK(mk_ctc_beam_search(ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, work, work_bytes, tokens, lens, scores, s));
+    m->have_acts = false;
+    return 0;
+}
+
+int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens) {
+    // where masr_recog_ctc_beam(m, .., B, T, K, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
+    const char* fn = "masr_test_ctc_beam_logits";
+    if (!m || !m->P || !logits || !ld || !enc_lens) { mk_set_error(fn, "null pointer or model not bound"); return -1; }
+    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    if (B <= 0 || T < 4 || K < 1 || K > 64) { mk_set_error(fn, "need B >= 1, T >= 4, 1 <= K <= 64"); return -1; }
+    Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    Acts a; float* cl = nullptr; void* w = nullptr; int64_t wb = 0;
+    plan_acts(m, ar, a, B, T, 1, false);
+    plan_ctc_beam(m, ar, B, T, CtcBeamPlan{K, &cl, &w, &wb});
+    if (ar.off > m->ws_bytes) { mk_set_error(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"); return -1; }
+    *logits = cl; *ld = m->Cp; *enc_lens = a.enc_lens;
+    return 0;
 }
 
 }  // extern "C"

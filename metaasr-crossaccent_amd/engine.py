@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, check, lib
+from ._cabi import MasrConfig, check, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -288,6 +288,40 @@ class MasrEngine:
         self._last_x = xs
         tok, lens = tok.cpu(), lens.cpu()
         return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
+
+    def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1):
+        """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
+        head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first."""
+        K, N = int(beam_size), int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        need = int(self._l.masr_ctc_beam_workspace_bytes(self.h, B, T, K))
+        check(need if need < 0 else 0, "masr_ctc_beam_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        tok = torch.empty(B, N, T // 4, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self._l.masr_recog_ctc_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, _ptr(tok), _ptr(lens), _ptr(scores),
+                                          self.stream()), "masr_recog_ctc_beam")
+        self._last_x = xs
+        return nbest_lists(tok, lens, scores)
+
+    def last_ctc_beam_logits(self, B, T, K):
+        """test hook (include/masr_test.h masr_test_ctc_beam_logits): what the last recog_ctc_beam of this (B, T, K) searched, as views
+        into the workspace: (head logits fp32 [B, T // 4, ld], enc_lens int32 [B])"""
+        lp, ep, ld = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._l.masr_test_ctc_beam_logits(self.h, B, T, K, C.byref(lp), C.byref(ld), C.byref(ep)), "masr_test_ctc_beam_logits")
+        base, n = self.ws.data_ptr(), B * (T // 4) * ld.value * 4
+        logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
+        return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)
 
     def read_stats(self):
         out = (C.c_float * 4)()

@@ -114,3 +114,9 @@ class MyTransformer:
         (B token lists without sos / eos, scores [B])"""
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_beam(xs_pad, ilens, beam_size, min_step_ratio, max_step_ratio, att_weight, ctc_weight)
+
+    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
+        """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam, hybrid models only): per utterance a list of at most
+        nbest (token list, score), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_ctc_beam(xs_pad, ilens, beam_size, nbest)

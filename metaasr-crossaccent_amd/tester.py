@@ -111,18 +111,35 @@ class Tester:
             self.write_hyp(y.tolist(), hyp)
         return True
 
+    def batch_ctc_beam_decode(self, xs, ilens, ys, olens):
+        for nbest, y in zip(self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size), ys):
+            hyp = nbest[0][0]
+            # (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is applied to keep the Tester's contract)
+            self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
+        return True
+
+    def _beam_size(self):
+        bd = self.config.get('solver', {}).get('beam_decode')
+        if not isinstance(bd, dict) or 'beam_size' not in bd:
+            raise ValueError(f"decode_mode '{self.decode_mode}' needs a solver.beam_decode block with at least beam_size in the config")
+        self.beam_size = int(bd['beam_size'])
+        if not 1 <= self.beam_size <= 64:
+            raise ValueError(f"solver.beam_decode.beam_size must be in [1, 64], got {self.beam_size}")
+        return bd
+
+    def _ctc_beam_settings(self):
+        self._beam_size()
+        if self.model_name != 'blstm' and not self.asr_model.engine.ctc_weight > 0.0:
+            raise ValueError("decode_mode 'ctc_beam' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
+                             "use --decode_mode beam or greedy")
+
     def _beam_settings(self):
         if self.decode_mode == 'lm_beam':
             raise NotImplementedError("lm_beam: this project has no language model to fuse")
         if self.model_name == 'blstm':
             raise NotImplementedError("beam: beam search is only implemented for the transformer (the reference's BLSTM beam "
                                       "decoder is dead code, DESIGN 9); use --decode_mode greedy")
-        bd = self.config.get('solver', {}).get('beam_decode')
-        if not isinstance(bd, dict) or 'beam_size' not in bd:
-            raise ValueError("decode_mode 'beam' needs a solver.beam_decode block with at least beam_size in the config")
-        self.beam_size = int(bd['beam_size'])
-        if not 1 <= self.beam_size <= 64:
-            raise ValueError(f"solver.beam_decode.beam_size must be in [1, 64], got {self.beam_size}")
+        bd = self._beam_size()
         self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
         self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
         ctc_w = self._weight(bd, 'ctc_w', 0.0)
@@ -149,10 +166,14 @@ class Tester:
         return w
 
     def exec(self):
-        if self.decode_mode not in ('greedy', 'beam', 'lm_beam'):
+        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam'):
             raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
         decode = self.batch_greedy_decode
-        if self.decode_mode != 'greedy':
+        if self.decode_mode == 'ctc_beam':
+            self._ctc_beam_settings()
+            decode = self.batch_ctc_beam_decode
+            logger.notice(f"Start CTC prefix beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
+        elif self.decode_mode != 'greedy':
             self._beam_settings()
             decode = self.batch_beam_decode
             logger.notice(f"Start beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
