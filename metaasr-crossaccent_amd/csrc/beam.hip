@@ -15,24 +15,9 @@
 // row order (z descending, token ascending) is also score order there; a score tie inside one row that the rounding made out of two
 // different logits is decided by the logit.  Hence K = 1 picks exactly the greedy arg-max (first maximal logit).
 #include "kernels.h"
+#include "search.h"
 
 namespace {
-
-constexpr float NEG_INF = -__builtin_inff();
-
-__device__ __forceinline__ uint32_t ord_f32(float v) {             // monotone float -> uint32 (larger float, larger key)
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), o, 64) << 32) |
-                                     (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 __global__ void beam_init_kernel(BeamArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,37 +63,10 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamArgs a, const fl
         return;
     }
     const float* z = logits + (long)r * ld;
-    const int no_eos = (st - 1) < a.minlen[u];                   // the hypothesis has st - 1 tokens
-    float mx = NEG_INF;
-    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
-    s = wave_sum(s);
-    const float lse = __logf(s);
-    // K rounds of "largest key below the previous one"; key = (ordered logit, inverted token): unique per token
-    unsigned long long prev = ~0ull;
-    for (int i = 0; i < a.K; ++i) {
-        unsigned long long best = 0;
-        for (int c = lane; c < a.C; c += 64) {
-            if (no_eos && c == a.eos) continue;
-            const unsigned long long key = ((unsigned long long)ord_f32(z[c]) << 32) | (uint32_t)(0x7fffffff - c);
-            if (key < prev && key > best) best = key;
-        }
-        best = wave_max_u64(best);
-        if (lane == 0) {
-            if (best == 0) { lt[i] = -1; ls[i] = NEG_INF; }
-            else {
-                const int c = 0x7fffffff - (int)(uint32_t)best;
-                lt[i] = c; ls[i] = ps + ((z[c] - mx) - lse);
-            }
-        }
-        prev = best;
-        if (best == 0) {                                         // fewer than K tokens: pad the rest of the list
-            for (int k = i + 1 + lane; k < a.K; k += 64) { lt[k] = -1; ls[k] = NEG_INF; }
-            break;
-        }
-    }
+    const bool no_eos = (st - 1) < a.minlen[u];                  // the hypothesis has st - 1 tokens
+    const RowLse l = row_lse(z, a.C, lane);
+    row_top_n<false>(z, a.C, a.K, lane, [&](int c) { return no_eos && c == a.eos; },
+                     [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + ((z[c] - l.mx) - l.log_s); });
 }
 
 // grid B, 64 threads (one wave; lane k = parent rank k).  JOINT (masr_recog_beam_ctc): the row lists are P long, sorted by joint score,
@@ -177,11 +135,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
             if (j == 0 || st >= maxlen || bs >= run_best) a.fin[u] = 1;
         }
     }
-    if (lane == 0) {
-        // the last utterance to finish advances the step (every block has read step[0] before taking its ticket)
-        __threadfence();
-        if (atomicAdd(a.step + 1, 1) == a.B - 1) { a.step[1] = 0; a.step[0] = st + 1; }
-    }
+    if (lane == 0) step_ticket(a.step, st, a.B);                 // the last utterance to finish advances the step
 }
 
 // ---------------------------------------------------------------- joint CTC/attention decoding (masr_recog_beam_ctc)
@@ -193,12 +147,6 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
 //   psi(h+c) = logsumexp(r^n_0, phi_{t-1} + x_t(c) for 1 <= t < T_b);  psi(h+eos) = phi_{T_b-1} (no plain-phi exception)
 // Joint score s(h+c) = s(h) + att_w * lp_att(c | h) + ctc_w * (psi(h+c) - psi(h)), fp32 in that order (no contraction).
 
-__device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e^b); -inf + -inf = -inf, never NaN
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return m + __logf(1.f + __expf(fminf(a, b) - m));
-}
-
 // grid ceil(B*Tp / 4), 256 threads: one wave per frame row b*Tp + t of the head's fp32 logits -> lp[b][c][t] (frames t < T_b only)
 __global__ __launch_bounds__(256) void beam_ctc_logsoftmax_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -206,15 +154,9 @@ __global__ __launch_bounds__(256) void beam_ctc_logsoftmax_kernel(BeamArgs a, co
     const int b = row / a.Tp, t = row % a.Tp;
     if (t >= a.enc_lens[b]) return;
     const float* z = logits + (long)row * ld;
-    float mx = NEG_INF;
-    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
-    s = wave_sum(s);
-    const float lse = __logf(s);
+    const RowLse l = row_lse(z, a.C, lane);
     float* out = const_cast<float*>(a.ctc_lp) + (long)b * a.C * a.Tp + t;
-    for (int c = lane; c < a.C; c += 64) out[(long)c * a.Tp] = (z[c] - mx) - lse;
+    for (int c = lane; c < a.C; c += 64) out[(long)c * a.Tp] = (z[c] - l.mx) - l.log_s;
 }
 
 // grid B, 64 threads, after beam_init_kernel: the empty hypothesis (r^n = -inf, r^b_t = x_0(blank) + ... + x_t(blank), psi 0) in
@@ -240,34 +182,10 @@ __global__ __launch_bounds__(256) void beam_ctc_prebeam_kernel(BeamArgs a, const
     int* pt = a.pre_tok + (long)r * a.P;
     float* pl = a.pre_lp + (long)r * a.P;
     const float* z = logits + (long)r * ld;
-    const int no_eos = (st - 1) < a.minlen[u];
-    float mx = NEG_INF;
-    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
-    s = wave_sum(s);
-    const float lse = __logf(s);
-    unsigned long long prev = ~0ull;
-    for (int i = 0; i < a.P; ++i) {
-        unsigned long long best = 0;
-        for (int c = lane; c < a.C; c += 64) {
-            if (c == 0 || (no_eos && c == a.eos)) continue;
-            const unsigned long long key = ((unsigned long long)ord_f32(z[c]) << 32) | (uint32_t)(0x7fffffff - c);
-            if (key < prev && key > best) best = key;
-        }
-        best = wave_max_u64(best);
-        if (lane == 0) {
-            const int c = 0x7fffffff - (int)(uint32_t)best;
-            pt[i] = best ? c : -1;
-            pl[i] = best ? (z[c] - mx) - lse : NEG_INF;
-        }
-        prev = best;
-        if (best == 0) {
-            for (int k = i + 1 + lane; k < a.P; k += 64) { pt[k] = -1; pl[k] = NEG_INF; }
-            break;
-        }
-    }
+    const bool no_eos = (st - 1) < a.minlen[u];
+    const RowLse l = row_lse(z, a.C, lane);
+    row_top_n<false>(z, a.C, a.P, lane, [&](int c) { return c == 0 || (no_eos && c == a.eos); },
+                     [&](int i, int c) { pt[i] = c; pl[i] = c < 0 ? NEG_INF : (z[c] - l.mx) - l.log_s; });
 }
 
 // grid R, 128 threads: thread i runs the chain of the row's pre-beam candidate i (i < P <= 96), serial over the T_b frames.  The parent's
@@ -362,8 +280,6 @@ __global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __r
 }
 
 }  // namespace
-
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : (mk_set_error(__func__, "launch failed"), -1))
 
 int mk_beam_init(const BeamArgs& a, hipStream_t s) {
     const int n = a.R > a.B ? a.R : a.B;

@@ -97,4 +97,7 @@ __device__ __forceinline__ void dropout_scale4(uint32_t seed, uint32_t site, uin
         if (_e != hipSuccess) { mk_set_error(#expr, hipGetErrorString(_e)); return -1; } \
     } while (0)
 
+// after a kernel launch: 0, or -1 with the launcher's name recorded
+#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : (mk_set_error(__func__, "launch failed"), -1))
+
 void mk_set_error(const char* what, const char* detail);

@@ -12,31 +12,13 @@
 // token, so "h + c is the beam entry h'" is  len(h') == len(h) + 1, parent_hash(h') == hash(h), last(h') == c.  Two different prefixes of
 // one beam with equal length and equal hash would be merged wrongly (DESIGN 5.3 has the odds).
 #include "kernels.h"
+#include "search.h"
 
 namespace {
 
-constexpr float NEG_INF = -__builtin_inff();
 constexpr int SW_THREADS = 256, SW_WAVES = SW_THREADS / 64, KMAX = 64;
 constexpr unsigned long long HASH_EMPTY = 0xcbf29ce484222325ull;
 
-__device__ __forceinline__ uint32_t ord_f32(float v) {             // monotone float -> uint32 (larger float, larger key)
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = ((unsigned long long)(uint32_t)__shfl_xor((int)(v >> 32), o, 64) << 32) |
-                                     (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e^b); -inf + -inf = -inf, never NaN
-    const float m = fmaxf(a, b);
-    if (m == NEG_INF) return NEG_INF;
-    return m + __logf(1.f + __expf(fminf(a, b) - m));
-}
 __device__ __forceinline__ unsigned long long hash_push(unsigned long long h, int c) {
     h = (h ^ (unsigned long long)(c + 1)) * 0x9E3779B97F4A7C15ull;
     return h ^ (h >> 29);
@@ -51,37 +33,14 @@ __global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
     const int b = (int)(row / a.Tp), t = (int)(row % a.Tp);
     if (t >= clamp_len(a.enc_lens[b], a.Tp)) return;
     const float* z = a.logits + row * a.ld;
-    float mx = NEG_INF;
-    for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < a.C; c += 64) s += __expf(z[c] - mx);
-    s = wave_sum(s);
-    const float lse = mx + __logf(s);
+    const RowLse l = row_lse(z, a.C, lane);
+    const float lse = l.mx + l.log_s;
     if (lane == 0) { a.lse[row] = lse; a.xb[row] = z[a.blank] - lse; }
     int* sc = a.s_cls + row * a.P;
     float* sl = a.s_lp + row * a.P;
-    // P rounds of "largest key below the previous one"; key = (ordered logit, inverted class): unique per class
-    unsigned long long prev = ~0ull;
-    for (int i = 0; i < a.P; ++i) {
-        unsigned long long best = 0;
-        for (int c = lane; c < a.C; c += 64) {
-            if (c == a.blank || c == a.eos) continue;
-            const unsigned long long key = ((unsigned long long)ord_f32(z[c] + 0.f) << 32) | (uint32_t)(0x7fffffff - c);   // (-0 orders as +0)
-            if (key < prev && key > best) best = key;
-        }
-        best = wave_max_u64(best);
-        if (lane == 0) {
-            const int c = 0x7fffffff - (int)(uint32_t)best;
-            sc[i] = best ? c : -1;
-            sl[i] = best ? z[c] - lse : NEG_INF;
-        }
-        prev = best;
-        if (best == 0) {                                         // (NaN rows only: P never exceeds the emittable classes)
-            for (int k = i + 1 + lane; k < a.P; k += 64) { sc[k] = -1; sl[k] = NEG_INF; }
-            break;
-        }
-    }
+    // (the row runs out on NaN rows only: P never exceeds the emittable classes)
+    row_top_n<true>(z, a.C, a.P, lane, [&](int c) { return c == a.blank || c == a.eos; },
+                    [&](int i, int c) { sc[i] = c; sl[i] = c < 0 ? NEG_INF : z[c] - lse; });
 }
 
 // grid B, 256 threads.  Candidate index of frame t: parent rank k, then stay (0) or position j in S_t (1 + j): idx = k * (P + 1) + ...,
@@ -247,6 +206,5 @@ int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B,
     a.rec = (int*)w;
     hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(ctc_beam_sweep_kernel, dim3(B), dim3(SW_THREADS), 0, s, a, nbest, tokens, lens, scores);
-    if (hipGetLastError() != hipSuccess) { mk_set_error(fn, "launch failed"); return -1; }
-    return 0;
+    return LAUNCH_OK();
 }

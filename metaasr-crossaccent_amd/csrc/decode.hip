@@ -9,6 +9,7 @@
 // from ONE device integer `*step`, so the launch sequence of a step is parameter-identical for every step and the engine
 // replays it as a hipGraph (engine.hip: masr_recog).
 #include "kernels.h"
+#include "search.h"
 
 namespace {
 
@@ -151,11 +152,7 @@ __global__ __launch_bounds__(256) void recog_argmax_step_kernel(int* step, const
     const float* z = logits + (long)b * ld;
     float mx = -INFINITY; int am = 0x7fffffff;             // (not -3.4e38f: a row whose only finite value is -FLT_MAX must return its index)
     for (int c = threadIdx.x; c < C; c += 256) { const float v = z[c]; if (v > mx) { mx = v; am = c; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(mx, o, 64); const int oa = __shfl_xor(am, o, 64);
-        if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-    }
+    wave_argmax_first(mx, am);
     if (lane == 0) { smx[wave] = mx; sam[wave] = am; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -163,9 +160,7 @@ __global__ __launch_bounds__(256) void recog_argmax_step_kernel(int* step, const
         if (am == 0x7fffffff) am = 0;                        // all-NaN / all -inf row: torch.argmax would still return an index
         const int st = step[0];
         out[(long)(st - 1) * B + b] = am;
-        // the last utterance to finish advances the step (every block has read step[0] before taking its ticket)
-        __threadfence();
-        if (atomicAdd(step + 1, 1) == B - 1) { step[1] = 0; step[0] = st + 1; }
+        step_ticket(step, st, B);                            // the last utterance to finish advances the step
     }
 }
 // fp32 logits of the greedy decode: z[r][c] = bias[c] + sum_k y[r][k] W[c][k] on the fp32 MASTER weights and the fp32 LayerNorm output
@@ -196,8 +191,6 @@ __global__ void recog_step_set_kernel(int* step, int value, int inc) {
 }
 
 }  // namespace
-
-#define LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : (mk_set_error(__func__, "launch failed"), -1))
 
 int mk_skinny_gemm(const SkinnyArgs& g, hipStream_t s) {
     if (g.K % 32 || (g.lda % 8) || (g.ldw % 8) || ((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) {

@@ -97,47 +97,78 @@ static int run_steps(masr_model* m, DecodeGraph& gc, const int (&key)[6], const 
     return 0;
 }
 
-// shared front half of the two decoders: argument checks, activation plan, enc_lens upload, encoder
-// beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
-// rows, and the beam state follows the activations in the same arena
-// joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
-// log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
-struct BeamPlan { int K, Lmax; BeamArgs* args; bf16** step_qkv; int P = 0, Tp = 0; float** ctc_logits = nullptr; };
-static void plan_beam(const masr_model* m, Arena& ar, int B, const BeamPlan& bp) {
-    const int R = B * bp.K, L = bp.Lmax, W = bp.P ? bp.P : bp.K;
-    BeamArgs& a = *bp.args;
-    a = BeamArgs{};
-    a.B = B; a.K = bp.K; a.R = R; a.Lmax = L; a.C = m->C; a.sos = 0; a.eos = m->C - 1;
-    *bp.step_qkv = ar.get<bf16>((int64_t)R * 3 * m->E);
+// argument checks of the entry points: 0, or -1 with the message recorded under the caller's name
+static int check_ctc_head(const char* fn, const masr_model* m) {
+    if (m->ctc_w > 0.f) return 0;
+    mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1;
+}
+static int check_beam_size(const char* fn, int K) {
+    if (K >= 1 && K <= 64) return 0;
+    mk_set_error(fn, "beam size K must be in [1, 64]"); return -1;
+}
+static int check_pointers(const char* fn, const float* xs, const int64_t* ilens, const int32_t* tokens, const int32_t* lens, const float* scores) {
+    if (xs && ilens && tokens && lens && scores) return 0;
+    mk_set_error(fn, "null pointer"); return -1;
+}
+
+// What a decoder plans into the arena: the activations, then its own state behind them.  plan_decode both sizes the workspace (a null
+// arena) and places the buffers in the bound one.
+//   greedy (K = 0): Ldec decoder positions per utterance, nothing else
+//   beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
+//   rows, and the beam state follows
+//   joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
+//   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
+//   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
+//   buffer follow
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; };
+struct DecodeBufs { BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes; };
+
+static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
+    const int R = B * d.K, L = d.Lmax, P = d.P, W = P ? P : d.K;
+    DecodeBufs o{};
+    BeamArgs& a = o.beam;
+    a.B = B; a.K = d.K; a.R = R; a.Lmax = L; a.C = m->C; a.sos = 0; a.eos = m->C - 1;
+    o.step_qkv = ar.get<bf16>((int64_t)R * 3 * m->E);
     a.tab = ar.get<int>(2 * (int64_t)R * L);
     a.tok_hist = ar.get<int>((int64_t)L * R); a.par_hist = ar.get<int>((int64_t)L * R);
     a.score = ar.get<float>(R);
     a.list_tok = ar.get<int>((int64_t)R * W); a.list_score = ar.get<float>((int64_t)R * W);
     int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
     a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
-    if (!bp.P) return;
-    const int P = bp.P, Tp = bp.Tp;
+    if (!P) return o;
     a.P = P; a.Tp = Tp;
-    *bp.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
     a.ctc_lp = ar.get<float>((int64_t)B * m->C * Tp);
     a.ctc_state = ar.get<float2>(2 * (int64_t)R * Tp * P);
     a.psi = ar.get<float>(R); a.src = ar.get<int>(R);
     a.pre_tok = ar.get<int>((int64_t)R * P); a.pre_lp = ar.get<float>((int64_t)R * P);
     a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
+    return o;
+}
+static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, int K) {
+    DecodeBufs o{};
+    o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    o.work_bytes = mk_ctc_beam_work_bytes(B, Tp, m->C, K);
+    o.work = ar.get<char>(o.work_bytes);
+    return o;
+}
+static DecodeBufs plan_decode(const masr_model* m, Arena& ar, Acts& a, int B, int T, int Ldec, const DecodeSpec& d) {
+    plan_acts(m, ar, a, B, T, d.ctc_only ? 1 : d.K ? d.K * d.Lmax : Ldec, false);
+    return d.ctc_only ? plan_ctc_beam(m, ar, B, T / 4, d.K) : d.K ? plan_beam(m, ar, B, T / 4, d) : DecodeBufs{};
+}
+// a decoder's workspace size; args_ok: B, T and the spec are in range (else the error `need`)
+static int64_t decode_workspace_bytes(const char* fn, const masr_model* m, bool args_ok, const char* need, int B, int T, const DecodeSpec& d) {
+    if (!m || !args_ok) { mk_set_error(fn, need); return -1; }
+    if (d.P || d.ctc_only) CK(check_ctc_head(fn, m));
+    Arena ar{nullptr, 0, 0};
+    Acts a;
+    plan_decode(m, ar, a, B, T, 0, d);
+    return m->persist_bytes + ar.off + 4096;
 }
 
-// CTC-only beam (masr_recog_ctc_beam): no decoder rows beyond one per utterance; the head's logits [B*Tp][Cp] and the search's work buffer
-// follow the activations
-struct CtcBeamPlan { int K; float** logits; void** work; int64_t* work_bytes; };
-static void plan_ctc_beam(const masr_model* m, Arena& ar, int B, int T, const CtcBeamPlan& cp) {
-    const int Tp = T / 4;
-    *cp.logits = ar.get<float>((int64_t)B * Tp * m->Cp);
-    *cp.work_bytes = mk_ctc_beam_work_bytes(B, Tp, m->C, cp.K);
-    *cp.work = ar.get<char>(*cp.work_bytes);
-}
-
+// shared front half of the decoders: argument checks, the plan, enc_lens upload, encoder
 static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
-                         const BeamPlan* beam = nullptr, const CtcBeamPlan* ctc = nullptr) {
+                         const DecodeSpec& d = DecodeSpec{}, DecodeBufs* bufs = nullptr) {     // bufs: where the plan put the decoder's state
     if (!m->P) { mk_set_error("masr_recog", "not bound"); return -1; }
     if (B <= 0 || T < 4) { mk_set_error("masr_recog", "need B >= 1 and T >= 4"); return -1; }
     int Ldec = 0;
@@ -146,14 +177,13 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
         if ((int)(ilens[b] / 4) > Ldec) Ldec = (int)(ilens[b] / 4);
     }
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    plan_acts(m, ar, m->acts, B, T, beam ? beam->K * beam->Lmax : ctc ? 1 : Ldec, false);
-    if (beam) plan_beam(m, ar, B, *beam);
-    if (ctc) plan_ctc_beam(m, ar, B, T, *ctc);
+    const DecodeBufs planned = plan_decode(m, ar, m->acts, B, T, Ldec, d);
+    if (bufs) *bufs = planned;
     if (ar.off > m->ws_bytes) {
-        mk_set_error("masr_recog", ctc ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
-                                   : !beam ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
-                                   : beam->P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
-                                             : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
+        mk_set_error("masr_recog", d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
+                                   : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
+                                         : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
         return -2;
     }
     Acts& a = m->acts; m->have_acts = true;
@@ -210,12 +240,8 @@ int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int 
 }
 
 int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
-    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
-    Arena ar{nullptr, 0, 0};
-    Acts a; BeamArgs ba; bf16* sq;
-    plan_acts(m, ar, a, B, T, K * Lmax, false);
-    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq});
-    return m->persist_bytes + ar.off + 4096;
+    return decode_workspace_bytes("masr_beam_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
+                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax});
 }
 
 // once per decode, shared by masr_recog_beam_ctc and masr_recog_ctc_beam: the CTC head over the encoder memory (training's GEMM: bf16
@@ -230,13 +256,8 @@ static int ctc_head_logits(Ctx& c, float* ctc_logits) {
 static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
 
 int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
-    if (!m || B <= 0 || T < 4 || K < 1 || K > 64 || Lmax < 1) { mk_set_error("masr_beam_ctc_workspace_bytes", "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1"); return -1; }
-    if (!(m->ctc_w > 0.f)) { mk_set_error("masr_beam_ctc_workspace_bytes", "the model has no CTC head (masr_create_ctc)"); return -1; }
-    Arena ar{nullptr, 0, 0};
-    Acts a; BeamArgs ba; bf16* sq; float* cl;
-    plan_acts(m, ar, a, B, T, K * Lmax, false);
-    plan_beam(m, ar, B, BeamPlan{K, Lmax, &ba, &sq, beam_prebeam_width(K), T / 4, &cl});
-    return m->persist_bytes + ar.off + 4096;
+    return decode_workspace_bytes("masr_beam_ctc_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
+                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, beam_prebeam_width(K)});
 }
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
@@ -262,8 +283,8 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
     // weights) and replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
-    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
-    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(check_beam_size(fn, K));
+    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (B <= 0) { mk_set_error(fn, "need B >= 1"); return -1; }
     std::vector<int> mx_len(B), mn_len(B);
     int Lmax = 0;
@@ -276,10 +297,10 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
         Lmax = std::max(Lmax, mx_len[b]);
     }
     hipStream_t s = (hipStream_t)stream;
-    BeamArgs ba; bf16* step_qkv = nullptr; float* ctc_logits = nullptr;
-    const BeamPlan bp{K, Lmax, &ba, &step_qkv, wts ? beam_prebeam_width(K) : 0, T / 4, &ctc_logits};
+    DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, &bp); if (rc) return rc; }
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0}, &bufs); if (rc) return rc; }
+    BeamArgs& ba = bufs.beam; bf16* step_qkv = bufs.step_qkv; float* ctc_logits = bufs.ctc_logits;
     Acts& a = m->acts;
     ba.step = a.step_dev;
     {   // per-utterance maxlen / minlen through the next staging slot (the one behind recog_prepare's enc_lens)
@@ -320,7 +341,7 @@ int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, in
     // joint CTC/attention beam (beam.hip): the attention beam's search with the CTC prefix score of the head's log-probs
     const char* fn = "masr_recog_beam_ctc";
     if (!m) { mk_set_error(fn, "null model"); return -1; }
-    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    CK(check_ctc_head(fn, m));
     if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
     if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
     const float wts[2] = {att_w, ctc_w};
@@ -328,14 +349,8 @@ int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, in
 }
 
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
-    const char* fn = "masr_ctc_beam_workspace_bytes";
-    if (!m || B <= 0 || T < 4 || K < 1 || K > 64) { mk_set_error(fn, "need B >= 1, T >= 4, 1 <= K <= 64"); return -1; }
-    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
-    Arena ar{nullptr, 0, 0};
-    Acts a; float* cl; void* w; int64_t wb;
-    plan_acts(m, ar, a, B, T, 1, false);
-    plan_ctc_beam(m, ar, B, T, CtcBeamPlan{K, &cl, &w, &wb});
-    return m->persist_bytes + ar.off + 4096;
+    return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64, "need B >= 1, T >= 4, 1 <= K <= 64", B, T,
+                                  DecodeSpec{K, 0, 0, true});
 }
 
 int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
@@ -343,19 +358,18 @@ int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, in
     // CTC prefix beam search on the head alone (ctc_beam.hip): one encoder pass, the head GEMM, one sweep over the T/4 frames
     const char* fn = "masr_recog_ctc_beam";
     if (!m) { mk_set_error(fn, "null model"); return -1; }
-    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
-    if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
+    CK(check_ctc_head(fn, m));
+    CK(check_beam_size(fn, K));
     if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
-    if (!tokens || !lens || !scores || !ilens || !xs) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     hipStream_t s = (hipStream_t)stream;
-    float* ctc_logits = nullptr; void* work = nullptr; int64_t work_bytes = 0;
-    const CtcBeamPlan cp{K, &ctc_logits, &work, &work_bytes};
+    DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, nullptr, &cp); if (rc) return rc; }
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true}, &bufs); if (rc) return rc; }
     Acts& a = m->acts;
     Ctx c{m, s, 0u, false, 0.f, 0.f};
-    CK(ctc_head_logits(c, ctc_logits));
-    CK(mk_ctc_beam_search(ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, work, work_bytes, tokens, lens, scores, s));
+    CK(ctc_head_logits(c, bufs.ctc_logits));
+    CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, bufs.work, bufs.work_bytes, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
 }
@@ -364,14 +378,13 @@ int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits
     // where masr_recog_ctc_beam(m, .., B, T, K, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
     const char* fn = "masr_test_ctc_beam_logits";
     if (!m || !m->P || !logits || !ld || !enc_lens) { mk_set_error(fn, "null pointer or model not bound"); return -1; }
-    if (!(m->ctc_w > 0.f)) { mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1; }
+    CK(check_ctc_head(fn, m));
     if (B <= 0 || T < 4 || K < 1 || K > 64) { mk_set_error(fn, "need B >= 1, T >= 4, 1 <= K <= 64"); return -1; }
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    Acts a; float* cl = nullptr; void* w = nullptr; int64_t wb = 0;
-    plan_acts(m, ar, a, B, T, 1, false);
-    plan_ctc_beam(m, ar, B, T, CtcBeamPlan{K, &cl, &w, &wb});
+    Acts a;
+    const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, DecodeSpec{K, 0, 0, true});
     if (ar.off > m->ws_bytes) { mk_set_error(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"); return -1; }
-    *logits = cl; *ld = m->Cp; *enc_lens = a.enc_lens;
+    *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
     return 0;
 }
 

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "folds.h"
+#include "search.h"
 
 namespace {
 
@@ -302,11 +303,7 @@ __global__ __launch_bounds__(256) void recog_argmax_kernel(const float* __restri
     const float* z = logits + (long)row * ld;
     float mx = -INFINITY; int am = 0;                        // (not -3.4e38f: a row whose only value above -inf is -FLT_MAX must return its index)
     for (int c = lane; c < C; c += 64) { const float v = z[c]; if (v > mx) { mx = v; am = c; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(mx, o, 64); const int oa = __shfl_xor(am, o, 64);
-        if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-    }
+    wave_argmax_first(mx, am);
     if (lane == 0) out[(row % L) * B + row / L] = am;
 }
 
@@ -326,7 +323,8 @@ __global__ __launch_bounds__(256) void ls_ce_kernel(const float* __restrict__ lo
     const int g = gold[row];
     float mx = -INFINITY; int amax = 0;                      // (as recog_argmax_kernel)
     for (int c = lane; c < C; c += 64) { const float v = z[c]; if (v > mx) { mx = v; amax = c; } }
-    // wave arg-max, ties -> lowest index (torch max(1) returns the first maximal index on CPU)
+    // wave arg-max, ties -> lowest index (torch max(1) returns the first maximal index on CPU).  search.h's wave_argmax_first spelled
+    // out: this kernel is on the training step, and through the helper its registers are allocated differently
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float om = __shfl_xor(mx, o, 64); const int oa = __shfl_xor(amax, o, 64);

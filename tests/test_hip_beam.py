@@ -13,9 +13,9 @@ import beam_ref  # noqa: E402
 from masr_amd._cabi import MasrError, lib  # noqa: E402
 from masr_amd.engine import MasrEngine  # noqa: E402
 from oracle import ref_cpu  # noqa: E402
-from oracle.make_goldens import TINY, ODIM, synth_batch, write_toy_shard  # noqa: E402
+from oracle.make_goldens import TINY, ODIM, synth_batch  # noqa: E402
+from decode_util import C_SMALL, make_tester, peaked_state_dict  # noqa: E402
 from test_hip_engine import HKUST  # noqa: E402
-from test_hip_fomaml import make_run  # noqa: E402
 
 EOS = ODIM - 1
 # Against the CPU restatement: a random-init model with 367 classes has near-flat log-probabilities, so the K-th and (K+1)-th
@@ -25,15 +25,6 @@ EOS = ODIM - 1
 # difference: of the order of 1e-4 nats per log-probability.  DELTA = 0.02 nats keeps a margin of two orders of magnitude over
 # that and still leaves most utterances qualified (the test prints how many; the worst score difference is printed too).
 DELTA = 0.02
-C_SMALL, OUT_SCALE = 12, 10.0
-
-
-def peaked_state_dict(cfg, seed):
-    sd = ref_cpu.deterministic_state_dict(cfg, C_SMALL, seed=seed)
-    sd["char_trans.weight"] = sd["char_trans.weight"] * OUT_SCALE
-    if "pre_embed.weight" in sd:
-        sd["pre_embed.weight"] = sd["char_trans.weight"]
-    return sd
 
 
 @pytest.fixture(scope="module")
@@ -172,23 +163,8 @@ def test_beam_errors(eng):
     assert l.masr_beam_workspace_bytes(eng.h, 1, 40, 65, 10) < 0 and b"1 <= K <= 64" in l.masr_last_error()
 
 
-def _tester(tmp_path, monkeypatch, mode, beam_decode=None, model_name="transformer", resume=False, bs=4):
-    from masr_amd.tester import Tester
-    monkeypatch.chdir(tmp_path)
-    cfg, paras, id2accent = make_run(tmp_path)
-    if beam_decode is not None:
-        cfg["solver"]["beam_decode"] = beam_decode
-    test_dir = tmp_path / "data" / "african" / "test"
-    if not test_dir.exists():
-        write_toy_shard(tmp_path / "data", "african", "test", 6, seed=300)
-    paras.accent, paras.eval_suffix, paras.pretrain_suffix, paras.algo = "af", "ev", None, "no"
-    paras.test_model, paras.decode_suffix, paras.decode_mode, paras.decode_batch_size = "model.wer.best", f"{mode}_decode", mode, bs
-    paras.model_name, paras.resume = model_name, resume
-    log_dir = tmp_path / "testing-logs" / "evaluation" / "gold" / "no" / "ev" / "ev" / "african" / "0"
-    if not (log_dir / "model.wer.best").exists():
-        log_dir.mkdir(parents=True, exist_ok=True)
-        torch.save(ref_cpu.deterministic_state_dict(cfg["asr_model"], ODIM, seed=7), log_dir / "model.wer.best")
-    return Tester(cfg, paras, id2accent), log_dir
+def _tester(*args, **kw):
+    return make_tester(*args, **kw)[:2]
 
 
 def test_tester_beam_end_to_end(tmp_path, monkeypatch):

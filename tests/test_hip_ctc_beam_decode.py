@@ -19,11 +19,9 @@ from masr_amd._cabi import MasrError, lib  # noqa: E402
 from masr_amd.blstm_engine import BlstmEngine  # noqa: E402
 from masr_amd.engine import MasrEngine  # noqa: E402
 from oracle import blstm_cpu, ref_cpu  # noqa: E402
-from oracle.make_goldens import BLSTM_TINY, ODIM, TINY, synth_batch, write_toy_shard  # noqa: E402
-from test_hip_beam import C_SMALL  # noqa: E402
-from test_hip_joint_beam import DELTA as ENC_DELTA  # noqa: E402
-from test_hip_joint_beam import _tester as _joint_tester  # noqa: E402
-from test_hip_joint_beam import joint_engine, joint_state_dict  # noqa: E402
+from oracle.make_goldens import BLSTM_TINY, ODIM, TINY, synth_batch  # noqa: E402
+from decode_util import JOINT_DELTA as ENC_DELTA  # noqa: E402
+from decode_util import C_SMALL, joint_engine, joint_state_dict, make_tester  # noqa: E402
 
 BLSTM_HEAD_SCALE = 30.0
 BLSTM_BATCHES = ((22, [57, 57, 44, 12]), (24, [36, 28, 20, 13]))
@@ -96,25 +94,11 @@ def test_hybrid_ctc_beam_vs_restatement_and_plain_model_errors():
 
 
 def _blstm_tester(tmp_path, monkeypatch, mode, bs, beam_decode, resume=False):
-    from types import SimpleNamespace
-    from masr_amd.tester import Tester
-    monkeypatch.chdir(tmp_path)
-    data = tmp_path / "data"
-    if not (data / "units.txt").exists():
-        data.mkdir(exist_ok=True)
-        write_toy_shard(data, "african", "test", 6, seed=300)
-        (data / "units.txt").write_text("".join(f"u{i} {i}\n" for i in range(1, 366)))
-    cfg = {"asr_model": dict(BLSTM_TINY), "solver": {"setting": "gold", "data_root": str(data), "spm_mapping": str(data / "units.txt"),
-                                                     "spm_model": "unused"}}
-    if beam_decode is not None:
-        cfg["solver"]["beam_decode"] = beam_decode
-    log_dir = tmp_path / "testing-logs" / "evaluation" / "gold" / "no" / "ev" / "ev" / "african" / "0"
-    log_dir.mkdir(parents=True, exist_ok=True)
-    torch.save(_blstm_sd(), log_dir / "model.wer.best")
-    paras = SimpleNamespace(accent="af", algo="no", pretrain_suffix=None, eval_suffix="ev", runs=0, model_name="blstm", test_model="model.wer.best",
-                            decode_suffix=f"{mode}_decode", decode_mode=mode, decode_batch_size=bs, njobs=1, resume=resume, overwrite=True,
-                            is_memmap=True, device="cuda:0")
-    return Tester(cfg, paras, {"af": "african"}), log_dir
+    return make_tester(tmp_path, monkeypatch, mode, beam_decode, blstm_sd=_blstm_sd(), bs=bs, resume=resume)[:2]
+
+
+def _joint_tester(tmp_path, monkeypatch, beam_decode, hybrid, **kw):
+    return make_tester(tmp_path, monkeypatch, "beam", beam_decode, hybrid=hybrid, **kw)
 
 
 def _run(t):

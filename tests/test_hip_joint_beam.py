@@ -14,36 +14,13 @@ import joint_beam_ref as jr  # noqa: E402
 from masr_amd._cabi import MasrError, lib  # noqa: E402
 from masr_amd.engine import MasrEngine  # noqa: E402
 from oracle import ref_cpu  # noqa: E402
-from oracle.make_goldens import TINY, ODIM, synth_batch, write_toy_shard  # noqa: E402
-from test_hip_beam import C_SMALL, peaked_state_dict  # noqa: E402
+from oracle.make_goldens import TINY, ODIM, synth_batch  # noqa: E402
+from decode_util import JOINT_DELTA as DELTA  # noqa: E402
+from decode_util import joint_engine, joint_state_dict, make_tester  # noqa: E402
 from test_hip_engine import HKUST  # noqa: E402
-from test_hip_fomaml import make_run  # noqa: E402
 
-# The 12-class peaked model of test_hip_beam, plus a CTC head (hybrid_ref.with_head) scaled by HEAD_SCALE so that its log-probs spread.
-# The random decoder prefers token 0 (sos, which is also the CTC blank and never a joint candidate); its bias is lowered so that the
-# attention term ranks real tokens.
-# Tolerances: the joint score carries the CTC prefix score, a log-sum over T_b frames of the head's log-probs.  The engine's encoder
-# memory differs from the restatement's by bf16-level rounding (test_hip_beam), and the scaled head turns that into ~1e-2 nats per
-# frame of log-prob: measured score differences reach 0.08 nats at -2.7 on TINY and 0.2 nats at -90 on hkust geometry.  So DELTA is
-# 0.05 nats (test_hip_beam: 0.02) and the score tolerance 0.1 + 3e-3 |score|; a near-tie under that noise can swap a hypothesis, so
-# only utterances whose every decision gap exceeds DELTA are compared, and the count that qualifies is checked over all weight pairs.
-DELTA = 0.05
-HEAD_SCALE = 6.0
+# The model, DELTA and the tolerances: decode_util.py (JOINT_DELTA).
 WEIGHTS = [(0.5, 0.5), (0.7, 0.3), (0.0, 1.0)]
-
-
-def joint_state_dict(cfg, seed):
-    sd = hybrid_ref.with_head(peaked_state_dict(cfg, seed), C_SMALL, seed=seed + 100)
-    sd[hybrid_ref.HEAD[0]] = sd[hybrid_ref.HEAD[0]] * HEAD_SCALE
-    sd["char_trans.bias"] = sd["char_trans.bias"].clone()
-    sd["char_trans.bias"][0] = -30.0
-    return sd
-
-
-def joint_engine(cfg, sd, C=C_SMALL):
-    e = MasrEngine(dict(cfg, ctc_weight=0.3), C)
-    e.load_state_dict(sd)
-    return e
 
 
 @pytest.fixture(scope="module")
@@ -209,26 +186,8 @@ def test_joint_errors(tiny):
     assert need >= 2 * 320 * 250 * 30 * 8
 
 
-def _tester(tmp_path, monkeypatch, beam_decode, hybrid, bs=4, suffix="beam_decode"):
-    from masr_amd.tester import Tester
-    monkeypatch.chdir(tmp_path)
-    cfg, paras, id2accent = make_run(tmp_path)
-    if hybrid:
-        cfg["asr_model"]["ctc_weight"] = 0.3
-    cfg["solver"]["beam_decode"] = beam_decode
-    test_dir = tmp_path / "data" / "african" / "test"
-    if not test_dir.exists():
-        write_toy_shard(tmp_path / "data", "african", "test", 6, seed=300)
-    paras.accent, paras.eval_suffix, paras.pretrain_suffix, paras.algo = "af", "ev", None, "no"
-    paras.test_model, paras.decode_suffix, paras.decode_mode, paras.decode_batch_size = "model.wer.best", suffix, "beam", bs
-    paras.model_name, paras.resume, paras.overwrite = "transformer", False, True
-    log_dir = tmp_path / "testing-logs" / "evaluation" / "gold" / "no" / "ev" / "ev" / "african" / "0"
-    log_dir.mkdir(parents=True, exist_ok=True)
-    sd = ref_cpu.deterministic_state_dict(cfg["asr_model"], ODIM, seed=7)
-    if hybrid:
-        sd = hybrid_ref.with_head(sd, ODIM, seed=3)
-    torch.save(sd, log_dir / "model.wer.best")
-    return Tester(cfg, paras, id2accent), log_dir, sd, cfg
+def _tester(tmp_path, monkeypatch, beam_decode, hybrid, **kw):
+    return make_tester(tmp_path, monkeypatch, "beam", beam_decode, hybrid=hybrid, **kw)
 
 
 def test_tester_joint_beam_end_to_end(tmp_path, monkeypatch):
