@@ -166,6 +166,41 @@ int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
  * Valid until the next call that uses the workspace. */
 int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens);
 
+/* ---- the BLSTM path's LSTM kernels alone (lstm.hip, lstm_rec.hip; tests/test_hip_lstm_kernels.py).  Rows are batch-first (b * T + t), the gate
+ * axis is unit-major (row / column u * 4 + g, g in torch's order i, f, g, o), index 0 / 1 = forward / reverse direction, KP = H rounded up to a
+ * multiple of 32.  Each entry vets on the host what the kernel would index with, calls the launcher and synchronises the stream.
+ * The weight shadows of one direction of one layer (mk_lstm_shadows): wih fp32 [4H][K], whh fp32 [4H][H], bih / bhh fp32 [4H] in torch's row order
+ * g * H + u -> wih16 bf16 [4H][K] (unit-major rows; pc > 0: column d * pc + c holds torch's column c * pd + d, K == pc * pd), its transpose
+ * wihT16 [K][4H], whh16 bf16 [4H][KP] (columns H .. KP zero), whhT16 bf16 [H][4H], bias fp32 [4H] = bih + bhh (unit-major). */
+int masr_test_lstm_shadows(const float* wih, const float* whh, const float* bih, const float* bhh, int H, int K, int pc, int pd, uint16_t* wih16,
+                           uint16_t* wihT16, uint16_t* whh16, uint16_t* whhT16, float* bias, void* stream);
+/* a gradient back to torch's order (mk_lstm_unperm): src fp32 [4H][K] (unit-major rows, the shadow's column order) -> dst [4H][K] and, when given,
+ * dst2 with the same values (the two biases, K = 1) */
+int masr_test_lstm_unperm(const float* src, float* dst, float* dst2, int H, int K, int pc, int pd, void* stream);
+/* the recurrence forward through time, both directions: lens int32 [B], gx0 / gx1 fp32 [B*T][4H] (input contribution + biases), whh16_0 / whh16_1
+ * bf16 [4H][KP] -> y16 bf16 [B*T][2H] (forward | reverse halves; zero at t >= len), act0 / act1 fp32 [B*T][4H] and c0 / c1 fp32 [B*T][H] (rows t >= len
+ * are not written).  resident == 0: one launch per timestep (mk_lstm_fwd_steps); resident == 1: one launch (mk_lstm_fwd_rec) with exchange words and an
+ * error word of the entry's own -- a non-zero error word after the launch returns < 0 ("timed out").  The ping-pong and running-state buffers are the
+ * entry's.  Refuses lens outside [1, T] and, with resident == 1, shapes for which the resident recurrence is not built (B > 32, KP > 384, 4H % 32). */
+int masr_test_lstm_fwd(int resident, int B, int T, int H, const int32_t* lens, const float* gx0, const float* gx1, const uint16_t* whh16_0,
+                       const uint16_t* whh16_1, uint16_t* y16, float* act0, float* act1, float* c0, float* c1, void* stream);
+/* the recurrence backward through time: dy fp32 [B*T][2H], the forward's act / c, whhT16_0 / whhT16_1 bf16 [H][4H] -> dz16_0 / dz16_1 bf16 [B*T][4H]
+ * (zero at t >= len).  mk_lstm_bwd_steps / mk_lstm_bwd_rec; the refusals of masr_test_lstm_fwd, and 4H % 32 != 0 in both forms. */
+int masr_test_lstm_bwd(int resident, int B, int T, int H, const int32_t* lens, const float* dy, const float* act0, const float* act1, const float* c0,
+                       const float* c1, const uint16_t* whhT16_0, const uint16_t* whhT16_1, uint16_t* dz16_0, uint16_t* dz16_1, void* stream);
+/* h_{t-1} as the forward pass saw it (mk_lstm_hprev): y16 bf16 [B*T][2H] -> hp0 [B*T][KP] = y16[b][t-1][0:H], hp1 = y16[b][t+1][H:2H], zero at the
+ * sequence ends and in columns H .. KP */
+int masr_test_lstm_hprev(const uint16_t* y16, uint16_t* hp0, uint16_t* hp1, int B, int T, int H, int KP, void* stream);
+/* x fp32 [rows][C] -> y bf16 [rows][Cp], columns C .. Cp zero (mk_cast_rows_pad) */
+int masr_test_cast_rows_pad(const float* x, uint16_t* y, int64_t rows, int C, int Cp, void* stream);
+/* dy == NULL: y32 [n] = tanh(x [n]), out16 = bf16(y32) (mk_tanh_fwd); else out16 [n] = bf16(dy (1 - x^2)) with x = the forward's y32 (mk_tanh_bwd) */
+int masr_test_tanh(const float* x, const float* dy, float* y32, uint16_t* out16, int64_t n, void* stream);
+/* rows (b, t >= lens[b]) of x32 fp32 / x16 bf16 [B*T][C] (either may be null) -> 0 (mk_mask_rows) */
+int masr_test_mask_rows(float* x32, uint16_t* x16, const int32_t* lens, int B, int T, int C, void* stream);
+/* time sub-sampling.  dys == NULL: ys bf16 [B][Tout][C] = y bf16 [B][Tin][C] rows t' * sub (mk_subsample_rows, C % 8 == 0); else its backward
+ * dy fp32 [B][Tin][C] = dys fp32 [B][Tout][C] at t % sub == 0, zero elsewhere (mk_subsample_rows_bwd, C % 4 == 0).  Tout == ceil(Tin / sub). */
+int masr_test_subsample_rows(const uint16_t* y, uint16_t* ys, const float* dys, float* dy, int B, int Tin, int Tout, int sub, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,15 @@ _SIGS = {
     "masr_test_layernorm": (i32, [vp] * 13 + [i32, i32, f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_attention_dropout_bwd": (i32, [vp] * 10 + [i32] * 6 + [f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "masr_test_lstm_shadows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "masr_test_lstm_unperm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "masr_test_lstm_fwd": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_lstm_bwd": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_lstm_hprev": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "masr_test_cast_rows_pad": (i32, [vp, vp, i64, i32, i32, vp]),
+    "masr_test_tanh": (i32, [vp, vp, vp, vp, i64, vp]),
+    "masr_test_mask_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "masr_test_subsample_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_NAMES = ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "conv2_dgrad", "conv3_dgrad", "conv4_dgrad", "conv2_wgrad",

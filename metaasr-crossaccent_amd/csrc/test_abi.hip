@@ -386,4 +386,141 @@ int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
     return 0;
 }
 
+// ---- the BLSTM path's LSTM kernels alone (tests/test_hip_lstm_kernels.py)
+static inline bool test_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline int test_kp(int H) { return (H + 31) / 32 * 32; }
+int masr_test_lstm_shadows(const float* wih, const float* whh, const float* bih, const float* bhh, int H, int K, int pc, int pd, uint16_t* wih16,
+                           uint16_t* wihT16, uint16_t* whh16, uint16_t* whhT16, float* bias, void* stream) {
+    const char* fn = "masr_test_lstm_shadows";
+    if (!wih || !whh || !bih || !bhh || !wih16 || !wihT16 || !whh16 || !whhT16 || !bias) { mk_set_error(fn, "null pointer"); return -1; }
+    if (H < 1 || K < 1 || pc < 0 || (pc > 0 && (pd < 1 || (int64_t)pc * pd != K))) { mk_set_error(fn, "need H, K >= 1 and, with pc > 0, K == pc * pd"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_lstm_shadows(wih, whh, bih, bhh, H, K, K, test_kp(H), (bf16*)wih16, (bf16*)wihT16, (bf16*)whh16, (bf16*)whhT16, bias, pc, pd, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_lstm_unperm(const float* src, float* dst, float* dst2, int H, int K, int pc, int pd, void* stream) {
+    const char* fn = "masr_test_lstm_unperm";
+    if (!src || !dst) { mk_set_error(fn, "null pointer"); return -1; }
+    if (H < 1 || K < 1 || pc < 0 || (pc > 0 && (pd < 1 || (int64_t)pc * pd != K))) { mk_set_error(fn, "need H, K >= 1 and, with pc > 0, K == pc * pd"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_lstm_unperm(src, dst, dst2, H, K, pc, pd, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+// what both recurrence entries vet: sizes, lens in [1, T] (read back), the resident form's shapes
+static int test_lstm_vet(const char* fn, int resident, int B, int T, int H, const int32_t* lens, bool bwd, hipStream_t s) {
+    if (resident != 0 && resident != 1) { mk_set_error(fn, "resident must be 0 or 1"); return -1; }
+    if (B < 1 || T < 1 || H < 1 || (int64_t)B * T * 4 * H > 0x7fffffffLL) { mk_set_error(fn, "need B, T, H >= 1 and B * T * 4H < 2^31"); return -1; }
+    if (bwd && (4 * H) % 32) { mk_set_error(fn, "4H must be a multiple of 32"); return -1; }
+    if (resident && !mk_lstm_rec_ok(B, H, test_kp(H))) { mk_set_error(fn, "shape not covered by the resident recurrence"); return -1; }
+    std::vector<int> hl;
+    CK(test_read_ints(lens, (size_t)B, hl, s));
+    for (int n : hl) if (n < 1 || n > T) { mk_set_error(fn, "lens must lie in [1, T]"); return -1; }
+    return 0;
+}
+// the entry's own scratch: h ping-pong bf16 [2][2][B][KP] | running state fp32 [2][B][H] | exchange words | the error word
+struct TestLstmScratch {
+    char* base = nullptr; bf16* h16[2][2]; float* cstate[2]; unsigned long long* words; int* err;
+    int alloc(int B, int H, int KP, hipStream_t s) {
+        const size_t hb = sizeof(bf16) * (size_t)B * KP, cb = sizeof(float) * (size_t)B * H, wb = sizeof(unsigned long long) * (size_t)mk_lstm_rec_words(B, H);
+        const size_t hb_al = (hb + 255) / 256 * 256, cb_al = (cb + 255) / 256 * 256, wb_al = (wb + 255) / 256 * 256;
+        const size_t total = wb_al + 4 * hb_al + 2 * cb_al + 256;
+        HIP_CHECK_RET(hipMalloc(&base, total));
+        if (hipMemsetAsync(base, 0, total, s) != hipSuccess) { mk_set_error("masr_test_lstm", "memset failed"); return -1; }
+        char* p = base;
+        words = reinterpret_cast<unsigned long long*>(p); p += wb_al;      // (the exchange words start the allocation: 16-byte loads through a buffer descriptor)
+        for (int d = 0; d < 2; ++d) for (int i = 0; i < 2; ++i) { h16[d][i] = reinterpret_cast<bf16*>(p); p += hb_al; }
+        for (int d = 0; d < 2; ++d) { cstate[d] = reinterpret_cast<float*>(p); p += cb_al; }
+        err = reinterpret_cast<int*>(p);
+        return 0;
+    }
+    ~TestLstmScratch() { if (base) hipFree(base); }
+    // after the launch: the stream is drained, the error word read back
+    int finish(const char* fn, int resident, hipStream_t s) {
+        int e = 0;
+        if (resident) HIP_CHECK_RET(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        if (e != 0) { mk_set_error(fn, "the resident recurrence timed out waiting for a peer workgroup"); return -2; }
+        return 0;
+    }
+};
+int masr_test_lstm_fwd(int resident, int B, int T, int H, const int32_t* lens, const float* gx0, const float* gx1, const uint16_t* whh16_0,
+                       const uint16_t* whh16_1, uint16_t* y16, float* act0, float* act1, float* c0, float* c1, void* stream) {
+    const char* fn = "masr_test_lstm_fwd";
+    if (!lens || !gx0 || !gx1 || !whh16_0 || !whh16_1 || !y16 || !act0 || !act1 || !c0 || !c1) { mk_set_error(fn, "null pointer"); return -1; }
+    if (!test_al16(whh16_0) || !test_al16(whh16_1) || !test_al16(act0) || !test_al16(act1)) { mk_set_error(fn, "whh16 and act must be 16-byte aligned"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(test_lstm_vet(fn, resident, B, T, H, lens, false, s));
+    const int KP = test_kp(H);
+    TestLstmScratch w;
+    CK(w.alloc(B, H, KP, s));
+    LstmStepArgs a{}; a.B = B; a.T = T; a.H = H; a.KP = KP; a.lens = lens; a.y16 = (bf16*)y16;
+    a.whh16[0] = (const bf16*)whh16_0; a.whh16[1] = (const bf16*)whh16_1; a.gx[0] = gx0; a.gx[1] = gx1; a.act[0] = act0; a.act[1] = act1; a.c[0] = c0; a.c[1] = c1;
+    for (int d = 0; d < 2; ++d) { a.h16[d][0] = w.h16[d][0]; a.h16[d][1] = w.h16[d][1]; a.cstate[d] = w.cstate[d]; }
+    if (resident) CK(mk_lstm_fwd_rec(a, w.words, w.err, s));
+    else CK(mk_lstm_fwd_steps(a, s));
+    return w.finish(fn, resident, s);
+}
+int masr_test_lstm_bwd(int resident, int B, int T, int H, const int32_t* lens, const float* dy, const float* act0, const float* act1, const float* c0,
+                       const float* c1, const uint16_t* whhT16_0, const uint16_t* whhT16_1, uint16_t* dz16_0, uint16_t* dz16_1, void* stream) {
+    const char* fn = "masr_test_lstm_bwd";
+    if (!lens || !dy || !act0 || !act1 || !c0 || !c1 || !whhT16_0 || !whhT16_1 || !dz16_0 || !dz16_1) { mk_set_error(fn, "null pointer"); return -1; }
+    if (!test_al16(whhT16_0) || !test_al16(whhT16_1) || !test_al16(act0) || !test_al16(act1) || !test_al16(dz16_0) || !test_al16(dz16_1)) {
+        mk_set_error(fn, "whhT16, act and dz16 must be 16-byte aligned"); return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CK(test_lstm_vet(fn, resident, B, T, H, lens, true, s));
+    const int KP = test_kp(H);
+    TestLstmScratch w;
+    CK(w.alloc(B, H, KP, s));
+    LstmStepArgs a{}; a.B = B; a.T = T; a.H = H; a.KP = KP; a.lens = lens; a.dy = dy;
+    a.whhT16[0] = (const bf16*)whhT16_0; a.whhT16[1] = (const bf16*)whhT16_1; a.act[0] = const_cast<float*>(act0); a.act[1] = const_cast<float*>(act1);
+    a.c[0] = const_cast<float*>(c0); a.c[1] = const_cast<float*>(c1); a.dz16[0] = (bf16*)dz16_0; a.dz16[1] = (bf16*)dz16_1;
+    for (int d = 0; d < 2; ++d) { a.h16[d][0] = w.h16[d][0]; a.h16[d][1] = w.h16[d][1]; a.cstate[d] = w.cstate[d]; }
+    if (resident) CK(mk_lstm_bwd_rec(a, w.words, w.err, s));
+    else CK(mk_lstm_bwd_steps(a, s));
+    return w.finish(fn, resident, s);
+}
+int masr_test_lstm_hprev(const uint16_t* y16, uint16_t* hp0, uint16_t* hp1, int B, int T, int H, int KP, void* stream) {
+    if (!y16 || !hp0 || !hp1 || B < 1 || T < 1 || H < 1 || KP < H) { mk_set_error("masr_test_lstm_hprev", "null pointer, B, T, H < 1 or KP < H"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_lstm_hprev((const bf16*)y16, (bf16*)hp0, (bf16*)hp1, B, T, H, KP, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_cast_rows_pad(const float* x, uint16_t* y, int64_t rows, int C, int Cp, void* stream) {
+    if (!x || !y || rows < 1 || C < 1 || Cp < C) { mk_set_error("masr_test_cast_rows_pad", "null pointer, rows, C < 1 or Cp < C"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_cast_rows_pad(x, (bf16*)y, (long)rows, C, Cp, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_tanh(const float* x, const float* dy, float* y32, uint16_t* out16, int64_t n, void* stream) {
+    if (!x || !out16 || (!dy && !y32) || n < 1) { mk_set_error("masr_test_tanh", "null pointer or n < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (dy) CK(mk_tanh_bwd(dy, x, (bf16*)out16, (long)n, s));
+    else CK(mk_tanh_fwd(x, y32, (bf16*)out16, (long)n, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_mask_rows(float* x32, uint16_t* x16, const int32_t* lens, int B, int T, int C, void* stream) {
+    if (!lens || B < 1 || T < 1 || C < 1) { mk_set_error("masr_test_mask_rows", "null lens or B, T, C < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_mask_rows(x32, (bf16*)x16, lens, B, T, C, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_subsample_rows(const uint16_t* y, uint16_t* ys, const float* dys, float* dy, int B, int Tin, int Tout, int sub, int C, void* stream) {
+    const char* fn = "masr_test_subsample_rows";
+    if (dys ? !dy : (!y || !ys)) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B < 1 || Tin < 1 || C < 1) { mk_set_error(fn, "need B, Tin, C >= 1"); return -1; }
+    if (dys ? (!test_al16(dys) || !test_al16(dy)) : (!test_al16(y) || !test_al16(ys))) { mk_set_error(fn, "operands must be 16-byte aligned"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    if (dys) CK(mk_subsample_rows_bwd(dys, dy, B, Tin, Tout, sub, C, s));
+    else CK(mk_subsample_rows((const bf16*)y, (bf16*)ys, B, Tin, Tout, sub, C, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // extern "C"
