@@ -254,6 +254,37 @@ int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K);
 int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
                         float* scores, void* stream);
 
+/* Attention rescoring of an N-best list (hybrid models of masr_create_ctc; the two-pass decode WeNet calls "attention
+ * rescoring").  For utterance b and list entry n with tokens h (length l >= 0, no sos / eos) and first-pass score c(b, n):
+ *   decoder input  [sos, h_0 .. h_{l-1}] padded with eos, targets [h_0 .. h_{l-1}, eos] padded with -1; L = 1 + the longest live l of the
+ *                  call.  The decoder runs ONCE, teacher-forced, over all B * N entries (the pass of masr_run_batch(MASR_EVAL): bf16-operand
+ *                  logits GEMM, fp32 logits);
+ *   att(b, n)      = sum_{i = 0 .. l} log_softmax(z_i)[target_i], l + 1 terms; the log-softmax in fp32 over the odim classes, the sum in
+ *                  fp32, position ascending, by one thread: a result does not depend on the launch geometry;
+ *   score          = att_w * att + ctc_w * c in fp32 (two rounded products, one rounded sum; the ctc term is left out when ctc_w == 0);
+ *   output order   score descending, then first-pass rank ascending.  Entries without a list (lens -1) stay last, in their first-pass
+ *                  order, with lens -1 and score = att = -inf.
+ * Results (device): tokens int32 [B][N][ld] (rows copied from the first pass), lens int32 [B][N], scores / att / ctc fp32 [B][N] (ctc:
+ * the first-pass scores, copied bit for bit), order int32 [B][N] = the first-pass rank of output entry j.  Needs a CTC head, att_w > 0,
+ * ctc_w >= 0 (both finite) and 1 <= N <= K <= 64; otherwise -1.
+ *   masr_recog_rescore  the first pass is the CTC prefix beam of masr_recog_ctc_beam(K, nbest = N) on the same encoder pass; ld = T / 4.
+ *   masr_rescore_nbest  the first pass is the caller's: tokens_in int32 [B][N][ld_tok], lens_in int32 [B][N] (-1 = no entry, else in
+ *                       [0, ld_tok]), ctc_in fp32 [B][N], device arrays that the outputs may not overlap; ld = ld_tok < 3000.  Every token
+ *                       of a live list must lie in [1, odim - 2]; a list with another token is refused with -1.  Runs the encoder and the
+ *                       second pass.
+ * Both copy the list lengths (masr_rescore_nbest: the lists) to the host between the passes and wait for the stream there -- the ONE
+ * host synchronisation of the call: the decoder pass is launched for L positions, not for the Lmax planned.
+ * Workspace: masr_rescore_workspace_bytes(B, T, K, N, Lmax) bound with masr_bind, Lmax = the longest hypothesis planned for (the decoder is
+ * planned for N * (Lmax + 1) positions per utterance).  masr_recog_rescore needs Lmax >= max(floor(ilens / 4)) (T / 4 always suffices: a
+ * CTC hypothesis is no longer than its frames); masr_rescore_nbest (pass K = N) needs Lmax >= its longest live list.  A call whose plan
+ * does not fit the bound workspace returns -2, as the other decoders do. */
+int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax);
+int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
+                       int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream);
+int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,
+                       const int32_t* lens_in, const float* ctc_in, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
+                       float* ctc, int32_t* order, void* stream);
+
 /* Levenshtein distance of two id sequences (host-side; replaces the `editdistance` extension the reference's metric
  * imports, src/monitor/metric.py:4,66,87).  Returns the distance, < 0 on bad arguments. */
 int64_t masr_edit_distance(const int32_t* a, int na, const int32_t* b, int nb);

@@ -165,6 +165,20 @@ int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
  * head's fp32 logits (row of utterance b, frame t at logits + (b * (T / 4) + t) * ld, C = odim valid columns) and enc_lens int32 [B].
  * Valid until the next call that uses the workspace. */
 int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens);
+/* ---- attention rescoring (rescore.hip; tests/test_hip_rescore_kernels.py, tests/test_hip_rescore.py)
+ * the score kernel alone (mk_rescore_score): logits fp32 [R*L][ld] (C <= ld valid columns), gold int32 [R*L] (-1 = no term; >= C is read as
+ * no term) -> att fp32 [R] = the sum over l ascending of log_softmax(logits[r*L + l])[gold], -inf where a hypothesis has no term; row_lp fp32
+ * [R*L] scratch (the terms) */
+int masr_test_rescore_score(const float* logits, int64_t ld, const int32_t* gold, int R, int L, int C, float* row_lp, float* att, void* stream);
+/* the select kernel alone (mk_rescore_select): the outputs of masr_rescore_nbest from lists, first-pass scores and attention scores att_in
+ * [B][N]; 1 <= N <= 64, outputs apart from the inputs */
+int masr_test_rescore_select(const int32_t* tokens_in, int64_t ld_tok, const int32_t* lens_in, const float* ctc_in, const float* att_in, int B, int N,
+                             float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc, int32_t* order,
+                             void* stream);
+/* where the last masr_recog_rescore / masr_rescore_nbest call on m left what its score kernel read in the bound workspace: the decoder's
+ * fp32 logits (row r * L + l at logits + (r * L + l) * ld, odim valid columns; r = b * N + first-pass rank) and gold int32 [R][L].  Valid until
+ * the next call that uses the workspace; -1 before the first rescoring call and after masr_bind. */
+int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t** gold, int* R, int* L);
 
 /* ---- the BLSTM path's LSTM kernels alone (lstm.hip, lstm_rec.hip; tests/test_hip_lstm_kernels.py).  Rows are batch-first (b * T + t), the gate
  * axis is unit-major (row / column u * 4 + g, g in torch's order i, f, g, o), index 0 / 1 = forward / reverse direction, KP = H rounded up to a

@@ -72,6 +72,9 @@ _SIGS = {
     "masr_recog_beam_ctc": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "masr_rescore_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
+    "masr_recog_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_rescore_nbest": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_edit_distance": (i64, [vp, i32, vp, i32]),
     "masr_blstm_create": (vp, [vp]),
     "masr_blstm_destroy": (None, [vp]),
@@ -109,6 +112,9 @@ _SIGS = {
     "masr_test_skinny_gemm": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "masr_test_ctc_prefix": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "masr_test_ctc_beam_logits": (i32, [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp)]),
+    "masr_test_rescore_score": (i32, [vp, i64, vp, i32, i32, i32, vp, vp, vp]),
+    "masr_test_rescore_select": (i32, [vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_rescore_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]),
     "masr_test_attn_decode": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
     "masr_test_logits_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "masr_test_recog_argmax_step": (i32, [vp, vp, i64, vp, i32, i32, vp]),

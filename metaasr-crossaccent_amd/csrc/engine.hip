@@ -310,7 +310,7 @@ int masr_bind(masr_model* m, float* params, float* grads, const float* pe, void*
         HIP_CHECK_RET(hipMemset(m->ctc.k16, 0, sizeof(bf16) * (size_t)m->Cp * m->E));
         HIP_CHECK_RET(hipMemset(m->ctc.t16, 0, sizeof(bf16) * (size_t)m->E * m->Cp));
     }
-    m->have_acts = false;
+    m->have_acts = false; m->last_rescore = {};
     return 0;
 }
 

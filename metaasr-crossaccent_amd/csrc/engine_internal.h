@@ -113,6 +113,7 @@ struct masr_model {
     // cached step graphs of the three decoders, each keyed on its own shape (recog.hip run_steps): alternating decoders do not evict
     // one another.  greedy {B, T, Ldec} + {ws, P, out}; beam {B, T, K, Lmax} + {ws, P}; joint: the beam's key + the two weights' bits
     DecodeGraph greedy_graph, beam_graph, joint_graph;
+    struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[MASR_PROF_N]; int prof_used[MASR_PROF_N] = {0};
@@ -169,4 +170,5 @@ void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, boo
 // train.hip: the forward pass over m->acts (the decoders run the encoder, the K|V projection and, masr_recog_full, the decoder too)
 int forward_encoder(Ctx& c, const float* xs);
 int project_memory_kv(Ctx& c);
-int forward_decoder(Ctx& c, bool project_kv = true, bool logits_f32 = false);
+struct DecoderGeom { int seqs, L; };                       // forward_decoder on other than the plan's a.B x a.L rows (the rescoring pass)
+int forward_decoder(Ctx& c, bool project_kv = true, bool logits_f32 = false, const DecoderGeom* gm = nullptr);

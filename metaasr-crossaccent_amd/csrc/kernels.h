@@ -199,6 +199,19 @@ int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K);
 int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos, void* work,
                        int64_t work_bytes, int* tokens, int* lens, float* scores, hipStream_t s);
 
+// ---------------------------------------------------------------- attention rescoring of an N-best list (rescore.hip)
+// tok [R][ld_tok], lens [R] (-1 = no entry; a live one is <= L - 1) -> the decoder's tok_in [R][L] = [sos, h.., eos ..] and gold [R][L] =
+// [h.., eos, -1 ..]; an entry without a list: all eos / all -1
+int mk_rescore_prepare(const int* tok, long ld_tok, const int* lens, int R, int L, int sos, int eos, int* tok_in, int* gold, hipStream_t s);
+// att[r] = sum over l (ascending) of log_softmax(logits[r*L + l][0 .. C))[gold[r*L + l]] over the rows with gold >= 0, -inf where there is none;
+// row_lp [R*L]: the terms (scratch, 0 where gold < 0)
+int mk_rescore_score(const float* logits, long ld, const int* gold, int R, int L, int C, float* row_lp, float* att, hipStream_t s);
+// per utterance: score = att_w att + ctc_w ctc (the ctc term is left out when ctc_w == 0), entries reordered by (filled first, score descending,
+// input rank ascending): order[b][j] = input rank of output entry j; tokens rows, lens and ctc are copies, scores / att -inf and lens -1
+// where lens_in < 0.  N <= 64; the outputs may not alias the inputs
+int mk_rescore_select(const int* tok_in, long ld_tok, const int* lens_in, const float* ctc_in, const float* att_in, int B, int N, float att_w,
+                      float ctc_w, int* tokens, int* lens, float* scores, float* att, float* ctc, int* order, hipStream_t s);
+
 // ---------------------------------------------------------------- row ops (rowops.hip)
 int mk_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y32, bf16* y16,
                        float* mean, float* rstd, int rows, int E, hipStream_t s);

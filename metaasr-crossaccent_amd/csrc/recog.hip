@@ -1,6 +1,8 @@
 // libmasr engine, the decoders (MyTransformer.recog, mono_transformer_torch.py:143-176, and the beam searches of beam.hip): the
 // literal whole-prefix re-decode, the KV-cached greedy decode, the attention beam and the joint CTC/attention beam.  Each of the
-// last three captures the launch sequence of ONE step into a hipGraph of its own and replays it once per step (run_steps).
+// last three captures the launch sequence of ONE step into a hipGraph of its own and replays it once per step (run_steps).  Behind them
+// the two decoders without steps: the CTC prefix beam on the head alone, and attention rescoring of its N-best (one teacher-forced
+// decoder pass).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -120,8 +122,14 @@ static int check_pointers(const char* fn, const float* xs, const int64_t* ilens,
 //   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
 //   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
 //   buffer follow
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; };
-struct DecodeBufs { BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes; };
+//   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
+//   of up to Lmax tokens behind their sos; with a first pass (K > 0) the CTC-only beam's buffers and its N-best list follow, then the
+//   second pass's scores
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; };
+struct DecodeBufs {
+    BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
+    int *rs_tok, *rs_lens; float *rs_ctc, *rs_att, *rs_row_lp;          // rescoring: first-pass list [B][N][Tp] / [B][N] / [B][N], att [B*N], row terms [B*N*(Lmax+1)]
+};
 
 static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
     const int R = B * d.K, L = d.Lmax, P = d.P, W = P ? P : d.K;
@@ -152,14 +160,28 @@ static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, i
     o.work = ar.get<char>(o.work_bytes);
     return o;
 }
+static DecodeBufs plan_rescore(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
+    DecodeBufs o{};
+    const int64_t R = (int64_t)B * d.N;
+    if (d.K) {
+        o = plan_ctc_beam(m, ar, B, Tp, d.K);
+        o.rs_tok = ar.get<int>(R * Tp); o.rs_lens = ar.get<int>(R); o.rs_ctc = ar.get<float>(R);
+    }
+    o.rs_att = ar.get<float>(R); o.rs_row_lp = ar.get<float>(R * (d.Lmax + 1));
+    return o;
+}
 static DecodeBufs plan_decode(const masr_model* m, Arena& ar, Acts& a, int B, int T, int Ldec, const DecodeSpec& d) {
+    if (d.N) {
+        plan_acts(m, ar, a, B, T, d.N * (d.Lmax + 1), false);
+        return plan_rescore(m, ar, B, T / 4, d);
+    }
     plan_acts(m, ar, a, B, T, d.ctc_only ? 1 : d.K ? d.K * d.Lmax : Ldec, false);
     return d.ctc_only ? plan_ctc_beam(m, ar, B, T / 4, d.K) : d.K ? plan_beam(m, ar, B, T / 4, d) : DecodeBufs{};
 }
 // a decoder's workspace size; args_ok: B, T and the spec are in range (else the error `need`)
 static int64_t decode_workspace_bytes(const char* fn, const masr_model* m, bool args_ok, const char* need, int B, int T, const DecodeSpec& d) {
     if (!m || !args_ok) { mk_set_error(fn, need); return -1; }
-    if (d.P || d.ctc_only) CK(check_ctc_head(fn, m));
+    if (d.P || d.ctc_only || d.N) CK(check_ctc_head(fn, m));
     Arena ar{nullptr, 0, 0};
     Acts a;
     plan_decode(m, ar, a, B, T, 0, d);
@@ -180,7 +202,8 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
     const DecodeBufs planned = plan_decode(m, ar, m->acts, B, T, Ldec, d);
     if (bufs) *bufs = planned;
     if (ar.off > m->ws_bytes) {
-        mk_set_error("masr_recog", d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
+        mk_set_error("masr_recog", d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
+                                   : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
                                          : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
@@ -385,6 +408,119 @@ int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits
     const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, DecodeSpec{K, 0, 0, true});
     if (ar.off > m->ws_bytes) { mk_set_error(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"); return -1; }
     *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- attention rescoring
+static int check_rescore_weights(const char* fn, float att_w, float ctc_w) {
+    if (!(att_w > 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and > 0"); return -1; }
+    if (!(ctc_w >= 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and >= 0"); return -1; }
+    return 0;
+}
+// The second pass over the lists tok [B*N][ld_tok] / lens / ctc (device), the encoder done: the decoder ONCE, teacher-forced, on B*N sequences
+// of L = 1 + the longest live list positions (the eval pass's bf16-operand logits GEMM), each list's attention score, and the re-ranked copies
+static int rescore_second_pass(Ctx& c, const DecodeBufs& bufs, const int* tok, long ld_tok, const int* lens, const float* ctc, int B, int N, int L,
+                               float att_w, float ctc_w, int32_t* tokens, int32_t* lens_out, float* scores, float* att, float* ctc_out, int32_t* order) {
+    masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
+    const int R = B * N;
+    CK(mk_rescore_prepare(tok, ld_tok, lens, R, L, 0, m->C - 1, a.tok_in, a.gold, s));
+    const DecoderGeom gm{R, L};
+    CK(forward_decoder(c, true, false, &gm));
+    CK(mk_rescore_score(a.logits, m->Cp, a.gold, R, L, m->C, bufs.rs_row_lp, bufs.rs_att, s));
+    CK(mk_rescore_select(tok, ld_tok, lens, ctc, bufs.rs_att, B, N, att_w, ctc_w, tokens, lens_out, scores, att, ctc_out, order, s));
+    m->last_rescore = {a.logits, a.gold, R, L};
+    m->have_acts = false;
+    return 0;
+}
+
+extern "C" {
+
+int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
+    return decode_workspace_bytes("masr_rescore_workspace_bytes", m, B > 0 && T >= 4 && N >= 1 && N <= K && K <= 64 && Lmax >= 0 && Lmax < MASR_PE_ROWS,
+                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, 0 <= Lmax < 3000", B, T, DecodeSpec{K, Lmax, 0, false, N});
+}
+
+int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
+                       int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream) {
+    const char* fn = "masr_recog_rescore";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    CK(check_ctc_head(fn, m));
+    CK(check_beam_size(fn, K));
+    if (N < 1 || N > K) { mk_set_error(fn, "N must be in [1, K]"); return -1; }
+    CK(check_rescore_weights(fn, att_w, ctc_w));
+    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
+    if (!att || !ctc || !order) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B <= 0 || T < 4) { mk_set_error(fn, "need B >= 1 and T >= 4"); return -1; }
+    int Lcap = 0;                                           // a CTC hypothesis has at most enc_len tokens
+    for (int b = 0; b < B; ++b) {
+        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error(fn, "ilens must be in [4, T]"); return -1; }
+        Lcap = std::max(Lcap, (int)(ilens[b] / 4));
+    }
+    Lcap = std::min(Lcap, MASR_PE_ROWS - 1);
+    hipStream_t s = (hipStream_t)stream;
+    DecodeBufs bufs;
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lcap, 0, false, N}, &bufs); if (rc) return rc; }
+    Acts& a = m->acts;
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    const int Tp = T / 4, R = B * N;
+    CK(ctc_head_logits(c, bufs.ctc_logits));
+    CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, bufs.rs_tok, bufs.rs_lens,
+                          bufs.rs_ctc, s));
+    // the one host synchronisation of the decode: the list lengths decide how many positions the decoder pass has
+    std::vector<int> h_lens(R);
+    HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), bufs.rs_lens, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    int mx = 0;
+    for (int v : h_lens) mx = std::max(mx, v);
+    if (mx > Lcap) { mk_set_error(fn, "a first-pass hypothesis is longer than the positions planned for"); return -1; }
+    return rescore_second_pass(c, bufs, bufs.rs_tok, Tp, bufs.rs_lens, bufs.rs_ctc, B, N, mx + 1, att_w, ctc_w, tokens, lens, scores, att, ctc, order);
+}
+
+int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,
+                       const int32_t* lens_in, const float* ctc_in, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
+                       float* ctc, int32_t* order, void* stream) {
+    const char* fn = "masr_rescore_nbest";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    CK(check_ctc_head(fn, m));
+    if (N < 1 || N > 64) { mk_set_error(fn, "N must be in [1, 64]"); return -1; }
+    CK(check_rescore_weights(fn, att_w, ctc_w));
+    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
+    if (!att || !ctc || !order || !lens_in || !ctc_in || (ld_tok > 0 && !tokens_in)) { mk_set_error(fn, "null pointer"); return -1; }
+    if (B <= 0 || T < 4 || ld_tok < 0 || ld_tok >= MASR_PE_ROWS) { mk_set_error(fn, "need B >= 1, T >= 4 and 0 <= ld_tok < 3000"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    // the one host synchronisation of the call: the lists come to the host, where their lengths decide the decoder's positions and every
+    // token is vetted (it indexes the embedding table)
+    const int R = B * N;
+    std::vector<int> h_lens(R), h_tok((size_t)R * ld_tok);
+    HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), lens_in, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
+    if (ld_tok) HIP_CHECK_RET(hipMemcpyAsync(h_tok.data(), tokens_in, sizeof(int) * h_tok.size(), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    int mx = 0;
+    for (int r = 0; r < R; ++r) {
+        const int n = h_lens[r];
+        if (n < 0) continue;
+        if (n > ld_tok) { mk_set_error(fn, "a list is longer than ld_tok"); return -1; }
+        for (int i = 0; i < n; ++i) {
+            const int t = h_tok[(size_t)r * ld_tok + i];
+            if (t < 1 || t > m->C - 2) { mk_set_error(fn, "tokens must lie in [1, odim - 2] (no sos / blank, no eos)"); return -1; }
+        }
+        mx = std::max(mx, n);
+    }
+    DecodeBufs bufs;
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{0, mx, 0, false, N}, &bufs); if (rc) return rc; }
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    return rescore_second_pass(c, bufs, tokens_in, (long)ld_tok, lens_in, ctc_in, B, N, mx + 1, att_w, ctc_w, tokens, lens, scores, att, ctc, order);
+}
+
+int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t** gold, int* R, int* L) {
+    const char* fn = "masr_test_rescore_logits";
+    if (!m || !logits || !ld || !gold || !R || !L) { mk_set_error(fn, "null pointer"); return -1; }
+    if (!m->last_rescore.logits) { mk_set_error(fn, "no rescoring call yet"); return -1; }
+    *logits = m->last_rescore.logits; *ld = m->Cp; *gold = m->last_rescore.gold; *R = m->last_rescore.R; *L = m->last_rescore.L;
     return 0;
 }
 

@@ -49,6 +49,19 @@ int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int
     g.residual = residual; g.ldres = N; g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
     return mk_skinny_gemm(g, (hipStream_t)stream);
 }
+int masr_test_rescore_score(const float* logits, int64_t ld, const int32_t* gold, int R, int L, int C, float* row_lp, float* att, void* stream) {
+    if (!logits || !gold || !row_lp || !att) { mk_set_error("masr_test_rescore_score", "null pointer"); return -1; }
+    return mk_rescore_score(logits, (long)ld, gold, R, L, C, row_lp, att, (hipStream_t)stream);
+}
+int masr_test_rescore_select(const int32_t* tokens_in, int64_t ld_tok, const int32_t* lens_in, const float* ctc_in, const float* att_in, int B, int N,
+                             float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc, int32_t* order,
+                             void* stream) {
+    if (!lens_in || !ctc_in || !att_in || !lens || !scores || !att || !ctc || !order || (ld_tok > 0 && (!tokens_in || !tokens))) {
+        mk_set_error("masr_test_rescore_select", "null pointer"); return -1;
+    }
+    return mk_rescore_select(tokens_in, (long)ld_tok, lens_in, ctc_in, att_in, B, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
+                             (hipStream_t)stream);
+}
 int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
                          const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
                          int32_t* list_slot, float* out_state, void* stream) {

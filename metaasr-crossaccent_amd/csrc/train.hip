@@ -75,7 +75,8 @@ static int gemm_or_ksplit(Ctx& c, GemmArgs g, LnSumArgs* defer, const LnSumArgs&
     return gemm(c, g);
 }
 
-int attn_block_fwd(Ctx& c, const Attn& at, const bf16* xq, int rows_q, int Tq, int Tk, bool self, bool causal, const int* klens,
+// nb: the attention's batches, rows_q = nb * Tq query rows
+int attn_block_fwd(Ctx& c, const Attn& at, const bf16* xq, int rows_q, int nb, int Tq, int Tk, bool self, bool causal, const int* klens,
                    bf16* qkv_or_q, bf16* kv, bf16* ao, float* lse, const float* resid, float* s_out, uint32_t site_p, uint32_t site_o,
                    LnSumArgs* defer = nullptr) {
     masr_model* m = c.m; const int E = m->E; const float* P = m->P;
@@ -90,7 +91,7 @@ int attn_block_fwd(Ctx& c, const Attn& at, const bf16* xq, int rows_q, int Tq, i
         // K|V of the encoder memory were projected for all layers at once (project_memory_kv); kv = this layer's columns
         a.q = qkv_or_q; a.ldq = E; a.k = kv; a.v = kv + E; a.ldk = a.ldv = m->NK;
     }
-    a.o = ao; a.ldo = E; a.lse = lse; a.klens = klens; a.B = m->acts.B; a.H = m->H; a.Tq = Tq; a.Tk = Tk; a.hd = m->hd;
+    a.o = ao; a.ldo = E; a.lse = lse; a.klens = klens; a.B = nb; a.H = m->H; a.Tq = Tq; a.Tk = Tk; a.hd = m->hd;
     a.causal = causal; a.drop_p = c.p_drop; a.seed = c.seed; a.seed_ptr = c.seed_ptr; a.site = site_p;
     { Prof p(m, Tk == m->acts.Tp && Tq == Tk ? MASR_PROF_ATTN_ENC : MASR_PROF_ATTN_DEC, c.s); CK(mk_attn_fwd(a, c.s)); }
     GemmArgs o = lin_fwd_args(ao, E, at.out.k16, rows_q, E, E, P + at.out.b);
@@ -186,7 +187,7 @@ int forward_encoder(Ctx& c, const float* xs) {
     for (int l = 0; l < m->NE; ++l) {
         EncAct& e = a.enc[l]; const EncL& w = m->enc[l];
         for (int i = 0; i < 4; ++i) e.site[i] = site++;
-        CK(attn_block_fwd(c, w.sa, a.x16[l], a.rows_e, a.Tp, a.Tp, true, false, a.enc_lens, e.qkv, nullptr, e.ao, e.lse, a.x32[l], e.s1,
+        CK(attn_block_fwd(c, w.sa, a.x16[l], a.rows_e, a.B, a.Tp, a.Tp, true, false, a.enc_lens, e.qkv, nullptr, e.ao, e.lse, a.x32[l], e.s1,
                           e.site[0], e.site[1]));
         CK(ln_fwd(c, w.n1, e.s1, e.x1_32, e.x1_16, e.m1, e.r1, a.rows_e));
         CK(ffn_fwd(c, w.l1, w.l2, e.x1_16, e.x1_32, a.rows_e, e.f, e.s2, e.site[2], e.site[3]));
@@ -204,34 +205,38 @@ int project_memory_kv(Ctx& c) {
     return gemm(c, h);
 }
 
-int forward_decoder(Ctx& c, bool project_kv, bool logits_f32) {
+// gm (null: the plan's a.B sequences of a.L positions, today's launches exactly): gm->seqs sequences of gm->L positions in the plan's buffers,
+// gm->seqs a multiple of a.B with the sequences of one utterance next to each other.  The embedding and the causal self-attention run per
+// sequence; the cross-attention runs per utterance, its seqs / a.B * L query rows (contiguous) against that utterance's memory.
+int forward_decoder(Ctx& c, bool project_kv, bool logits_f32, const DecoderGeom* gm) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
-    const int E = m->E, L = a.L;
+    const int E = m->E, L = gm ? gm->L : a.L, seqs = gm ? gm->seqs : a.B, rows_d = gm ? gm->seqs * gm->L : a.rows_d;
+    const int Tq_cross = rows_d / a.B;
     uint32_t site = 100;
     a.site_emb = site++;
     if (project_kv) CK(project_memory_kv(c));
-    { Prof p(m, MASR_PROF_MISC, s); CK(mk_embed_fwd(a.tok_in, P + m->embed_w, m->pe, a.y32[0], a.y16[0], a.B, L, E, c.p_pos, c.seed, a.site_emb, s, c.seed_ptr)); }
+    { Prof p(m, MASR_PROF_MISC, s); CK(mk_embed_fwd(a.tok_in, P + m->embed_w, m->pe, a.y32[0], a.y16[0], seqs, L, E, c.p_pos, c.seed, a.site_emb, s, c.seed_ptr)); }
     for (int l = 0; l < m->ND; ++l) {
         DecAct& d = a.dec[l]; const DecL& w = m->dec[l];
         for (int i = 0; i < 6; ++i) d.site[i] = site++;
         LnSumArgs ks{};                                        // (k-split GEMMs: their partial products are summed by the LayerNorm behind them)
-        CK(attn_block_fwd(c, w.sa, a.y16[l], a.rows_d, L, L, true, true, nullptr, d.qkv, nullptr, d.ao, d.lse_s, a.y32[l], d.s1, d.site[0],
+        CK(attn_block_fwd(c, w.sa, a.y16[l], rows_d, seqs, L, L, true, true, nullptr, d.qkv, nullptr, d.ao, d.lse_s, a.y32[l], d.s1, d.site[0],
                           d.site[1], &ks));
-        CK(ln_fwd(c, w.n1, d.s1, d.y1_32, d.y1_16, d.m1, d.r1, a.rows_d, &ks));
-        CK(attn_block_fwd(c, w.ca, d.y1_16, a.rows_d, L, a.Tp, false, false, a.enc_lens, d.q, d.kv, d.co, d.lse_c, d.y1_32, d.s2, d.site[2],
+        CK(ln_fwd(c, w.n1, d.s1, d.y1_32, d.y1_16, d.m1, d.r1, rows_d, &ks));
+        CK(attn_block_fwd(c, w.ca, d.y1_16, rows_d, a.B, Tq_cross, a.Tp, false, false, a.enc_lens, d.q, d.kv, d.co, d.lse_c, d.y1_32, d.s2, d.site[2],
                           d.site[3], &ks));
-        CK(ln_fwd(c, w.n2, d.s2, d.y2_32, d.y2_16, d.m2, d.r2, a.rows_d, &ks));
-        CK(ffn_fwd(c, w.l1, w.l2, d.y2_16, d.y2_32, a.rows_d, d.f, d.s3, d.site[4], d.site[5], &ks));
-        CK(ln_fwd(c, w.n3, d.s3, a.y32[l + 1], a.y16[l + 1], d.m3, d.r3, a.rows_d, &ks));
+        CK(ln_fwd(c, w.n2, d.s2, d.y2_32, d.y2_16, d.m2, d.r2, rows_d, &ks));
+        CK(ffn_fwd(c, w.l1, w.l2, d.y2_16, d.y2_32, rows_d, d.f, d.s3, d.site[4], d.site[5], &ks));
+        CK(ln_fwd(c, w.n3, d.s3, a.y32[l + 1], a.y16[l + 1], d.m3, d.r3, rows_d, &ks));
     }
     if (logits_f32) {
         // greedy decode: the last projection in fp32 on the master weights (see mk_logits_f32); layer 0's pre-LayerNorm sum is free by now
         float* yf32 = a.dec[0].s1;
-        CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], yf32, nullptr, a.mdf, a.rdf, a.rows_d));
-        return mk_logits_f32(yf32, P + m->ct.w, P + m->ct.b, a.logits, m->Cp, a.rows_d, m->C, E, c.s);
+        CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], yf32, nullptr, a.mdf, a.rdf, rows_d));
+        return mk_logits_f32(yf32, P + m->ct.w, P + m->ct.b, a.logits, m->Cp, rows_d, m->C, E, c.s);
     }
-    CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], nullptr, a.yf16, a.mdf, a.rdf, a.rows_d));
-    GemmArgs g = lin_fwd_args(a.yf16, E, m->ct.k16, a.rows_d, m->C, E, P + m->ct.b);
+    CK(ln_fwd(c, m->dec_norm, a.y32[m->ND], nullptr, a.yf16, a.mdf, a.rdf, rows_d));
+    GemmArgs g = lin_fwd_args(a.yf16, E, m->ct.k16, rows_d, m->C, E, P + m->ct.b);
     g.C32 = a.logits; g.ldc = m->Cp;
     CK(gemm(c, g));
     return 0;

@@ -289,9 +289,10 @@ class MasrEngine:
         tok, lens = tok.cpu(), lens.cpu()
         return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
 
-    def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1):
+    def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
-        head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first."""
+        head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first
+        (raw: the device tensors tokens [B, nbest, T // 4], lens, scores instead)."""
         K, N = int(beam_size), int(nbest)
         if not 1 <= K <= 64:
             raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
@@ -312,7 +313,91 @@ class MasrEngine:
         check(self._l.masr_recog_ctc_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, _ptr(tok), _ptr(lens), _ptr(scores),
                                           self.stream()), "masr_recog_ctc_beam")
         self._last_x = xs
-        return nbest_lists(tok, lens, scores)
+        return (tok, lens, scores) if raw else nbest_lists(tok, lens, scores)
+
+    @staticmethod
+    def _rescore_weights(att_w, ctc_w):
+        att_w, ctc_w = float(att_w), float(ctc_w)
+        if not (math.isfinite(att_w) and att_w > 0.0):
+            raise ValueError(f"att_w must be finite and > 0, got {att_w}")
+        if not (math.isfinite(ctc_w) and ctc_w >= 0.0):
+            raise ValueError(f"ctc_w must be finite and >= 0, got {ctc_w}")
+        return att_w, ctc_w
+
+    def _rescore_outputs(self, B, N, ld):
+        i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
+        return (torch.empty(B, N, ld, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **f32), torch.empty(B, N, **f32),
+                torch.empty(B, N, **f32), torch.empty(B, N, **i32))
+
+    @staticmethod
+    def _rescore_lists(out):
+        tok, lens, scores, att, ctc, order = (t.cpu() for t in out)
+        return [[(tok[b, j, :int(lens[b, j])].tolist(), float(scores[b, j]), float(att[b, j]), float(ctc[b, j]), int(order[b, j]))
+                 for j in range(lens.size(1)) if int(lens[b, j]) >= 0] for b in range(lens.size(0))]
+
+    def recog_rescore(self, xs: torch.Tensor, ilens, beam_size: int, nbest=None, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
+        """attention rescoring of the CTC beam's N-best (masr_recog_rescore; needs a hybrid model): the CTC prefix beam of
+        recog_ctc_beam(beam_size, nbest), then ONE teacher-forced decoder pass over all B * nbest hypotheses, and the list re-ranked by
+        att_w * log p_att + ctc_w * log p_ctc.  Returns per utterance a list of (tokens, score, att, ctc, first_pass_rank), best first
+        (raw: the device tensors tokens, lens, scores, att, ctc, order instead).  The call waits for the stream once, between the passes."""
+        K = int(beam_size)
+        N = K if nbest is None else int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, K, N, T // 4))
+        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        out = self._rescore_outputs(B, N, T // 4)
+        check(self._l.masr_recog_rescore(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, att_w, ctc_w, *[_ptr(t) for t in out],
+                                         self.stream()), "masr_recog_rescore")
+        self._last_x = xs
+        return out if raw else self._rescore_lists(out)
+
+    def rescore_nbest(self, xs: torch.Tensor, ilens, tokens, lens, ctc, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
+        """attention rescoring of a caller's N-best lists (masr_rescore_nbest): tokens int32 [B, N, ld], lens int32 [B, N] (-1 = no entry),
+        ctc fp32 [B, N] (the first-pass scores); every token of a live list in [1, odim - 2].  Returns what recog_rescore returns."""
+        att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        tokens = torch.as_tensor(tokens).to(self.device, torch.int32).contiguous()
+        lens = torch.as_tensor(lens).to(self.device, torch.int32).contiguous()
+        ctc = torch.as_tensor(ctc).to(self.device, torch.float32).contiguous()
+        if tokens.dim() != 3 or tokens.size(0) != B or lens.shape != tokens.shape[:2] or ctc.shape != lens.shape:
+            raise ValueError("rescore_nbest needs tokens [B, N, ld], lens [B, N] and ctc [B, N]")
+        N, ld = tokens.size(1), tokens.size(2)
+        if not 1 <= N <= 64:
+            raise ValueError(f"N must be in [1, 64], got {N}")
+        Lmax = max(0, int(lens.max()))
+        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, N, N, Lmax))
+        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        out = self._rescore_outputs(B, N, ld)
+        check(self._l.masr_rescore_nbest(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, N, _ptr(tokens), ld, _ptr(lens), _ptr(ctc), att_w, ctc_w,
+                                         *[_ptr(t) for t in out], self.stream()), "masr_rescore_nbest")
+        self._last_x = xs
+        return out if raw else self._rescore_lists(out)
+
+    def last_rescore_logits(self):
+        """test hook (include/masr_test.h masr_test_rescore_logits): what the last rescoring call's score kernel read, as views into the
+        workspace: (decoder logits fp32 [R, L, ld], gold int32 [R, L]); row r = b * N + first-pass rank"""
+        lp, gp, ld, R, L = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int(), C.c_int()
+        check(self._l.masr_test_rescore_logits(self.h, C.byref(lp), C.byref(ld), C.byref(gp), C.byref(R), C.byref(L)), "masr_test_rescore_logits")
+        base, n = self.ws.data_ptr(), R.value * L.value
+        logits = self.ws[lp.value - base:lp.value - base + n * ld.value * 4].view(torch.float32).view(R.value, L.value, ld.value)
+        return logits, self.ws[gp.value - base:gp.value - base + n * 4].view(torch.int32).view(R.value, L.value)
 
     def last_ctc_beam_logits(self, B, T, K):
         """test hook (include/masr_test.h masr_test_ctc_beam_logits): what the last recog_ctc_beam of this (B, T, K) searched, as views

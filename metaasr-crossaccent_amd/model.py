@@ -120,3 +120,10 @@ class MyTransformer:
         nbest (token list, score), best first"""
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_ctc_beam(xs_pad, ilens, beam_size, nbest)
+
+    def rescore_decode(self, xs_pad, ilens, beam_size, nbest=None, att_weight=0.5, ctc_weight=0.5):
+        """attention rescoring (masr_recog_rescore, hybrid models only): the CTC prefix beam's nbest list re-ranked by
+        att_weight * log p_att + ctc_weight * log p_ctc after one teacher-forced decoder pass; per utterance a list of
+        (tokens, score, att, ctc, first_pass_rank), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_rescore(xs_pad, ilens, beam_size, nbest, att_weight, ctc_weight)

@@ -6,7 +6,10 @@ transformer runs this project's GPU beam search (masr_recog_beam) with the confi
 best hypothesis of each utterance in the same line format.  On a hybrid model (asr_model.ctc_weight > 0) a block with ctc_w > 0 runs
 the joint CTC/attention search (masr_recog_beam_ctc) with att_w (default 1 - ctc_w) and ctc_w.  The weights are checked on every model,
 hybrid or plain, before anything is decoded: a negative or non-finite ctc_w or att_w raises ValueError, and so does ctc_w > 1 without an
-att_w (the default 1 - ctc_w is then negative).  A plain model with valid weights decodes as before and logs that they are ignored."""
+att_w (the default 1 - ctc_w is then negative).  A plain model with valid weights decodes as before and logs that they are ignored.
+`--decode_mode rescore` (hybrid transformers) is the two-pass decode of DESIGN 5.4 (masr_recog_rescore): the CTC prefix beam of
+`ctc_beam` with beam_size, its nbest (default beam_size) best re-ranked by att_w * attention score + ctc_w * CTC score after one
+teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_w must be > 0."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -118,6 +121,27 @@ class Tester:
             self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
         return True
 
+    def batch_rescore_decode(self, xs, ilens, ys, olens):
+        for nbest, y in zip(self.asr_model.rescore_decode(xs, ilens, self.beam_size, self.nbest, self.att_weight, self.ctc_weight), ys):
+            self.write_hyp(y.tolist(), nbest[0][0])
+        return True
+
+    def _rescore_settings(self):
+        if self.model_name == 'blstm':
+            raise NotImplementedError("rescore: attention rescoring needs the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self.nbest = int(bd.get('nbest', self.beam_size))
+        if not 1 <= self.nbest <= self.beam_size:
+            raise ValueError(f"solver.beam_decode.nbest must be in [1, beam_size], got {self.nbest}")
+        self.ctc_weight = self._weight(bd, 'ctc_w', 0.5)
+        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
+        if not self.att_weight > 0.0:
+            raise ValueError(f"solver.beam_decode.att_w must be > 0 for decode_mode 'rescore', got {self.att_weight}")
+        if not self.asr_model.engine.ctc_weight > 0.0:
+            raise ValueError("decode_mode 'rescore' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
+                             "use --decode_mode beam or greedy")
+
     def _beam_size(self):
         bd = self.config.get('solver', {}).get('beam_decode')
         if not isinstance(bd, dict) or 'beam_size' not in bd:
@@ -166,13 +190,18 @@ class Tester:
         return w
 
     def exec(self):
-        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam'):
+        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore'):
             raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
         decode = self.batch_greedy_decode
         if self.decode_mode == 'ctc_beam':
             self._ctc_beam_settings()
             decode = self.batch_ctc_beam_decode
             logger.notice(f"Start CTC prefix beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
+        elif self.decode_mode == 'rescore':
+            self._rescore_settings()
+            decode = self.batch_rescore_decode
+            logger.notice(f"Start attention rescoring (CTC beam {self.beam_size}, {self.nbest}-best, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}): "
+                          f"{len(self.eval_set)} batches of <= {self.batch_size}")
         elif self.decode_mode != 'greedy':
             self._beam_settings()
             decode = self.batch_beam_decode
