@@ -220,7 +220,8 @@ const float* masr_stats_device(masr_model* m);
 int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 int masr_recog_full(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int32_t* out, void* stream);
 
-/* Beam search over the KV-cached decoder step (no LM, no CTC -- see masr_recog_beam_ctc: the scores are sums of fp32 log_softmax of the decoder's logits).
+/* Beam search over the KV-cached decoder step (no LM -- see masr_recog_beam_lm --, no CTC -- see masr_recog_beam_ctc: the scores are sums of fp32
+ * log_softmax of the decoder's logits).
  * Per utterance b: enc_len = floor(ilens[b] / 4); maxlen = enc_len if max_step_ratio <= 0, else max(1, floor(max_step_ratio * enc_len)),
  * capped at the 3000 rows of pe; minlen = floor(min_step_ratio * enc_len); Lmax = max over b of maxlen.  1 <= K <= 64.
  * At every step the K best extensions (score descending, parent rank ascending, token ascending) of the live hypotheses are kept;
@@ -245,6 +246,34 @@ int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B,
 int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
 int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
                         float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
+
+/* Shallow fusion of a backoff n-gram language model into the attention beam.
+ * The LM: order N in [1, 4] over the model's C <= 65535 output units with the model's ids (<s> = sos = 0, </s> = eos = C - 1, units 1 .. C - 2).
+ * An n-gram of order n has ids (w_1 .. w_n), a natural-log probability logp and a natural-log backoff weight bo (0 for the highest order), both
+ * finite fp32 and <= 0: every LM term is <= 0 and the beam's stop rule stays exact.  Order 1 is dense (every class 0 .. C - 1 has a unigram).
+ * masr_lm_create: per order n, grams[n - 1] is int32 [counts[n - 1]][n], logp[n - 1] / backoff[n - 1] fp32 [counts[n - 1]] (host arrays;
+ * backoff[order - 1] may be null).  Builds the device tables (dense unigrams; per order >= 2 one open-addressing table of 16-byte slots, capacity a
+ * power of two >= 2 x the count, n-grams inserted in input order) on the current device and returns the handle; NULL + masr_last_error() for
+ * a duplicate n-gram, an id outside [0, C - 1], </s> anywhere but last or <s> anywhere but first in an n-gram, a non-finite or positive value
+ * or a missing unigram -- all found on the host, before anything touches the device.  masr_lm_bytes: device bytes held.
+ * lm(c | h), the LM score of class c after hypothesis h: ctx = the last min(N - 1, |h| + 1) tokens of [sos] + h; acc = 0.f; for k = |ctx| down to 0,
+ * with g = the last k tokens of ctx: if (g, c) is an n-gram of order k + 1, lm = fl(acc + logp(g, c)) and stop; else if k >= 1 and g is an n-gram
+ * of order k, acc = fl(acc + bo(g)).  k = 0 always hits.  fp32 additions in this order.
+ * masr_recog_beam_lm: the search of masr_recog_beam (attention decoder alone, also on a hybrid model) with the per-step increment
+ *   f(c) = fl(lp(c) + fl(lm_w * lm(c | h))), lp(c) = (z_c - mx) - log_s as masr_recog_beam composes it (no fused multiply-add),
+ * over all C classes (no pre-beam).  A hypothesis's list is its K best classes by (f descending, class ascending), eos excluded below minlen;
+ * a candidate scores fl(s(h) + f(c)); candidates are kept by score descending, parent rank ascending, f descending, class ascending.  Selection,
+ * ended / running bookkeeping, the stop rule, minlen / maxlen and the result layout are masr_recog_beam's; K = 1 is greedy on the fused score;
+ * lm_w = 0 gives masr_recog_beam's scores bit for bit.  Same bounds and messages as masr_recog_beam; lm_w finite and >= 0; the LM's C must equal
+ * the model's odim.  Needs a workspace of masr_beam_lm_workspace_bytes(B, T, K, Lmax) = the beam's plus the fp32 fused rows [B*K][odim padded
+ * to 128].  The step is captured as its own hipGraph, keyed on the LM and lm_w as well: a call with another LM or weight captures anew. */
+typedef struct masr_lm masr_lm;
+masr_lm* masr_lm_create(int order, int C, const int64_t* counts, const int32_t* const* grams, const float* const* logp, const float* const* backoff);
+void masr_lm_destroy(masr_lm* lm);
+int64_t masr_lm_bytes(const masr_lm* lm);
+int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
+int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
+                       float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
 /* CTC prefix beam search on the CTC head alone (hybrid models of masr_create_ctc): the encoder and the head GEMM of
  * masr_recog_beam_ctc, then masr_ctc_beam_search (below) on the head's fp32 logits with blank 0, eos = odim - 1, Tp = T / 4 and

@@ -179,6 +179,19 @@ int masr_test_rescore_select(const int32_t* tokens_in, int64_t ld_tok, const int
  * fp32 logits (row r * L + l at logits + (r * L + l) * ld, odim valid columns; r = b * N + first-pass rank) and gold int32 [R][L].  Valid until
  * the next call that uses the workspace; -1 before the first rescoring call and after masr_bind. */
 int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t** gold, int* R, int* L);
+/* ---- n-gram LM shallow fusion (lm.hip; tests/test_hip_lm_kernels.py)
+ * the LM's score rule alone: ctx int32 [R][order - 1] (null at order 1), oldest first, -1 = nothing further left (a shorter context has its
+ * -1 in front) -> out fp32 [R][C] = lm(c | ctx) for every class.  Reads ctx back first and refuses an id outside [-1, C) and a -1 behind an id;
+ * all arrays on the device; synchronises the stream. */
+int masr_test_lm_score(const masr_lm* lm, const int32_t* ctx, int R, float* out, void* stream);
+/* the longest probe chain (slots examined) an insertion walked while the LM's tables were built; 1 = no n-gram ever met an occupied slot */
+int masr_test_lm_max_probe(const masr_lm* lm);
+/* the beam's LM step kernel alone (beam_lm_topk_kernel) at step t >= 1 on R = B*K rows of caller-given fp32 logits [R][ld] (C = the LM's classes
+ * <= ld): score fp32 [R] (-inf = dead row), minlen int32 [B], and the token / parent-row histories of the steps before, tok_hist / par_hist
+ * int32 [t - 1][R] (null at t = 1; the kernel clamps what it reads).  Out: list_tok int32 / list_score fp32 [R][K].  The fused rows and the
+ * step scalar are the entry's; no utterance is finished.  All arrays on the device; synchronises the stream. */
+int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                           const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* list_tok, float* list_score, void* stream);
 
 /* ---- the BLSTM path's LSTM kernels alone (lstm.hip, lstm_rec.hip; tests/test_hip_lstm_kernels.py).  Rows are batch-first (b * T + t), the gate
  * axis is unit-major (row / column u * 4 + g, g in torch's order i, f, g, o), index 0 / 1 = forward / reverse direction, KP = H rounded up to a

@@ -70,6 +70,11 @@ _SIGS = {
     "masr_recog_beam": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
     "masr_beam_ctc_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_ctc": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_lm_create": (vp, [i32, i32, C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "masr_lm_destroy": (None, [vp]),
+    "masr_lm_bytes": (i64, [vp]),
+    "masr_beam_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
+    "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "masr_rescore_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
@@ -115,6 +120,9 @@ _SIGS = {
     "masr_test_rescore_score": (i32, [vp, i64, vp, i32, i32, i32, vp, vp, vp]),
     "masr_test_rescore_select": (i32, [vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_rescore_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]),
+    "masr_test_lm_score": (i32, [vp, vp, i32, vp, vp]),
+    "masr_test_lm_max_probe": (i32, [vp]),
+    "masr_test_beam_lm_topk": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_test_attn_decode": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
     "masr_test_logits_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "masr_test_recog_argmax_step": (i32, [vp, vp, i64, vp, i32, i32, vp]),

@@ -183,6 +183,12 @@ int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
 int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
 int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s);                // also advances step[0]
+// n-gram LM shallow fusion (lm.hip, lm.h): in place of mk_beam_row_topk -- the row's K best classes by the fused increment
+// f(c) = lp(c) + lm_w * lm(c | h), through the fp32 workspace fused [R][ldf]; then mk_beam_select as ever
+struct LmDev;
+int mk_beam_lm_topk(const BeamArgs& a, const LmDev& lm, float lm_w, const float* logits, long ld, float* fused, long ldf, hipStream_t s);
+// out [R][C] = lm(c | ctx row) for every class; ctx int32 [R][order - 1], oldest first, -1 in front of a shorter context
+int mk_lm_score(const LmDev& lm, const int* ctx, int R, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------- CTC prefix beam search (ctc_beam.hip)
 // logits: row of utterance b, frame t at logits + (b*Tp + t)*ld.  P = min(K, emittable classes).  The arrays below are carved from the work buffer.

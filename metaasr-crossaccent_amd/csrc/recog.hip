@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "engine_internal.h"
+#include "lm.h"
 #include "../../include/masr_test.h"
 
 // The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
@@ -118,6 +119,7 @@ static int check_pointers(const char* fn, const float* xs, const int64_t* ilens,
 //   greedy (K = 0): Ldec decoder positions per utterance, nothing else
 //   beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
 //   rows, and the beam state follows
+//   LM fusion (masr_recog_beam_lm, lm): the beam's plan, then the fp32 fused rows [B*K][Cp]
 //   joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
 //   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
 //   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
@@ -125,9 +127,10 @@ static int check_pointers(const char* fn, const float* xs, const int64_t* ilens,
 //   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
 //   of up to Lmax tokens behind their sos; with a first pass (K > 0) the CTC-only beam's buffers and its N-best list follow, then the
 //   second pass's scores
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; };
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; };
 struct DecodeBufs {
     BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
+    float* lm_fused;                                                    // LM fusion: the rows' fused increments [R][Cp]
     int *rs_tok, *rs_lens; float *rs_ctc, *rs_att, *rs_row_lp;          // rescoring: first-pass list [B][N][Tp] / [B][N] / [B][N], att [B*N], row terms [B*N*(Lmax+1)]
 };
 
@@ -143,6 +146,7 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
     a.list_tok = ar.get<int>((int64_t)R * W); a.list_score = ar.get<float>((int64_t)R * W);
     int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
     a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
+    if (d.lm) o.lm_fused = ar.get<float>((int64_t)R * m->Cp);
     if (!P) return o;
     a.P = P; a.Tp = Tp;
     o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
@@ -206,6 +210,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
+                                   : d.lm ? "workspace too small (masr_beam_lm_workspace_bytes(B, T, K, Lmax))"
                                          : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
         return -2;
     }
@@ -284,8 +289,10 @@ int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, 
 }
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
-// CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.
-static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv) {
+// CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.  LM fusion (lm): the
+// fused top-K (lm.hip) in place of the row top-K.
+struct LmStep { LmDev dev; float w; float* fused; };
+static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* lm = nullptr) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
     CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
@@ -295,17 +302,21 @@ static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv) {
         CK(mk_beam_ctc_select(ba, s));                          // also advances *step_dev
         return 0;
     }
-    CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
+    if (lm) CK(mk_beam_lm_topk(ba, lm->dev, lm->w, a.logits, m->Cp, lm->fused, m->Cp, s));
+    else CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
     CK(mk_beam_select(ba, s));                                  // also advances *step_dev
     return 0;
 }
 
-// masr_recog_beam (wts == null) and masr_recog_beam_ctc (wts = {att_w, ctc_w}): the same decode, each with its own cached step graph
+// masr_recog_beam (wts == null), masr_recog_beam_ctc (wts = {att_w, ctc_w}) and masr_recog_beam_lm (lm, lm_w; wts == null): the same decode,
+// each with its own cached step graph
 static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
-                           const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn) {
+                           const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn,
+                           const masr_lm* lm = nullptr, float lm_w = 0.f) {
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
-    // weights) and replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
+    // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers) and
+    // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
     CK(check_beam_size(fn, K));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (B <= 0) { mk_set_error(fn, "need B >= 1"); return -1; }
@@ -322,7 +333,8 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0}, &bufs); if (rc) return rc; }
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0, false, 0, lm != nullptr}, &bufs);
+      if (rc) return rc; }
     BeamArgs& ba = bufs.beam; bf16* step_qkv = bufs.step_qkv; float* ctc_logits = bufs.ctc_logits;
     Acts& a = m->acts;
     ba.step = a.step_dev;
@@ -346,8 +358,13 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     }
     int key[6] = {B, T, K, Lmax, 0, 0}; const void* const kp[3] = {m->ws, m->P, nullptr};
     if (wts) memcpy(key + 4, wts, 2 * sizeof(float));
-    CK(run_steps(m, wts ? m->joint_graph : m->beam_graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
-                 [&] { return beam_step(c, ba, step_qkv); }));
+    LmStep ls{};
+    if (lm) {
+        ls = LmStep{lm->dev, lm_w, bufs.lm_fused};
+        memcpy(key + 4, &lm_w, sizeof(float)); key[5] = (int)lm->serial;
+    }
+    CK(run_steps(m, wts ? m->joint_graph : lm ? m->lm_graph : m->beam_graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
+                 [&] { return beam_step(c, ba, step_qkv, lm ? &ls : nullptr); }));
     CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
@@ -369,6 +386,22 @@ int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, in
     if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
     const float wts[2] = {att_w, ctc_w};
     return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn);
+}
+
+int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    return decode_workspace_bytes("masr_beam_lm_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
+                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, 0, false, 0, true});
+}
+
+int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
+                       float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // n-gram LM shallow fusion into the attention beam (lm.hip): masr_recog_beam with the fused top-K in place of the row top-K
+    const char* fn = "masr_recog_beam_lm";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
+    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
+    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, fn, lm, lm_w);
 }
 
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {

@@ -6,6 +6,7 @@
 #include "../../include/masr_test.h"
 #include "kernels.h"
 #include "host_util.h"
+#include "lm.h"
 
 extern "C" {
 
@@ -181,6 +182,59 @@ int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int3
         HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+// ---- n-gram LM shallow fusion (lm.hip)
+int masr_test_lm_score(const masr_lm* lm, const int32_t* ctx, int R, float* out, void* stream) {
+    const char* fn = "masr_test_lm_score";
+    if (!lm || !out || R < 1 || (lm->dev.order > 1 && !ctx)) { mk_set_error(fn, "null pointer or R < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int w = lm->dev.order - 1;
+    if (w > 0) {
+        std::vector<int> h((size_t)R * w);
+        HIP_CHECK_RET(hipMemcpyAsync(h.data(), ctx, sizeof(int) * h.size(), hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        for (int r = 0; r < R; ++r)
+            for (int i = 0; i < w; ++i) {
+                const int t = h[(size_t)r * w + i];
+                if (t < -1 || t >= lm->dev.C) { mk_set_error(fn, "context ids must lie in [-1, C)"); return -1; }
+                if (t == -1 && i > 0 && h[(size_t)r * w + i - 1] != -1) { mk_set_error(fn, "-1 may only stand in front of a context"); return -1; }
+            }
+    }
+    CK(mk_lm_score(lm->dev, ctx, R, out, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_lm_max_probe(const masr_lm* lm) {
+    if (!lm) { mk_set_error("masr_test_lm_max_probe", "null model"); return -1; }
+    return lm->max_probe;
+}
+int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                           const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* list_tok, float* list_score, void* stream) {
+    const char* fn = "masr_test_beam_lm_topk";
+    if (!lm || !minlen || !logits || !score || !list_tok || !list_score || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
+    const int C = lm->dev.C;
+    if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    char* w = nullptr;                                       // step[2] | fin [B] | fused [R][ld]
+    const size_t fin_off = 64, fused_off = (fin_off + sizeof(int) * (size_t)B + 255) & ~(size_t)255;
+    HIP_CHECK_RET(hipMalloc(&w, fused_off + sizeof(float) * (size_t)R * ld));
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen;
+    a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
+    a.list_tok = list_tok; a.list_score = list_score; a.fin = (int*)(w + fin_off);
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        CK(mk_beam_lm_topk(a, lm->dev, lm_w, logits, ld, (float*)(w + fused_off), ld, s));
         HIP_CHECK_RET(hipStreamSynchronize(s));
         return 0;
     };

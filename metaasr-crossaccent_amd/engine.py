@@ -289,6 +289,36 @@ class MasrEngine:
         tok, lens = tok.cpu(), lens.cpu()
         return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
 
+    def recog_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
+        """beam search with an n-gram LM fused in (masr_recog_beam_lm): recog_beam's attention-only search with the per-step
+        increment log p_att(c | h) + lm_w * lm(c | h).  lm: an NGramLM (lm.py) over this model's odim classes; lm_w finite and >= 0.
+        Returns what recog_beam returns: (B token lists without sos / eos, fp32 scores [B] on the host)."""
+        K, lm_w = int(beam_size), float(lm_w)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not (math.isfinite(lm_w) and lm_w >= 0.0):
+            raise ValueError(f"lm_w must be finite and >= 0, got {lm_w}")
+        if getattr(lm, "h", None) is None:
+            raise ValueError("lm must be a live NGramLM")
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
+        need = int(self._l.masr_beam_lm_workspace_bytes(self.h, B, T, K, Lmax))
+        check(need if need < 0 else 0, "masr_beam_lm_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        tok = torch.empty(B, Lmax, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, dtype=torch.float32, device=self.device)
+        check(self._l.masr_recog_beam_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
+                                         lm_w, _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam_lm")
+        self._last_x = xs
+        tok, lens = tok.cpu(), lens.cpu()
+        return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
+
     def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
         head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first

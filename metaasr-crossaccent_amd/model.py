@@ -115,6 +115,12 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_beam(xs_pad, ilens, beam_size, min_step_ratio, max_step_ratio, att_weight, ctc_weight)
 
+    def lm_beam_decode(self, xs_pad, ilens, beam_size, lm, lm_weight, min_step_ratio=0.0, max_step_ratio=1.0):
+        """beam search with shallow fusion of the n-gram LM `lm` (an NGramLM; masr_recog_beam_lm): (B token lists without sos / eos,
+        scores [B])"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_lm(xs_pad, ilens, beam_size, lm, lm_weight, min_step_ratio, max_step_ratio)
+
     def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam, hybrid models only): per utterance a list of at most
         nbest (token list, score), best first"""

@@ -9,7 +9,11 @@ hybrid or plain, before anything is decoded: a negative or non-finite ctc_w or a
 att_w (the default 1 - ctc_w is then negative).  A plain model with valid weights decodes as before and logs that they are ignored.
 `--decode_mode rescore` (hybrid transformers) is the two-pass decode of DESIGN 5.4 (masr_recog_rescore): the CTC prefix beam of
 `ctc_beam` with beam_size, its nbest (default beam_size) best re-ranked by att_w * attention score + ctc_w * CTC score after one
-teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_w must be > 0."""
+teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_w must be > 0.
+`--decode_mode lm_beam` (transformers) is the attention beam with an n-gram LM fused in (masr_recog_beam_lm): the ARPA file of
+`--lm_model_path` over the output units, weighted by beam_decode.lm_w (default 0.3); beam_size and the step ratios as for `beam`.  The path is
+read at exec(): without one the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed).  The LM
+is not fused into the joint CTC/attention beam: a hybrid model with beam_decode.ctc_w > 0 raises ValueError."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -114,6 +118,12 @@ class Tester:
             self.write_hyp(y.tolist(), hyp)
         return True
 
+    def batch_lm_beam_decode(self, xs, ilens, ys, olens):
+        hyps, _ = self.asr_model.lm_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.min_step_ratio, self.max_step_ratio)
+        for hyp, y in zip(hyps, ys):
+            self.write_hyp(y.tolist(), hyp)
+        return True
+
     def batch_ctc_beam_decode(self, xs, ilens, ys, olens):
         for nbest, y in zip(self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size), ys):
             hyp = nbest[0][0]
@@ -157,9 +167,29 @@ class Tester:
             raise ValueError("decode_mode 'ctc_beam' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
                              "use --decode_mode beam or greedy")
 
+    def _lm_beam_settings(self):
+        lm_path = getattr(self.paras, 'lm_model_path', None)
+        if lm_path is None:
+            raise NotImplementedError("lm_beam: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
+        if self.model_name == 'blstm':
+            raise NotImplementedError("lm_beam: LM fusion is only implemented for the transformer's attention beam; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
+        self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        ctc_w = self._weight(bd, 'ctc_w', 0.0)
+        if ctc_w > 0.0:
+            if self.asr_model.engine.ctc_weight > 0.0:
+                raise ValueError(f"lm_beam: the LM is not fused into the joint CTC/attention beam (beam_decode.ctc_w = {bd['ctc_w']}); "
+                                 "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
+            logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
+        from .lm import NGramLM
+        self.lm = NGramLM.from_arpa(lm_path, self.id2ch, self.sos_id, self.eos_id)
+        logger.notice(f"LM shallow fusion: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
+                      f"lm_w = {self.lm_weight}")
+
     def _beam_settings(self):
-        if self.decode_mode == 'lm_beam':
-            raise NotImplementedError("lm_beam: this project has no language model to fuse")
         if self.model_name == 'blstm':
             raise NotImplementedError("beam: beam search is only implemented for the transformer (the reference's BLSTM beam "
                                       "decoder is dead code, DESIGN 9); use --decode_mode greedy")
@@ -202,6 +232,10 @@ class Tester:
             decode = self.batch_rescore_decode
             logger.notice(f"Start attention rescoring (CTC beam {self.beam_size}, {self.nbest}-best, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}): "
                           f"{len(self.eval_set)} batches of <= {self.batch_size}")
+        elif self.decode_mode == 'lm_beam':
+            self._lm_beam_settings()
+            decode = self.batch_lm_beam_decode
+            logger.notice(f"Start beam decoding with LM fusion (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
         elif self.decode_mode != 'greedy':
             self._beam_settings()
             decode = self.batch_beam_decode

@@ -1,0 +1,81 @@
+"""What n-gram LM shallow fusion costs over the plain attention beam: masr_recog_beam and masr_recog_beam_lm side by side in one process on
+the hkust geometry, B = 16, T = 1000 (as tools/bench_beam.py), random-init weights, K = 1 / 4 / 10 / 20, with a synthetic 3-gram LM of about
+10^6 n-grams over the 367 classes (random n-grams with random log-probabilities: the kernel's work -- up to two table probes and the dense
+unigram per class -- does not depend on the values).  Both decodes replay all T / 4 steps (random weights never end a hypothesis early at
+lm_w = 0.3 with min_step_ratio = 1), so ms per step = ms per decode / steps includes the encoder's share in both columns alike; the
+difference of the two columns is beam_lm_topk against beam_row_topk.
+usage: python tools/bench_lm_beam.py [B] [T] [n-grams in all]"""
+import json
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+import masr_amd  # noqa
+from masr_amd.engine import MasrEngine
+from masr_amd.lm import NGramLM
+from masr_amd.model import reference_init_state_dict
+
+HKUST = {"idim": 80, "nheads": 8, "d_model": 512, "d_inner": 2048, "dropout": 0.1, "pos_dropout": 0.1, "tgt_share_weight": 1,
+         "encoder": {"nlayers": 2}, "decoder": {"nlayers": 4}}
+C_ = 367
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+T = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
+N_TOTAL = int(sys.argv[3]) if len(sys.argv) > 3 else 1_000_000
+
+
+def synthetic_lm(n_total, seed=7):
+    """order 3 over C_ classes, n_total n-grams in all: dense unigrams, distinct random bigrams (at most half of n_total; there are only
+    365^2 of them) and distinct random trigrams of the units 1 .. C_ - 2"""
+    rng = np.random.RandomState(seed)
+    U = C_ - 2
+    grams = [np.arange(C_, dtype=np.int32).reshape(-1, 1)]
+    want = {2: min(U * U, n_total // 2)}
+    want[3] = n_total - C_ - want[2]
+    for n in (2, 3):
+        total = U ** n
+        idx = np.unique(rng.randint(total, size=int(want[n] * 1.2) + 16)) if want[n] < total else np.arange(total)
+        idx = rng.permutation(idx)[:want[n]]
+        grams.append(np.stack([(idx // U ** (n - 1 - j)) % U + 1 for j in range(n)], axis=1).astype(np.int32))
+    logp = [(-8.0 * rng.rand(len(g))).astype(np.float32) for g in grams]
+    bo = [(-2.0 * rng.rand(len(g))).astype(np.float32) for g in grams]
+    return NGramLM(3, C_, grams, logp, bo)
+
+
+torch.manual_seed(531)
+eng = MasrEngine(HKUST, C_)
+eng.load_state_dict(reference_init_state_dict(HKUST, C_))
+t0 = time.perf_counter()
+lm = synthetic_lm(N_TOTAL)
+build_s = time.perf_counter() - t0
+xs = torch.randn(B, T, 80, device="cuda")
+il = torch.full((B,), T, dtype=torch.int64)
+side = torch.cuda.Stream()
+steps = T // 4
+res = {"B": B, "T": T, "steps": steps, "lm_ngrams": lm.counts, "lm_device_mb": round(lm.device_bytes / 2 ** 20, 1), "lm_build_s": round(build_s, 2),
+       "decode_ms": {}}
+
+
+def timed(fn, n=4):
+    with torch.cuda.stream(side):
+        out = fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with torch.cuda.stream(side):
+        for _ in range(n):
+            fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e3, out
+
+
+for K in (1, 4, 10, 20):
+    plain, (tp, _) = timed(lambda: eng.recog_beam(xs, il, K, min_step_ratio=1.0))
+    fused, (tf, _) = timed(lambda: eng.recog_beam_lm(xs, il, K, lm, 0.3, min_step_ratio=1.0))
+    assert all(len(t) == steps for t in tp + tf), "a decode ended before the last step"
+    res["decode_ms"][f"K{K}"] = {"beam": round(plain, 2), "beam_lm": round(fused, 2), "beam_step": round(plain / steps, 4),
+                                 "beam_lm_step": round(fused / steps, 4), "lm_extra_us_per_step": round((fused - plain) / steps * 1e3, 1)}
+    print(f"K = {K:2d}: beam {plain:7.2f} ms ({plain / steps:.4f} per step)  beam + LM {fused:7.2f} ms ({fused / steps:.4f} per step)  "
+          f"LM extra {(fused - plain) / steps * 1e3:6.1f} us per step", flush=True)
+print(json.dumps(res))
