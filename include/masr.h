@@ -282,6 +282,12 @@ int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const 
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K);
 int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
                         float* scores, void* stream);
+/* masr_recog_ctc_beam with the n-gram LM fused into the search: the same encoder pass, head GEMM and workspace, then
+ * masr_ctc_beam_search_lm (below) with blank 0 and eos = odim - 1.  scores fp32 [B][nbest] are the fused finals, am fp32 [B][nbest] the acoustic
+ * totals.  -1 besides masr_recog_ctc_beam's refusals: a null LM, an LM whose C is not the model's odim, lm_w negative or not finite, len_bonus
+ * not finite. */
+int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
+                           float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream);
 
 /* Attention rescoring of an N-best list (hybrid models of masr_create_ctc; the two-pass decode WeNet calls "attention
  * rescoring").  For utterance b and list entry n with tokens h (length l >= 0, no sos / eos) and first-pass score c(b, n):
@@ -310,6 +316,12 @@ int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, in
 int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax);
 int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
                        int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream);
+/* masr_recog_rescore whose first pass is the LM-fused search of masr_recog_ctc_beam_lm(K, nbest = N, lm_w, len_bonus): c(b, n) is that pass's
+ * fused score, copied bit for bit into `ctc`; everything else, the single host synchronisation and the workspace included, is
+ * masr_recog_rescore's.  The full two-pass pipeline: LM-fused CTC first pass, attention rescoring. */
+int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
+                          float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
+                          int32_t* order, void* stream);
 int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,
                        const int32_t* lens_in, const float* ctc_in, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
                        float* ctc, int32_t* order, void* stream);
@@ -424,6 +436,29 @@ int masr_ctc_loss(const float* logits, const int32_t* targets, const int32_t* tg
 int64_t masr_ctc_beam_work_bytes(int B, int Tp, int C, int K);
 int masr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                          void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens, float* scores, void* stream);
+
+/* masr_ctc_beam_search with a backoff n-gram LM (masr_lm_create) and a per-token bonus fused into the ranking (Hannun et al. 2014).
+ * Model-free.  Everything is the search above unless stated.  Needs blank == 0, eos == C - 1 and lm->C == C <= 4096: the LM's ids are <s> = 0 --
+ * the blank's slot, which is never emitted -- and </s> = C - 1.  lm_w finite and >= 0; len_bonus finite, of any sign (no stop rule depends on it).
+ *   LM state   each entry keeps, besides the purely acoustic (p_b, p_nb), an fp32 lmacc(h): lmacc(()) = 0.f,
+ *              lmacc(h + c) = fl(lmacc(h) + fl(fl(lm_w * lm(c | h)) + len_bonus)), lm(c | h) the rule of masr_recog_beam_lm; every product
+ *              and sum rounded on its own (no fused multiply-add).  lmacc is a function of the token sequence alone: a prefix that is
+ *              merged into, or leaves the beam and is created again, has the same bits whichever parent produced it.
+ *   acoustics  the stay / extension recursion, S_t (by acoustic logit: no LM in the pre-beam), the merge test and the prefix identity are
+ *              unchanged; p_b and p_nb never contain an LM term.
+ *   ranking    a candidate scores fl(logaddexp(p_b', p_nb') + lmacc(prefix)): a stay uses lmacc(h), an extension lmacc(h + c).  Selection
+ *              order as above (score descending, parent rank ascending, stay first, position in S_t ascending); -inf is never kept.
+ *   the end    final(h) = fl(fl(am(h) + lmacc(h)) + fl(lm_w * lm(eos | h))), am = logaddexp(p_b, p_nb); the whole final beam is re-ranked by
+ *              (final descending, beam rank ascending) and its first nbest entries are returned.
+ * Result (device): tokens / lens as above, scores fp32 [B][nbest] = final, am fp32 [B][nbest] = the acoustic total; slots that are not live
+ * hold lens -1 and scores = am = -inf; enc_len 0 gives the empty prefix with am 0 and score fl(lm_w * lm(eos | ())).
+ * With lm_w == 0 and len_bonus == 0, tokens, lens and scores equal masr_ctc_beam_search's bit for bit and am == scores (DESIGN 5.6 has the
+ * argument).  Every refusal returns -1 with its text in masr_last_error() before anything is launched.  The work buffer is
+ * masr_ctc_beam_lm_work_bytes(B, Tp, C, K) bytes (today the plain search's size: the LM state lives on chip). */
+int64_t masr_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K);
+int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                            const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
+                            float* scores, float* am, void* stream);
 
 /* device timing (HIP events on the launch stream) for bench.py's roofline block: one slot per conv launch of the VGG
  * front-end (each is ONE launch per step, so slot time / launches = that kernel's average duration) and one per kernel

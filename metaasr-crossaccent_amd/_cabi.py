@@ -1,6 +1,7 @@
 """ctypes binding of libmasr.so (include/masr.h; the masr_test_* entries are include/masr_test.h).  No fallback: if the HIP library is missing the
 import raises -- the product path never runs on the CPU oracle."""
 import ctypes as C
+import math
 import os
 from pathlib import Path
 
@@ -77,8 +78,10 @@ _SIGS = {
     "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "masr_recog_ctc_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
     "masr_rescore_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
     "masr_recog_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_recog_rescore_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_rescore_nbest": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_edit_distance": (i64, [vp, i32, vp, i32]),
     "masr_blstm_create": (vp, [vp]),
@@ -106,6 +109,8 @@ _SIGS = {
     "masr_ctc_loss": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "masr_ctc_beam_work_bytes": (i64, [i32, i32, i32, i32]),
     "masr_ctc_beam_search": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
+    "masr_ctc_beam_lm_work_bytes": (i64, [i32, i32, i32, i32]),
+    "masr_ctc_beam_search_lm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_profile_enable": (i32, [vp, i32]),
     "masr_profile_read": (i32, [vp, C.POINTER(f32), C.POINTER(i32)]),
     "masr_test_blstm_stall": (None, [vp, i32]),          # include/masr_test.h from here on
@@ -195,6 +200,25 @@ def nbest_lists(tok, lens, scores):
     tok, lens, scores = tok.cpu(), lens.cpu(), scores.cpu()
     return [[(tok[b, i, :int(lens[b, i])].tolist(), float(scores[b, i])) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
             for b in range(lens.size(0))]
+
+
+def nbest_lists_lm(tok, lens, scores, am):
+    """the same for masr_ctc_beam_search_lm: [(token list, fused score, acoustic score), ...]"""
+    tok, lens, scores, am = tok.cpu(), lens.cpu(), scores.cpu(), am.cpu()
+    return [[(tok[b, i, :int(lens[b, i])].tolist(), float(scores[b, i]), float(am[b, i])) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
+            for b in range(lens.size(0))]
+
+
+def check_lm_args(lm, lm_w, len_bonus):
+    """what the LM-fused CTC searches vet on the Python side -> (lm_w, len_bonus) as floats"""
+    lm_w, len_bonus = float(lm_w), float(len_bonus)
+    if not (math.isfinite(lm_w) and lm_w >= 0.0):
+        raise ValueError(f"lm_w must be finite and >= 0, got {lm_w}")
+    if not math.isfinite(len_bonus):
+        raise ValueError(f"len_bonus must be finite, got {len_bonus}")
+    if getattr(lm, "h", None) is None:
+        raise ValueError("lm must be a live NGramLM")
+    return lm_w, len_bonus
 
 
 def check(rc, what=""):

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import check, lib, nbest_lists
+from ._cabi import check, check_lm_args, lib, nbest_lists, nbest_lists_lm
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -138,11 +138,15 @@ class BlstmEngine:
         check(self._l.masr_blstm_check(self.h, self.stream()), "masr_blstm_check")
         return self.last_logits()
 
-    def ctc_beam(self, xs, ilens, K, nbest=1, blank=0):
+    def ctc_beam(self, xs, ilens, K, nbest=1, blank=0, lm=None, lm_w=0.0, len_bonus=0.0):
         """CTC prefix beam search over the head's output (masr_ctc_beam_search; `blank` and eos = odim - 1 are never emitted): the
         forward with its check, then the search on last_logits() with a work tensor of this engine's own.  Returns per utterance a list
-        of at most nbest (token list, score), best first."""
+        of at most nbest (token list, score), best first.  With lm (an NGramLM over the odim classes, <s> in the blank's slot 0) the search
+        is masr_ctc_beam_search_lm (lm_w finite and >= 0, len_bonus finite, blank 0) and the entries are
+        (token list, fused score, acoustic score)."""
         K, N = int(K), int(nbest)
+        if lm is not None:
+            lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
         if not 1 <= K <= 64:
             raise ValueError(f"beam_size must be in [1, 64], got {K}")
         if not 1 <= N <= K:
@@ -156,6 +160,12 @@ class BlstmEngine:
         tok = torch.empty(B, N, Tp, dtype=torch.int32, device=self.device)
         ln = torch.empty(B, N, dtype=torch.int32, device=self.device)
         sc = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        if lm is not None:
+            am = torch.empty(B, N, dtype=torch.float32, device=self.device)
+            check(self._l.masr_ctc_beam_search_lm(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, lm.h, lm_w, len_bonus,
+                                                  _ptr(self._beam_work), self._beam_work.numel(), _ptr(tok), _ptr(ln), _ptr(sc), _ptr(am),
+                                                  self.stream()), "masr_ctc_beam_search_lm")
+            return nbest_lists_lm(tok, ln, sc, am)
         check(self._l.masr_ctc_beam_search(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, _ptr(self._beam_work),
                                            self._beam_work.numel(), _ptr(tok), _ptr(ln), _ptr(sc), self.stream()), "masr_ctc_beam_search")
         return nbest_lists(tok, ln, sc)
@@ -259,14 +269,16 @@ class MonoBLSTM:
 
     greedy_decode = __call__                                  # mono_blstm.py:63-64
 
-    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
-        """CTC prefix beam search on the head (BlstmEngine.ctc_beam; the reference's own beam decoder is dead code).
+    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1, lm=None, lm_weight=0.0, len_bonus=0.0):
+        """CTC prefix beam search on the head (BlstmEngine.ctc_beam; the reference's own beam decoder is dead code); with lm,
+        the LM-fused search, entries (token list, fused score, acoustic score).
         Each utterance is run alone, cut to its own length.  The VGG front end does not mask padded frames (as in the reference: behind
         the first conv they hold relu(bias), which the next convs read at the utterance's last frames), so in a padded batch an
         utterance's logits depend on the batch's length; alone, its hypotheses are a function of the utterance, whatever the batch size."""
         out = []
         for b, n in enumerate(torch.as_tensor(ilens).tolist()):
-            out += self.engine.ctc_beam(xs_pad[b:b + 1, :int(n)], [int(n)], beam_size, nbest, blank=self.blank_id)
+            out += self.engine.ctc_beam(xs_pad[b:b + 1, :int(n)], [int(n)], beam_size, nbest, blank=self.blank_id, lm=lm, lm_w=lm_weight,
+                                        len_bonus=len_bonus)
         return out
 
     def train(self):

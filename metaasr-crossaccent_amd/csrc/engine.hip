@@ -492,6 +492,13 @@ int masr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* enc_len
                          void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
     return mk_ctc_beam_search(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, (hipStream_t)stream);
 }
+int64_t masr_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K) { return mk_ctc_beam_lm_work_bytes(B, Tp, C, K); }
+int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                            const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
+                            float* scores, float* am, void* stream) {
+    return mk_ctc_beam_search_lm(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, work, work_bytes, tokens, lens, scores,
+                                 am, (hipStream_t)stream);
+}
 
 int masr_profile_enable(masr_model* m, int on) {
     m->prof = on != 0;

@@ -204,6 +204,13 @@ int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K);
 // tokens int32 [B][nbest][Tp] (-1 behind each list), lens int32 [B][nbest] (-1 = no entry), scores fp32 [B][nbest] (-inf = no entry)
 int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos, void* work,
                        int64_t work_bytes, int* tokens, int* lens, float* scores, hipStream_t s);
+// the same search with an n-gram LM and a per-token bonus in the ranking: scores = the fused finals, am [B][nbest] = the acoustic
+// totals; blank 0 and eos C - 1 only
+struct masr_lm;
+int64_t mk_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K);
+int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                          const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int* tokens, int* lens, float* scores,
+                          float* am, hipStream_t s);
 
 // ---------------------------------------------------------------- attention rescoring of an N-best list (rescore.hip)
 // tok [R][ld_tok], lens [R] (-1 = no entry; a live one is <= L - 1) -> the decoder's tok_in [R][L] = [sos, h.., eos ..] and gold [R][L] =

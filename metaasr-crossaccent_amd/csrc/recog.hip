@@ -2,7 +2,7 @@
 // literal whole-prefix re-decode, the KV-cached greedy decode, the attention beam and the joint CTC/attention beam.  Each of the
 // last three captures the launch sequence of ONE step into a hipGraph of its own and replays it once per step (run_steps).  Behind them
 // the two decoders without steps: the CTC prefix beam on the head alone, and attention rescoring of its N-best (one teacher-forced
-// decoder pass).
+// decoder pass) -- each also with the n-gram LM fused into the prefix beam.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -430,6 +430,39 @@ int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, in
     return 0;
 }
 
+// what the LM-fused CTC first pass vets before anything is launched (masr_recog_ctc_beam_lm, masr_recog_rescore_lm)
+static int check_ctc_lm(const char* fn, const masr_model* m, const masr_lm* lm, float lm_w, float len_bonus) {
+    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
+    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
+    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
+    if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
+    return 0;
+}
+
+int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
+                           float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
+    // masr_recog_ctc_beam with the LM-fused sweep (ctc_beam.hip): the same plan, encoder pass and head GEMM
+    const char* fn = "masr_recog_ctc_beam_lm";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    CK(check_ctc_head(fn, m));
+    CK(check_beam_size(fn, K));
+    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
+    CK(check_ctc_lm(fn, m, lm, lm_w, len_bonus));
+    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
+    if (!am) { mk_set_error(fn, "null pointer"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    DecodeBufs bufs;
+    int Ldec = 0;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true}, &bufs); if (rc) return rc; }
+    Acts& a = m->acts;
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(ctc_head_logits(c, bufs.ctc_logits));
+    CK(mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
+                             tokens, lens, scores, am, s));
+    m->have_acts = false;
+    return 0;
+}
+
 int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens) {
     // where masr_recog_ctc_beam(m, .., B, T, K, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
     const char* fn = "masr_test_ctc_beam_logits";
@@ -475,14 +508,19 @@ int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, i
                                   "need B >= 1, T >= 4, 1 <= N <= K <= 64, 0 <= Lmax < 3000", B, T, DecodeSpec{K, Lmax, 0, false, N});
 }
 
-int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
-                       int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream) {
-    const char* fn = "masr_recog_rescore";
+}  // extern "C"
+
+// masr_recog_rescore (lm == null) and masr_recog_rescore_lm: the two-pass decode on one encoder pass; with an LM the first pass is the fused
+// search, its fused scores the c(b, n) of the second pass, and its acoustic totals land in the plan's scratch (rs_att, free until the second pass)
+static int recog_rescore_impl(const char* fn, masr_model* m, const masr_lm* lm, float lm_w, float len_bonus, const float* xs, const int64_t* ilens,
+                              int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
+                              float* ctc, int32_t* order, bool with_lm, void* stream) {
     if (!m) { mk_set_error(fn, "null model"); return -1; }
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
     if (N < 1 || N > K) { mk_set_error(fn, "N must be in [1, K]"); return -1; }
     CK(check_rescore_weights(fn, att_w, ctc_w));
+    if (with_lm) CK(check_ctc_lm(fn, m, lm, lm_w, len_bonus));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (!att || !ctc || !order) { mk_set_error(fn, "null pointer"); return -1; }
     if (B <= 0 || T < 4) { mk_set_error(fn, "need B >= 1 and T >= 4"); return -1; }
@@ -500,8 +538,12 @@ int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     const int Tp = T / 4, R = B * N;
     CK(ctc_head_logits(c, bufs.ctc_logits));
-    CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, bufs.rs_tok, bufs.rs_lens,
-                          bufs.rs_ctc, s));
+    if (with_lm)
+        CK(mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
+                                 bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att, s));
+    else
+        CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, bufs.rs_tok, bufs.rs_lens,
+                              bufs.rs_ctc, s));
     // the one host synchronisation of the decode: the list lengths decide how many positions the decoder pass has
     std::vector<int> h_lens(R);
     HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), bufs.rs_lens, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
@@ -510,6 +552,21 @@ int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int
     for (int v : h_lens) mx = std::max(mx, v);
     if (mx > Lcap) { mk_set_error(fn, "a first-pass hypothesis is longer than the positions planned for"); return -1; }
     return rescore_second_pass(c, bufs, bufs.rs_tok, Tp, bufs.rs_lens, bufs.rs_ctc, B, N, mx + 1, att_w, ctc_w, tokens, lens, scores, att, ctc, order);
+}
+
+extern "C" {
+
+int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
+                       int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream) {
+    return recog_rescore_impl("masr_recog_rescore", m, nullptr, 0.f, 0.f, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
+                              false, stream);
+}
+
+int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
+                          float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
+                          int32_t* order, void* stream) {
+    return recog_rescore_impl("masr_recog_rescore_lm", m, lm, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
+                              order, true, stream);
 }
 
 int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, check, lib, nbest_lists
+from ._cabi import MasrConfig, check, check_lm_args, lib, nbest_lists, nbest_lists_lm
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -345,6 +345,35 @@ class MasrEngine:
         self._last_x = xs
         return (tok, lens, scores) if raw else nbest_lists(tok, lens, scores)
 
+    def recog_ctc_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
+                          raw: bool = False):
+        """recog_ctc_beam with the n-gram LM `lm` (an NGramLM over this model's odim classes) and a per-token bonus fused into the search
+        (masr_recog_ctc_beam_lm).  lm_w finite and >= 0, len_bonus finite of any sign.  Returns per utterance a list of at most
+        nbest (token list, fused score, acoustic score), best first (raw: the device tensors tokens, lens, scores, am instead)."""
+        K, N = int(beam_size), int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        need = int(self._l.masr_ctc_beam_workspace_bytes(self.h, B, T, K))
+        check(need if need < 0 else 0, "masr_ctc_beam_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        tok = torch.empty(B, N, T // 4, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        am = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self._l.masr_recog_ctc_beam_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, lm_w, len_bonus, _ptr(tok), _ptr(lens),
+                                             _ptr(scores), _ptr(am), self.stream()), "masr_recog_ctc_beam_lm")
+        self._last_x = xs
+        return (tok, lens, scores, am) if raw else nbest_lists_lm(tok, lens, scores, am)
+
     @staticmethod
     def _rescore_weights(att_w, ctc_w):
         att_w, ctc_w = float(att_w), float(ctc_w)
@@ -389,6 +418,33 @@ class MasrEngine:
         out = self._rescore_outputs(B, N, T // 4)
         check(self._l.masr_recog_rescore(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, att_w, ctc_w, *[_ptr(t) for t in out],
                                          self.stream()), "masr_recog_rescore")
+        self._last_x = xs
+        return out if raw else self._rescore_lists(out)
+
+    def recog_rescore_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest=None,
+                         att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
+        """recog_rescore whose first pass is recog_ctc_beam_lm's LM-fused search (masr_recog_rescore_lm): the `ctc` of an entry
+        is that pass's fused score.  Returns what recog_rescore returns."""
+        K = int(beam_size)
+        N = K if nbest is None else int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, K, N, T // 4))
+        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        out = self._rescore_outputs(B, N, T // 4)
+        check(self._l.masr_recog_rescore_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, lm_w, len_bonus, att_w, ctc_w,
+                                            *[_ptr(t) for t in out], self.stream()), "masr_recog_rescore_lm")
         self._last_x = xs
         return out if raw else self._rescore_lists(out)
 

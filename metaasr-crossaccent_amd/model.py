@@ -127,6 +127,18 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_ctc_beam(xs_pad, ilens, beam_size, nbest)
 
+    def lm_ctc_beam_decode(self, xs_pad, ilens, beam_size, lm, lm_weight=0.3, len_bonus=0.0, nbest=1):
+        """CTC prefix beam search with the n-gram LM `lm` and a per-token bonus fused in (masr_recog_ctc_beam_lm, hybrid models only): per
+        utterance a list of at most nbest (token list, fused score, acoustic score), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_ctc_beam_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest)
+
+    def lm_rescore_decode(self, xs_pad, ilens, beam_size, lm, lm_weight=0.3, len_bonus=0.0, nbest=None, att_weight=0.5, ctc_weight=0.5):
+        """attention rescoring of the LM-fused CTC beam's nbest list (masr_recog_rescore_lm, hybrid models only): rescore_decode with
+        lm_ctc_beam_decode's search as the first pass"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_rescore_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest, att_weight, ctc_weight)
+
     def rescore_decode(self, xs_pad, ilens, beam_size, nbest=None, att_weight=0.5, ctc_weight=0.5):
         """attention rescoring (masr_recog_rescore, hybrid models only): the CTC prefix beam's nbest list re-ranked by
         att_weight * log p_att + ctc_weight * log p_ctc after one teacher-forced decoder pass; per utterance a list of

@@ -13,7 +13,12 @@ teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_
 `--decode_mode lm_beam` (transformers) is the attention beam with an n-gram LM fused in (masr_recog_beam_lm): the ARPA file of
 `--lm_model_path` over the output units, weighted by beam_decode.lm_w (default 0.3); beam_size and the step ratios as for `beam`.  The path is
 read at exec(): without one the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed).  The LM
-is not fused into the joint CTC/attention beam: a hybrid model with beam_decode.ctc_w > 0 raises ValueError."""
+is not fused into the joint CTC/attention beam: a hybrid model with beam_decode.ctc_w > 0 raises ValueError.
+`--decode_mode lm_ctc_beam` (BLSTM-CTC and hybrid transformers) is the CTC prefix beam of `ctc_beam` with that n-gram LM and a per-token
+bonus fused into the search (masr_ctc_beam_search_lm): `--lm_model_path` as for `lm_beam`, beam_decode.beam_size, lm_w (default
+0.3, finite and >= 0) and len_bonus (default 0, finite, any sign).  `--decode_mode lm_rescore` (hybrid transformers) is `rescore` with that
+search as its first pass (masr_recog_rescore_lm): nbest, att_w and ctc_w as for `rescore`.  Both vet every setting at exec(), before
+anything is decoded, and build the LM once per Tester."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -131,6 +136,23 @@ class Tester:
             self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
         return True
 
+    def batch_lm_ctc_beam_decode(self, xs, ilens, ys, olens):
+        if self.model_name == 'blstm':
+            lists = self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus)
+        else:
+            lists = self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
+        for nbest, y in zip(lists, ys):
+            hyp = nbest[0][0]
+            self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
+        return True
+
+    def batch_lm_rescore_decode(self, xs, ilens, ys, olens):
+        lists = self.asr_model.lm_rescore_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus, self.nbest, self.att_weight,
+                                                 self.ctc_weight)
+        for nbest, y in zip(lists, ys):
+            self.write_hyp(y.tolist(), nbest[0][0])
+        return True
+
     def batch_rescore_decode(self, xs, ilens, ys, olens):
         for nbest, y in zip(self.asr_model.rescore_decode(xs, ilens, self.beam_size, self.nbest, self.att_weight, self.ctc_weight), ys):
             self.write_hyp(y.tolist(), nbest[0][0])
@@ -189,6 +211,33 @@ class Tester:
         logger.notice(f"LM shallow fusion: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
                       f"lm_w = {self.lm_weight}")
 
+    def _lm_ctc_settings(self):
+        """lm_ctc_beam and lm_rescore: the path, the model, then every setting -- all before anything is decoded"""
+        mode = self.decode_mode
+        lm_path = getattr(self.paras, 'lm_model_path', None)
+        if lm_path is None:
+            raise NotImplementedError(f"{mode}: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
+        if mode == 'lm_rescore':
+            self._rescore_settings()                             # (BLSTM: NotImplementedError; no CTC head: ValueError; nbest, att_w, ctc_w)
+        else:
+            self._beam_size()
+            if self.model_name != 'blstm' and not self.asr_model.engine.ctc_weight > 0.0:
+                raise ValueError(f"decode_mode '{mode}' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or "
+                                 "absent); use --decode_mode lm_beam, beam or greedy")
+            if self.model_name == 'blstm' and self.blank_id != 0:
+                raise ValueError(f"decode_mode '{mode}' needs the blank at id 0 (its slot serves as the LM's <s>), got {self.blank_id}")
+        bd = self.config['solver']['beam_decode']
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self.len_bonus = float(bd.get('len_bonus', 0.0))
+        if not math.isfinite(self.len_bonus):
+            raise ValueError(f"solver.beam_decode.len_bonus must be finite, got {bd.get('len_bonus')}")
+        if getattr(self, 'lm', None) is None or getattr(self, '_lm_path', None) != lm_path:
+            from .lm import NGramLM
+            self.lm = NGramLM.from_arpa(lm_path, self.id2ch, 0, len(self.id2ch) - 1)       # <s> = 0 (the BLSTM's <blank> slot), </s> last
+            self._lm_path = lm_path
+        logger.notice(f"LM-fused CTC beam: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
+                      f"lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
+
     def _beam_settings(self):
         if self.model_name == 'blstm':
             raise NotImplementedError("beam: beam search is only implemented for the transformer (the reference's BLSTM beam "
@@ -220,7 +269,7 @@ class Tester:
         return w
 
     def exec(self):
-        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore'):
+        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore'):
             raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
         decode = self.batch_greedy_decode
         if self.decode_mode == 'ctc_beam':
@@ -232,6 +281,11 @@ class Tester:
             decode = self.batch_rescore_decode
             logger.notice(f"Start attention rescoring (CTC beam {self.beam_size}, {self.nbest}-best, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}): "
                           f"{len(self.eval_set)} batches of <= {self.batch_size}")
+        elif self.decode_mode in ('lm_ctc_beam', 'lm_rescore'):
+            self._lm_ctc_settings()
+            decode = self.batch_lm_ctc_beam_decode if self.decode_mode == 'lm_ctc_beam' else self.batch_lm_rescore_decode
+            logger.notice(f"Start {'LM-fused CTC prefix beam decoding' if self.decode_mode == 'lm_ctc_beam' else 'attention rescoring of the LM-fused CTC beam'}"
+                          f" (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
         elif self.decode_mode == 'lm_beam':
             self._lm_beam_settings()
             decode = self.batch_lm_beam_decode
