@@ -275,6 +275,33 @@ int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, i
 int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
                        float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
+/* One-pass joint CTC/attention beam search with the n-gram LM, a length bonus and an N-best list (what ESPnet-style recipes decode
+ * with).  It is masr_recog_beam_ctc with these differences; everything else (P = floor(3K/2), blank never, eos from minlen tokens on, -inf never
+ * kept nor ended, minlen / maxlen, dead rows) is that search's:
+ *   pre-beam   a hypothesis's P candidates are its best classes by g(c) = fl(lp(c) + fl(lm_w * lm(c | h))), masr_recog_beam_lm's fused increment
+ *              composed the same way, in the order (g descending, class ascending): the LM takes part in the pre-beam
+ *   score      s(h+c) = fl(fl(fl(fl(s(h) + fl(att_w * lp(c))) + fl(ctc_w * fl(psi(h+c) - psi(h)))) + fl(lm_w * lm(c | h))) + b), b = len_bonus
+ *              for a token and 0 for eos (the bonus counts emitted tokens); every product and sum is rounded on its own
+ *   N-best     an utterance keeps its N best ended hypotheses, 1 <= N <= K, ordered by score descending and, on equal scores, the one that ended
+ *              first (the earlier step, then the lower rank); at st >= maxlen the running hypotheses end as they are and compete too.  The
+ *              entries are distinct token sequences
+ *   stop rule  an utterance is finished when nothing runs, st >= maxlen, or the list is full and its N-th score is
+ *              >= fl(run_best + fl((maxlen - st) * max(len_bonus, 0))): every other increment is <= 0 (up to the few-ulp caveat on psi of
+ *              DESIGN 5.2) and a running hypothesis of st tokens collects at most maxlen - st more bonuses, so the result is what the same
+ *              beam gives when it runs to maxlen with no stop rule.  At len_bonus <= 0 and N = 1 it is masr_recog_beam's rule
+ * Result (device): tokens int32 [B][N][Lmax] (-1 behind each hypothesis), lens int32 [B][N], scores fp32 [B][N]; a slot without a hypothesis
+ * holds lens -1, scores -inf, tokens -1.  lm_w = 0, len_bonus = 0, N = 1 gives masr_recog_beam_ctc's scores (its pre-beam orders by logit, this
+ * one by lp: the two differ only where rounding ties two logits' lp).
+ * -1 with a message, before any launch: masr_recog_beam_ctc's refusals (a CTC head, ctc_w finite and > 0, att_w finite and >= 0, its bounds), a
+ * null LM, an LM whose C is not the model's odim, lm_w negative or not finite, len_bonus not finite, N outside [1, K]; -2: a workspace below
+ * masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax) = the joint beam's plus the fused rows [B*K][odim padded to 128], the LM terms [B*K][P] and the
+ * list.  The step is captured as its own hipGraph, keyed on the LM and N; the four weights are device values written before the replays, so a call
+ * with other weights replays the same graph and never an old value. */
+int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax);
+int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float min_step_ratio,
+                           float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
+                           void* stream);
+
 /* CTC prefix beam search on the CTC head alone (hybrid models of masr_create_ctc): the encoder and the head GEMM of
  * masr_recog_beam_ctc, then masr_ctc_beam_search (below) on the head's fp32 logits with blank 0, eos = odim - 1, Tp = T / 4 and
  * enc_len = floor(ilens[b] / 4).  Result (device): tokens int32 [B][nbest][T/4], lens int32 [B][nbest], scores fp32 [B][nbest].  A model

@@ -193,6 +193,28 @@ int masr_test_lm_max_probe(const masr_lm* lm);
 int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
                            const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* list_tok, float* list_score, void* stream);
 
+/* ---- the joint LM beam's step kernels alone (tests/test_hip_joint_lm_kernels.py).  All arrays on the device; each entry
+ * synchronises the stream.
+ * the fused pre-beam (lm.hip beam_ctc_lm_prebeam_kernel): masr_test_beam_lm_topk's inputs; P = floor(3K/2).  Out: pre_tok int32 / pre_lp / pre_lm
+ * fp32 [R][P] -- the row's P best classes by g (blank never, eos from minlen on; -1 / -inf / 0 past the end), their attention log-probs and
+ * fl(lm_w * lm(c | h)).  A dead row's entries are left as the caller gave them. */
+int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                               const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* pre_tok, float* pre_lp, float* pre_lm,
+                               void* stream);
+/* masr_test_ctc_prefix through beam_ctc_prefix_kernel<LM>: pre_lm fp32 [n] the candidates' weighted LM terms, len_bonus added to a token's score
+ * (not to eos's); list_score = fl(fl(fl(fl(score + fl(att_w lp)) + fl(ctc_w fl(psi - psi_par))) + pre_lm) + b) */
+int masr_test_ctc_prefix_lm(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                            const float* att_lp, const float* pre_lm, int n, float att_w, float ctc_w, float len_bonus, int32_t* list_tok,
+                            float* list_score, float* list_psi, int32_t* list_slot, float* out_state, void* stream);
+/* one step t of the select with the N-best list (beam.hip beam_select_nbest_kernel) on caller-given sorted row lists list_tok / list_score /
+ * list_psi / list_slot [B*K][P], P = floor(3K/2), eos = C - 1.  In / out: fin int32 [B], nb_score fp32 / nb_len / nb_row int32 [B][N] (the list
+ * state), tok_hist_row / par_hist_row int32 [B*K] (row t - 1 of the histories, so untouched entries show).  Out: score / psi fp32 [B*K], src int32
+ * [B*K], step_out int32 [2] (the step scalar and the ticket after the launch). */
+int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, const int32_t* list_tok,
+                                const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,
+                                int32_t* fin, float* nb_score, int32_t* nb_len, int32_t* nb_row, int32_t* tok_hist_row, int32_t* par_hist_row,
+                                int32_t* step_out, void* stream);
+
 /* ---- the BLSTM path's LSTM kernels alone (lstm.hip, lstm_rec.hip; tests/test_hip_lstm_kernels.py).  Rows are batch-first (b * T + t), the gate
  * axis is unit-major (row / column u * 4 + g, g in torch's order i, f, g, o), index 0 / 1 = forward / reverse direction, KP = H rounded up to a
  * multiple of 32.  Each entry vets on the host what the kernel would index with, calls the launcher and synchronises the stream.

@@ -76,6 +76,8 @@ _SIGS = {
     "masr_lm_bytes": (i64, [vp]),
     "masr_beam_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_beam_ctc_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
+    "masr_recog_beam_ctc_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "masr_recog_ctc_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
@@ -128,6 +130,9 @@ _SIGS = {
     "masr_test_lm_score": (i32, [vp, vp, i32, vp, vp]),
     "masr_test_lm_max_probe": (i32, [vp]),
     "masr_test_beam_lm_topk": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "masr_test_joint_lm_prebeam": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_ctc_prefix_lm": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "masr_test_beam_select_nbest": (i32, [i32, i32, i32, i32, i32, vp, f32] + [vp] * 15),
     "masr_test_attn_decode": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
     "masr_test_logits_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "masr_test_recog_argmax_step": (i32, [vp, vp, i64, vp, i32, i32, vp]),

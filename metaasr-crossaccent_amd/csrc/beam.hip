@@ -24,6 +24,11 @@ __global__ void beam_init_kernel(BeamArgs a) {
     if (i == 0) { a.step[0] = 1; a.step[1] = 0; }
     if (i < a.R) a.score[i] = (i % a.K == 0) ? 0.f : NEG_INF;     // at t = 1 only row 0 of each utterance is live
     if (i < a.B) { a.fin[i] = 0; a.best_score[i] = NEG_INF; a.best_len[i] = 0; a.best_row[i] = i * a.K; }
+    if (i < a.B * a.N) { a.nb_score[i] = NEG_INF; a.nb_len[i] = -1; a.nb_row[i] = (i / a.N) * a.K; }      // (N <= K: inside the R threads)
+}
+// one thread: the joint LM beam's weights, read by its step kernels from the device
+__global__ void beam_set_weights_kernel(float* w, float att_w, float ctc_w, float lm_w, float len_bonus) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { w[0] = att_w; w[1] = ctc_w; w[2] = lm_w; w[3] = len_bonus; }
 }
 
 // grid R, 256 threads
@@ -69,43 +74,51 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamArgs a, const fl
                      [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + ((z[c] - l.mx) - l.log_s); });
 }
 
-// grid B, 64 threads (one wave; lane k = parent rank k).  JOINT (masr_recog_beam_ctc): the row lists are P long, sorted by joint score,
-// and a kept candidate also takes its prefix score and the place of its CTC state
+// K-way merge of an utterance's K sorted row lists by one wave (lane k = parent rank k): the n <= K best candidates, rank order, into the
+// caller's LDS arrays [64]; returns n.  Lane k's head is the best untaken entry of row r0 + k; key = (ordered score, 63 - parent, max - list
+// position).  JOINT: the row lists are P long, and a candidate also brings its prefix score and the place of its CTC state
+template <bool JOINT>
+__device__ __forceinline__ int beam_merge_lists(const BeamArgs& a, int r0, int lane, float* s_score, int* s_tok, int* s_par, float* s_psi, int* s_slot) {
+    constexpr int HB = JOINT ? 7 : 6;                            // bits of the list position in the merge key (P <= 96, K <= 64)
+    const int K = a.K, W = JOINT ? a.P : K;                      // list length
+    int h = 0;
+    auto head_key = [&]() -> unsigned long long {
+        if (lane >= K || h >= W) return 0ull;
+        const float sc = a.list_score[(long)(r0 + lane) * W + h];
+        if (a.list_tok[(long)(r0 + lane) * W + h] < 0 || sc == NEG_INF) return 0ull;
+        return ((unsigned long long)ord_f32(sc) << 32) | (uint32_t)(((63 - lane) << HB) | ((1 << HB) - 1 - h));
+    };
+    unsigned long long key = head_key();
+    int n = 0;
+    for (; n < K; ++n) {
+        const unsigned long long top = wave_max_u64(key);
+        if (top == 0) break;
+        const int k = 63 - (int)((top >> HB) & 63);
+        if (lane == k) {
+            const long e = (long)(r0 + k) * W + h;
+            s_score[n] = a.list_score[e];
+            s_tok[n] = a.list_tok[e];
+            s_par[n] = r0 + k;
+            if constexpr (JOINT) { s_psi[n] = a.list_psi[e]; s_slot[n] = a.list_slot[e]; }
+            ++h;
+            key = head_key();
+        }
+    }
+    return n;
+}
+
+// grid B, 64 threads (one wave).  JOINT (masr_recog_beam_ctc): the row lists are P long, sorted by joint score, and a kept candidate also
+// takes its prefix score and the place of its CTC state
 template <bool JOINT>
 __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
-    constexpr int HB = JOINT ? 7 : 6;                            // bits of the list position in the merge key (P <= 96, K <= 64)
     __shared__ float s_score[64];
     __shared__ int s_tok[64], s_par[64];
     __shared__ float s_psi[JOINT ? 64 : 1];
     __shared__ int s_slot[JOINT ? 64 : 1];
     const int u = blockIdx.x, lane = threadIdx.x, K = a.K, st = *a.step;
-    const int W = JOINT ? a.P : K;                               // list length
     if (!a.fin[u]) {
         const int r0 = u * K;
-        // K-way merge: lane k's head is the best untaken entry of row r0 + k.  key = (ordered score, 63 - parent, max - list position)
-        int h = 0;
-        auto head_key = [&]() -> unsigned long long {
-            if (lane >= K || h >= W) return 0ull;
-            const float sc = a.list_score[(long)(r0 + lane) * W + h];
-            if (a.list_tok[(long)(r0 + lane) * W + h] < 0 || sc == NEG_INF) return 0ull;
-            return ((unsigned long long)ord_f32(sc) << 32) | (uint32_t)(((63 - lane) << HB) | ((1 << HB) - 1 - h));
-        };
-        unsigned long long key = head_key();
-        int n = 0;
-        for (; n < K; ++n) {
-            const unsigned long long top = wave_max_u64(key);
-            if (top == 0) break;
-            const int k = 63 - (int)((top >> HB) & 63);
-            if (lane == k) {
-                const long e = (long)(r0 + k) * W + h;
-                s_score[n] = a.list_score[e];
-                s_tok[n] = a.list_tok[e];
-                s_par[n] = r0 + k;
-                if constexpr (JOINT) { s_psi[n] = a.list_psi[e]; s_slot[n] = a.list_slot[e]; }
-                ++h;
-                key = head_key();
-            }
-        }
+        const int n = beam_merge_lists<JOINT>(a, r0, lane, s_score, s_tok, s_par, s_psi, s_slot);
         __syncthreads();
         if (lane == 0) {
             float bs = a.best_score[u]; int bl = a.best_len[u], br = a.best_row[u];
@@ -133,6 +146,74 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
             a.best_score[u] = bs; a.best_len[u] = bl; a.best_row[u] = br;
             // log-probabilities are <= 0: no running hypothesis can overtake an ended one that is at least as good
             if (j == 0 || st >= maxlen || bs >= run_best) a.fin[u] = 1;
+        }
+    }
+    if (lane == 0) step_ticket(a.step, st, a.B);                 // the last utterance to finish advances the step
+}
+
+// The joint select with an N-best list and the bound stop rule (masr_recog_beam_ctc_lm).  grid B, 64 threads (one wave).  After
+// the merge lane i owns candidate i of the n selected (rank order = score descending): ballots give a running one its row and an ended one
+// (eos, or anything at st >= maxlen) its place e among the step's ne ended, which are thereby sorted too.  The list [N] is merged with them
+// by rank computation: old entry l moves to l + #{new with a larger score}, new entry e to e + #{old with a score >= its own} -- an old entry
+// ended at an earlier step and wins a tie.  Positions >= N fall off; empty slots (len -1) stay the last.
+// Stop: nothing runs, st >= maxlen, or the list is full and its N-th score >= fl(run_best + fl((maxlen - st) * max(len_bonus, 0))): every
+// other increment is <= 0, so no running hypothesis can still enter the list.
+__global__ __launch_bounds__(64) void beam_select_nbest_kernel(BeamArgs a) {
+    __shared__ float s_score[64], s_psi[64];
+    __shared__ int s_tok[64], s_par[64], s_slot[64];
+    __shared__ float s_es[64], s_os[64], s_ms[64];               // the step's ended / the old list / the merged list: scores
+    __shared__ int s_ml[64], s_mr[64];
+    const int u = blockIdx.x, lane = threadIdx.x, K = a.K, N = a.N, st = *a.step;
+    if (!a.fin[u]) {
+        const int r0 = u * K, maxlen = a.maxlen[u];
+        const int n = beam_merge_lists<true>(a, r0, lane, s_score, s_tok, s_par, s_psi, s_slot);
+        float* nbs = a.nb_score + (long)u * N; int* nbl = a.nb_len + (long)u * N; int* nbr = a.nb_row + (long)u * N;
+        const float os = lane < N ? nbs[lane] : NEG_INF;
+        const int ol = lane < N ? nbl[lane] : -1, orow = lane < N ? nbr[lane] : r0;
+        const bool old_live = ol >= 0;
+        s_os[lane] = os;
+        __syncthreads();                                         // the merge's LDS stores and the old list
+        const bool have = lane < n;
+        const float sc = have ? s_score[lane] : NEG_INF;
+        const bool is_eos = have && s_tok[lane] == a.eos, runs = have && !is_eos, ends = have && (is_eos || st >= maxlen);
+        const unsigned long long below = (1ull << lane) - 1, m_run = __ballot(runs), m_end = __ballot(ends);
+        const int j = __popcll(m_run & below), nrun = __popcll(m_run), e = __popcll(m_end & below), ne = __popcll(m_end);
+        const int no = __popcll(__ballot(old_live));
+        const int row = r0 + j;
+        if (runs) {
+            a.tok_hist[(long)(st - 1) * a.R + row] = s_tok[lane];
+            a.par_hist[(long)(st - 1) * a.R + row] = s_par[lane];
+            a.score[row] = sc;
+            a.psi[row] = s_psi[lane]; a.src[row] = s_par[lane] * a.P + s_slot[lane];
+        }
+        if (lane >= nrun && lane < K) {                          // the beam shrank: dead rows
+            a.tok_hist[(long)(st - 1) * a.R + r0 + lane] = a.sos;
+            a.par_hist[(long)(st - 1) * a.R + r0 + lane] = r0 + lane;
+            a.score[r0 + lane] = NEG_INF;
+        }
+        if (ends) s_es[e] = sc;
+        __syncthreads();
+        if (old_live) {
+            int pos = lane;
+            for (int i = 0; i < ne; ++i) pos += s_es[i] > os;
+            if (pos < N) { s_ms[pos] = os; s_ml[pos] = ol; s_mr[pos] = orow; }
+        }
+        if (ends) {
+            int pos = e;
+            for (int i = 0; i < no; ++i) pos += s_os[i] >= sc;
+            // ended by eos: the parent's tokens, without eos; at maxlen a running hypothesis ends as it is
+            if (pos < N) { s_ms[pos] = sc; s_ml[pos] = is_eos ? st - 1 : st; s_mr[pos] = is_eos ? s_par[lane] : row; }
+        }
+        __syncthreads();
+        const int total = min(N, no + ne);
+        if (lane < total) { nbs[lane] = s_ms[lane]; nbl[lane] = s_ml[lane]; nbr[lane] = s_mr[lane]; }
+        if (lane == 0) {
+            bool done = nrun == 0 || st >= maxlen;
+            if (!done && total == N) {
+                const float run_best = s_score[__ffsll((long long)m_run) - 1];      // the first running candidate: the best one
+                done = s_ms[N - 1] >= add_rn(run_best, mul_rn((float)(maxlen - st), fmaxf(a.wts[3], 0.f)));
+            }
+            if (done) a.fin[u] = 1;
         }
     }
     if (lane == 0) step_ticket(a.step, st, a.B);                 // the last utterance to finish advances the step
@@ -192,7 +273,10 @@ __global__ __launch_bounds__(256) void beam_ctc_prebeam_kernel(BeamArgs a, const
 // phi_t, r^b_t and x_t(blank) are staged in LDS by chunks of CTC_CH frames (every chain of the row shares them); the candidate's
 // (r^n_t, r^b_t) go to ctc_state[st & 1][r][t][i], so a wave's stores at one frame are contiguous.  Then the row's candidates are
 // sorted by (joint score descending, pre-beam position ascending) into list_tok / list_score / list_psi / list_slot.
+// LM (masr_recog_beam_ctc_lm): the same chains; the score takes the weights from a.wts and adds the pre-beam's weighted LM
+// term and, for a token, the length bonus -- five roundings, no multiply-add.
 constexpr int CTC_CH = 256;
+template <bool LM>
 __global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
     __shared__ float s_phi[CTC_CH], s_rbp[CTC_CH], s_xb[CTC_CH];
     __shared__ unsigned long long s_key[128];
@@ -247,7 +331,12 @@ __global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
     float js = NEG_INF;
     if (c > 0 && psi != NEG_INF) {
         const float d = __fsub_rn(psi, a.psi[r]);
-        js = __fadd_rn(__fadd_rn(ps, __fmul_rn(a.att_w, a.pre_lp[lo + i])), __fmul_rn(a.ctc_w, d));
+        if constexpr (LM) {
+            js = add_rn(add_rn(ps, mul_rn(a.wts[0], a.pre_lp[lo + i])), mul_rn(a.wts[1], d));
+            js = add_rn(add_rn(js, a.pre_lm[lo + i]), c == a.eos ? 0.f : a.wts[3]);
+        } else {
+            js = __fadd_rn(__fadd_rn(ps, __fmul_rn(a.att_w, a.pre_lp[lo + i])), __fmul_rn(a.ctc_w, d));
+        }
         if (js != NEG_INF) key = ((unsigned long long)ord_f32(js) << 32) | (uint32_t)(127 - i);
     }
     s_key[i] = key;
@@ -276,6 +365,25 @@ __global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __r
         }
         lens[u] = n;
         scores[u] = a.best_score[u];
+    }
+}
+
+// grid B * N, 64 threads: entry n of utterance u -> tokens [B][N][Lmax] (-1 past the end), lens / scores [B][N]; an empty slot: -1, -inf, all -1
+// and nothing is walked.  The walk stays inside the Lmax history rows and the utterance's K rows whatever the list holds.
+__global__ __launch_bounds__(64) void beam_backtrace_nbest_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
+    const int e = blockIdx.x, u0 = (e / a.N) * a.K;
+    const int n = min(a.nb_len[e], a.Lmax);
+    int* out = tokens + (long)e * a.Lmax;
+    for (int i = threadIdx.x; i < a.Lmax; i += 64) if (i >= n) out[i] = -1;
+    if (threadIdx.x == 0) {
+        int row = a.nb_row[e];
+        for (int s = n; s >= 1; --s) {
+            if (row < u0 || row >= u0 + a.K) row = u0;
+            out[s - 1] = a.tok_hist[(long)(s - 1) * a.R + row];
+            row = a.par_hist[(long)(s - 1) * a.R + row];
+        }
+        lens[e] = n < 0 ? -1 : n;
+        scores[e] = n < 0 ? NEG_INF : a.nb_score[e];
     }
 }
 
@@ -318,11 +426,34 @@ int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStre
 }
 int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s) {
     if (a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_prefix", "pre-beam width must be in [1, 96]"); return -1; }
-    hipLaunchKernelGGL(beam_ctc_prefix_kernel, dim3(a.R), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(beam_ctc_prefix_kernel<false>, dim3(a.R), dim3(128), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_prefix_lm(const BeamArgs& a, hipStream_t s) {
+    if (a.P < 1 || a.P > 96 || !a.wts || !a.pre_lm) { mk_set_error("mk_beam_ctc_prefix_lm", "need 1 <= P <= 96, the weights and the LM terms"); return -1; }
+    hipLaunchKernelGGL(beam_ctc_prefix_kernel<true>, dim3(a.R), dim3(128), 0, s, a);
     return LAUNCH_OK();
 }
 int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s) {
     if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_select", "need 1 <= K <= 64, 1 <= P <= 96"); return -1; }
     hipLaunchKernelGGL(beam_select_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
+    return LAUNCH_OK();
+}
+
+int mk_beam_set_weights(const BeamArgs& a, float att_w, float ctc_w, float lm_w, float len_bonus, hipStream_t s) {
+    if (!a.wts) { mk_set_error("mk_beam_set_weights", "null pointer"); return -1; }
+    hipLaunchKernelGGL(beam_set_weights_kernel, dim3(1), dim3(64), 0, s, const_cast<float*>(a.wts), att_w, ctc_w, lm_w, len_bonus);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_select_nbest(const BeamArgs& a, hipStream_t s) {
+    if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96 || a.N < 1 || a.N > a.K || !a.wts || !a.nb_score || !a.nb_len || !a.nb_row) {
+        mk_set_error("mk_beam_ctc_select_nbest", "need 1 <= N <= K <= 64, 1 <= P <= 96, the weights and the list"); return -1;
+    }
+    hipLaunchKernelGGL(beam_select_nbest_kernel, dim3(a.B), dim3(64), 0, s, a);
+    return LAUNCH_OK();
+}
+int mk_beam_backtrace_nbest(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
+    if (a.N < 1 || a.N > a.K || !a.nb_score || !a.nb_len || !a.nb_row) { mk_set_error("mk_beam_backtrace_nbest", "need 1 <= N <= K and the list"); return -1; }
+    hipLaunchKernelGGL(beam_backtrace_nbest_kernel, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores);
     return LAUNCH_OK();
 }

@@ -40,17 +40,6 @@ __device__ __forceinline__ int clamp_len(int n, int Tp) { return n < 0 ? 0 : (n 
 // ---- the LM side of ctc_beam_sweep<true>
 struct CtcLmArgs { LmDev lm; float lm_w, len_bonus; float* am; };      // am [B][nbest]: the acoustic totals
 
-// fl(a * b) and fl(a + b) that no later pass fuses into a multiply-add: under the default -ffp-contract the plain operators (and __fmul_rn /
-// __fadd_rn, which are the plain operators) were contracted here, fma(lm_w, lm, len_bonus)
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
 constexpr unsigned long long CTX_MASK = (1ull << 48) - 1;
 __device__ __forceinline__ unsigned long long ctx_push(unsigned long long ctx, int c) { return ((ctx << 16) | (unsigned long long)(c + 1)) & CTX_MASK; }
 __device__ __forceinline__ unsigned long long ctx_key(unsigned long long ctx, int k) { return ctx & ((1ull << (16 * k)) - 1); }   // 1 <= k <= 3

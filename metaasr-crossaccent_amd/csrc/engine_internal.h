@@ -112,8 +112,9 @@ struct masr_model {
     bool step_graphs_on = false;                           // masr_set_step_graphs
     // cached step graphs of the three decoders, each keyed on its own shape (recog.hip run_steps): alternating decoders do not evict
     // one another.  greedy {B, T, Ldec} + {ws, P, out}; beam {B, T, K, Lmax} + {ws, P}; joint: the beam's key + the two weights' bits;
-    // LM fusion: the beam's key + lm_w's bits + the LM's serial number
-    DecodeGraph greedy_graph, beam_graph, joint_graph, lm_graph;
+    // LM fusion: the beam's key + lm_w's bits + the LM's serial number; joint with LM: the beam's key + N + the LM's serial number (its
+    // weights are device values, not part of the graph)
+    DecodeGraph greedy_graph, beam_graph, joint_graph, lm_graph, joint_lm_graph;
     struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
     bool prof = false;

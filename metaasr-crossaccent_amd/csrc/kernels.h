@@ -170,6 +170,13 @@ struct BeamArgs {
     int* src;                                  // [R] its CTC state: parent row * P + candidate slot of the previous step
     int* pre_tok; float* pre_lp;               // [R][P] pre-beam: the P best tokens by logit, their attention log-probs
     int* list_slot; float* list_psi;           // [R][P] beside list_tok / list_score: the candidate's chain slot and prefix score
+    // joint decode with an n-gram LM, a length bonus and an N-best list (masr_recog_beam_ctc_lm; N = 0 and null otherwise).  The
+    // four weights live on the device, so that a cached step graph never holds a value of theirs
+    const float* wts;                          // [4] att_w, ctc_w, lm_w, len_bonus (att_w / ctc_w above are not read)
+    float* pre_lm;                             // [R][P] beside pre_tok / pre_lp: the weighted LM term fl(lm_w * lm(c | h))
+    int N;                                     // entries of the N-best list, 1 <= N <= K
+    float* nb_score; int *nb_len, *nb_row;     // [B][N] ended hypotheses, best first (best_* are not used): score, token count, row at step nb_len;
+                                               // an empty slot holds -inf / -1 / the utterance's first row, and the empty slots are the last
 };
 int mk_beam_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s);
@@ -183,10 +190,18 @@ int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
 int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
 int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s);                // also advances step[0]
+// joint beam with LM, bonus and N-best: the four weights into a.wts (a plain launch in front of the step replays); per step
+// mk_beam_ctc_lm_prebeam (lm.hip: the P best classes by g(c) = lp(c) + lm_w * lm(c | h), through the fp32 workspace fused [R][ldf]),
+// mk_beam_ctc_prefix_lm and mk_beam_ctc_select_nbest (also advances step[0]); mk_beam_backtrace_nbest: tokens [B][N][Lmax], lens / scores [B][N]
+int mk_beam_set_weights(const BeamArgs& a, float att_w, float ctc_w, float lm_w, float len_bonus, hipStream_t s);
+int mk_beam_ctc_prefix_lm(const BeamArgs& a, hipStream_t s);
+int mk_beam_ctc_select_nbest(const BeamArgs& a, hipStream_t s);
+int mk_beam_backtrace_nbest(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
 // n-gram LM shallow fusion (lm.hip, lm.h): in place of mk_beam_row_topk -- the row's K best classes by the fused increment
 // f(c) = lp(c) + lm_w * lm(c | h), through the fp32 workspace fused [R][ldf]; then mk_beam_select as ever
 struct LmDev;
 int mk_beam_lm_topk(const BeamArgs& a, const LmDev& lm, float lm_w, const float* logits, long ld, float* fused, long ldf, hipStream_t s);
+int mk_beam_ctc_lm_prebeam(const BeamArgs& a, const LmDev& lm, const float* logits, long ld, float* fused, long ldf, hipStream_t s);
 // out [R][C] = lm(c | ctx row) for every class; ctx int32 [R][order - 1], oldest first, -1 in front of a shorter context
 int mk_lm_score(const LmDev& lm, const int* ctx, int R, float* out, hipStream_t s);
 

@@ -21,12 +21,36 @@
 
 namespace {
 
+// The LM context of row r's hypothesis (st - 1 tokens), for the whole wave: token s of h is tok_hist[s - 1][row], row = the hypothesis's row
+// after step s; position 0 is sos.  Lane 0 walks the histories and broadcasts.  Reads are clamped as in beam_embed_step: a stale entry can
+// neither leave the class range nor the utterance's rows; n <= order - 1, so no order the LM lacks is ever indexed
+__device__ __forceinline__ LmCtx row_lm_context(const BeamArgs& a, const LmDev& lm, int r, int st, int lane) {
+    const int u0 = (r / a.K) * a.K;
+    const int n = min(lm.order - 1, st);
+    int tok[LM_MAX_ORDER - 1];
+    int row = r;
+#pragma unroll
+    for (int i = 0; i < LM_MAX_ORDER - 1; ++i) {
+        int t = a.sos;
+        const int s = st - 1 - i;
+        if (lane == 0 && i < n && s >= 1) {
+            t = a.tok_hist[(long)(s - 1) * a.R + row];
+            int par = a.par_hist[(long)(s - 1) * a.R + row];
+            if (t < 0 || t >= a.C) t = a.sos;
+            if (par < u0 || par >= u0 + a.K) par = row;
+            row = par;
+        }
+        tok[i] = __shfl(t, 0, 64);
+    }
+    return lm_context(lm, tok, n);
+}
+
 // grid ceil(R / 4), 256 threads: one wave per row
 __global__ __launch_bounds__(256) void beam_lm_topk_kernel(BeamArgs a, LmDev lm, float lm_w, const float* __restrict__ logits, long ld,
                                                           float* __restrict__ fused, long ldf) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.R) return;
-    const int u = r / a.K, st = *a.step, u0 = u * a.K;
+    const int u = r / a.K, st = *a.step;
     if (a.fin[u]) return;
     const float ps = a.score[r];
     int* lt = a.list_tok + (long)r * a.K;
@@ -35,27 +59,7 @@ __global__ __launch_bounds__(256) void beam_lm_topk_kernel(BeamArgs a, LmDev lm,
         for (int i = lane; i < a.K; i += 64) { lt[i] = -1; ls[i] = NEG_INF; }
         return;
     }
-    // the context: token s of h is tok_hist[s - 1][row], row = the hypothesis's row after step s; position 0 is sos.  Reads are clamped as
-    // in beam_embed_step: a stale entry can neither leave the class range nor the utterance's rows
-    const int n = min(lm.order - 1, st);
-    int tok[LM_MAX_ORDER - 1];
-    {
-        int row = r;
-#pragma unroll
-        for (int i = 0; i < LM_MAX_ORDER - 1; ++i) {
-            int t = a.sos;
-            const int s = st - 1 - i;
-            if (lane == 0 && i < n && s >= 1) {
-                t = a.tok_hist[(long)(s - 1) * a.R + row];
-                int par = a.par_hist[(long)(s - 1) * a.R + row];
-                if (t < 0 || t >= a.C) t = a.sos;
-                if (par < u0 || par >= u0 + a.K) par = row;
-                row = par;
-            }
-            tok[i] = __shfl(t, 0, 64);
-        }
-    }
-    const LmCtx x = lm_context(lm, tok, n);
+    const LmCtx x = row_lm_context(a, lm, r, st, lane);
     const float* z = logits + (long)r * ld;
     float* fz = fused + (long)r * ldf;
     const bool no_eos = (st - 1) < a.minlen[u];                  // the hypothesis has st - 1 tokens
@@ -67,6 +71,36 @@ __global__ __launch_bounds__(256) void beam_lm_topk_kernel(BeamArgs a, LmDev lm,
     __threadfence_block();                                       // lane 0 reads below what the other lanes of its wave stored
     row_top_n<false>(fz, a.C, a.K, lane, [&](int c) { return no_eos && c == a.eos; },
                      [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + fz[c]; });
+}
+
+// The pre-beam of the joint LM beam (masr_recog_beam_ctc_lm).  grid ceil(R / 4), 256 threads: one wave per live row.  The
+// fused row g(c) = fl(lp(c) + fl(lm_w * lm(c | h))) is beam_lm_topk's f(c), composed the same way; the row's P best classes by (g
+// descending, class ascending; blank never, eos once the hypothesis has minlen tokens) go to pre_tok, token -1 past the end.  Then the lanes
+// share the P entries: the attention lp(c) to pre_lp and the weighted LM term fl(lm_w * lm(c | h)) to pre_lm, each computed again from
+// its inputs (the same expressions: the same bits), so no second [R][Cp] row is kept for them.
+__global__ __launch_bounds__(256) void beam_ctc_lm_prebeam_kernel(BeamArgs a, LmDev lm, const float* __restrict__ logits, long ld,
+                                                                 float* __restrict__ fused, long ldf) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const int u = r / a.K, st = *a.step;
+    if (a.fin[u] || a.score[r] == NEG_INF) return;               // (the prefix kernel gives a dead row its empty list)
+    const float lm_w = a.wts[2];
+    int* pt = a.pre_tok + (long)r * a.P;
+    const LmCtx x = row_lm_context(a, lm, r, st, lane);
+    const float* z = logits + (long)r * ld;
+    float* gz = fused + (long)r * ldf;
+    const bool no_eos = (st - 1) < a.minlen[u];
+    const RowLse l = row_lse(z, a.C, lane);
+    for (int c = lane; c < a.C; c += 64) gz[c] = add_rn((z[c] - l.mx) - l.log_s, mul_rn(lm_w, lm_score(lm, x, c)));
+    __threadfence_block();                                       // lane 0 reads below what the other lanes of its wave stored
+    row_top_n<false>(gz, a.C, a.P, lane, [&](int c) { return c == 0 || (no_eos && c == a.eos); }, [&](int i, int c) { pt[i] = c; });
+    __threadfence_block();                                       // and the lanes read what lane 0 stored
+    for (int i = lane; i < a.P; i += 64) {
+        const int c = pt[i];
+        const bool ok = c > 0 && c < a.C;
+        a.pre_lp[(long)r * a.P + i] = ok ? (z[c] - l.mx) - l.log_s : NEG_INF;
+        a.pre_lm[(long)r * a.P + i] = ok ? mul_rn(lm_w, lm_score(lm, x, c)) : 0.f;
+    }
 }
 
 // grid ceil(R / 4), 256 threads: one wave per context row.  ctx [R][order - 1], oldest first, -1 in front of a shorter context
@@ -100,6 +134,13 @@ int mk_beam_lm_topk(const BeamArgs& a, const LmDev& lm, float lm_w, const float*
         mk_set_error("mk_beam_lm_topk", "need 1 <= K <= 64, an LM of order 1 .. 4 over the beam's classes, ldf >= C"); return -1;
     }
     hipLaunchKernelGGL(beam_lm_topk_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, lm, lm_w, logits, ld, fused, ldf);
+    return LAUNCH_OK();
+}
+int mk_beam_ctc_lm_prebeam(const BeamArgs& a, const LmDev& lm, const float* logits, long ld, float* fused, long ldf, hipStream_t s) {
+    if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96 || lm.order < 1 || lm.order > LM_MAX_ORDER || lm.C != a.C || ldf < a.C || !a.wts || !a.pre_lm) {
+        mk_set_error("mk_beam_ctc_lm_prebeam", "need 1 <= K <= 64, 1 <= P <= 96, an LM of order 1 .. 4 over the beam's classes, ldf >= C"); return -1;
+    }
+    hipLaunchKernelGGL(beam_ctc_lm_prebeam_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, lm, logits, ld, fused, ldf);
     return LAUNCH_OK();
 }
 int mk_lm_score(const LmDev& lm, const int* ctx, int R, float* out, hipStream_t s) {

@@ -122,12 +122,14 @@ static int check_pointers(const char* fn, const float* xs, const int64_t* ilens,
 //   LM fusion (masr_recog_beam_lm, lm): the beam's plan, then the fp32 fused rows [B*K][Cp]
 //   joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
 //   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
+//   joint with LM, bonus and N-best (masr_recog_beam_ctc_lm, P > 0, lm, NB > 0): both of the above, then the candidates' LM terms [R][P], the
+//   four weights and the N-best list [B][NB]
 //   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
 //   buffer follow
 //   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
 //   of up to Lmax tokens behind their sos; with a first pass (K > 0) the CTC-only beam's buffers and its N-best list follow, then the
 //   second pass's scores
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; };
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; };
 struct DecodeBufs {
     BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
     float* lm_fused;                                                    // LM fusion: the rows' fused increments [R][Cp]
@@ -155,6 +157,10 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
     a.psi = ar.get<float>(R); a.src = ar.get<int>(R);
     a.pre_tok = ar.get<int>((int64_t)R * P); a.pre_lp = ar.get<float>((int64_t)R * P);
     a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
+    if (!d.NB) return o;
+    a.N = d.NB;
+    a.pre_lm = ar.get<float>((int64_t)R * P); a.wts = ar.get<float>(4);
+    a.nb_score = ar.get<float>((int64_t)B * d.NB); a.nb_len = ar.get<int>((int64_t)B * d.NB); a.nb_row = ar.get<int>((int64_t)B * d.NB);
     return o;
 }
 static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, int K) {
@@ -209,6 +215,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
         mk_set_error("masr_recog", d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : d.NB ? "workspace too small (masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
                                    : d.lm ? "workspace too small (masr_beam_lm_workspace_bytes(B, T, K, Lmax))"
                                          : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
@@ -290,12 +297,19 @@ int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, 
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
 // CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.  LM fusion (lm): the
-// fused top-K (lm.hip) in place of the row top-K.
+// fused top-K (lm.hip) in place of the row top-K.  Both (ba.N > 0): the fused pre-beam, the prefix scores with the LM term and
+// the bonus, the select with the N-best list; the weights are read from ba.wts, lm->w is not used.
 struct LmStep { LmDev dev; float w; float* fused; };
 static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* lm = nullptr) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
     CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
+    if (ba.N) {
+        CK(mk_beam_ctc_lm_prebeam(ba, lm->dev, a.logits, m->Cp, lm->fused, m->Cp, s));
+        CK(mk_beam_ctc_prefix_lm(ba, s));
+        CK(mk_beam_ctc_select_nbest(ba, s));                    // also advances *step_dev
+        return 0;
+    }
     if (ba.P) {
         CK(mk_beam_ctc_prebeam(ba, a.logits, m->Cp, s));
         CK(mk_beam_ctc_prefix(ba, s));
@@ -308,14 +322,16 @@ static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* l
     return 0;
 }
 
-// masr_recog_beam (wts == null), masr_recog_beam_ctc (wts = {att_w, ctc_w}) and masr_recog_beam_lm (lm, lm_w; wts == null): the same decode,
-// each with its own cached step graph
+// masr_recog_beam (wts == null), masr_recog_beam_ctc (wts = {att_w, ctc_w}), masr_recog_beam_lm (lm, lm_w; wts == null) and
+// masr_recog_beam_ctc_lm (wts, lm, lm_w, nb = {N, len_bonus}): the same decode, each with its own cached step graph
+struct NbestSpec { int N; float len_bonus; };
 static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
                            const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn,
-                           const masr_lm* lm = nullptr, float lm_w = 0.f) {
+                           const masr_lm* lm = nullptr, float lm_w = 0.f, const NbestSpec* nb = nullptr) {
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
-    // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers) and
+    // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers; joint with
+    // LM: N and the serial number -- its four weights are device values written in front of the replays, no graph holds one) and
     // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
     CK(check_beam_size(fn, K));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
@@ -333,7 +349,7 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0, false, 0, lm != nullptr}, &bufs);
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0, false, 0, lm != nullptr, nb ? nb->N : 0}, &bufs);
       if (rc) return rc; }
     BeamArgs& ba = bufs.beam; bf16* step_qkv = bufs.step_qkv; float* ctc_logits = bufs.ctc_logits;
     Acts& a = m->acts;
@@ -363,9 +379,14 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
         ls = LmStep{lm->dev, lm_w, bufs.lm_fused};
         memcpy(key + 4, &lm_w, sizeof(float)); key[5] = (int)lm->serial;
     }
-    CK(run_steps(m, wts ? m->joint_graph : lm ? m->lm_graph : m->beam_graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
-                 [&] { return beam_step(c, ba, step_qkv, lm ? &ls : nullptr); }));
-    CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
+    if (nb) {
+        CK(mk_beam_set_weights(ba, wts[0], wts[1], lm_w, nb->len_bonus, s));
+        key[4] = nb->N;
+    }
+    CK(run_steps(m, nb ? m->joint_lm_graph : wts ? m->joint_graph : lm ? m->lm_graph : m->beam_graph, key, kp, Lmax, s, fn,
+                 "stream capture of the beam step failed", [&] { return beam_step(c, ba, step_qkv, lm ? &ls : nullptr); }));
+    if (nb) CK(mk_beam_backtrace_nbest(ba, tokens, lens, scores, s));
+    else CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
 }
@@ -402,6 +423,31 @@ int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const 
     if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
     if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
     return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, fn, lm, lm_w);
+}
+
+int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
+    return decode_workspace_bytes("masr_beam_ctc_lm_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && N >= 1 && N <= K && Lmax >= 1,
+                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, beam_prebeam_width(K), false, 0, true, N});
+}
+
+int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float min_step_ratio,
+                           float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
+                           void* stream) {
+    // the joint beam with the n-gram LM in the pre-beam and the score, a bonus per emitted token and an N-best list
+    const char* fn = "masr_recog_beam_ctc_lm";
+    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    CK(check_ctc_head(fn, m));
+    if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
+    if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
+    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
+    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
+    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
+    if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
+    CK(check_beam_size(fn, K));
+    if (N < 1 || N > K) { mk_set_error(fn, "N must be in [1, K]"); return -1; }
+    const float wts[2] = {att_w, ctc_w};
+    const NbestSpec nb{N, len_bonus};
+    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn, lm, lm_w, &nb);
 }
 
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {

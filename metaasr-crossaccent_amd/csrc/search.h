@@ -24,6 +24,18 @@ __device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e
     return m + __logf(1.f + __expf(fminf(a, b) - m));
 }
 
+// fl(a * b) and fl(a + b) that no later pass fuses into a multiply-add: under the default -ffp-contract the plain operators (and __fmul_rn /
+// __fadd_rn, which are the plain operators) were contracted in ctc_beam_sweep<true>, fma(lm_w, lm, len_bonus).  The LM-fused searches
+// (ctc_beam.hip, the joint LM beam of beam.hip / lm.hip) compose their scores from these two
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // Wave arg-max, ties to the lowest index (torch's first maximal index): every lane brings the (mx, am) of its own scan and leaves
 // with the wave's.  The lanes' initial am is the caller's business: it is what a row with nothing above -inf returns.
 __device__ __forceinline__ void wave_argmax_first(float& mx, int& am) {

@@ -63,10 +63,11 @@ int masr_test_rescore_select(const int32_t* tokens_in, int64_t ld_tok, const int
     return mk_rescore_select(tokens_in, (long)ld_tok, lens_in, ctc_in, att_in, B, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
                              (hipStream_t)stream);
 }
-int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
-                         const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
-                         int32_t* list_slot, float* out_state, void* stream) {
-    const char* fn = "masr_test_ctc_prefix";
+}  // extern "C"
+// masr_test_ctc_prefix (pre_lm == null) and masr_test_ctc_prefix_lm
+static int test_ctc_prefix(const char* fn, const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                           const float* att_lp, const float* pre_lm, int n, float att_w, float ctc_w, float len_bonus, int32_t* list_tok,
+                           float* list_score, float* list_psi, int32_t* list_slot, float* out_state, void* stream) {
     if (!lp || !cand || !att_lp || !list_tok || !list_score || !list_psi || !list_slot || !out_state || (last >= 0 && !parent)) {
         mk_set_error(fn, "null pointer"); return -1;
     }
@@ -94,14 +95,16 @@ int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* p
     a.ctc_lp = lp; a.ctc_state = reinterpret_cast<float2*>(w + 256);
     a.pre_tok = const_cast<int*>(cand); a.pre_lp = const_cast<float*>(att_lp);
     a.list_tok = list_tok; a.list_score = list_score; a.list_psi = list_psi; a.list_slot = list_slot;
+    if (pre_lm) { a.pre_lm = const_cast<float*>(pre_lm); a.wts = flts + 4; a.att_w = a.ctc_w = 0.f; }      // (the LM kernel reads its weights from a.wts)
     int rc = 0;
     auto run = [&]() -> int {
         HIP_CHECK_RET(hipMemcpyAsync(ints, h_ints, sizeof h_ints, hipMemcpyHostToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(flts, h_flts, sizeof h_flts, hipMemcpyHostToDevice, s));
+        if (pre_lm) CK(mk_beam_set_weights(a, att_w, ctc_w, 0.f, len_bonus, s));
         if (last < 0) CK(mk_beam_ctc_init(a, s));            // (writes psi 0 and src 0: the empty hypothesis)
         else HIP_CHECK_RET(hipMemcpy2DAsync(a.ctc_state + plane, (size_t)n * sizeof(float2), parent, sizeof(float2), sizeof(float2), T,
                                             hipMemcpyDeviceToDevice, s));
-        CK(mk_beam_ctc_prefix(a, s));
+        CK(pre_lm ? mk_beam_ctc_prefix_lm(a, s) : mk_beam_ctc_prefix(a, s));
         HIP_CHECK_RET(hipMemcpyAsync(out_state, a.ctc_state + (st & 1) * plane, plane * sizeof(float2), hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipStreamSynchronize(s));
         return 0;
@@ -109,6 +112,20 @@ int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* p
     rc = run();
     hipFree(w);
     return rc;
+}
+extern "C" {
+int masr_test_ctc_prefix(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                         const float* att_lp, int n, float att_w, float ctc_w, int32_t* list_tok, float* list_score, float* list_psi,
+                         int32_t* list_slot, float* out_state, void* stream) {
+    return test_ctc_prefix("masr_test_ctc_prefix", lp, C, T, last, parent, psi_par, score, cand, att_lp, nullptr, n, att_w, ctc_w, 0.f, list_tok,
+                           list_score, list_psi, list_slot, out_state, stream);
+}
+int masr_test_ctc_prefix_lm(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,
+                            const float* att_lp, const float* pre_lm, int n, float att_w, float ctc_w, float len_bonus, int32_t* list_tok,
+                            float* list_score, float* list_psi, int32_t* list_slot, float* out_state, void* stream) {
+    if (!pre_lm) { mk_set_error("masr_test_ctc_prefix_lm", "null pointer"); return -1; }
+    return test_ctc_prefix("masr_test_ctc_prefix_lm", lp, C, T, last, parent, psi_par, score, cand, att_lp, pre_lm, n, att_w, ctc_w, len_bonus, list_tok,
+                           list_score, list_psi, list_slot, out_state, stream);
 }
 int masr_test_attn_decode(const uint16_t* q, int64_t ldq, const uint16_t* k, const uint16_t* v, int64_t ldk, int64_t kv_batch_stride,
                           const uint16_t* knew, const uint16_t* vnew, int64_t ldnew, const int32_t* step, const int32_t* klens, uint16_t* o,
@@ -235,6 +252,78 @@ int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, c
         HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
         HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
         CK(mk_beam_lm_topk(a, lm->dev, lm_w, logits, ld, (float*)(w + fused_off), ld, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+// ---- the joint LM beam's step kernels
+int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                               const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* pre_tok, float* pre_lp, float* pre_lm,
+                               void* stream) {
+    const char* fn = "masr_test_joint_lm_prebeam";
+    if (!lm || !minlen || !logits || !score || !pre_tok || !pre_lp || !pre_lm || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
+    const int C = lm->dev.C;
+    if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    char* w = nullptr;                                       // step[2] | weights [4] | fin [B] | fused [R][ld]
+    const size_t wts_off = 64, fin_off = 128, fused_off = (fin_off + sizeof(int) * (size_t)B + 255) & ~(size_t)255;
+    HIP_CHECK_RET(hipMalloc(&w, fused_off + sizeof(float) * (size_t)R * ld));
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen; a.P = std::max(1, 3 * K / 2);
+    a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
+    a.pre_tok = pre_tok; a.pre_lp = pre_lp; a.pre_lm = pre_lm; a.fin = (int*)(w + fin_off); a.wts = (float*)(w + wts_off);
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        CK(mk_beam_set_weights(a, 0.f, 0.f, lm_w, 0.f, s));
+        CK(mk_beam_ctc_lm_prebeam(a, lm->dev, logits, ld, (float*)(w + fused_off), ld, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, const int32_t* list_tok,
+                                const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,
+                                int32_t* fin, float* nb_score, int32_t* nb_len, int32_t* nb_row, int32_t* tok_hist_row, int32_t* par_hist_row,
+                                int32_t* step_out, void* stream) {
+    const char* fn = "masr_test_beam_select_nbest";
+    if (!maxlen || !list_tok || !list_score || !list_psi || !list_slot || !score || !psi || !src || !fin || !nb_score || !nb_len || !nb_row ||
+        !tok_hist_row || !par_hist_row || !step_out) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (K < 1 || K > 64 || N < 1 || N > K) { mk_set_error(fn, "need 1 <= N <= K <= 64"); return -1; }
+    if (B < 1 || C < 2 || t < 1) { mk_set_error(fn, "need B, t >= 1, C >= 2"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    const size_t hist = (size_t)t * R * sizeof(int);
+    int* w = nullptr;                                        // step[2] | weights [4] at int 16 | tok_hist [t][R] | par_hist [t][R]
+    HIP_CHECK_RET(hipMalloc(&w, 128 + 2 * hist));
+    int* tok_hist = w + 32;
+    int* par_hist = tok_hist + (size_t)t * R;
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.maxlen = maxlen; a.P = std::max(1, 3 * K / 2); a.N = N;
+    a.tok_hist = tok_hist; a.par_hist = par_hist; a.score = score; a.psi = psi; a.src = src; a.fin = fin;
+    a.list_tok = const_cast<int*>(list_tok); a.list_score = const_cast<float*>(list_score);
+    a.list_psi = const_cast<float*>(list_psi); a.list_slot = const_cast<int*>(list_slot);
+    a.nb_score = nb_score; a.nb_len = nb_len; a.nb_row = nb_row; a.wts = reinterpret_cast<float*>(w + 16);
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_set_weights(a, 0.f, 0.f, 0.f, len_bonus, s));
+        CK(mk_beam_ctc_select_nbest(a, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipStreamSynchronize(s));
         return 0;
     };

@@ -319,6 +319,38 @@ class MasrEngine:
         tok, lens = tok.cpu(), lens.cpu()
         return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
 
+    def recog_beam_ctc_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
+                          min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, att_weight: float = 0.7, ctc_weight: float = 0.3,
+                          raw: bool = False):
+        """one-pass joint CTC/attention beam search with the n-gram LM `lm`, a per-token bonus and an N-best list (masr_recog_beam_ctc_lm,
+        DESIGN 5.7; needs a hybrid model): recog_beam's joint search with the LM in the pre-beam and in the score.  lm_w finite and >= 0,
+        len_bonus finite of any sign, ctc_weight > 0, att_weight >= 0, nbest in [1, beam_size].  Returns per utterance a list of at most
+        nbest (token list, score), best first (raw: the device tensors tokens [B, nbest, Lmax], lens, scores instead)."""
+        K, N = int(beam_size), int(nbest)
+        if not 1 <= K <= 64:
+            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        if not 1 <= N <= K:
+            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        B, T, D = xs.shape
+        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
+        need = int(self._l.masr_beam_ctc_lm_workspace_bytes(self.h, B, T, K, N, Lmax))
+        check(need if need < 0 else 0, "masr_beam_ctc_lm_workspace_bytes")
+        self._ensure_ws_bytes(need)
+        self.refresh()
+        tok = torch.empty(B, N, Lmax, dtype=torch.int32, device=self.device)
+        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        check(self._l.masr_recog_beam_ctc_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, float(min_step_ratio),
+                                             float(max_step_ratio), float(att_weight), float(ctc_weight), lm_w, len_bonus, _ptr(tok), _ptr(lens),
+                                             _ptr(scores), self.stream()), "masr_recog_beam_ctc_lm")
+        self._last_x = xs
+        return (tok, lens, scores) if raw else nbest_lists(tok, lens, scores)
+
     def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
         head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first

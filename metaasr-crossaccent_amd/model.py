@@ -121,6 +121,14 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_beam_lm(xs_pad, ilens, beam_size, lm, lm_weight, min_step_ratio, max_step_ratio)
 
+    def lm_joint_beam_decode(self, xs_pad, ilens, beam_size, lm, lm_weight=0.3, len_bonus=0.0, nbest=1, min_step_ratio=0.0, max_step_ratio=1.0,
+                             att_weight=0.7, ctc_weight=0.3):
+        """one-pass joint CTC/attention beam search with the n-gram LM `lm`, a per-token bonus and an N-best list (masr_recog_beam_ctc_lm,
+        hybrid models only): per utterance a list of at most nbest (token list, score), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_ctc_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest, min_step_ratio, max_step_ratio,
+                                             att_weight, ctc_weight)
+
     def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam, hybrid models only): per utterance a list of at most
         nbest (token list, score), best first"""

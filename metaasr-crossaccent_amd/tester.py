@@ -13,12 +13,18 @@ teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_
 `--decode_mode lm_beam` (transformers) is the attention beam with an n-gram LM fused in (masr_recog_beam_lm): the ARPA file of
 `--lm_model_path` over the output units, weighted by beam_decode.lm_w (default 0.3); beam_size and the step ratios as for `beam`.  The path is
 read at exec(): without one the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed).  The LM
-is not fused into the joint CTC/attention beam: a hybrid model with beam_decode.ctc_w > 0 raises ValueError.
+is not fused into the joint CTC/attention beam by this mode: a hybrid model with beam_decode.ctc_w > 0 raises ValueError (`lm_joint_beam` below
+is that search).
 `--decode_mode lm_ctc_beam` (BLSTM-CTC and hybrid transformers) is the CTC prefix beam of `ctc_beam` with that n-gram LM and a per-token
 bonus fused into the search (masr_ctc_beam_search_lm): `--lm_model_path` as for `lm_beam`, beam_decode.beam_size, lm_w (default
 0.3, finite and >= 0) and len_bonus (default 0, finite, any sign).  `--decode_mode lm_rescore` (hybrid transformers) is `rescore` with that
 search as its first pass (masr_recog_rescore_lm): nbest, att_w and ctc_w as for `rescore`.  Both vet every setting at exec(), before
-anything is decoded, and build the LM once per Tester."""
+anything is decoded, and build the LM once per Tester.
+`--decode_mode lm_joint_beam` (hybrid transformers) is the one-pass joint CTC/attention beam with that n-gram LM in the pre-beam and the score,
+a per-token bonus and an N-best list (masr_recog_beam_ctc_lm): `--lm_model_path` as for `lm_beam`; beam_size, att_w / ctc_w and the
+step ratios as for `beam`, with ctc_w > 0 required (ctc_w absent or 0 raises ValueError: that search is `lm_beam`); lm_w (default 0.3),
+len_bonus (default 0, finite, any sign) and nbest (default 1, in [1, beam_size]).  The best entry of each utterance is written.  Every
+setting is vetted at exec(): no path or a BLSTM raises NotImplementedError, a transformer without a CTC head ValueError."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -153,6 +159,13 @@ class Tester:
             self.write_hyp(y.tolist(), nbest[0][0])
         return True
 
+    def batch_lm_joint_beam_decode(self, xs, ilens, ys, olens):
+        lists = self.asr_model.lm_joint_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus, self.nbest,
+                                                    self.min_step_ratio, self.max_step_ratio, self.att_weight, self.ctc_weight)
+        for nbest, y in zip(lists, ys):
+            self.write_hyp(y.tolist(), nbest[0][0] if nbest else [])
+        return True
+
     def batch_rescore_decode(self, xs, ilens, ys, olens):
         for nbest, y in zip(self.asr_model.rescore_decode(xs, ilens, self.beam_size, self.nbest, self.att_weight, self.ctc_weight), ys):
             self.write_hyp(y.tolist(), nbest[0][0])
@@ -210,6 +223,40 @@ class Tester:
         self.lm = NGramLM.from_arpa(lm_path, self.id2ch, self.sos_id, self.eos_id)
         logger.notice(f"LM shallow fusion: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
                       f"lm_w = {self.lm_weight}")
+
+    def _lm_joint_settings(self):
+        """lm_joint_beam: the path, the model, then every setting -- all before anything is decoded"""
+        lm_path = getattr(self.paras, 'lm_model_path', None)
+        if lm_path is None:
+            raise NotImplementedError("lm_joint_beam: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
+        if self.model_name == 'blstm':
+            raise NotImplementedError("lm_joint_beam: the joint CTC/attention beam needs the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode lm_ctc_beam, ctc_beam or greedy")
+        bd = self._beam_size()
+        if not self.asr_model.engine.ctc_weight > 0.0:
+            raise ValueError("decode_mode 'lm_joint_beam' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or "
+                             "absent); use --decode_mode lm_beam, beam or greedy")
+        self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
+        self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
+        self.ctc_weight = self._weight(bd, 'ctc_w', 0.0)
+        if not self.ctc_weight > 0.0:
+            raise ValueError("lm_joint_beam: solver.beam_decode.ctc_w must be > 0 (it is absent or 0); to fuse the LM into the attention beam "
+                             "alone use --decode_mode lm_beam")
+        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self.len_bonus = float(bd.get('len_bonus', 0.0))
+        if not math.isfinite(self.len_bonus):
+            raise ValueError(f"solver.beam_decode.len_bonus must be finite, got {bd.get('len_bonus')}")
+        self.nbest = int(bd.get('nbest', 1))
+        if not 1 <= self.nbest <= self.beam_size:
+            raise ValueError(f"solver.beam_decode.nbest must be in [1, beam_size], got {self.nbest}")
+        if getattr(self, 'lm', None) is None or getattr(self, '_lm_path', None) != lm_path:
+            from .lm import NGramLM
+            self.lm = NGramLM.from_arpa(lm_path, self.id2ch, self.sos_id, self.eos_id)
+            self._lm_path = lm_path
+        logger.notice(f"Joint CTC/attention beam with LM: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
+                      f"att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}, "
+                      f"nbest = {self.nbest}")
 
     def _lm_ctc_settings(self):
         """lm_ctc_beam and lm_rescore: the path, the model, then every setting -- all before anything is decoded"""
@@ -269,7 +316,7 @@ class Tester:
         return w
 
     def exec(self):
-        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore'):
+        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore', 'lm_joint_beam'):
             raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
         decode = self.batch_greedy_decode
         if self.decode_mode == 'ctc_beam':
@@ -286,6 +333,11 @@ class Tester:
             decode = self.batch_lm_ctc_beam_decode if self.decode_mode == 'lm_ctc_beam' else self.batch_lm_rescore_decode
             logger.notice(f"Start {'LM-fused CTC prefix beam decoding' if self.decode_mode == 'lm_ctc_beam' else 'attention rescoring of the LM-fused CTC beam'}"
                           f" (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
+        elif self.decode_mode == 'lm_joint_beam':
+            self._lm_joint_settings()
+            decode = self.batch_lm_joint_beam_decode
+            logger.notice(f"Start joint CTC/attention beam decoding with LM fusion (beam {self.beam_size}): {len(self.eval_set)} batches of "
+                          f"<= {self.batch_size}")
         elif self.decode_mode == 'lm_beam':
             self._lm_beam_settings()
             decode = self.batch_lm_beam_decode
