@@ -199,19 +199,27 @@ class MasrError(RuntimeError):
     pass
 
 
-def nbest_lists(tok, lens, scores):
+def nbest_lists(tok, lens, scores, *more):
     """device results of masr_ctc_beam_search (tokens [B][N][Tp], lens [B][N], scores [B][N] torch tensors) -> per utterance
-    [(token list, score), ...] without the slots beyond the live entries (lens -1)"""
-    tok, lens, scores = tok.cpu(), lens.cpu(), scores.cpu()
-    return [[(tok[b, i, :int(lens[b, i])].tolist(), float(scores[b, i])) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
+    [(token list, score), ...] without the slots beyond the live entries (lens -1); of masr_ctc_beam_search_lm, with `more` = its acoustic
+    scores [B][N]: [(token list, fused score, acoustic score), ...]"""
+    tok, lens, *vals = (t.cpu() for t in (tok, lens, scores, *more))
+    return [[(tok[b, i, :int(lens[b, i])].tolist(), *[float(v[b, i]) for v in vals]) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
             for b in range(lens.size(0))]
 
 
-def nbest_lists_lm(tok, lens, scores, am):
-    """the same for masr_ctc_beam_search_lm: [(token list, fused score, acoustic score), ...]"""
-    tok, lens, scores, am = tok.cpu(), lens.cpu(), scores.cpu(), am.cpu()
-    return [[(tok[b, i, :int(lens[b, i])].tolist(), float(scores[b, i]), float(am[b, i])) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
-            for b in range(lens.size(0))]
+nbest_lists_lm = nbest_lists                                   # (the name the LM-fused searches' callers know)
+
+
+def check_beam_args(beam_size, nbest=1):
+    """the beam size and list length every beam decoder vets on the Python side -> (K, N) as ints; nbest None = beam_size"""
+    K = int(beam_size)
+    N = K if nbest is None else int(nbest)
+    if not 1 <= K <= 64:
+        raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+    if not 1 <= N <= K:
+        raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+    return K, N
 
 
 def check_lm_args(lm, lm_w, len_bonus):

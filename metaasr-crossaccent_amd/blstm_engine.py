@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import check, check_lm_args, lib, nbest_lists, nbest_lists_lm
+from ._cabi import check, check_beam_args, check_lm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -144,31 +144,24 @@ class BlstmEngine:
         of at most nbest (token list, score), best first.  With lm (an NGramLM over the odim classes, <s> in the blank's slot 0) the search
         is masr_ctc_beam_search_lm (lm_w finite and >= 0, len_bonus finite, blank 0) and the entries are
         (token list, fused score, acoustic score)."""
-        K, N = int(K), int(nbest)
+        K = int(K)
         if lm is not None:
             lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {K}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        K, N = check_beam_args(K, nbest)
         logits, lens = self.forward(xs, ilens)                 # (runs masr_blstm_check)
         B, Tp, Cc = logits.shape
         need = int(self._l.masr_ctc_beam_work_bytes(B, Tp, Cc, K))
         check(need if need < 0 else 0, "masr_ctc_beam_work_bytes")
         if getattr(self, "_beam_work", None) is None or self._beam_work.numel() < need:
             self._beam_work = torch.empty(need, dtype=torch.uint8, device=self.device)
-        tok = torch.empty(B, N, Tp, dtype=torch.int32, device=self.device)
-        ln = torch.empty(B, N, dtype=torch.int32, device=self.device)
-        sc = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
+        out = [torch.empty(B, N, Tp, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **f32)]      # tokens, lens, scores
         if lm is not None:
-            am = torch.empty(B, N, dtype=torch.float32, device=self.device)
-            check(self._l.masr_ctc_beam_search_lm(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, lm.h, lm_w, len_bonus,
-                                                  _ptr(self._beam_work), self._beam_work.numel(), _ptr(tok), _ptr(ln), _ptr(sc), _ptr(am),
-                                                  self.stream()), "masr_ctc_beam_search_lm")
-            return nbest_lists_lm(tok, ln, sc, am)
-        check(self._l.masr_ctc_beam_search(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, _ptr(self._beam_work),
-                                           self._beam_work.numel(), _ptr(tok), _ptr(ln), _ptr(sc), self.stream()), "masr_ctc_beam_search")
-        return nbest_lists(tok, ln, sc)
+            out.append(torch.empty(B, N, **f32))                                                    # acoustic scores
+        fn, lm_args = ("masr_ctc_beam_search_lm", (lm.h, lm_w, len_bonus)) if lm is not None else ("masr_ctc_beam_search", ())
+        check(getattr(self._l, fn)(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, *lm_args, _ptr(self._beam_work),
+                                   self._beam_work.numel(), *map(_ptr, out), self.stream()), fn)
+        return nbest_lists(*out)
 
     def set_resident_recurrence(self, on: bool):
         """the LSTM recurrence as one launch per layer and pass (include/masr.h masr_blstm_set_resident_recurrence); default on"""

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include <algorithm>
 
@@ -101,18 +102,39 @@ static int run_steps(masr_model* m, DecodeGraph& gc, const int (&key)[6], const 
 }
 
 // argument checks of the entry points: 0, or -1 with the message recorded under the caller's name
-static int check_ctc_head(const char* fn, const masr_model* m) {
-    if (m->ctc_w > 0.f) return 0;
-    mk_set_error(fn, "the model has no CTC head (masr_create_ctc)"); return -1;
+static int fail(const char* fn, const char* msg) { mk_set_error(fn, msg); return -1; }
+static int check_model(const char* fn, const masr_model* m) { return m ? 0 : fail(fn, "null model"); }
+static int check_ctc_head(const char* fn, const masr_model* m) { return m->ctc_w > 0.f ? 0 : fail(fn, "the model has no CTC head (masr_create_ctc)"); }
+static int check_beam_size(const char* fn, int K) { return K >= 1 && K <= 64 ? 0 : fail(fn, "beam size K must be in [1, 64]"); }
+// `name`: what the entry point calls its list length (nbest in the CTC beam's, N elsewhere)
+static int check_nbest(const char* fn, const char* name, int N, int K) {
+    return N >= 1 && N <= K ? 0 : fail(fn, (std::string(name) + " must be in [1, K]").c_str());
 }
-static int check_beam_size(const char* fn, int K) {
-    if (K >= 1 && K <= 64) return 0;
-    mk_set_error(fn, "beam size K must be in [1, 64]"); return -1;
+// a weight is finite and, strict, > 0, else >= 0
+static int check_weight(const char* fn, const char* name, float v, bool strict) {
+    if (std::isfinite(v) && (strict ? v > 0.f : v >= 0.f)) return 0;
+    return fail(fn, (std::string(name) + " must be finite and " + (strict ? "> 0" : ">= 0")).c_str());
+}
+// LM fusion: the LM, its weight and, where the search has one (len_bonus != null), the per-token bonus
+static int check_lm(const char* fn, const masr_model* m, const masr_lm* lm, float lm_w, const float* len_bonus) {
+    if (!lm) return fail(fn, "null language model");
+    if (lm->dev.C != m->C) return fail(fn, "the language model's classes differ from the model's odim");
+    CK(check_weight(fn, "lm_w", lm_w, false));
+    return !len_bonus || std::isfinite(*len_bonus) ? 0 : fail(fn, "len_bonus must be finite");
 }
 static int check_pointers(const char* fn, const float* xs, const int64_t* ilens, const int32_t* tokens, const int32_t* lens, const float* scores) {
-    if (xs && ilens && tokens && lens && scores) return 0;
-    mk_set_error(fn, "null pointer"); return -1;
+    return xs && ilens && tokens && lens && scores ? 0 : fail(fn, "null pointer");
 }
+// every ilens[b] in [4, T]; each(b, enc) gets the encoder length ilens[b] / 4 of the utterances up to the first that is not
+template <class Each>
+static int check_ilens(const char* fn, const int64_t* ilens, int B, int T, Each each) {
+    for (int b = 0; b < B; ++b) {
+        if (ilens[b] < 4 || ilens[b] > T) return fail(fn, "ilens must be in [4, T]");
+        each(b, (int)(ilens[b] / 4));
+    }
+    return 0;
+}
+static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && K <= 64; }     // what every beam's workspace query needs
 
 // What a decoder plans into the arena: the activations, then its own state behind them.  plan_decode both sizes the workspace (a null
 // arena) and places the buffers in the bound one.
@@ -198,16 +220,25 @@ static int64_t decode_workspace_bytes(const char* fn, const masr_model* m, bool 
     return m->persist_bytes + ar.off + 4096;
 }
 
+// n ints to dst on stream s through the next of the four pinned staging slots: fill(h) writes them once the slot's last copy has landed
+template <class Fill>
+static int stage_upload(masr_model* m, int* dst, int n, hipStream_t s, Fill fill) {
+    const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
+    HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
+    int* h = m->h_stage + (int64_t)slot * m->stage_ints;
+    fill(h);
+    HIP_CHECK_RET(hipMemcpyAsync(dst, h, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
+    return 0;
+}
+
 // shared front half of the decoders: argument checks, the plan, enc_lens upload, encoder
 static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, hipStream_t s, int* Ldec_out,
                          const DecodeSpec& d = DecodeSpec{}, DecodeBufs* bufs = nullptr) {     // bufs: where the plan put the decoder's state
     if (!m->P) { mk_set_error("masr_recog", "not bound"); return -1; }
     if (B <= 0 || T < 4) { mk_set_error("masr_recog", "need B >= 1 and T >= 4"); return -1; }
     int Ldec = 0;
-    for (int b = 0; b < B; ++b) {
-        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error("masr_recog", "ilens must be in [4, T]"); return -1; }
-        if ((int)(ilens[b] / 4) > Ldec) Ldec = (int)(ilens[b] / 4);
-    }
+    CK(check_ilens("masr_recog", ilens, B, T, [&](int, int enc) { Ldec = std::max(Ldec, enc); }));
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
     const DecodeBufs planned = plan_decode(m, ar, m->acts, B, T, Ldec, d);
     if (bufs) *bufs = planned;
@@ -222,12 +253,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
         return -2;
     }
     Acts& a = m->acts; m->have_acts = true;
-    const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
-    HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
-    int* h_len = m->h_stage + (int64_t)slot * m->stage_ints;
-    for (int b = 0; b < B; ++b) h_len[b] = (int)(ilens[b] / 4);
-    HIP_CHECK_RET(hipMemcpyAsync(a.enc_lens, h_len, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, s));
-    HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
+    CK(stage_upload(m, a.enc_lens, B, s, [&](int* h) { for (int b = 0; b < B; ++b) h[b] = (int)(ilens[b] / 4); }));
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     CK(forward_encoder(c, xs));
     *Ldec_out = Ldec;
@@ -274,13 +300,10 @@ int masr_recog(masr_model* m, const float* xs, const int64_t* ilens, int B, int 
     return 0;
 }
 
-int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
-    return decode_workspace_bytes("masr_beam_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
-                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax});
-}
+}  // extern "C"
 
-// once per decode, shared by masr_recog_beam_ctc and masr_recog_ctc_beam: the CTC head over the encoder memory (training's GEMM: bf16
-// operands, fp32 logits [B*Tp][Cp])
+// once per decode, shared by the joint beam and the CTC first pass: the CTC head over the encoder memory (training's GEMM: bf16 operands,
+// fp32 logits [B*Tp][Cp])
 static int ctc_head_logits(Ctx& c, float* ctc_logits) {
     masr_model* m = c.m; Acts& a = m->acts;
     GemmArgs g = lin_fwd_args(a.mem16, m->E, m->ctc.k16, a.rows_e, m->C, m->E, m->P + m->ctc.b);
@@ -290,9 +313,11 @@ static int ctc_head_logits(Ctx& c, float* ctc_logits) {
 
 static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
 
-int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
-    return decode_workspace_bytes("masr_beam_ctc_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
-                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, beam_prebeam_width(K)});
+// the four step beams' workspace queries: one predicate, and one message but for the N-best variant's (N < 0: no list)
+static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, int T, int K, int Lmax, bool joint, bool lm, int N = -1) {
+    return decode_workspace_bytes(fn, m, shape_ok(B, T, K) && Lmax >= 1 && (N < 0 || (N >= 1 && N <= K)),
+                                  N < 0 ? "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1" : "need B >= 1, T >= 4, 1 <= N <= K <= 64, Lmax >= 1", B, T,
+                                  DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0)});
 }
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
@@ -322,12 +347,15 @@ static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* l
     return 0;
 }
 
-// masr_recog_beam (wts == null), masr_recog_beam_ctc (wts = {att_w, ctc_w}), masr_recog_beam_lm (lm, lm_w; wts == null) and
-// masr_recog_beam_ctc_lm (wts, lm, lm_w, nb = {N, len_bonus}): the same decode, each with its own cached step graph
-struct NbestSpec { int N; float len_bonus; };
-static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
-                           const float* wts, int32_t* tokens, int32_t* lens, float* scores, void* stream, const char* fn,
-                           const masr_lm* lm = nullptr, float lm_w = 0.f, const NbestSpec* nb = nullptr) {
+// which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm) or masr_recog_beam_ctc_lm (joint, lm
+// and the N-best list); each has its own cached step graph
+struct BeamMode {
+    bool joint = false; float att_w = 0.f, ctc_w = 0.f;         // joint CTC/attention: the two weights
+    const masr_lm* lm = nullptr; float lm_w = 0.f;              // n-gram LM fusion
+    int N = 0; float len_bonus = 0.f;                           // N-best list (N > 0) and the bonus per emitted token
+};
+static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, const float* xs, const int64_t* ilens, int B, int T, int K,
+                           float min_step_ratio, float max_step_ratio, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
     // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers; joint with
@@ -335,201 +363,91 @@ static int recog_beam_impl(masr_model* m, const float* xs, const int64_t* ilens,
     // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
     CK(check_beam_size(fn, K));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
-    if (B <= 0) { mk_set_error(fn, "need B >= 1"); return -1; }
+    if (B <= 0) return fail(fn, "need B >= 1");
     std::vector<int> mx_len(B), mn_len(B);
     int Lmax = 0;
-    for (int b = 0; b < B; ++b) {
-        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error(fn, "ilens must be in [4, T]"); return -1; }
-        const int enc = (int)(ilens[b] / 4);
-        int ml = max_step_ratio <= 0.f ? enc : std::max(1, (int)std::floor((double)max_step_ratio * enc));
+    CK(check_ilens(fn, ilens, B, T, [&](int b, int enc) {
+        const int ml = max_step_ratio <= 0.f ? enc : std::max(1, (int)std::floor((double)max_step_ratio * enc));
         mx_len[b] = std::min(ml, MASR_PE_ROWS);
         mn_len[b] = std::max(0, (int)std::floor((double)min_step_ratio * enc));
         Lmax = std::max(Lmax, mx_len[b]);
-    }
+    }));
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, wts ? beam_prebeam_width(K) : 0, false, 0, lm != nullptr, nb ? nb->N : 0}, &bufs);
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, mode.joint ? beam_prebeam_width(K) : 0, false, 0, mode.lm != nullptr, mode.N},
+                                   &bufs);
       if (rc) return rc; }
-    BeamArgs& ba = bufs.beam; bf16* step_qkv = bufs.step_qkv; float* ctc_logits = bufs.ctc_logits;
+    BeamArgs& ba = bufs.beam;
     Acts& a = m->acts;
     ba.step = a.step_dev;
-    {   // per-utterance maxlen / minlen through the next staging slot (the one behind recog_prepare's enc_lens)
-        const int slot = m->stage_slot; m->stage_slot = (slot + 1) & 3;
-        HIP_CHECK_RET(hipEventSynchronize(m->stage_ev[slot]));
-        int* h = m->h_stage + (int64_t)slot * m->stage_ints;
-        for (int b = 0; b < B; ++b) { h[b] = mx_len[b]; h[B + b] = mn_len[b]; }
-        HIP_CHECK_RET(hipMemcpyAsync(const_cast<int*>(ba.maxlen), h, sizeof(int) * 2 * (size_t)B, hipMemcpyHostToDevice, s));
-        HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
-    }
+    // per-utterance maxlen / minlen through the next staging slot (the one behind recog_prepare's enc_lens)
+    CK(stage_upload(m, const_cast<int*>(ba.maxlen), 2 * B, s, [&](int* h) { for (int b = 0; b < B; ++b) { h[b] = mx_len[b]; h[B + b] = mn_len[b]; } }));
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     CK(project_memory_kv(c));
     CK(mk_beam_init(ba, s));
-    if (wts) {
-        // once per decode: the CTC head over the memory, its log-softmax per frame, the empty hypothesis's state
-        ba.att_w = wts[0]; ba.ctc_w = wts[1]; ba.enc_lens = a.enc_lens;
-        CK(ctc_head_logits(c, ctc_logits));
-        CK(mk_beam_ctc_logsoftmax(ba, ctc_logits, m->Cp, s));
-        CK(mk_beam_ctc_init(ba, s));
-    }
     int key[6] = {B, T, K, Lmax, 0, 0}; const void* const kp[3] = {m->ws, m->P, nullptr};
-    if (wts) memcpy(key + 4, wts, 2 * sizeof(float));
+    if (mode.joint) {
+        // once per decode: the CTC head over the memory, its log-softmax per frame, the empty hypothesis's state
+        ba.att_w = mode.att_w; ba.ctc_w = mode.ctc_w; ba.enc_lens = a.enc_lens;
+        CK(ctc_head_logits(c, bufs.ctc_logits));
+        CK(mk_beam_ctc_logsoftmax(ba, bufs.ctc_logits, m->Cp, s));
+        CK(mk_beam_ctc_init(ba, s));
+        memcpy(key + 4, &mode.att_w, sizeof(float)); memcpy(key + 5, &mode.ctc_w, sizeof(float));
+    }
     LmStep ls{};
-    if (lm) {
-        ls = LmStep{lm->dev, lm_w, bufs.lm_fused};
-        memcpy(key + 4, &lm_w, sizeof(float)); key[5] = (int)lm->serial;
+    if (mode.lm) {
+        ls = LmStep{mode.lm->dev, mode.lm_w, bufs.lm_fused};
+        memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.lm->serial;
     }
-    if (nb) {
-        CK(mk_beam_set_weights(ba, wts[0], wts[1], lm_w, nb->len_bonus, s));
-        key[4] = nb->N;
+    if (mode.N) {
+        CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
+        key[4] = mode.N;
     }
-    CK(run_steps(m, nb ? m->joint_lm_graph : wts ? m->joint_graph : lm ? m->lm_graph : m->beam_graph, key, kp, Lmax, s, fn,
-                 "stream capture of the beam step failed", [&] { return beam_step(c, ba, step_qkv, lm ? &ls : nullptr); }));
-    if (nb) CK(mk_beam_backtrace_nbest(ba, tokens, lens, scores, s));
+    DecodeGraph& graph = mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
+    CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
+                 [&] { return beam_step(c, ba, bufs.step_qkv, mode.lm ? &ls : nullptr); }));
+    if (mode.N) CK(mk_beam_backtrace_nbest(ba, tokens, lens, scores, s));
     else CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
 }
 
-int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
-                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
-    if (!m) { mk_set_error("masr_recog_beam", "null model"); return -1; }
-    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, "masr_recog_beam");
+// the CTC prefix beam over the head's logits of the encoder memory (ctc_beam.hip), with an LM the fused sweep: the first pass of
+// masr_recog_ctc_beam(_lm) and masr_recog_rescore(_lm)
+static int ctc_first_pass(Ctx& c, const DecodeBufs& bufs, int B, int Tp, int K, int N, const masr_lm* lm, float lm_w, float len_bonus, int32_t* tokens,
+                          int32_t* lens, float* scores, float* am) {
+    masr_model* m = c.m; Acts& a = m->acts;
+    CK(ctc_head_logits(c, bufs.ctc_logits));
+    if (lm) return mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
+                                         tokens, lens, scores, am, c.s);
+    return mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, tokens, lens, scores, c.s);
 }
 
-int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
-                        float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
-    // joint CTC/attention beam (beam.hip, DESIGN 5.2): the attention beam's search with the CTC prefix score of the head's log-probs
-    const char* fn = "masr_recog_beam_ctc";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
-    CK(check_ctc_head(fn, m));
-    if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
-    if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
-    const float wts[2] = {att_w, ctc_w};
-    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn);
-}
-
-int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
-    return decode_workspace_bytes("masr_beam_lm_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && Lmax >= 1,
-                                  "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, 0, false, 0, true});
-}
-
-int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
-                       float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
-    // n-gram LM shallow fusion into the attention beam (lm.hip, DESIGN 5.5): masr_recog_beam with the fused top-K in place of the row top-K
-    const char* fn = "masr_recog_beam_lm";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
-    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
-    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
-    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
-    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, nullptr, tokens, lens, scores, stream, fn, lm, lm_w);
-}
-
-int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
-    return decode_workspace_bytes("masr_beam_ctc_lm_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64 && N >= 1 && N <= K && Lmax >= 1,
-                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, Lmax >= 1", B, T, DecodeSpec{K, Lmax, beam_prebeam_width(K), false, 0, true, N});
-}
-
-int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float min_step_ratio,
-                           float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
-                           void* stream) {
-    // the joint beam with the n-gram LM in the pre-beam and the score, a bonus per emitted token and an N-best list (DESIGN 5.7)
-    const char* fn = "masr_recog_beam_ctc_lm";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
-    CK(check_ctc_head(fn, m));
-    if (!(ctc_w > 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and > 0"); return -1; }
-    if (!(att_w >= 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and >= 0"); return -1; }
-    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
-    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
-    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
-    if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
-    CK(check_beam_size(fn, K));
-    if (N < 1 || N > K) { mk_set_error(fn, "N must be in [1, K]"); return -1; }
-    const float wts[2] = {att_w, ctc_w};
-    const NbestSpec nb{N, len_bonus};
-    return recog_beam_impl(m, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, wts, tokens, lens, scores, stream, fn, lm, lm_w, &nb);
-}
-
-int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
-    return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, B > 0 && T >= 4 && K >= 1 && K <= 64, "need B >= 1, T >= 4, 1 <= K <= 64", B, T,
-                                  DecodeSpec{K, 0, 0, true});
-}
-
-int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
-                        float* scores, void* stream) {
-    // CTC prefix beam search on the head alone (ctc_beam.hip): one encoder pass, the head GEMM, one sweep over the T/4 frames
-    const char* fn = "masr_recog_ctc_beam";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
+// masr_recog_ctc_beam (with_lm false) and masr_recog_ctc_beam_lm: one encoder pass, the head GEMM, one sweep over the T/4 frames
+static int recog_ctc_beam_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, float lm_w, float len_bonus, const float* xs,
+                               const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
+    CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
-    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
+    CK(check_nbest(fn, "nbest", nbest, K));
+    if (with_lm) CK(check_lm(fn, m, lm, lm_w, &len_bonus));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
+    if (with_lm && !am) return fail(fn, "null pointer");
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
     { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true}, &bufs); if (rc) return rc; }
-    Acts& a = m->acts;
     Ctx c{m, s, 0u, false, 0.f, 0.f};
-    CK(ctc_head_logits(c, bufs.ctc_logits));
-    CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, bufs.work, bufs.work_bytes, tokens, lens, scores, s));
+    CK(ctc_first_pass(c, bufs, B, T / 4, K, nbest, lm, lm_w, len_bonus, tokens, lens, scores, am));
     m->have_acts = false;
     return 0;
 }
-
-// what the LM-fused CTC first pass vets before anything is launched (masr_recog_ctc_beam_lm, masr_recog_rescore_lm)
-static int check_ctc_lm(const char* fn, const masr_model* m, const masr_lm* lm, float lm_w, float len_bonus) {
-    if (!lm) { mk_set_error(fn, "null language model"); return -1; }
-    if (lm->dev.C != m->C) { mk_set_error(fn, "the language model's classes differ from the model's odim"); return -1; }
-    if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
-    if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
-    return 0;
-}
-
-int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
-                           float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
-    // masr_recog_ctc_beam with the LM-fused sweep (ctc_beam.hip, DESIGN 5.6): the same plan, encoder pass and head GEMM
-    const char* fn = "masr_recog_ctc_beam_lm";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
-    CK(check_ctc_head(fn, m));
-    CK(check_beam_size(fn, K));
-    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
-    CK(check_ctc_lm(fn, m, lm, lm_w, len_bonus));
-    CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
-    if (!am) { mk_set_error(fn, "null pointer"); return -1; }
-    hipStream_t s = (hipStream_t)stream;
-    DecodeBufs bufs;
-    int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true}, &bufs); if (rc) return rc; }
-    Acts& a = m->acts;
-    Ctx c{m, s, 0u, false, 0.f, 0.f};
-    CK(ctc_head_logits(c, bufs.ctc_logits));
-    CK(mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, T / 4, m->C, K, nbest, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
-                             tokens, lens, scores, am, s));
-    m->have_acts = false;
-    return 0;
-}
-
-int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens) {
-    // where masr_recog_ctc_beam(m, .., B, T, K, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
-    const char* fn = "masr_test_ctc_beam_logits";
-    if (!m || !m->P || !logits || !ld || !enc_lens) { mk_set_error(fn, "null pointer or model not bound"); return -1; }
-    CK(check_ctc_head(fn, m));
-    if (B <= 0 || T < 4 || K < 1 || K > 64) { mk_set_error(fn, "need B >= 1, T >= 4, 1 <= K <= 64"); return -1; }
-    Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
-    Acts a;
-    const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, DecodeSpec{K, 0, 0, true});
-    if (ar.off > m->ws_bytes) { mk_set_error(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"); return -1; }
-    *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
-    return 0;
-}
-
-}  // extern "C"
 
 // ---------------------------------------------------------------- attention rescoring
 static int check_rescore_weights(const char* fn, float att_w, float ctc_w) {
-    if (!(att_w > 0.f) || !std::isfinite(att_w)) { mk_set_error(fn, "att_w must be finite and > 0"); return -1; }
-    if (!(ctc_w >= 0.f) || !std::isfinite(ctc_w)) { mk_set_error(fn, "ctc_w must be finite and >= 0"); return -1; }
-    return 0;
+    CK(check_weight(fn, "att_w", att_w, true));
+    return check_weight(fn, "ctc_w", ctc_w, false);
 }
 // The second pass over the lists tok [B*N][ld_tok] / lens / ctc (device), the encoder done: the decoder ONCE, teacher-forced, on B*N sequences
 // of L = 1 + the longest live list positions (the eval pass's bf16-operand logits GEMM), each list's attention score, and the re-ranked copies
@@ -547,85 +465,157 @@ static int rescore_second_pass(Ctx& c, const DecodeBufs& bufs, const int* tok, l
     return 0;
 }
 
-extern "C" {
-
-int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
-    return decode_workspace_bytes("masr_rescore_workspace_bytes", m, B > 0 && T >= 4 && N >= 1 && N <= K && K <= 64 && Lmax >= 0 && Lmax < MASR_PE_ROWS,
-                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, 0 <= Lmax < 3000", B, T, DecodeSpec{K, Lmax, 0, false, N});
-}
-
-}  // extern "C"
-
-// masr_recog_rescore (lm == null) and masr_recog_rescore_lm: the two-pass decode on one encoder pass; with an LM the first pass is the fused
+// masr_recog_rescore (with_lm false) and masr_recog_rescore_lm: the two-pass decode on one encoder pass; with an LM the first pass is the fused
 // search, its fused scores the c(b, n) of the second pass, and its acoustic totals land in the plan's scratch (rs_att, free until the second pass)
-static int recog_rescore_impl(const char* fn, masr_model* m, const masr_lm* lm, float lm_w, float len_bonus, const float* xs, const int64_t* ilens,
-                              int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
-                              float* ctc, int32_t* order, bool with_lm, void* stream) {
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
+static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, float lm_w, float len_bonus, const float* xs,
+                              const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
+                              float* att, float* ctc, int32_t* order, void* stream) {
+    CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
-    if (N < 1 || N > K) { mk_set_error(fn, "N must be in [1, K]"); return -1; }
+    CK(check_nbest(fn, "N", N, K));
     CK(check_rescore_weights(fn, att_w, ctc_w));
-    if (with_lm) CK(check_ctc_lm(fn, m, lm, lm_w, len_bonus));
+    if (with_lm) CK(check_lm(fn, m, lm, lm_w, &len_bonus));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
-    if (!att || !ctc || !order) { mk_set_error(fn, "null pointer"); return -1; }
-    if (B <= 0 || T < 4) { mk_set_error(fn, "need B >= 1 and T >= 4"); return -1; }
+    if (!att || !ctc || !order) return fail(fn, "null pointer");
+    if (B <= 0 || T < 4) return fail(fn, "need B >= 1 and T >= 4");
     int Lcap = 0;                                           // a CTC hypothesis has at most enc_len tokens
-    for (int b = 0; b < B; ++b) {
-        if (ilens[b] < 4 || ilens[b] > T) { mk_set_error(fn, "ilens must be in [4, T]"); return -1; }
-        Lcap = std::max(Lcap, (int)(ilens[b] / 4));
-    }
+    CK(check_ilens(fn, ilens, B, T, [&](int, int enc) { Lcap = std::max(Lcap, enc); }));
     Lcap = std::min(Lcap, MASR_PE_ROWS - 1);
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
     { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lcap, 0, false, N}, &bufs); if (rc) return rc; }
-    Acts& a = m->acts;
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     const int Tp = T / 4, R = B * N;
-    CK(ctc_head_logits(c, bufs.ctc_logits));
-    if (with_lm)
-        CK(mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
-                                 bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att, s));
-    else
-        CK(mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, bufs.rs_tok, bufs.rs_lens,
-                              bufs.rs_ctc, s));
+    CK(ctc_first_pass(c, bufs, B, Tp, K, N, lm, lm_w, len_bonus, bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att));
     // the one host synchronisation of the decode: the list lengths decide how many positions the decoder pass has
     std::vector<int> h_lens(R);
     HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), bufs.rs_lens, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
     HIP_CHECK_RET(hipStreamSynchronize(s));
     int mx = 0;
     for (int v : h_lens) mx = std::max(mx, v);
-    if (mx > Lcap) { mk_set_error(fn, "a first-pass hypothesis is longer than the positions planned for"); return -1; }
+    if (mx > Lcap) return fail(fn, "a first-pass hypothesis is longer than the positions planned for");
     return rescore_second_pass(c, bufs, bufs.rs_tok, Tp, bufs.rs_lens, bufs.rs_ctc, B, N, mx + 1, att_w, ctc_w, tokens, lens, scores, att, ctc, order);
 }
 
 extern "C" {
 
+int64_t masr_beam_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    return beam_workspace_bytes("masr_beam_workspace_bytes", m, B, T, K, Lmax, false, false);
+}
+int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    return beam_workspace_bytes("masr_beam_ctc_workspace_bytes", m, B, T, K, Lmax, true, false);
+}
+int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    return beam_workspace_bytes("masr_beam_lm_workspace_bytes", m, B, T, K, Lmax, false, true);
+}
+int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
+    return beam_workspace_bytes("masr_beam_ctc_lm_workspace_bytes", m, B, T, K, Lmax, true, true, N);
+}
+int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
+    return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, shape_ok(B, T, K), "need B >= 1, T >= 4, 1 <= K <= 64", B, T, DecodeSpec{K, 0, 0, true});
+}
+int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
+    return decode_workspace_bytes("masr_rescore_workspace_bytes", m, shape_ok(B, T, K) && N >= 1 && N <= K && Lmax >= 0 && Lmax < MASR_PE_ROWS,
+                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, 0 <= Lmax < 3000", B, T, DecodeSpec{K, Lmax, 0, false, N});
+}
+
+int masr_recog_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                    int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    const char* fn = "masr_recog_beam";
+    CK(check_model(fn, m));
+    return recog_beam_impl(fn, m, BeamMode{}, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio, float max_step_ratio,
+                        float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // joint CTC/attention beam (beam.hip, DESIGN 5.2): the attention beam's search with the CTC prefix score of the head's log-probs
+    const char* fn = "masr_recog_beam_ctc";
+    CK(check_model(fn, m));
+    CK(check_ctc_head(fn, m));
+    CK(check_weight(fn, "ctc_w", ctc_w, true));
+    CK(check_weight(fn, "att_w", att_w, false));
+    BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
+                       float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // n-gram LM shallow fusion into the attention beam (lm.hip, DESIGN 5.5): masr_recog_beam with the fused top-K in place of the row top-K
+    const char* fn = "masr_recog_beam_lm";
+    CK(check_model(fn, m));
+    CK(check_lm(fn, m, lm, lm_w, nullptr));
+    BeamMode mode; mode.lm = lm; mode.lm_w = lm_w;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float min_step_ratio,
+                           float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
+                           void* stream) {
+    // the joint beam with the n-gram LM in the pre-beam and the score, a bonus per emitted token and an N-best list (DESIGN 5.7)
+    const char* fn = "masr_recog_beam_ctc_lm";
+    CK(check_model(fn, m));
+    CK(check_ctc_head(fn, m));
+    CK(check_weight(fn, "ctc_w", ctc_w, true));
+    CK(check_weight(fn, "att_w", att_w, false));
+    CK(check_lm(fn, m, lm, lm_w, &len_bonus));
+    CK(check_beam_size(fn, K));
+    CK(check_nbest(fn, "N", N, K));
+    BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w; mode.lm = lm; mode.lm_w = lm_w; mode.N = N; mode.len_bonus = len_bonus;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
+                        float* scores, void* stream) {
+    // CTC prefix beam search on the head alone (ctc_beam.hip)
+    return recog_ctc_beam_impl("masr_recog_ctc_beam", m, false, nullptr, 0.f, 0.f, xs, ilens, B, T, K, nbest, tokens, lens, scores, nullptr, stream);
+}
+
+int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
+                           float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
+    // masr_recog_ctc_beam with the LM-fused sweep (ctc_beam.hip, DESIGN 5.6): the same plan, encoder pass and head GEMM
+    return recog_ctc_beam_impl("masr_recog_ctc_beam_lm", m, true, lm, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am, stream);
+}
+
+int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens) {
+    // where masr_recog_ctc_beam(m, .., B, T, K, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
+    const char* fn = "masr_test_ctc_beam_logits";
+    if (!m || !m->P || !logits || !ld || !enc_lens) return fail(fn, "null pointer or model not bound");
+    CK(check_ctc_head(fn, m));
+    if (!shape_ok(B, T, K)) return fail(fn, "need B >= 1, T >= 4, 1 <= K <= 64");
+    Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    Acts a;
+    const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, DecodeSpec{K, 0, 0, true});
+    if (ar.off > m->ws_bytes) return fail(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))");
+    *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
+    return 0;
+}
+
 int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
                        int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream) {
-    return recog_rescore_impl("masr_recog_rescore", m, nullptr, 0.f, 0.f, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
-                              false, stream);
+    return recog_rescore_impl("masr_recog_rescore", m, false, nullptr, 0.f, 0.f, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
+                              stream);
 }
 
 int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
                           float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
                           int32_t* order, void* stream) {
-    return recog_rescore_impl("masr_recog_rescore_lm", m, lm, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
-                              order, true, stream);
+    return recog_rescore_impl("masr_recog_rescore_lm", m, true, lm, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
+                              order, stream);
 }
 
 int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,
                        const int32_t* lens_in, const float* ctc_in, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
                        float* ctc, int32_t* order, void* stream) {
     const char* fn = "masr_rescore_nbest";
-    if (!m) { mk_set_error(fn, "null model"); return -1; }
+    CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
-    if (N < 1 || N > 64) { mk_set_error(fn, "N must be in [1, 64]"); return -1; }
+    if (N < 1 || N > 64) return fail(fn, "N must be in [1, 64]");
     CK(check_rescore_weights(fn, att_w, ctc_w));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
-    if (!att || !ctc || !order || !lens_in || !ctc_in || (ld_tok > 0 && !tokens_in)) { mk_set_error(fn, "null pointer"); return -1; }
-    if (B <= 0 || T < 4 || ld_tok < 0 || ld_tok >= MASR_PE_ROWS) { mk_set_error(fn, "need B >= 1, T >= 4 and 0 <= ld_tok < 3000"); return -1; }
+    if (!att || !ctc || !order || !lens_in || !ctc_in || (ld_tok > 0 && !tokens_in)) return fail(fn, "null pointer");
+    if (B <= 0 || T < 4 || ld_tok < 0 || ld_tok >= MASR_PE_ROWS) return fail(fn, "need B >= 1, T >= 4 and 0 <= ld_tok < 3000");
     hipStream_t s = (hipStream_t)stream;
     // the one host synchronisation of the call: the lists come to the host, where their lengths decide the decoder's positions and every
     // token is vetted (it indexes the embedding table)
@@ -638,10 +628,10 @@ int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int
     for (int r = 0; r < R; ++r) {
         const int n = h_lens[r];
         if (n < 0) continue;
-        if (n > ld_tok) { mk_set_error(fn, "a list is longer than ld_tok"); return -1; }
+        if (n > ld_tok) return fail(fn, "a list is longer than ld_tok");
         for (int i = 0; i < n; ++i) {
             const int t = h_tok[(size_t)r * ld_tok + i];
-            if (t < 1 || t > m->C - 2) { mk_set_error(fn, "tokens must lie in [1, odim - 2] (no sos / blank, no eos)"); return -1; }
+            if (t < 1 || t > m->C - 2) return fail(fn, "tokens must lie in [1, odim - 2] (no sos / blank, no eos)");
         }
         mx = std::max(mx, n);
     }
@@ -654,8 +644,8 @@ int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int
 
 int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t** gold, int* R, int* L) {
     const char* fn = "masr_test_rescore_logits";
-    if (!m || !logits || !ld || !gold || !R || !L) { mk_set_error(fn, "null pointer"); return -1; }
-    if (!m->last_rescore.logits) { mk_set_error(fn, "no rescoring call yet"); return -1; }
+    if (!m || !logits || !ld || !gold || !R || !L) return fail(fn, "null pointer");
+    if (!m->last_rescore.logits) return fail(fn, "no rescoring call yet");
     *logits = m->last_rescore.logits; *ld = m->Cp; *gold = m->last_rescore.gold; *R = m->last_rescore.R; *L = m->last_rescore.L;
     return 0;
 }

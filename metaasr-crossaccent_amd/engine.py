@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, check, check_lm_args, lib, nbest_lists, nbest_lists_lm
+from ._cabi import MasrConfig, check, check_beam_args, check_lm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -226,20 +226,46 @@ class MasrEngine:
               "masr_run_batch")
         self._last_x = xs          # keep the input alive until the stream has consumed it
 
-    def recog(self, xs: torch.Tensor, ilens, full: bool = False):
-        """greedy decode (MyTransformer.recog): returns int64 [Ldec, B] on the device, Ldec = max(ilens // 4).
-        Default = KV-cached incremental decode; full=True = the reference's literal whole-prefix re-decode per step."""
+    # ------------------------------------------------------------------ decoding: what the wrappers below share
+    def _decode_inputs(self, xs, ilens):
+        """xs on this device as contiguous fp32 and ilens as a host int64 tensor -> (xs, il, B, T)"""
         if xs.device != self.device:
             xs = xs.to(self.device, non_blocking=True)
         xs = xs.contiguous().float()
         B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        Ldec = int(il.max()) // 4
-        self._ensure_ws(B, T, Ldec)
+        return xs, torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous(), B, T
+
+    def _decode_ws(self, ws_fn, *args):
+        """a workspace of at least ws_fn(*args) bytes, bound, with the shadows fresh; a refusal raises under ws_fn's name"""
+        need = int(getattr(self._l, ws_fn)(self.h, *args))
+        check(need if need < 0 else 0, ws_fn)
+        self._ensure_ws_bytes(need)
         self.refresh()
+
+    def _outputs(self, *lead, ld, extra=""):
+        """device outputs of a decode: tokens int32 [*lead, ld], lens int32 [*lead], scores fp32 [*lead], then one [*lead] tensor per letter
+        of `extra` (f: fp32, i: int32)"""
+        kinds = {"i": torch.int32, "f": torch.float32}
+        return (torch.empty(*lead, ld, dtype=torch.int32, device=self.device),
+                *[torch.empty(*lead, dtype=kinds[k], device=self.device) for k in "if" + extra])
+
+    def _beam_lmax(self, il, min_step_ratio, max_step_ratio):
+        return max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
+
+    @staticmethod
+    def _best_lists(tok, lens, scores):
+        tok, lens = tok.cpu(), lens.cpu()
+        return [tok[b, :int(lens[b])].tolist() for b in range(lens.size(0))], scores.cpu()
+
+    def recog(self, xs: torch.Tensor, ilens, full: bool = False):
+        """greedy decode (MyTransformer.recog): returns int64 [Ldec, B] on the device, Ldec = max(ilens // 4).
+        Default = KV-cached incremental decode; full=True = the reference's literal whole-prefix re-decode per step."""
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Ldec = int(il.max()) // 4
+        self._decode_ws("masr_workspace_bytes", B, T, Ldec)
         out = torch.zeros(Ldec, B, dtype=torch.int32, device=self.device)
         fn = self._l.masr_recog_full if full else self._l.masr_recog
-        check(fn(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, _ptr(out), self.stream()), "masr_recog")
+        check(fn(self.h, _ptr(xs), _ptr(il), B, T, _ptr(out), self.stream()), "masr_recog")
         self._last_x = xs
         return out.to(torch.int64)
 
@@ -260,64 +286,32 @@ class MasrEngine:
         K = beam_size in [1, 64]; an utterance's result does not depend on the rest of its batch.  ctc_weight != 0 runs the joint
         CTC/attention search (masr_recog_beam_ctc: needs a hybrid model, ctc_weight > 0, att_weight >= 0); with ctc_weight == 0 the
         attention decoder alone decides and att_weight is not used."""
-        K = int(beam_size)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
+        K, _ = check_beam_args(beam_size)
         joint = float(ctc_weight) != 0.0
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
-        ws_fn = "masr_beam_ctc_workspace_bytes" if joint else "masr_beam_workspace_bytes"
-        need = int(getattr(self._l, ws_fn)(self.h, B, T, K, Lmax))
-        check(need if need < 0 else 0, ws_fn)
-        self._ensure_ws_bytes(need)
-        self.refresh()
-        tok = torch.empty(B, Lmax, dtype=torch.int32, device=self.device)
-        lens = torch.empty(B, dtype=torch.int32, device=self.device)
-        scores = torch.empty(B, dtype=torch.float32, device=self.device)
-        if joint:
-            check(self._l.masr_recog_beam_ctc(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
-                                              float(att_weight), float(ctc_weight), _ptr(tok), _ptr(lens), _ptr(scores), self.stream()),
-                  "masr_recog_beam_ctc")
-        else:
-            check(self._l.masr_recog_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
-                                          _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam")
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_ctc_workspace_bytes" if joint else "masr_beam_workspace_bytes", B, T, K, Lmax)
+        out = self._outputs(B, ld=Lmax)
+        fn, wts = ("masr_recog_beam_ctc", (float(att_weight), float(ctc_weight))) if joint else ("masr_recog_beam", ())
+        check(getattr(self._l, fn)(self.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), *wts, *map(_ptr, out),
+                                   self.stream()), fn)
         self._last_x = xs
-        tok, lens = tok.cpu(), lens.cpu()
-        return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
+        return self._best_lists(*out)
 
     def recog_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
         """beam search with an n-gram LM fused in (masr_recog_beam_lm): recog_beam's attention-only search with the per-step
         increment log p_att(c | h) + lm_w * lm(c | h).  lm: an NGramLM (lm.py) over this model's odim classes; lm_w finite and >= 0.
         Returns what recog_beam returns: (B token lists without sos / eos, fp32 scores [B] on the host)."""
-        K, lm_w = int(beam_size), float(lm_w)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not (math.isfinite(lm_w) and lm_w >= 0.0):
-            raise ValueError(f"lm_w must be finite and >= 0, got {lm_w}")
-        if getattr(lm, "h", None) is None:
-            raise ValueError("lm must be a live NGramLM")
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
-        need = int(self._l.masr_beam_lm_workspace_bytes(self.h, B, T, K, Lmax))
-        check(need if need < 0 else 0, "masr_beam_lm_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
-        tok = torch.empty(B, Lmax, dtype=torch.int32, device=self.device)
-        lens = torch.empty(B, dtype=torch.int32, device=self.device)
-        scores = torch.empty(B, dtype=torch.float32, device=self.device)
-        check(self._l.masr_recog_beam_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, float(min_step_ratio), float(max_step_ratio),
-                                         lm_w, _ptr(tok), _ptr(lens), _ptr(scores), self.stream()), "masr_recog_beam_lm")
+        K, _ = check_beam_args(beam_size)
+        lm_w, _ = check_lm_args(lm, lm_w, 0.0)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_lm_workspace_bytes", B, T, K, Lmax)
+        out = self._outputs(B, ld=Lmax)
+        check(self._l.masr_recog_beam_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), lm_w,
+                                         *map(_ptr, out), self.stream()), "masr_recog_beam_lm")
         self._last_x = xs
-        tok, lens = tok.cpu(), lens.cpu()
-        return [tok[b, :int(lens[b])].tolist() for b in range(B)], scores.cpu()
+        return self._best_lists(*out)
 
     def recog_beam_ctc_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                           min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, att_weight: float = 0.7, ctc_weight: float = 0.3,
@@ -326,85 +320,44 @@ class MasrEngine:
         DESIGN 5.7; needs a hybrid model): recog_beam's joint search with the LM in the pre-beam and in the score.  lm_w finite and >= 0,
         len_bonus finite of any sign, ctc_weight > 0, att_weight >= 0, nbest in [1, beam_size].  Returns per utterance a list of at most
         nbest (token list, score), best first (raw: the device tensors tokens [B, nbest, Lmax], lens, scores instead)."""
-        K, N = int(beam_size), int(nbest)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        Lmax = max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
-        need = int(self._l.masr_beam_ctc_lm_workspace_bytes(self.h, B, T, K, N, Lmax))
-        check(need if need < 0 else 0, "masr_beam_ctc_lm_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
-        tok = torch.empty(B, N, Lmax, dtype=torch.int32, device=self.device)
-        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
-        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        check(self._l.masr_recog_beam_ctc_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, float(min_step_ratio),
-                                             float(max_step_ratio), float(att_weight), float(ctc_weight), lm_w, len_bonus, _ptr(tok), _ptr(lens),
-                                             _ptr(scores), self.stream()), "masr_recog_beam_ctc_lm")
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_ctc_lm_workspace_bytes", B, T, K, N, Lmax)
+        out = self._outputs(B, N, ld=Lmax)
+        check(self._l.masr_recog_beam_ctc_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio), float(max_step_ratio),
+                                             float(att_weight), float(ctc_weight), lm_w, len_bonus, *map(_ptr, out), self.stream()),
+              "masr_recog_beam_ctc_lm")
         self._last_x = xs
-        return (tok, lens, scores) if raw else nbest_lists(tok, lens, scores)
+        return out if raw else nbest_lists(*out)
 
     def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
         head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first
         (raw: the device tensors tokens [B, nbest, T // 4], lens, scores instead)."""
-        K, N = int(beam_size), int(nbest)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        need = int(self._l.masr_ctc_beam_workspace_bytes(self.h, B, T, K))
-        check(need if need < 0 else 0, "masr_ctc_beam_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
-        tok = torch.empty(B, N, T // 4, dtype=torch.int32, device=self.device)
-        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
-        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        check(self._l.masr_recog_ctc_beam(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, _ptr(tok), _ptr(lens), _ptr(scores),
-                                          self.stream()), "masr_recog_ctc_beam")
+        K, N = check_beam_args(beam_size, nbest)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
+        out = self._outputs(B, N, ld=T // 4)
+        check(self._l.masr_recog_ctc_beam(self.h, _ptr(xs), _ptr(il), B, T, K, N, *map(_ptr, out), self.stream()), "masr_recog_ctc_beam")
         self._last_x = xs
-        return (tok, lens, scores) if raw else nbest_lists(tok, lens, scores)
+        return out if raw else nbest_lists(*out)
 
     def recog_ctc_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                           raw: bool = False):
         """recog_ctc_beam with the n-gram LM `lm` (an NGramLM over this model's odim classes) and a per-token bonus fused into the search
         (masr_recog_ctc_beam_lm).  lm_w finite and >= 0, len_bonus finite of any sign.  Returns per utterance a list of at most
         nbest (token list, fused score, acoustic score), best first (raw: the device tensors tokens, lens, scores, am instead)."""
-        K, N = int(beam_size), int(nbest)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        need = int(self._l.masr_ctc_beam_workspace_bytes(self.h, B, T, K))
-        check(need if need < 0 else 0, "masr_ctc_beam_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
-        tok = torch.empty(B, N, T // 4, dtype=torch.int32, device=self.device)
-        lens = torch.empty(B, N, dtype=torch.int32, device=self.device)
-        scores = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        am = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        check(self._l.masr_recog_ctc_beam_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, lm_w, len_bonus, _ptr(tok), _ptr(lens),
-                                             _ptr(scores), _ptr(am), self.stream()), "masr_recog_ctc_beam_lm")
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
+        out = self._outputs(B, N, ld=T // 4, extra="f")
+        check(self._l.masr_recog_ctc_beam_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, *map(_ptr, out), self.stream()),
+              "masr_recog_ctc_beam_lm")
         self._last_x = xs
-        return (tok, lens, scores, am) if raw else nbest_lists_lm(tok, lens, scores, am)
+        return out if raw else nbest_lists(*out)
 
     @staticmethod
     def _rescore_weights(att_w, ctc_w):
@@ -416,9 +369,8 @@ class MasrEngine:
         return att_w, ctc_w
 
     def _rescore_outputs(self, B, N, ld):
-        i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
-        return (torch.empty(B, N, ld, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **f32), torch.empty(B, N, **f32),
-                torch.empty(B, N, **f32), torch.empty(B, N, **i32))
+        """tokens, lens, scores, att, ctc, order"""
+        return self._outputs(B, N, ld=ld, extra="ffi")
 
     @staticmethod
     def _rescore_lists(out):
@@ -431,25 +383,12 @@ class MasrEngine:
         recog_ctc_beam(beam_size, nbest), then ONE teacher-forced decoder pass over all B * nbest hypotheses, and the list re-ranked by
         att_w * log p_att + ctc_w * log p_ctc.  Returns per utterance a list of (tokens, score, att, ctc, first_pass_rank), best first
         (raw: the device tensors tokens, lens, scores, att, ctc, order instead).  The call waits for the stream once, between the passes."""
-        K = int(beam_size)
-        N = K if nbest is None else int(nbest)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        K, N = check_beam_args(beam_size, nbest)
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, K, N, T // 4))
-        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
         out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, att_w, ctc_w, *[_ptr(t) for t in out],
-                                         self.stream()), "masr_recog_rescore")
+        check(self._l.masr_recog_rescore(self.h, _ptr(xs), _ptr(il), B, T, K, N, att_w, ctc_w, *map(_ptr, out), self.stream()), "masr_recog_rescore")
         self._last_x = xs
         return out if raw else self._rescore_lists(out)
 
@@ -457,26 +396,14 @@ class MasrEngine:
                          att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
         """recog_rescore whose first pass is recog_ctc_beam_lm's LM-fused search (masr_recog_rescore_lm): the `ctc` of an entry
         is that pass's fused score.  Returns what recog_rescore returns."""
-        K = int(beam_size)
-        N = K if nbest is None else int(nbest)
-        if not 1 <= K <= 64:
-            raise ValueError(f"beam_size must be in [1, 64], got {beam_size}")
-        if not 1 <= N <= K:
-            raise ValueError(f"nbest must be in [1, beam_size], got {nbest}")
+        K, N = check_beam_args(beam_size, nbest)
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
-        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, K, N, T // 4))
-        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
         out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore_lm(self.h, lm.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, K, N, lm_w, len_bonus, att_w, ctc_w,
-                                            *[_ptr(t) for t in out], self.stream()), "masr_recog_rescore_lm")
+        check(self._l.masr_recog_rescore_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, att_w, ctc_w, *map(_ptr, out),
+                                            self.stream()), "masr_recog_rescore_lm")
         self._last_x = xs
         return out if raw else self._rescore_lists(out)
 
@@ -484,11 +411,7 @@ class MasrEngine:
         """attention rescoring of a caller's N-best lists (masr_rescore_nbest): tokens int32 [B, N, ld], lens int32 [B, N] (-1 = no entry),
         ctc fp32 [B, N] (the first-pass scores); every token of a live list in [1, odim - 2].  Returns what recog_rescore returns."""
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
-        if xs.device != self.device:
-            xs = xs.to(self.device, non_blocking=True)
-        xs = xs.contiguous().float()
-        B, T, D = xs.shape
-        il = torch.as_tensor(ilens, dtype=torch.int64).cpu().contiguous()
+        xs, il, B, T = self._decode_inputs(xs, ilens)
         tokens = torch.as_tensor(tokens).to(self.device, torch.int32).contiguous()
         lens = torch.as_tensor(lens).to(self.device, torch.int32).contiguous()
         ctc = torch.as_tensor(ctc).to(self.device, torch.float32).contiguous()
@@ -497,14 +420,10 @@ class MasrEngine:
         N, ld = tokens.size(1), tokens.size(2)
         if not 1 <= N <= 64:
             raise ValueError(f"N must be in [1, 64], got {N}")
-        Lmax = max(0, int(lens.max()))
-        need = int(self._l.masr_rescore_workspace_bytes(self.h, B, T, N, N, Lmax))
-        check(need if need < 0 else 0, "masr_rescore_workspace_bytes")
-        self._ensure_ws_bytes(need)
-        self.refresh()
+        self._decode_ws("masr_rescore_workspace_bytes", B, T, N, N, max(0, int(lens.max())))
         out = self._rescore_outputs(B, N, ld)
-        check(self._l.masr_rescore_nbest(self.h, _ptr(xs), C.c_void_p(il.data_ptr()), B, T, N, _ptr(tokens), ld, _ptr(lens), _ptr(ctc), att_w, ctc_w,
-                                         *[_ptr(t) for t in out], self.stream()), "masr_rescore_nbest")
+        check(self._l.masr_rescore_nbest(self.h, _ptr(xs), _ptr(il), B, T, N, _ptr(tokens), ld, _ptr(lens), _ptr(ctc), att_w, ctc_w,
+                                         *map(_ptr, out), self.stream()), "masr_rescore_nbest")
         self._last_x = xs
         return out if raw else self._rescore_lists(out)
 

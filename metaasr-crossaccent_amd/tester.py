@@ -1,30 +1,36 @@
-"""Tester: greedy decoding of the test shard into `<log_dir>/<decode_suffix>/best-hyp` (reference: src/tester.py:18-273).
+"""Tester: decoding of the test shard into `<log_dir>/<decode_suffix>/best-hyp` (reference: src/tester.py:18-273).
 Line format "<ref ids> TAB <hyp ids>" (space separated), `trim` = cut at the first </s> after position 0 -- unchanged, so
-translate.py / score.sh of the reference run on these files as they are.  Only the transformer + greedy path exists in
-the reference for this model (beam search raises NotImplementedError there, tester.py:121-124); `--decode_mode beam` with the
-transformer runs this project's GPU beam search (masr_recog_beam) with the config's solver.beam_decode block and writes the
-best hypothesis of each utterance in the same line format.  On a hybrid model (asr_model.ctc_weight > 0) a block with ctc_w > 0 runs
-the joint CTC/attention search (masr_recog_beam_ctc) with att_w (default 1 - ctc_w) and ctc_w.  The weights are checked on every model,
-hybrid or plain, before anything is decoded: a negative or non-finite ctc_w or att_w raises ValueError, and so does ctc_w > 1 without an
-att_w (the default 1 - ctc_w is then negative).  A plain model with valid weights decodes as before and logs that they are ignored.
-`--decode_mode rescore` (hybrid transformers) is the two-pass decode of DESIGN 5.4 (masr_recog_rescore): the CTC prefix beam of
-`ctc_beam` with beam_size, its nbest (default beam_size) best re-ranked by att_w * attention score + ctc_w * CTC score after one
-teacher-forced decoder pass; ctc_w defaults to 0.5, att_w to 1 - ctc_w, and att_w must be > 0.
-`--decode_mode lm_beam` (transformers) is the attention beam with an n-gram LM fused in (masr_recog_beam_lm): the ARPA file of
-`--lm_model_path` over the output units, weighted by beam_decode.lm_w (default 0.3); beam_size and the step ratios as for `beam`.  The path is
-read at exec(): without one the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed).  The LM
-is not fused into the joint CTC/attention beam by this mode: a hybrid model with beam_decode.ctc_w > 0 raises ValueError (`lm_joint_beam` below
-is that search).
-`--decode_mode lm_ctc_beam` (BLSTM-CTC and hybrid transformers) is the CTC prefix beam of `ctc_beam` with that n-gram LM and a per-token
-bonus fused into the search (masr_ctc_beam_search_lm): `--lm_model_path` as for `lm_beam`, beam_decode.beam_size, lm_w (default
-0.3, finite and >= 0) and len_bonus (default 0, finite, any sign).  `--decode_mode lm_rescore` (hybrid transformers) is `rescore` with that
-search as its first pass (masr_recog_rescore_lm): nbest, att_w and ctc_w as for `rescore`.  Both vet every setting at exec(), before
-anything is decoded, and build the LM once per Tester.
-`--decode_mode lm_joint_beam` (hybrid transformers) is the one-pass joint CTC/attention beam with that n-gram LM in the pre-beam and the score,
-a per-token bonus and an N-best list (masr_recog_beam_ctc_lm): `--lm_model_path` as for `lm_beam`; beam_size, att_w / ctc_w and the
-step ratios as for `beam`, with ctc_w > 0 required (ctc_w absent or 0 raises ValueError: that search is `lm_beam`); lm_w (default 0.3),
-len_bonus (default 0, finite, any sign) and nbest (default 1, in [1, beam_size]).  The best entry of each utterance is written.  Every
-setting is vetted at exec(): no path or a BLSTM raises NotImplementedError, a transformer without a CTC head ValueError."""
+translate.py / score.sh of the reference run on these files as they are.  Only the transformer + greedy path exists in the reference
+for this model (beam search raises NotImplementedError there, tester.py:121-124); every other `--decode_mode` is this project's GPU
+search and writes the best hypothesis of each utterance in the same line format.  All read the config's solver.beam_decode block
+(beam_size in [1, 64] is required; every weight must be finite and >= 0, else ValueError) and vet every setting at exec(), before
+anything is decoded.  Tester.MODES is the table of them:
+  greedy         masr_recog; transformer and BLSTM-CTC.
+  beam           masr_recog_beam; transformers (a BLSTM: NotImplementedError).  min_step_ratio (0), max_step_ratio (1).  On a hybrid model
+                 (asr_model.ctc_weight > 0) ctc_w > 0 runs the joint CTC/attention search masr_recog_beam_ctc with att_w (default 1 - ctc_w,
+                 so ctc_w > 1 without an att_w is refused) and ctc_w.  The weights are checked on every model, hybrid or plain; a plain
+                 model with valid weights decodes as before and logs that they are ignored.
+  ctc_beam       masr_recog_ctc_beam (BLSTM-CTC: masr_ctc_beam_search per utterance); needs a CTC output layer (a transformer without
+                 one: ValueError).
+  rescore        masr_recog_rescore, the two-pass decode of DESIGN 5.4: the CTC prefix beam of `ctc_beam`, its nbest (default beam_size, in
+                 [1, beam_size]) best re-ranked by att_w * attention score + ctc_w * CTC score after one teacher-forced decoder pass.
+                 ctc_w (0.5), att_w (1 - ctc_w, must be > 0).  Hybrid transformers (a BLSTM: NotImplementedError, no head: ValueError).
+  lm_beam        masr_recog_beam_lm, the attention beam with an n-gram LM fused in: the ARPA file of `--lm_model_path` over
+                 the output units, weighted by lm_w (0.3); the step ratios as for `beam`.  The path is read at exec(): without one
+                 the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed); so does a BLSTM.
+                 The LM is not fused into the joint beam by this mode: a hybrid model with ctc_w > 0 raises ValueError (that search is
+                 `lm_joint_beam`); a plain model logs that ctc_w is ignored.
+  lm_ctc_beam    masr_recog_ctc_beam_lm (BLSTM-CTC: masr_ctc_beam_search_lm), `ctc_beam` with that LM and a per-token bonus fused into
+                 the search: `--lm_model_path` as for `lm_beam`, lm_w (0.3), len_bonus (0, finite, any sign).  Refuses what
+                 `ctc_beam` refuses, and a BLSTM whose blank is not id 0 (its slot serves as the LM's <s>).
+  lm_rescore     masr_recog_rescore_lm, `rescore` with `lm_ctc_beam`'s search as its first pass: nbest, att_w and ctc_w as for `rescore`, the
+                 path, lm_w and len_bonus as for `lm_ctc_beam`.  Refuses what `rescore` refuses.
+  lm_joint_beam  masr_recog_beam_ctc_lm, the one-pass joint CTC/attention beam with that LM in the pre-beam and the score, a per-token
+                 bonus and an N-best list whose best entry is written: `--lm_model_path` as for `lm_beam`; att_w / ctc_w and
+                 the step ratios as for `beam`, with ctc_w > 0 required (absent or 0: ValueError, that search is `lm_beam`); lm_w (0.3),
+                 len_bonus (0, finite, any sign), nbest (1, in [1, beam_size]).  No path or a BLSTM raises NotImplementedError, a
+                 transformer without a CTC head ValueError.
+The LM modes build the LM once per Tester and (path, <s> id, </s> id)."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -122,71 +128,7 @@ class Tester:
         with open(Path(self.decode_dir, 'best-hyp'), 'a') as fout:
             fout.write("{}\t{}\n".format(" ".join(str(i) for i in y), " ".join(str(i) for i in hyp)))
 
-    def batch_beam_decode(self, xs, ilens, ys, olens):
-        hyps, _ = self.asr_model.beam_decode(xs, ilens, self.beam_size, self.min_step_ratio, self.max_step_ratio,
-                                             self.att_weight, self.ctc_weight)
-        for hyp, y in zip(hyps, ys):
-            self.write_hyp(y.tolist(), hyp)
-        return True
-
-    def batch_lm_beam_decode(self, xs, ilens, ys, olens):
-        hyps, _ = self.asr_model.lm_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.min_step_ratio, self.max_step_ratio)
-        for hyp, y in zip(hyps, ys):
-            self.write_hyp(y.tolist(), hyp)
-        return True
-
-    def batch_ctc_beam_decode(self, xs, ilens, ys, olens):
-        for nbest, y in zip(self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size), ys):
-            hyp = nbest[0][0]
-            # (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is applied to keep the Tester's contract)
-            self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
-        return True
-
-    def batch_lm_ctc_beam_decode(self, xs, ilens, ys, olens):
-        if self.model_name == 'blstm':
-            lists = self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus)
-        else:
-            lists = self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
-        for nbest, y in zip(lists, ys):
-            hyp = nbest[0][0]
-            self.write_hyp(y.tolist(), self.trim(hyp) if self.model_name == 'blstm' else hyp)
-        return True
-
-    def batch_lm_rescore_decode(self, xs, ilens, ys, olens):
-        lists = self.asr_model.lm_rescore_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus, self.nbest, self.att_weight,
-                                                 self.ctc_weight)
-        for nbest, y in zip(lists, ys):
-            self.write_hyp(y.tolist(), nbest[0][0])
-        return True
-
-    def batch_lm_joint_beam_decode(self, xs, ilens, ys, olens):
-        lists = self.asr_model.lm_joint_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus, self.nbest,
-                                                    self.min_step_ratio, self.max_step_ratio, self.att_weight, self.ctc_weight)
-        for nbest, y in zip(lists, ys):
-            self.write_hyp(y.tolist(), nbest[0][0] if nbest else [])
-        return True
-
-    def batch_rescore_decode(self, xs, ilens, ys, olens):
-        for nbest, y in zip(self.asr_model.rescore_decode(xs, ilens, self.beam_size, self.nbest, self.att_weight, self.ctc_weight), ys):
-            self.write_hyp(y.tolist(), nbest[0][0])
-        return True
-
-    def _rescore_settings(self):
-        if self.model_name == 'blstm':
-            raise NotImplementedError("rescore: attention rescoring needs the transformer's decoder, the BLSTM has none; "
-                                      "use --decode_mode ctc_beam or greedy")
-        bd = self._beam_size()
-        self.nbest = int(bd.get('nbest', self.beam_size))
-        if not 1 <= self.nbest <= self.beam_size:
-            raise ValueError(f"solver.beam_decode.nbest must be in [1, beam_size], got {self.nbest}")
-        self.ctc_weight = self._weight(bd, 'ctc_w', 0.5)
-        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
-        if not self.att_weight > 0.0:
-            raise ValueError(f"solver.beam_decode.att_w must be > 0 for decode_mode 'rescore', got {self.att_weight}")
-        if not self.asr_model.engine.ctc_weight > 0.0:
-            raise ValueError("decode_mode 'rescore' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
-                             "use --decode_mode beam or greedy")
-
+    # ------------------------------------------------------------------ settings: what the modes' vetting shares
     def _beam_size(self):
         bd = self.config.get('solver', {}).get('beam_decode')
         if not isinstance(bd, dict) or 'beam_size' not in bd:
@@ -196,102 +138,54 @@ class Tester:
             raise ValueError(f"solver.beam_decode.beam_size must be in [1, 64], got {self.beam_size}")
         return bd
 
-    def _ctc_beam_settings(self):
-        self._beam_size()
-        if self.model_name != 'blstm' and not self.asr_model.engine.ctc_weight > 0.0:
-            raise ValueError("decode_mode 'ctc_beam' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
-                             "use --decode_mode beam or greedy")
+    @staticmethod
+    def _weight(bd, key, default):
+        w = float(bd.get(key, default))
+        if not math.isfinite(w) or w < 0.0:
+            raise ValueError(f"solver.beam_decode.{key} must be finite and >= 0, got {bd.get(key, default)}")
+        return w
 
-    def _lm_beam_settings(self):
-        lm_path = getattr(self.paras, 'lm_model_path', None)
-        if lm_path is None:
-            raise NotImplementedError("lm_beam: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
-        if self.model_name == 'blstm':
-            raise NotImplementedError("lm_beam: LM fusion is only implemented for the transformer's attention beam; "
-                                      "use --decode_mode ctc_beam or greedy")
-        bd = self._beam_size()
-        self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
-        self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
-        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
-        ctc_w = self._weight(bd, 'ctc_w', 0.0)
-        if ctc_w > 0.0:
-            if self.asr_model.engine.ctc_weight > 0.0:
-                raise ValueError(f"lm_beam: the LM is not fused into the joint CTC/attention beam (beam_decode.ctc_w = {bd['ctc_w']}); "
-                                 "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
-            logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
-        from .lm import NGramLM
-        self.lm = NGramLM.from_arpa(lm_path, self.id2ch, self.sos_id, self.eos_id)
-        logger.notice(f"LM shallow fusion: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
-                      f"lm_w = {self.lm_weight}")
+    def _lm_model_path(self):
+        path = getattr(self.paras, 'lm_model_path', None)
+        if path is None:
+            raise NotImplementedError(f"{self.decode_mode}: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
+        return path
 
-    def _lm_joint_settings(self):
-        """lm_joint_beam: the path, the model, then every setting -- all before anything is decoded"""
-        lm_path = getattr(self.paras, 'lm_model_path', None)
-        if lm_path is None:
-            raise NotImplementedError("lm_joint_beam: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
-        if self.model_name == 'blstm':
-            raise NotImplementedError("lm_joint_beam: the joint CTC/attention beam needs the transformer's decoder, the BLSTM has none; "
-                                      "use --decode_mode lm_ctc_beam, ctc_beam or greedy")
-        bd = self._beam_size()
+    def _need_ctc_head(self, mode, instead):
         if not self.asr_model.engine.ctc_weight > 0.0:
-            raise ValueError("decode_mode 'lm_joint_beam' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or "
-                             "absent); use --decode_mode lm_beam, beam or greedy")
+            raise ValueError(f"decode_mode '{mode}' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
+                             f"use --decode_mode {instead}")
+
+    def _step_ratios(self, bd):
         self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
         self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
-        self.ctc_weight = self._weight(bd, 'ctc_w', 0.0)
-        if not self.ctc_weight > 0.0:
-            raise ValueError("lm_joint_beam: solver.beam_decode.ctc_w must be > 0 (it is absent or 0); to fuse the LM into the attention beam "
-                             "alone use --decode_mode lm_beam")
-        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
-        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+
+    def _len_bonus(self, bd):
         self.len_bonus = float(bd.get('len_bonus', 0.0))
         if not math.isfinite(self.len_bonus):
             raise ValueError(f"solver.beam_decode.len_bonus must be finite, got {bd.get('len_bonus')}")
-        self.nbest = int(bd.get('nbest', 1))
+
+    def _nbest(self, bd, default):
+        self.nbest = int(bd.get('nbest', default))
         if not 1 <= self.nbest <= self.beam_size:
             raise ValueError(f"solver.beam_decode.nbest must be in [1, beam_size], got {self.nbest}")
-        if getattr(self, 'lm', None) is None or getattr(self, '_lm_path', None) != lm_path:
-            from .lm import NGramLM
-            self.lm = NGramLM.from_arpa(lm_path, self.id2ch, self.sos_id, self.eos_id)
-            self._lm_path = lm_path
-        logger.notice(f"Joint CTC/attention beam with LM: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
-                      f"att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}, "
-                      f"nbest = {self.nbest}")
 
-    def _lm_ctc_settings(self):
-        """lm_ctc_beam and lm_rescore: the path, the model, then every setting -- all before anything is decoded"""
-        mode = self.decode_mode
-        lm_path = getattr(self.paras, 'lm_model_path', None)
-        if lm_path is None:
-            raise NotImplementedError(f"{mode}: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
-        if mode == 'lm_rescore':
-            self._rescore_settings()                             # (BLSTM: NotImplementedError; no CTC head: ValueError; nbest, att_w, ctc_w)
-        else:
-            self._beam_size()
-            if self.model_name != 'blstm' and not self.asr_model.engine.ctc_weight > 0.0:
-                raise ValueError(f"decode_mode '{mode}' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or "
-                                 "absent); use --decode_mode lm_beam, beam or greedy")
-            if self.model_name == 'blstm' and self.blank_id != 0:
-                raise ValueError(f"decode_mode '{mode}' needs the blank at id 0 (its slot serves as the LM's <s>), got {self.blank_id}")
-        bd = self.config['solver']['beam_decode']
-        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
-        self.len_bonus = float(bd.get('len_bonus', 0.0))
-        if not math.isfinite(self.len_bonus):
-            raise ValueError(f"solver.beam_decode.len_bonus must be finite, got {bd.get('len_bonus')}")
-        if getattr(self, 'lm', None) is None or getattr(self, '_lm_path', None) != lm_path:
+    def _load_lm(self, path, sos, eos):
+        """self.lm = the ARPA file as an NGramLM with <s> / </s> at the ids sos / eos, built once per Tester and (path, sos, eos) -> what the
+        modes' log lines say about it"""
+        key = (path, sos, eos)
+        if getattr(self, 'lm', None) is None or getattr(self, '_lm_key', None) != key:
             from .lm import NGramLM
-            self.lm = NGramLM.from_arpa(lm_path, self.id2ch, 0, len(self.id2ch) - 1)       # <s> = 0 (the BLSTM's <blank> slot), </s> last
-            self._lm_path = lm_path
-        logger.notice(f"LM-fused CTC beam: {lm_path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}, "
-                      f"lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
+            self.lm, self._lm_key = NGramLM.from_arpa(path, self.id2ch, sos, eos), key
+        return f"{path}, order {self.lm.order}, n-grams {' / '.join(str(c) for c in self.lm.counts)}"
 
+    # ------------------------------------------------------------------ settings per mode: everything is vetted before anything is decoded
     def _beam_settings(self):
         if self.model_name == 'blstm':
             raise NotImplementedError("beam: beam search is only implemented for the transformer (the reference's BLSTM beam "
                                       "decoder is dead code, DESIGN 9); use --decode_mode greedy")
         bd = self._beam_size()
-        self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
-        self.max_step_ratio = float(bd.get('max_step_ratio', 1.0))
+        self._step_ratios(bd)
         ctc_w = self._weight(bd, 'ctc_w', 0.0)
         att_w = self._weight(bd, 'att_w', 1.0 - ctc_w)
         self.att_weight, self.ctc_weight = 1.0, 0.0                 # attention decoder alone (masr_recog_beam)
@@ -308,46 +202,123 @@ class Tester:
             if 'att_w' in bd:
                 logger.notice(f"beam_decode.att_w = {bd['att_w']} ignored: this model has no CTC head to weigh against the attention decoder")
 
-    @staticmethod
-    def _weight(bd, key, default):
-        w = float(bd.get(key, default))
-        if not math.isfinite(w) or w < 0.0:
-            raise ValueError(f"solver.beam_decode.{key} must be finite and >= 0, got {bd.get(key, default)}")
-        return w
+    def _lm_beam_settings(self):
+        lm_path = self._lm_model_path()
+        if self.model_name == 'blstm':
+            raise NotImplementedError("lm_beam: LM fusion is only implemented for the transformer's attention beam; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self._step_ratios(bd)
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        if self._weight(bd, 'ctc_w', 0.0) > 0.0:
+            if self.asr_model.engine.ctc_weight > 0.0:
+                raise ValueError(f"lm_beam: the LM is not fused into the joint CTC/attention beam (beam_decode.ctc_w = {bd['ctc_w']}); "
+                                 "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
+            logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
+        logger.notice(f"LM shallow fusion: {self._load_lm(lm_path, self.sos_id, self.eos_id)}, lm_w = {self.lm_weight}")
+
+    def _ctc_beam_settings(self):
+        self._beam_size()
+        if self.model_name != 'blstm':
+            self._need_ctc_head('ctc_beam', "beam or greedy")
+
+    def _rescore_settings(self):
+        if self.model_name == 'blstm':
+            raise NotImplementedError("rescore: attention rescoring needs the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self._nbest(bd, self.beam_size)
+        self.ctc_weight = self._weight(bd, 'ctc_w', 0.5)
+        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
+        if not self.att_weight > 0.0:
+            raise ValueError(f"solver.beam_decode.att_w must be > 0 for decode_mode 'rescore', got {self.att_weight}")
+        self._need_ctc_head('rescore', "beam or greedy")
+
+    def _lm_ctc_settings(self):
+        """lm_ctc_beam and lm_rescore"""
+        mode = self.decode_mode
+        lm_path = self._lm_model_path()
+        if mode == 'lm_rescore':
+            self._rescore_settings()                             # (BLSTM: NotImplementedError; no CTC head: ValueError; nbest, att_w, ctc_w)
+        else:
+            self._beam_size()
+            if self.model_name != 'blstm':
+                self._need_ctc_head(mode, "lm_beam, beam or greedy")
+            elif self.blank_id != 0:
+                raise ValueError(f"decode_mode '{mode}' needs the blank at id 0 (its slot serves as the LM's <s>), got {self.blank_id}")
+        bd = self.config['solver']['beam_decode']
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self._len_bonus(bd)
+        lm = self._load_lm(lm_path, 0, len(self.id2ch) - 1)         # <s> = 0 (the BLSTM's <blank> slot), </s> last
+        logger.notice(f"LM-fused CTC beam: {lm}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
+
+    def _lm_joint_settings(self):
+        lm_path = self._lm_model_path()
+        if self.model_name == 'blstm':
+            raise NotImplementedError("lm_joint_beam: the joint CTC/attention beam needs the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode lm_ctc_beam, ctc_beam or greedy")
+        bd = self._beam_size()
+        self._need_ctc_head('lm_joint_beam', "lm_beam, beam or greedy")
+        self._step_ratios(bd)
+        self.ctc_weight = self._weight(bd, 'ctc_w', 0.0)
+        if not self.ctc_weight > 0.0:
+            raise ValueError("lm_joint_beam: solver.beam_decode.ctc_w must be > 0 (it is absent or 0); to fuse the LM into the attention beam "
+                             "alone use --decode_mode lm_beam")
+        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self._len_bonus(bd)
+        self._nbest(bd, 1)
+        lm = self._load_lm(lm_path, self.sos_id, self.eos_id)
+        logger.notice(f"Joint CTC/attention beam with LM: {lm}, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, lm_w = {self.lm_weight}, "
+                      f"len_bonus = {self.len_bonus}, nbest = {self.nbest}")
+
+    # ------------------------------------------------------------------ the decode modes
+    def _ctc_best(self, lists):
+        """the best entry of each N-best list of a CTC beam (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is
+        applied to keep the Tester's contract)"""
+        return [self.trim(n[0][0]) if self.model_name == 'blstm' else n[0][0] for n in lists]
+
+    def _lm_ctc_beam_lists(self, xs, ilens):
+        if self.model_name == 'blstm':
+            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus)
+        return self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
+
+    # mode -> (its settings function, (Tester, xs, ilens) -> the best hypothesis of each utterance, Tester -> what the start-up line names);
+    # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself
+    MODES = {
+        'greedy': (None, None, lambda t: "greedy decoding"),
+        'beam': (_beam_settings,
+                 lambda t, xs, il: t.asr_model.beam_decode(xs, il, t.beam_size, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)[0],
+                 lambda t: f"beam decoding (beam {t.beam_size})"),
+        'lm_beam': (_lm_beam_settings,
+                    lambda t, xs, il: t.asr_model.lm_beam_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.min_step_ratio, t.max_step_ratio)[0],
+                    lambda t: f"beam decoding with LM fusion (beam {t.beam_size})"),
+        'ctc_beam': (_ctc_beam_settings,
+                     lambda t, xs, il: t._ctc_best(t.asr_model.ctc_beam_decode(xs, il, t.beam_size)),
+                     lambda t: f"CTC prefix beam decoding (beam {t.beam_size})"),
+        'rescore': (_rescore_settings,
+                    lambda t, xs, il: [n[0][0] for n in t.asr_model.rescore_decode(xs, il, t.beam_size, t.nbest, t.att_weight, t.ctc_weight)],
+                    lambda t: f"attention rescoring (CTC beam {t.beam_size}, {t.nbest}-best, att_w = {t.att_weight}, ctc_w = {t.ctc_weight})"),
+        'lm_ctc_beam': (_lm_ctc_settings,
+                        lambda t, xs, il: t._ctc_best(t._lm_ctc_beam_lists(xs, il)),
+                        lambda t: f"LM-fused CTC prefix beam decoding (beam {t.beam_size})"),
+        'lm_rescore': (_lm_ctc_settings,
+                       lambda t, xs, il: [n[0][0] for n in t.asr_model.lm_rescore_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest,
+                                                                                         t.att_weight, t.ctc_weight)],
+                       lambda t: f"attention rescoring of the LM-fused CTC beam (beam {t.beam_size})"),
+        'lm_joint_beam': (_lm_joint_settings,
+                          lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
+                              xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],
+                          lambda t: f"joint CTC/attention beam decoding with LM fusion (beam {t.beam_size})"),
+    }
 
     def exec(self):
-        if self.decode_mode not in ('greedy', 'beam', 'lm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore', 'lm_joint_beam'):
+        if self.decode_mode not in self.MODES:
             raise NotImplementedError(f"{self.decode_mode} haven't supported yet")
-        decode = self.batch_greedy_decode
-        if self.decode_mode == 'ctc_beam':
-            self._ctc_beam_settings()
-            decode = self.batch_ctc_beam_decode
-            logger.notice(f"Start CTC prefix beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
-        elif self.decode_mode == 'rescore':
-            self._rescore_settings()
-            decode = self.batch_rescore_decode
-            logger.notice(f"Start attention rescoring (CTC beam {self.beam_size}, {self.nbest}-best, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}): "
-                          f"{len(self.eval_set)} batches of <= {self.batch_size}")
-        elif self.decode_mode in ('lm_ctc_beam', 'lm_rescore'):
-            self._lm_ctc_settings()
-            decode = self.batch_lm_ctc_beam_decode if self.decode_mode == 'lm_ctc_beam' else self.batch_lm_rescore_decode
-            logger.notice(f"Start {'LM-fused CTC prefix beam decoding' if self.decode_mode == 'lm_ctc_beam' else 'attention rescoring of the LM-fused CTC beam'}"
-                          f" (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
-        elif self.decode_mode == 'lm_joint_beam':
-            self._lm_joint_settings()
-            decode = self.batch_lm_joint_beam_decode
-            logger.notice(f"Start joint CTC/attention beam decoding with LM fusion (beam {self.beam_size}): {len(self.eval_set)} batches of "
-                          f"<= {self.batch_size}")
-        elif self.decode_mode == 'lm_beam':
-            self._lm_beam_settings()
-            decode = self.batch_lm_beam_decode
-            logger.notice(f"Start beam decoding with LM fusion (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
-        elif self.decode_mode != 'greedy':
-            self._beam_settings()
-            decode = self.batch_beam_decode
-            logger.notice(f"Start beam decoding (beam {self.beam_size}): {len(self.eval_set)} batches of <= {self.batch_size}")
-        else:
-            logger.notice(f"Start greedy decoding: {len(self.eval_set)} batches of <= {self.batch_size}")
+        settings, best_hyps, what = self.MODES[self.decode_mode]
+        if settings is not None:
+            settings(self)
+        logger.notice(f"Start {what(self)}: {len(self.eval_set)} batches of <= {self.batch_size}")
         # --resume: prev_decode_step counts the LINES (utterances) already in best-hyp.  The reference's batch path does not
         # skip at all (tester.py:149-152: a resumed batch decode appends everything again); its per-utterance path skips
         # by step.  Here whole batches are skipped while all their utterances are already written; a partially written
@@ -360,6 +331,11 @@ class Tester:
                 seen += n
                 continue
             self._skip_lines = done - seen if seen < done else 0
-            decode(*self.eval_set.materialize(idxs))
+            xs, ilens, ys, olens = self.eval_set.materialize(idxs)
+            if best_hyps is None:
+                self.batch_greedy_decode(xs, ilens, ys, olens)
+            else:
+                for hyp, y in zip(best_hyps(self, xs, ilens), ys):
+                    self.write_hyp(y.tolist(), hyp)
             seen += n
         self._skip_lines = 0

@@ -4,47 +4,28 @@ ms per step = decode time / Lmax.  usage: python tools/bench_beam.py [B] [T]"""
 import ctypes as C
 import json
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, ".")
 import masr_amd  # noqa
 from masr_amd import _cabi
-from masr_amd.engine import MasrEngine
-from masr_amd.model import reference_init_state_dict
+from decode_bench import hkust_engine, timed
 
-HKUST = {"idim": 80, "nheads": 8, "d_model": 512, "d_inner": 2048, "dropout": 0.1, "pos_dropout": 0.1, "tgt_share_weight": 1,
-         "encoder": {"nlayers": 2}, "decoder": {"nlayers": 4}}
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
-torch.manual_seed(531)
-eng = MasrEngine(HKUST, 367)
-eng.load_state_dict(reference_init_state_dict(HKUST, 367))
+eng = hkust_engine(ctc=False)
 xs = torch.randn(B, T, 80, device="cuda")
 il = torch.full((B,), T, dtype=torch.int64)
 side = torch.cuda.Stream()
 L = T // 4
 res = {"B": B, "T": T, "steps": L, "decode": {}, "gemm_us": []}
 
-
-def timed(fn, n):
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    with torch.cuda.stream(side):
-        for _ in range(n):
-            r = fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3, r
-
-
-ms, _ = timed(lambda: eng.recog(xs, il), 3)
+ms, _ = timed(lambda: eng.recog(xs, il), 3, side)
 res["decode"]["greedy"] = {"ms": round(ms, 2), "ms_per_step": round(ms / L, 3), "utt_per_s": round(B / ms * 1e3, 1)}
 print(f"greedy        : {ms:8.1f} ms  {ms / L:6.3f} ms/step  {B / ms * 1e3:7.1f} utt/s", flush=True)
 for K in (1, 4, 10, 20):
-    ms, (toks, sc) = timed(lambda: eng.recog_beam(xs, il, K), 2)
+    ms, (toks, sc) = timed(lambda: eng.recog_beam(xs, il, K), 2, side)
     steps = L   # the graph is replayed Lmax times whatever ends earlier
     res["decode"][f"beam{K}"] = {"ms": round(ms, 2), "ms_per_step": round(ms / steps, 3), "utt_per_s": round(B / ms * 1e3, 1),
                                  "mean_len": sum(map(len, toks)) / B}

@@ -9,7 +9,6 @@ usage: python tools/bench_ctc_beam.py"""
 import ctypes as C
 import json
 import sys
-import time
 
 import torch
 
@@ -18,20 +17,13 @@ import masr_amd  # noqa
 from masr_amd._cabi import lib
 from masr_amd.blstm_engine import BlstmEngine
 from masr_amd.blstm_engine import reference_init_state_dict as blstm_init
-from masr_amd.engine import MasrEngine
-from masr_amd.model import reference_init_state_dict
+from decode_bench import hkust_engine, timed as timed_on
 
 KS = (1, 4, 10, 20)
 
 
 def timed(fn, n=3):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return round((time.perf_counter() - t0) / n * 1e3, 3)
+    return round(timed_on(fn, n)[0], 3)
 
 
 def search_alone(B, Tp, Cn, K, scale):
@@ -70,10 +62,7 @@ def main():
     res["blstm"] = r
     print(json.dumps({"blstm": r}), flush=True)
     del eng
-    hk = {"idim": 80, "nheads": 8, "d_model": 512, "d_inner": 2048, "dropout": 0.1, "pos_dropout": 0.1, "tgt_share_weight": 1,
-          "encoder": {"nlayers": 2}, "decoder": {"nlayers": 4}, "ctc_weight": 0.3}
-    eng = MasrEngine(hk, 367)
-    eng.load_state_dict(reference_init_state_dict(hk, 367))
+    eng = hkust_engine(ctc=True, seed=None)                     # (the seed of this process was set above)
     B, T = 16, 1000
     xs = torch.randn(B, T, 80, device="cuda")
     il = torch.full((B,), T, dtype=torch.int64)

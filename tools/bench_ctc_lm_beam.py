@@ -8,47 +8,21 @@ usage: python tools/bench_ctc_lm_beam.py [n-grams in all]"""
 import ctypes as C
 import json
 import sys
-import time
 
-import numpy as np
 import torch
 
 sys.path.insert(0, ".")
 import masr_amd  # noqa
 from masr_amd._cabi import lib
-from masr_amd.lm import NGramLM
+from decode_bench import C_, synthetic_lm, timed as timed_on
 
-C_ = 367
 KS = (1, 4, 10, 20)
 SHAPES = ((8, 100), (16, 250))
 N_TOTAL = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 
 
-def synthetic_lm(n_total, seed=7):
-    """tools/bench_lm_beam.py's: order 3 over C_ classes, dense unigrams, distinct random bigrams and trigrams of the units 1 .. C_ - 2"""
-    rng = np.random.RandomState(seed)
-    U = C_ - 2
-    grams = [np.arange(C_, dtype=np.int32).reshape(-1, 1)]
-    want = {2: min(U * U, n_total // 2)}
-    want[3] = n_total - C_ - want[2]
-    for n in (2, 3):
-        total = U ** n
-        idx = np.unique(rng.randint(total, size=int(want[n] * 1.2) + 16)) if want[n] < total else np.arange(total)
-        idx = rng.permutation(idx)[:want[n]]
-        grams.append(np.stack([(idx // U ** (n - 1 - j)) % U + 1 for j in range(n)], axis=1).astype(np.int32))
-    logp = [(-8.0 * rng.rand(len(g))).astype(np.float32) for g in grams]
-    bo = [(-2.0 * rng.rand(len(g))).astype(np.float32) for g in grams]
-    return NGramLM(3, C_, grams, logp, bo)
-
-
 def timed(fn, n=10):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3
+    return timed_on(fn, n)[0]
 
 
 def main():

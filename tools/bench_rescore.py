@@ -6,22 +6,16 @@ rescoring time includes its one host synchronisation between the passes; `L` is 
 usage: python tools/bench_rescore.py [B] [T]"""
 import json
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, ".")
 import masr_amd  # noqa
-from masr_amd.engine import MasrEngine
-from masr_amd.model import reference_init_state_dict
+from decode_bench import hkust_engine, timed as timed_on
 
-HKUST = {"idim": 80, "nheads": 8, "d_model": 512, "d_inner": 2048, "dropout": 0.1, "pos_dropout": 0.1, "tgt_share_weight": 1,
-         "encoder": {"nlayers": 2}, "decoder": {"nlayers": 4}, "ctc_weight": 0.3}
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
-torch.manual_seed(531)
-eng = MasrEngine(HKUST, 367)
-eng.load_state_dict(reference_init_state_dict(HKUST, 367))
+eng = hkust_engine(ctc=True)
 xs = torch.randn(B, T, 80, device="cuda")
 il = torch.full((B,), T, dtype=torch.int64)
 side = torch.cuda.Stream()
@@ -29,15 +23,7 @@ res = {"B": B, "T": T, "decode_ms": {}}
 
 
 def timed(fn, n=40):
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    with torch.cuda.stream(side):
-        for _ in range(n):
-            fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3
+    return timed_on(fn, n, side)[0]
 
 
 for K in (4, 10, 20):
