@@ -56,7 +56,7 @@ int masr_param_count(const masr_model* m);
 int masr_param_info(const masr_model* m, int idx, char* name, int name_cap, int64_t shape[4], int* ndim, int64_t* offset);
 
 /* workspace needed for a batch of B utterances x T frames with L = max(olen)+1 target positions (with a CTC head: its logits, gradient
- * operand and lattice work buffer included) */
+ * operand and lattice work buffer included; with a SpecAugment policy set: the augmented batch) */
 int64_t masr_workspace_bytes(const masr_model* m, int B, int T, int L);
 /* params/grads: fp32 [masr_param_numel]; pe: fp32 [3000][d_model] (PositionalEncoding buffer, :16-28) */
 int masr_bind(masr_model* m, float* params, float* grads, const float* pe, void* workspace, int64_t ws_bytes);
@@ -85,7 +85,7 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
  * the host's enqueue time 6x and leaves the step time unchanged -- the step is GPU-bound -- hence off by default.
  * counters: out[0] = steps launched kernel by kernel, out[1] = graphs captured, out[2] = steps replayed from a graph, out[3] = k-split GEMM
  * launches of the last step launched or captured (0 = whole reductions).  Captured graphs hold the launch geometry of the settings they were
- * captured under: masr_set_concurrency / masr_set_ksplit / masr_set_split_wgrad_launches drop them (after a device synchronisation). */
+ * captured under: masr_set_concurrency / masr_set_ksplit / masr_set_split_wgrad_launches / masr_set_specaug drop them (after a device synchronisation). */
 void masr_set_step_graphs(masr_model* m, int on);
 /* The Linear weight gradients of a step are ONE launch (the decoder-row tiles fill the CUs the encoder-row tiles leave idle); on: two
  * launches, encoder rows then decoder rows (A/B; identical bits -- each element of dW is reduced by one workgroup either way). */
@@ -116,6 +116,39 @@ const float* masr_stats_peek(masr_model* m, int64_t ticket);
 int masr_stats_wait(masr_model* m, int64_t ticket, float out[4]);
 /* device view of the last forward's logits: fp32 [rows = B*L][ld], first odim columns valid; and gold */
 int masr_last_logits(masr_model* m, const float** logits, const int32_t** gold, int* rows, int* L, int* ld);
+
+/* Extension (the reference feeds every utterance as it sits in the shard): SpecAugment (Park et al. 2019) on the training batch, inside the step
+ * (YAML asr_model.specaug).  xs fp32 [B][T][D] with raw frame lengths n_b -> out fp32 [B][T][D] in ANOTHER buffer; rows t >= n_b of
+ * out are 0.0f whatever xs holds there (the padding of xs is never read); masked cells are 0.0f (the features are mean-normalised).
+ * All draws are integers from the step's 32-bit seed: step_seed = (uint32)((seed * 0x9E3779B97F4A7C15) >> 32) + (uint32)step * 7919 (what
+ * masr_run_batch forms from masr_dropout_state for its dropout masks), key = the dropout key of (step_seed, site 0x53504147),
+ * word(b, j) = the dropout hash word of (key, b * 64 + j), uni(w, r) = (uint64(w) * r) >> 32 in [0, r).  Per utterance b of length n:
+ *   warp        only if time_warp = W > 0 and n > 2W: c = W + uni(word(b, 0), n - 2W), c' = c + uni(word(b, 1), 2W - 1) - (W - 1), so 1 <= c' <= n - 2.
+ *               Output row t reads source position i + r / den: t < c': num = t c, den = c', i = num / den; else num = (t - c')(n - 1 - c),
+ *               den = n - 1 - c', i = c + num / den; r = num % den (integer division).  r == 0: x[i], copied bit for bit; else
+ *               x[i] + (float(r) / float(den)) * (x[i + 1] - x[i]) in fp32.  Rows 0 and n - 1 stay; c' == c or no warp: a bit-exact copy.
+ *   freq masks  for i < freq_masks: f = uni(word(b, 2 + 2i), min(freq_width, freq_bins) + 1), f0 = uni(word(b, 3 + 2i), freq_bins - f + 1);
+ *               feature dims [f0, f0 + f) are zero.  Masks lie inside the first freq_bins dims (80 spares the 3 pitch dims of the 83-dim rows).
+ *   time masks  for i < time_masks: cap = min(time_width, (int)floorf(time_ratio * (float)n)) (one fp32 product), tau = uni(word(b, 18 + 2i), cap + 1),
+ *               t0 = uni(word(b, 19 + 2i), n - tau + 1); rows [t0, t0 + tau) are zero.  Masks apply after the warp.
+ * A policy with time_warp = freq_masks = time_masks = 0 is "off": a plain copy with zeroed padding.
+ * Bounds: time_warp >= 0, freq_masks in [0, 8], freq_width >= 0, freq_bins in [1, D], time_masks in [0, 8], time_width >= 0, time_ratio in [0, 1]. */
+typedef struct masr_specaug_policy {
+    int32_t time_warp, freq_masks, freq_width, freq_bins, time_masks, time_width;
+    float time_ratio;
+} masr_specaug_policy;
+/* the stateless operator: one launch on `stream`; lens_dev int32 [B] on the device (each clamped to [0, T] by the kernel).  -1 with a message for
+ * a policy out of bounds, a null pointer, out == xs, B outside [1, 65535], or T so large that T * T or T * D leaves an int. */
+int masr_specaug(const float* xs, const int32_t* lens_dev, float* out, int B, int T, int D, const masr_specaug_policy* p, uint64_t seed,
+                 uint64_t step, void* stream);
+/* the model's policy (null or an all-zero policy: off, the default).  While one is set, every masr_run_batch(MASR_TRAIN) augments its batch as
+ * its first launch -- masr_specaug at the (seed, step) masr_dropout_state reports before the call -- and both conv1's forward and conv1's weight
+ * gradient read the augmented batch; MASR_EVAL and every masr_recog* never augment.  masr_workspace_bytes grows by B * T * D floats.  The step's seed
+ * and the raw ilens travel in the per-step upload, so captured step graphs replay with the current ones.  Changing the policy drops captured step
+ * graphs; a policy out of bounds (freq_bins against the model's idim) returns -1 and leaves the old one in place. */
+int masr_set_specaug(masr_model* m, const masr_specaug_policy* p);
+/* device view of the augmented batch of the last masr_run_batch(MASR_TRAIN) under a policy: fp32 [B][T][D].  -1 if that step did not augment. */
+int masr_specaug_last(masr_model* m, const float** xa, int* B, int* T, int* D);
 
 /* nn.utils.clip_grad_norm_(parameters, max_norm) (fo_meta_interface.py:148-149,242-243): norm only */
 int masr_grad_norm(masr_model* m, void* stream);

@@ -16,6 +16,11 @@ class MasrConfig(C.Structure):
                 ("label_smoothing", C.c_float)]
 
 
+class MasrSpecaugPolicy(C.Structure):
+    _fields_ = [("time_warp", C.c_int32), ("freq_masks", C.c_int32), ("freq_width", C.c_int32), ("freq_bins", C.c_int32),
+                ("time_masks", C.c_int32), ("time_width", C.c_int32), ("time_ratio", C.c_float)]
+
+
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _SIGS = {
     "masr_version": (C.c_int, []),
@@ -43,6 +48,9 @@ _SIGS = {
     "masr_stats_peek": (C.POINTER(C.c_uint32), [vp, i64]),
     "masr_stats_wait": (i32, [vp, i64, C.POINTER(f32)]),
     "masr_last_logits": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "masr_specaug": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(MasrSpecaugPolicy), C.c_uint64, C.c_uint64, vp]),
+    "masr_set_specaug": (i32, [vp, C.POINTER(MasrSpecaugPolicy)]),
+    "masr_specaug_last": (i32, [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "masr_grad_norm": (i32, [vp, vp]),
     "masr_clip_sgd_step": (i32, [vp, vp, f32, f32, f32, i32, i32, vp]),
     "masr_clip_grads": (i32, [vp, f32, vp]),

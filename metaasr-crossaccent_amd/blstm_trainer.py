@@ -32,6 +32,8 @@ class ReduceLROnPlateau:
 
 
 def get_trainer(cls, config, paras, id2accent):
+    if config['asr_model'].get('specaug') is not None:          # SpecAugment lives in the transformer engine's training step (engine.py specaug_of)
+        raise ValueError("asr_model.specaug: transformer only")
     logger.notice("BLSTM Trainer Init...")
 
     class BLSTMTrainer(cls):

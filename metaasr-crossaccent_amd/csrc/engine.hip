@@ -82,10 +82,11 @@ void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, boo
     a.rows_e = B * a.Tp; a.rows_d = B * L;
     const int64_t re = a.rows_e, rd = a.rows_d;
     const bool hybrid = m->ctc_w > 0.f;
-    a.tok_in = ar.get<int>(3 * rd + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0)); a.gold = a.tok_in + rd; a.enc_lens = a.gold + rd;   // one block: one H2D copy per step
+    a.tok_in = ar.get<int>(3 * rd + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0) + (m->aug_on ? B : 0)); a.gold = a.tok_in + rd; a.enc_lens = a.gold + rd;   // one block: one H2D copy per step
     a.meta = reinterpret_cast<uint32_t*>(a.enc_lens + B);
     a.tok_order = a.enc_lens + B + 8; a.tok_start = a.tok_order + rd;
     a.ctc_tgt = hybrid ? a.tok_start + m->C + 1 : nullptr;
+    a.raw_lens = m->aug_on ? a.tok_start + m->C + 1 + (hybrid ? 2 * B : 0) : nullptr;
     a.step_dev = ar.get<int>(4);
     a.step_qkv = ar.get<bf16>((int64_t)B * 3 * E);
     const int64_t P1 = (int64_t)B * T * m->D, P2 = (int64_t)B * a.H2 * a.W2;
@@ -158,6 +159,19 @@ void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, boo
         a.ctc_work = ar.get<float>(mk_ctc_work_floats(a.Tp, B, a.ctc_maxS));
         a.ctc_d16 = train ? ar.get<bf16>(re * m->Cp) : nullptr;
     }
+    a.xa = (m->aug_on && ctc && train) ? ar.get<float>(P1) : nullptr;      // (last: every other offset is the policy-free plan's)
+}
+
+const char* specaug_policy_error(const masr_specaug_policy& p, int D) {
+    if (p.time_warp < 0) return "time_warp must be >= 0";
+    if (p.freq_masks < 0 || p.freq_masks > 8) return "freq_masks must lie in [0, 8]";
+    if (p.freq_width < 0) return "freq_width must be >= 0";
+    const bool off = !p.time_warp && !p.freq_masks && !p.time_masks;
+    if (!(off && p.freq_bins == 0) && (p.freq_bins < 1 || p.freq_bins > D)) return "freq_bins must lie in [1, D]";     // (an all-zero policy is "off")
+    if (p.time_masks < 0 || p.time_masks > 8) return "time_masks must lie in [0, 8]";
+    if (p.time_width < 0) return "time_width must be >= 0";
+    if (!(p.time_ratio >= 0.f && p.time_ratio <= 1.f)) return "time_ratio must lie in [0, 1]";
+    return nullptr;
 }
 
 // =========================================================================== C ABI
@@ -340,6 +354,31 @@ int masr_refresh(masr_model* m, void* stream) {
     // gathered cross-attention K/V operand) in ONE launch; the pads of the char_trans shadows are zeroed once in masr_bind
     for (const ShadowJobs& J : m->shadows) CK(mk_all_shadows(m->P, J, s));
     return 0;
+}
+
+int masr_set_specaug(masr_model* m, const masr_specaug_policy* p) {
+    masr_specaug_policy q{};
+    if (p) q = *p;
+    if (const char* bad = specaug_policy_error(q, m->D)) { mk_set_error("masr_set_specaug", bad); return -1; }
+    const bool on = q.time_warp > 0 || q.freq_masks > 0 || q.time_masks > 0;
+    if (on != m->aug_on || (on && memcmp(&q, &m->aug, sizeof q))) drop_step_graphs(m);       // (the policy is a kernel argument of the captured launch)
+    if (on != m->aug_on) m->aug_ran = false;                                                  // the next plan differs: the upload block and the batch buffer
+    m->aug = q; m->aug_on = on;
+    return 0;
+}
+int masr_specaug_last(masr_model* m, const float** xa, int* B, int* T, int* D) {
+    if (!m->have_acts || !m->aug_ran || !m->acts.xa) { mk_set_error("masr_specaug_last", "the last step did not augment (no policy, MASR_EVAL, or no step yet)"); return -1; }
+    *xa = m->acts.xa; *B = m->acts.B; *T = m->acts.T; *D = m->acts.D;
+    return 0;
+}
+int masr_specaug(const float* xs, const int32_t* lens_dev, float* out, int B, int T, int D, const masr_specaug_policy* p, uint64_t seed, uint64_t step,
+                 void* stream) {
+    if (!xs || !lens_dev || !out || !p) { mk_set_error("masr_specaug", "null pointer"); return -1; }
+    if (out == xs) { mk_set_error("masr_specaug", "out must be another buffer than xs (the warp reads neighbouring rows)"); return -1; }
+    if (B < 1 || B > 65535 || T < 1 || D < 1) { mk_set_error("masr_specaug", "need 1 <= B <= 65535, T >= 1, D >= 1"); return -1; }
+    if ((int64_t)T * T > INT32_MAX || (int64_t)T * D > INT32_MAX) { mk_set_error("masr_specaug", "T * T and T * D must fit an int"); return -1; }
+    if (const char* bad = specaug_policy_error(*p, D)) { mk_set_error("masr_specaug", bad); return -1; }
+    return mk_specaug(xs, lens_dev, out, B, T, D, *p, step_seed_of(seed, step), nullptr, (hipStream_t)stream);
 }
 
 void masr_set_step_graphs(masr_model* m, int on) { m->step_graphs_on = on != 0; }

@@ -54,6 +54,9 @@ struct Acts {
     // CTC gradient as the bf16 operand of the head's backward [rows_e][Cp] (training only), per-utterance nll [B], the lattice's work buffer,
     // and the targets' offsets | lengths into `gold` [2][B] (behind tok_start, in the same upload)
     float *ctc_logits = nullptr, *ctc_nll = nullptr, *ctc_work = nullptr; bf16* ctc_d16 = nullptr; int* ctc_tgt = nullptr; int ctc_maxS = 0;
+    // SpecAugment (masr_set_specaug; null otherwise): the raw frame lengths [B] at the end of the tok_in upload (enc_lens is ilens / 4), and the
+    // augmented batch [B][T][D] that conv1's forward and conv1's weight gradient read instead of xs (training plans only)
+    int* raw_lens = nullptr; float* xa = nullptr;
 };
 
 // The captured launch sequence of ONE decode step, replayed once per step (recog.hip run_steps).  key / key_ptr: what it was captured
@@ -95,6 +98,8 @@ struct masr_model {
     float* h_ring = nullptr; hipEvent_t ring_ev[RING]; bool ring_used[RING]; int64_t ring_next = 0;
     int* h_stage = nullptr; int64_t stage_ints = 0; int stage_slot = 0; hipEvent_t stage_ev[4];
     uint64_t seed = 0x1234; uint64_t step = 0;
+    masr_specaug_policy aug{}; bool aug_on = false;        // masr_set_specaug
+    bool aug_ran = false;                                  // the last masr_run_batch left its augmented batch in acts.xa (masr_specaug_last)
     Acts acts; bool have_acts = false;
     LnReduceGroup lng; int64_t ln_slab_used = 0;           // LayerNorm dgamma/dbeta partials, folded by one grouped launch
     bool split_wgrad = false;                              // masr_set_split_wgrad_launches
@@ -146,6 +151,11 @@ inline GemmArgs lin_fwd_args(const bf16* x, long ldx, const bf16* wk, int M, int
     return g;
 }
 
+// the 32-bit seed of one step: what every dropout mask and SpecAugment draw of the step is hashed from (masr_run_batch, masr_specaug)
+inline uint32_t step_seed_of(uint64_t seed, uint64_t step) { return (uint32_t)(seed * 0x9E3779B97F4A7C15ull >> 32) + (uint32_t)step * 7919u; }
+// host check of a policy against the batch geometry it will run on; null, or what is wrong (engine.hip)
+const char* specaug_policy_error(const masr_specaug_policy& p, int D);
+
 // seed_ptr / inv_ptr: non-null while a step is being captured into a graph -- the dropout seed and 1/n_total of the step
 // then live in device memory (Acts::meta, uploaded with the tokens), so one captured launch sequence serves every step
 struct Ctx { masr_model* m; hipStream_t s; uint32_t seed; bool train; float p_drop, p_pos; const uint32_t* seed_ptr = nullptr; const float* inv_ptr = nullptr; };
@@ -167,7 +177,8 @@ inline int ln_fwd(Ctx& c, const Norm& n, const float* x, float* y32, bf16* y16, 
     return mk_layernorm_fwd(x, m->P + n.w, m->P + n.b, y32, y16, mean, rstd, rows, m->E, c.s);
 }
 
-// engine.hip.  ctc: the joint objective's branch (hybrid models; masr_run_batch only -- the decoders do not plan it)
+// engine.hip.  ctc: the branches of masr_run_batch alone, which the decoders do not plan -- the joint objective's (hybrid models) and
+// SpecAugment's batch
 void plan_acts(const masr_model* m, Arena& ar, Acts& a, int B, int T, int L, bool train, bool ctc = false);
 // train.hip: the forward pass over m->acts (the decoders run the encoder, the K|V projection and, masr_recog_full, the decoder too)
 int forward_encoder(Ctx& c, const float* xs);

@@ -345,6 +345,11 @@ int mk_vgg2enc_grad_unpermute(const float* g_nhwc, float* dw, int E, int C, int 
 // ---------------------------------------------------------------- data (data.hip)
 // ragged gather + zero pad: rows of feat [sum T_i][D] -> xs [B][Tmax][D]
 int mk_gather_pad(const float* feat, const long* row_start, const int* lens, float* xs, int B, int Tmax, int D, hipStream_t s);
+// SpecAugment of xs [B][T][D] into out (another buffer) with the raw frame lengths lens [B] (device); rows >= lens[b] of out are zero.
+// p: include/masr.h masr_specaug_policy, vetted by the caller; seed / seed_ptr: the step's seed, as every dropout kernel takes it
+struct masr_specaug_policy;
+int mk_specaug(const float* xs, const int* lens, float* out, int B, int T, int D, const masr_specaug_policy& p, uint32_t seed,
+               const uint32_t* seed_ptr, hipStream_t s);
 
 // ---------------------------------------------------------------- bidirectional LSTM (lstm.hip) -- BLSTM-P encoder of the CTC config
 // rows are batch-first (b*T + t); the gate axis is unit-major (u*4 + g, g in torch order i,f,g,o); index [2] = direction

@@ -438,8 +438,10 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
     Acts& a = m->acts; m->have_acts = true;
     const bool hybrid = m->ctc_w > 0.f;
     if (hybrid && 2 * maxo + 1 > 2048) { mk_set_error("masr_run_batch", "CTC objective: labels longer than 1023 tokens"); return -1; }
-    // tok_in | gold | enc_lens | meta | tok_order | tok_start (| CTC target offsets | lengths)
-    const int64_t stage_n = (int64_t)3 * B * L + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0);
+    const bool aug = train && m->aug_on;                           // SpecAugment: training steps under a policy (masr_set_specaug)
+    if (aug && ((int64_t)T * T > INT32_MAX || (int64_t)T * m->D > INT32_MAX || B > 65535)) { mk_set_error("masr_run_batch", "SpecAugment: T * T and T * idim must fit an int, B <= 65535"); return -1; }
+    // tok_in | gold | enc_lens | meta | tok_order | tok_start (| CTC target offsets | lengths) (| raw ilens)
+    const int64_t stage_n = (int64_t)3 * B * L + B + 8 + m->C + 1 + (hybrid ? 2 * B : 0) + (m->aug_on ? B : 0);
     if (stage_n > m->stage_ints) {
         // the pinned staging ring grows with the batch (B * L) and the vocabulary (C): drain the copies in flight, then re-allocate
         for (auto& ev : m->stage_ev) HIP_CHECK_RET(hipEventSynchronize(ev));
@@ -470,7 +472,7 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
         h_len[b] = (int)(ilens[b] / 4);                             // enc_lens = floor(ilens/4) (:117)
         if (h_len[b] < 1 || ilens[b] > T) { mk_set_error("masr_run_batch", "ilens must be in [4, T]"); return -1; }
     }
-    Ctx c{m, s, (uint32_t)(m->seed * 0x9E3779B97F4A7C15ull >> 32) + (uint32_t)m->step * 7919u, train,
+    Ctx c{m, s, step_seed_of(m->seed, m->step), train,
           train ? m->cfg.dropout : 0.f, train ? m->cfg.pos_dropout : 0.f};
     m->step++;
     const float inv_ntot = 1.0f / (float)ntot;
@@ -488,21 +490,34 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
             int* h_ctc = h_start + V + 1;
             for (int b = 0; b < B; ++b) { h_ctc[b] = b * L; h_ctc[B + b] = (int)olens[b]; }
         }
+        if (m->aug_on) {
+            // the raw frame lengths, behind everything else: SpecAugment draws its centres and masks inside [0, ilens) (enc_lens is ilens / 4)
+            int* h_raw = h_start + V + 1 + (hybrid ? 2 * B : 0);
+            for (int b = 0; b < B; ++b) h_raw[b] = (int)ilens[b];
+        }
     }
     HIP_CHECK_RET(hipMemcpyAsync(a.tok_in, h, sizeof(int) * (size_t)stage_n, hipMemcpyHostToDevice, s));   // tok_in | gold | enc_lens | meta | tok_order | tok_start
     HIP_CHECK_RET(hipEventRecord(m->stage_ev[slot], s));
 
     auto run = [&](Ctx& cc) -> int {
         m->n_ksplit = 0;
-        CK(forward_encoder(cc, xs));
+        // under a policy the step's first launch augments the batch; conv1's forward AND conv1's weight gradient (backward) read the result
+        const float* x_in = xs;
+        if (aug) {
+            Prof p(m, MASR_PROF_MISC, s);
+            CK(mk_specaug(xs, a.raw_lens, a.xa, B, T, a.D, m->aug, cc.seed, cc.seed_ptr, s));
+            x_in = a.xa;
+        }
+        CK(forward_encoder(cc, x_in));
         CK(forward_decoder(cc));
         { Prof p(m, MASR_PROF_MISC, s);
           CK(mk_ls_ce(a.logits, m->Cp, a.gold, a.rows_d, m->C, m->cfg.label_smoothing, inv_ntot, a.dlogits, a.row_loss, a.row_correct,
                       m->stats, s, cc.inv_ptr, 1.f - m->ctc_w)); }
         if (hybrid) CK(ctc_forward(cc));
-        if (train) CK(backward(cc, xs));
+        if (train) CK(backward(cc, x_in));
         return 0;
     };
+    m->aug_ran = aug;
     // ---- a batch shape seen twice in a row is captured once and replayed from then on (everything that changes from step to
     // step -- tokens, lengths, dropout seed, 1/n_total -- reaches the kernels through the upload above)
     const bool graphs_on = m->step_graphs_on;

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, check, check_beam_args, check_lm_args, lib, nbest_lists
+from ._cabi import MasrConfig, MasrSpecaugPolicy, check, check_beam_args, check_lm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -26,6 +26,67 @@ def ctc_weight_of(model_para: dict) -> float:
     if not 0.0 <= w < 1.0:
         raise ValueError(f"asr_model.ctc_weight must lie in [0, 1), got {w}")
     return w
+
+
+SPECAUG_KEYS = ("time_warp", "freq_masks", "freq_width", "freq_bins", "time_masks", "time_width", "time_ratio")
+
+
+def _specaug_policy(policy, idim: int, what: str = "asr_model.specaug"):
+    """a SpecAugment policy dict (None: off) -> the complete validated dict, or None when it augments nothing.  Absent keys are 0, freq_bins
+    idim.  The bounds are include/masr.h masr_specaug_policy's; a ValueError names the key."""
+    if policy is None:
+        return None
+    if not isinstance(policy, dict):
+        raise ValueError(f"{what} must be a mapping of {', '.join(SPECAUG_KEYS)}, got {type(policy).__name__}")
+    unknown = sorted(set(policy) - set(SPECAUG_KEYS))
+    if unknown:
+        raise ValueError(f"{what}: unknown key {unknown[0]} (known: {', '.join(SPECAUG_KEYS)})")
+    out = {}
+    for k in SPECAUG_KEYS[:-1]:
+        v = policy.get(k, idim if k == "freq_bins" else 0)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}.{k} must be an integer, got {v!r}")
+        out[k] = int(v)
+    r = policy.get("time_ratio", 0.0)
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not 0.0 <= float(r) <= 1.0:
+        raise ValueError(f"{what}.time_ratio must lie in [0, 1], got {r!r}")
+    out["time_ratio"] = float(r)
+    for k in ("time_warp", "freq_width", "time_width"):
+        if out[k] < 0 or out[k] >= 2 ** 31:
+            raise ValueError(f"{what}.{k} must be >= 0, got {out[k]}")
+    for k in ("freq_masks", "time_masks"):
+        if not 0 <= out[k] <= 8:
+            raise ValueError(f"{what}.{k} must lie in [0, 8], got {out[k]}")
+    if not 1 <= out["freq_bins"] <= idim:
+        raise ValueError(f"{what}.freq_bins must lie in [1, idim = {idim}], got {out['freq_bins']}")
+    if out["time_warp"] == 0 and out["freq_masks"] == 0 and out["time_masks"] == 0:
+        return None
+    return out
+
+
+def specaug_of(model_para: dict):
+    """asr_model.specaug (absent or null = off), validated: the policy dict that MasrEngine hands to masr_set_specaug, or None"""
+    return _specaug_policy(model_para.get('specaug'), int(model_para["idim"]))
+
+
+def _policy_struct(policy):
+    return MasrSpecaugPolicy(*[policy[k] for k in SPECAUG_KEYS])
+
+
+def specaug(xs: torch.Tensor, ilens, policy, seed: int, step: int) -> torch.Tensor:
+    """the stateless operator (include/masr.h masr_specaug): SpecAugment of the device batch xs fp32 [B, T, D] with raw frame lengths ilens
+    under `policy` (a dict of SPECAUG_KEYS; absent keys 0, freq_bins D) at the dropout position (seed, step) -> a new tensor.  What an engine with
+    this policy feeds its encoder in the training step it runs from dropout_state() == (seed, step)."""
+    if not xs.is_cuda:
+        raise RuntimeError("specaug needs a device tensor; there is no CPU path")
+    xs = xs.contiguous().float()
+    B, T, D = xs.shape
+    pol = _specaug_policy(policy or {}, D, "policy") or {**dict.fromkeys(SPECAUG_KEYS, 0), "freq_bins": D}
+    lens = torch.as_tensor(ilens, dtype=torch.int32).reshape(B).to(xs.device)
+    out = torch.empty_like(xs)
+    check(lib().masr_specaug(_ptr(xs), _ptr(lens), _ptr(out), B, T, D, C.byref(_policy_struct(pol)), C.c_uint64(seed & (2 ** 64 - 1)),
+                             C.c_uint64(step & (2 ** 64 - 1)), C.c_void_p(torch.cuda.current_stream(xs.device).cuda_stream)), "masr_specaug")
+    return out
 
 
 def sinusoid_pe(max_len: int, E: int) -> torch.Tensor:
@@ -85,6 +146,7 @@ class MasrEngine:
         self.model_para = model_para
         self.odim = odim
         self.ctc_weight = ctc_weight_of(model_para)      # joint CTC/attention objective: loss = (1 - w) CE + w CTC (include/masr.h masr_create_ctc)
+        policy = specaug_of(model_para)                  # SpecAugment inside the training step (include/masr.h masr_set_specaug; None = off)
         self.cfg = MasrConfig(
             idim=model_para["idim"], odim=odim, d_model=model_para["d_model"], nheads=model_para["nheads"],
             d_inner=model_para["d_inner"], enc_layers=model_para["encoder"]["nlayers"],
@@ -110,6 +172,8 @@ class MasrEngine:
             self.table[name.value.decode()] = (int(off.value), tuple(int(shape[k]) for k in range(ndim.value)))
         self.ws = None
         self._ws_key = (0, 0, 0)
+        self.specaug = None
+        self.set_specaug(policy)                         # (before the first bind: the plan holds the augmented batch)
         self._ensure_ws(1, 64, 8)
         self._dirty = True
 
@@ -188,6 +252,20 @@ class MasrEngine:
     def set_concurrency(self, slots: int):
         """this engine is one of `slots` task slots sharing the GPU (include/masr.h masr_set_concurrency)"""
         self._l.masr_set_concurrency(self.h, int(slots))
+
+    def set_specaug(self, policy):
+        """SpecAugment policy of the training steps (include/masr.h masr_set_specaug): a dict of SPECAUG_KEYS as asr_model.specaug, or None = off.
+        Evaluation and every recog* never augment.  The next run_batch re-sizes the workspace for the augmented batch."""
+        pol = _specaug_policy(policy, self.cfg.idim)
+        check(self._l.masr_set_specaug(self.h, C.byref(_policy_struct(pol)) if pol else None), "masr_set_specaug")
+        self.specaug = pol
+
+    def specaug_last(self):
+        """[B, T, idim] fp32 view (into the workspace) of the augmented batch the last training run_batch fed the encoder"""
+        xp, B, T, D = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
+        check(self._l.masr_specaug_last(self.h, C.byref(xp), C.byref(B), C.byref(T), C.byref(D)), "masr_specaug_last")
+        lo, n = xp.value - self.ws.data_ptr(), B.value * T.value * D.value
+        return self.ws[lo:lo + n * 4].view(torch.float32).view(B.value, T.value, D.value)
 
     def dropout_state(self):
         """(seed, batches run since set_seed): the position of the dropout mask stream (include/masr.h masr_dropout_state)"""
