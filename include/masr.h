@@ -349,6 +349,17 @@ int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, in
 int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
                            float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream);
 
+/* CTC forced alignment of each utterance's transcript on the CTC head (hybrid models of masr_create_ctc): the encoder and the head
+ * GEMM of masr_recog_ctc_beam, then masr_ctc_align (below) on the head's fp32 logits with blank 0, Tp = T / 4 and enc_len = floor(ilens[b] / 4)
+ * -- frames, start and end count ENCODER frames, one per 4 input frames.  ys_flat / olens are host int64 as masr_run_batch takes them: the
+ * tokens of all utterances one after the other, without sos / eos, olens[b] of them for utterance b.  A length or token the operator refuses
+ * on the device (below) is passed on and refused there: that utterance's score is NaN.  Result (device): frames int32 [B][T/4], start / end int32
+ * [B][maxL], score fp32 [B].  -1 with a message, before any launch: a null model or pointer, a model without a CTC head, B < 1, T < 4,
+ * maxL < 0 or 2 * maxL + 1 > 2048, ilens outside [4, T], B * (maxL + 2) above the model's staging buffer (65536 ints, more once a training batch has grown it); -2: a workspace below masr_ctc_align_workspace_bytes(B, T, maxL). */
+int64_t masr_ctc_align_workspace_bytes(const masr_model* m, int B, int T, int maxL);
+int masr_recog_ctc_align(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, const int64_t* ys_flat, const int64_t* olens, int maxL,
+                         int32_t* frames, int32_t* start, int32_t* end, float* score, void* stream);
+
 /* Attention rescoring of an N-best list (hybrid models of masr_create_ctc; the two-pass decode WeNet calls "attention
  * rescoring").  For utterance b and list entry n with tokens h (length l >= 0, no sos / eos) and first-pass score c(b, n):
  *   decoder input  [sos, h_0 .. h_{l-1}] padded with eos, targets [h_0 .. h_{l-1}, eos] padded with -1; L = 1 + the longest live l of the
@@ -519,6 +530,34 @@ int64_t masr_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K);
 int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                             const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
                             float* scores, float* am, void* stream);
+
+/* CTC forced alignment: the single best alignment (Viterbi path) of a known transcript to the frames of a CTC output layer, model-free like
+ * masr_ctc_loss and masr_ctc_beam_search.  logits and enc_lens as for masr_ctc_beam_search (row of utterance b, frame t at
+ * logits + (b * Tp + t) * ld, ld >= C; enc_lens device int32 [B], each clamped to [0, Tp]; frames past it and columns >= C are never read);
+ * targets as for masr_ctc_loss (device int32: utterance b's tokens are targets[tgt_off[b] .. + tgt_len[b])).  With n = enc_len, L = tgt_len,
+ * S = 2L + 1 and label(s) = blank for even s, y[(s - 1) / 2] for odd s:
+ *   emissions  u_t(c) = fl(z_t(c) - max_t), max_t the maximum of the row's C classes (exact, whatever the order): one fp32 subtraction.  The path
+ *              is decided on these raw, max-shifted logits, not on log_softmax: the normaliser is the same for every state of a frame and
+ *              cannot change an arg-max, and without it the path is a function of fp32 additions and comparisons only -- no exp / log.
+ *   start      v_0(0) = u_0(blank), v_0(1) = u_0(y[0]) if L > 0, every other state -inf.
+ *   recursion  v_t(s) = fl(m + u_t(label(s))), m the largest of v_{t-1}(s) (back-pointer 0), v_{t-1}(s - 1) (1; s >= 1) and v_{t-1}(s - 2)
+ *              (2; s odd, s >= 3, label(s) != label(s - 2)).  A tie goes to the smaller back-pointer.  m = -inf: the state is -inf, back-pointer 0.
+ *   end        the final state is S - 1, or S - 2 if L > 0 and v_{n-1}(S - 2) > v_{n-1}(S - 1) (a tie: S - 1); the back-pointers are walked from it.
+ *   score      the path's log-probability under the frame-wise softmax: acc = 0.f; for t = 0 .. n - 1 in this order acc = fl(acc + lsum_t), with
+ *              lsum_t = log(sum_c exp(u_t(c))) in fp32 (strided sum of __expf over the lanes of one wave, wave sum, __logf); then
+ *              score = fl(v_{n-1}(final) - acc).
+ * Result (device): frames int32 [B][Tp] -- at t < n the target index i in [0, L) while the path is in state 2i + 1, -1 in a blank state, and -2 at
+ * t >= n; start / end int32 [B][maxL] -- the first frame of token i and one past its last, -1 for i >= L (every token of a feasible alignment
+ * has end > start); score fp32 [B].  L = 0 gives the all-blank path, n = 0 with L = 0 score 0.  Infeasible (both final states -inf: n below L
+ * plus the number of adjacent equal tokens, or n = 0 with L > 0): score -inf, frames -2 throughout, start / end -1.  Refused on the device, the
+ * targets being device arrays (tgt_len < 0 or > maxL, a token outside [0, C) or equal to blank): score NaN, the rest as for infeasible; no
+ * status word, no synchronisation.  Non-finite logits give an unspecified path, but no access outside the arrays.
+ * -1 (text in masr_last_error()), before any launch, unless B >= 1, Tp >= 1, 2 <= C <= 4096, ld >= C, 0 <= blank < C, maxL >= 0,
+ * 2 * maxL + 1 <= 2048 (the lattice width of masr_ctc_loss), work_bytes >= masr_ctc_align_work_bytes(B, Tp, maxL), and no pointer is null. */
+int64_t masr_ctc_align_work_bytes(int B, int Tp, int maxL);
+int masr_ctc_align(const float* logits, int64_t ld, const int32_t* enc_lens, const int32_t* targets, const int32_t* tgt_off, const int32_t* tgt_len,
+                   int B, int Tp, int C, int blank, int maxL, void* work, int64_t work_bytes, int32_t* frames, int32_t* start, int32_t* end,
+                   float* score, void* stream);
 
 /* device timing (HIP events on the launch stream) for bench.py's roofline block: one slot per conv launch of the VGG
  * front-end (each is ONE launch per step, so slot time / launches = that kernel's average duration) and one per kernel

@@ -165,6 +165,14 @@ int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
  * head's fp32 logits (row of utterance b, frame t at logits + (b * (T / 4) + t) * ld, C = odim valid columns) and enc_lens int32 [B].
  * Valid until the next call that uses the workspace. */
 int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens);
+/* the same for the last masr_recog_ctc_align call with this B, T, maxL: the inputs of its masr_ctc_align */
+int masr_test_ctc_align_logits(masr_model* m, int B, int T, int maxL, float** logits, int64_t* ld, int32_t** enc_lens);
+/* include/masr.h's masr_ctc_align, with its arguments and refusals, whose sweep ends behind the score: no back-trace, and frames / start / end of a
+ * feasible utterance are left as they were.  For tools/bench_ctc_align.py: the difference to the whole call is what the back-trace and the
+ * start / end pass cost. */
+int masr_test_ctc_align_no_trace(const float* logits, int64_t ld, const int32_t* enc_lens, const int32_t* targets, const int32_t* tgt_off,
+                                 const int32_t* tgt_len, int B, int Tp, int C, int blank, int maxL, void* work, int64_t work_bytes, int32_t* frames,
+                                 int32_t* start, int32_t* end, float* score, void* stream);
 /* ---- attention rescoring (rescore.hip; tests/test_hip_rescore_kernels.py, tests/test_hip_rescore.py)
  * the score kernel alone (mk_rescore_score): logits fp32 [R*L][ld] (C <= ld valid columns), gold int32 [R*L] (-1 = no term; >= C is read as
  * no term) -> att fp32 [R] = the sum over l ascending of log_softmax(logits[r*L + l])[gold], -inf where a hypothesis has no term; row_lp fp32

@@ -89,6 +89,8 @@ _SIGS = {
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "masr_recog_ctc_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+    "masr_ctc_align_workspace_bytes": (i64, [vp, i32, i32, i32]),
+    "masr_recog_ctc_align": (i32, [vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "masr_rescore_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
     "masr_recog_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_recog_rescore_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
@@ -121,6 +123,8 @@ _SIGS = {
     "masr_ctc_beam_search": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "masr_ctc_beam_lm_work_bytes": (i64, [i32, i32, i32, i32]),
     "masr_ctc_beam_search_lm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
+    "masr_ctc_align_work_bytes": (i64, [i32, i32, i32]),
+    "masr_ctc_align": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_profile_enable": (i32, [vp, i32]),
     "masr_profile_read": (i32, [vp, C.POINTER(f32), C.POINTER(i32)]),
     "masr_test_blstm_stall": (None, [vp, i32]),          # include/masr_test.h from here on
@@ -132,6 +136,8 @@ _SIGS = {
     "masr_test_skinny_gemm": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "masr_test_ctc_prefix": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "masr_test_ctc_beam_logits": (i32, [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp)]),
+    "masr_test_ctc_align_logits": (i32, [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp)]),
+    "masr_test_ctc_align_no_trace": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_test_rescore_score": (i32, [vp, i64, vp, i32, i32, i32, vp, vp, vp]),
     "masr_test_rescore_select": (i32, [vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_rescore_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]),
@@ -214,6 +220,51 @@ def nbest_lists(tok, lens, scores, *more):
     tok, lens, *vals = (t.cpu() for t in (tok, lens, scores, *more))
     return [[(tok[b, i, :int(lens[b, i])].tolist(), *[float(v[b, i]) for v in vals]) for i in range(lens.size(1)) if int(lens[b, i]) >= 0]
             for b in range(lens.size(0))]
+
+
+def align_lists(frames, start, end, score, ys, olens):
+    """device results of masr_ctc_align (frames [B][Tp], start / end [B][maxL], score [B] torch tensors) and the targets (per-utterance token
+    lists, lengths) -> per utterance (score, [(token, start, end), ...], frames list without the -2 tail); an infeasible or refused utterance
+    has no segments and no frames"""
+    frames, start, end, score = (t.cpu().tolist() for t in (frames, start, end, score))
+    out = []
+    for b, L in enumerate(olens):
+        segs = list(zip(map(int, ys[b][:int(L)]), start[b], end[b])) if math.isfinite(score[b]) else []
+        out.append((score[b], segs, [f for f in frames[b] if f != -2]))
+    return out
+
+
+def align_outputs(B, Tp, maxL, device):
+    """device outputs of masr_ctc_align -> ((frames int32 [B, Tp], start int32 [B, maxL], end int32 [B, maxL], score fp32 [B]), their four
+    pointers for the call).  An empty tensor's data_ptr() is null, which the operator refuses, so start and end are views of backing tensors
+    of at least one element and the pointers are the backings': with maxL = 0 the views are [B, 0] and the pointers still point somewhere."""
+    import torch
+    i32 = dict(dtype=torch.int32, device=device)
+    backing = [torch.empty(max(B * maxL, 1), **i32) for _ in range(2)]
+    frames, score = torch.empty(B, Tp, **i32), torch.empty(B, dtype=torch.float32, device=device)
+    st, en = (t[:B * maxL].view(B, maxL) for t in backing)
+    return (frames, st, en, score), [C.c_void_p(t.data_ptr()) for t in (frames, *backing, score)]
+
+
+def check_target_lengths(ys, olens):
+    """what both engines' ctc_align vet on the Python side: one transcript per length, none shorter than its length says"""
+    if len(ys) != len(olens):
+        raise ValueError(f"ctc_align needs one transcript per utterance, got {len(ys)} for {len(olens)} lengths")
+    for b, (y, n) in enumerate(zip(ys, olens)):
+        if int(n) > len(y):
+            raise ValueError(f"olens[{b}] = {int(n)} but ys[{b}] holds {len(y)} tokens")
+
+
+def align_targets(ys, olens, device):
+    """the device arrays masr_ctc_align takes for per-utterance token lists, each cut to its olens[b] (ValueError where it is shorter than
+    that): (targets int32 [sum], tgt_off int32 [B], tgt_len int32 [B], maxL)"""
+    import torch
+    ol = [int(n) for n in olens]
+    check_target_lengths(ys, ol)
+    flat = [int(t) for y, n in zip(ys, ol) for t in list(y)[:max(n, 0)]]
+    off = [sum(max(n, 0) for n in ol[:b]) for b in range(len(ol))]
+    i32 = dict(dtype=torch.int32, device=device)
+    return torch.tensor(flat or [0], **i32), torch.tensor(off, **i32), torch.tensor(ol, **i32), max(ol + [0])
 
 
 nbest_lists_lm = nbest_lists                                   # (the name the LM-fused searches' callers know)

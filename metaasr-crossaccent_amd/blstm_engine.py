@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import check, check_beam_args, check_lm_args, lib, nbest_lists
+from ._cabi import align_lists, align_outputs, align_targets, check, check_beam_args, check_lm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -163,6 +163,26 @@ class BlstmEngine:
                                    self._beam_work.numel(), *map(_ptr, out), self.stream()), fn)
         return nbest_lists(*out)
 
+    def ctc_align(self, xs, ilens, ys, olens, blank=0, raw=False):
+        """CTC forced alignment of each utterance's transcript to the head's output (masr_ctc_align): the forward with its check,
+        then the alignment on last_logits() with a work tensor of this engine's own.  ys: per-utterance token lists without sos / eos, olens
+        their lengths.  Returns per utterance (score, [(token, start, end), ...], frames list) in ENCODER frames (4 input frames each); an
+        infeasible utterance has score -inf and empty lists (raw: the device tensors frames, start, end, score instead)."""
+        logits, lens = self.forward(xs, ilens)                 # (runs masr_blstm_check)
+        B, Tp, Cc = logits.shape
+        ys = [[int(t) for t in torch.as_tensor(y).reshape(-1).tolist()] for y in ys]
+        ol = [int(n) for n in torch.as_tensor(olens).reshape(-1).tolist()]
+        tgt, off, tl, maxL = align_targets(ys, ol, self.device)
+        need = int(self._l.masr_ctc_align_work_bytes(B, Tp, maxL))
+        check(need if need < 0 else 0, "masr_ctc_align_work_bytes")
+        if getattr(self, "_align_work", None) is None or self._align_work.numel() < need:
+            self._align_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out, ptrs = align_outputs(B, Tp, maxL, self.device)
+        check(self._l.masr_ctc_align(_ptr(logits), Cc, _ptr(lens), _ptr(tgt), _ptr(off), _ptr(tl), B, Tp, Cc, int(blank), maxL, _ptr(self._align_work),
+                                     self._align_work.numel(), *ptrs, self.stream()), "masr_ctc_align")
+        self._align_targets = (tgt, off, tl)                   # alive until the stream has read them
+        return out if raw else align_lists(*out, ys, ol)
+
     def set_resident_recurrence(self, on: bool):
         """the LSTM recurrence as one launch per layer and pass (include/masr.h masr_blstm_set_resident_recurrence); default on"""
         self._l.masr_blstm_set_resident_recurrence(self.h, int(bool(on)))
@@ -272,6 +292,15 @@ class MonoBLSTM:
         for b, n in enumerate(torch.as_tensor(ilens).tolist()):
             out += self.engine.ctc_beam(xs_pad[b:b + 1, :int(n)], [int(n)], beam_size, nbest, blank=self.blank_id, lm=lm, lm_w=lm_weight,
                                         len_bonus=len_bonus)
+        return out
+
+    def ctc_align(self, xs_pad, ilens, ys, olens):
+        """CTC forced alignment of each utterance's transcript on the head (BlstmEngine.ctc_align): per utterance
+        (score, [(token, start, end), ...], frames list) in encoder frames.  Each utterance is run alone, cut to its own length, for the
+        reason ctc_beam_decode gives: alone, its alignment is a function of the utterance, whatever the batch."""
+        out = []
+        for b, n in enumerate(torch.as_tensor(ilens).tolist()):
+            out += self.engine.ctc_align(xs_pad[b:b + 1, :int(n)], [int(n)], [ys[b]], [int(torch.as_tensor(olens)[b])], blank=self.blank_id)
         return out
 
     def train(self):

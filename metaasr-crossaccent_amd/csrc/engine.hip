@@ -538,6 +538,13 @@ int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_
     return mk_ctc_beam_search_lm(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, work, work_bytes, tokens, lens, scores,
                                  am, (hipStream_t)stream);
 }
+int64_t masr_ctc_align_work_bytes(int B, int Tp, int maxL) { return mk_ctc_align_work_bytes(B, Tp, maxL); }
+int masr_ctc_align(const float* logits, int64_t ld, const int32_t* enc_lens, const int32_t* targets, const int32_t* tgt_off, const int32_t* tgt_len,
+                   int B, int Tp, int C, int blank, int maxL, void* work, int64_t work_bytes, int32_t* frames, int32_t* start, int32_t* end,
+                   float* score, void* stream) {
+    return mk_ctc_align(logits, (long)ld, enc_lens, targets, tgt_off, tgt_len, B, Tp, C, blank, maxL, work, work_bytes, frames, start, end, score,
+                        (hipStream_t)stream);
+}
 
 int masr_profile_enable(masr_model* m, int on) {
     m->prof = on != 0;

@@ -227,6 +227,14 @@ int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int
                           const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int* tokens, int* lens, float* scores,
                           float* am, hipStream_t s);
 
+// ---------------------------------------------------------------- CTC forced alignment (ctc_align.hip)
+// the best alignment of each utterance's transcript (targets[tgt_off[b] .. + tgt_len[b]), device arrays as mk_ctc_loss takes them) to its
+// frames: frames int32 [B][Tp] (token index, -1 = blank, -2 past enc_len), start / end int32 [B][maxL] (-1 behind tgt_len), score fp32 [B].
+// trace false (the benchmark, through masr_test_ctc_align_no_trace): only score is written, for feasible utterances the rest is left as it was
+int64_t mk_ctc_align_work_bytes(int B, int Tp, int maxL);
+int mk_ctc_align(const float* logits, long ld, const int* enc_lens, const int* targets, const int* tgt_off, const int* tgt_len, int B, int Tp, int C,
+                 int blank, int maxL, void* work, int64_t work_bytes, int* frames, int* start, int* end, float* score, hipStream_t s, bool trace = true);
+
 // ---------------------------------------------------------------- attention rescoring of an N-best list (rescore.hip)
 // tok [R][ld_tok], lens [R] (-1 = no entry; a live one is <= L - 1) -> the decoder's tok_in [R][L] = [sos, h.., eos ..] and gold [R][L] =
 // [h.., eos, -1 ..]; an entry without a list: all eos / all -1

@@ -2,7 +2,8 @@
 // literal whole-prefix re-decode, the KV-cached greedy decode, the attention beam and the joint CTC/attention beam.  Each of the
 // last three captures the launch sequence of ONE step into a hipGraph of its own and replays it once per step (run_steps).  Behind them
 // the two decoders without steps: the CTC prefix beam on the head alone, and attention rescoring of its N-best (one teacher-forced
-// decoder pass) -- each also with the n-gram LM fused into the prefix beam.
+// decoder pass) -- each also with the n-gram LM fused into the prefix beam -- and the forced alignment of a known
+// transcript on the head.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -151,11 +152,14 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
 //   of up to Lmax tokens behind their sos; with a first pass (K > 0) the CTC-only beam's buffers and its N-best list follow, then the
 //   second pass's scores
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; };
+//   CTC forced alignment (masr_recog_ctc_align, AL = maxL >= 0): one decoder position per utterance; the head's logits, the targets
+//   [B*maxL] with their offsets [B] and lengths [B], and the alignment's work buffer follow
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; int AL = -1; };
 struct DecodeBufs {
     BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
     float* lm_fused;                                                    // LM fusion: the rows' fused increments [R][Cp]
     int *rs_tok, *rs_lens; float *rs_ctc, *rs_att, *rs_row_lp;          // rescoring: first-pass list [B][N][Tp] / [B][N] / [B][N], att [B*N], row terms [B*N*(Lmax+1)]
+    int* al_tgt;                                                        // alignment: targets [B*maxL], then tgt_off [B], then tgt_len [B]
 };
 
 static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
@@ -192,6 +196,14 @@ static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, i
     o.work = ar.get<char>(o.work_bytes);
     return o;
 }
+static DecodeBufs plan_ctc_align(const masr_model* m, Arena& ar, int B, int Tp, int maxL) {
+    DecodeBufs o{};
+    o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
+    o.al_tgt = ar.get<int>((int64_t)B * maxL + 2 * B);
+    o.work_bytes = mk_ctc_align_work_bytes(B, Tp, maxL);
+    o.work = ar.get<char>(o.work_bytes);
+    return o;
+}
 static DecodeBufs plan_rescore(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
     DecodeBufs o{};
     const int64_t R = (int64_t)B * d.N;
@@ -207,13 +219,17 @@ static DecodeBufs plan_decode(const masr_model* m, Arena& ar, Acts& a, int B, in
         plan_acts(m, ar, a, B, T, d.N * (d.Lmax + 1), false);
         return plan_rescore(m, ar, B, T / 4, d);
     }
+    if (d.AL >= 0) {
+        plan_acts(m, ar, a, B, T, 1, false);
+        return plan_ctc_align(m, ar, B, T / 4, d.AL);
+    }
     plan_acts(m, ar, a, B, T, d.ctc_only ? 1 : d.K ? d.K * d.Lmax : Ldec, false);
     return d.ctc_only ? plan_ctc_beam(m, ar, B, T / 4, d.K) : d.K ? plan_beam(m, ar, B, T / 4, d) : DecodeBufs{};
 }
 // a decoder's workspace size; args_ok: B, T and the spec are in range (else the error `need`)
 static int64_t decode_workspace_bytes(const char* fn, const masr_model* m, bool args_ok, const char* need, int B, int T, const DecodeSpec& d) {
     if (!m || !args_ok) { mk_set_error(fn, need); return -1; }
-    if (d.P || d.ctc_only || d.N) CK(check_ctc_head(fn, m));
+    if (d.P || d.ctc_only || d.N || d.AL >= 0) CK(check_ctc_head(fn, m));
     Arena ar{nullptr, 0, 0};
     Acts a;
     plan_decode(m, ar, a, B, T, 0, d);
@@ -243,7 +259,8 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
     const DecodeBufs planned = plan_decode(m, ar, m->acts, B, T, Ldec, d);
     if (bufs) *bufs = planned;
     if (ar.off > m->ws_bytes) {
-        mk_set_error("masr_recog", d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
+        mk_set_error("masr_recog", d.AL >= 0 ? "workspace too small (masr_ctc_align_workspace_bytes(B, T, maxL))"
+                                   : d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
                                    : d.NB ? "workspace too small (masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax))"
@@ -588,6 +605,68 @@ int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits
     Acts a;
     const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, DecodeSpec{K, 0, 0, true});
     if (ar.off > m->ws_bytes) return fail(fn, "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))");
+    *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
+    return 0;
+}
+
+static bool align_shape_ok(int B, int T, int maxL) { return B > 0 && T >= 4 && maxL >= 0 && 2 * (int64_t)maxL + 1 <= 2048; }
+
+int64_t masr_ctc_align_workspace_bytes(const masr_model* m, int B, int T, int maxL) {
+    DecodeSpec d; d.AL = maxL;
+    return decode_workspace_bytes("masr_ctc_align_workspace_bytes", m, align_shape_ok(B, T, maxL), "need B >= 1, T >= 4, maxL >= 0 and 2 * maxL + 1 <= 2048", B,
+                                  T, d);
+}
+
+int masr_recog_ctc_align(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, const int64_t* ys_flat, const int64_t* olens, int maxL,
+                         int32_t* frames, int32_t* start, int32_t* end, float* score, void* stream) {
+    // forced alignment of each utterance's transcript on the CTC head (ctc_align.hip): the encoder pass and the head GEMM of
+    // masr_recog_ctc_beam, then masr_ctc_align with blank 0.  Lengths and tokens the operator refuses on the device are passed on as they
+    // are (clamped into int32): the refusal is the operator's.
+    const char* fn = "masr_recog_ctc_align";
+    CK(check_model(fn, m));
+    CK(check_ctc_head(fn, m));
+    if (!xs || !ilens || !olens || !frames || !start || !end || !score) return fail(fn, "null pointer");
+    if (!align_shape_ok(B, T, maxL)) return fail(fn, "need B >= 1, T >= 4, maxL >= 0 and 2 * maxL + 1 <= 2048");
+    int64_t total = 0;                                      // tokens uploaded: those of the utterances whose length is in range
+    for (int b = 0; b < B; ++b) if (olens[b] > 0 && olens[b] <= maxL) total += olens[b];
+    if (total > 0 && !ys_flat) return fail(fn, "null pointer");
+    if ((int64_t)B * maxL + 2 * B > m->stage_ints) return fail(fn, ("B * (maxL + 2) exceeds the staging buffer (" + std::to_string(m->stage_ints) + " ints)").c_str());
+    hipStream_t s = (hipStream_t)stream;
+    DecodeBufs bufs;
+    int Ldec = 0;
+    DecodeSpec d; d.AL = maxL;
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, d, &bufs); if (rc) return rc; }
+    const auto i32 = [](int64_t v) { return (int)std::max<int64_t>(std::min<int64_t>(v, INT32_MAX), INT32_MIN); };
+    int* tgt = bufs.al_tgt; int* off = tgt + (int64_t)B * maxL; int* len = off + B;
+    CK(stage_upload(m, tgt, B * maxL + 2 * B, s, [&](int* h) {
+        // ys_flat holds olens[b] tokens per utterance with olens[b] > 0, whatever the operator will make of that length
+        int64_t src = 0; int dst = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = olens[b];
+            h[B * maxL + b] = dst; h[B * maxL + B + b] = i32(n);
+            if (n > 0 && n <= maxL) for (int64_t i = 0; i < n; ++i) h[dst++] = i32(ys_flat[src + i]);
+            if (n > 0) src += n;
+        }
+        for (; dst < B * maxL; ++dst) h[dst] = 0;
+    }));
+    Ctx c{m, s, 0u, false, 0.f, 0.f};
+    CK(ctc_head_logits(c, bufs.ctc_logits));
+    CK(mk_ctc_align(bufs.ctc_logits, m->Cp, m->acts.enc_lens, tgt, off, len, B, T / 4, m->C, 0, maxL, bufs.work, bufs.work_bytes, frames, start, end, score, s));
+    m->have_acts = false;
+    return 0;
+}
+
+int masr_test_ctc_align_logits(masr_model* m, int B, int T, int maxL, float** logits, int64_t* ld, int32_t** enc_lens) {
+    // where masr_recog_ctc_align(m, .., B, T, .., maxL, ..) put the head's logits and enc_lens in the bound workspace: the same plan, run again
+    const char* fn = "masr_test_ctc_align_logits";
+    if (!m || !m->P || !logits || !ld || !enc_lens) return fail(fn, "null pointer or model not bound");
+    CK(check_ctc_head(fn, m));
+    if (!align_shape_ok(B, T, maxL)) return fail(fn, "need B >= 1, T >= 4, maxL >= 0 and 2 * maxL + 1 <= 2048");
+    Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    Acts a;
+    DecodeSpec d; d.AL = maxL;
+    const DecodeBufs bufs = plan_decode(m, ar, a, B, T, 0, d);
+    if (ar.off > m->ws_bytes) return fail(fn, "workspace too small (masr_ctc_align_workspace_bytes(B, T, maxL))");
     *logits = bufs.ctc_logits; *ld = m->Cp; *enc_lens = a.enc_lens;
     return 0;
 }

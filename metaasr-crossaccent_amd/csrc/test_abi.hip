@@ -127,6 +127,12 @@ int masr_test_ctc_prefix_lm(const float* lp, int C, int T, int last, const float
     return test_ctc_prefix("masr_test_ctc_prefix_lm", lp, C, T, last, parent, psi_par, score, cand, att_lp, pre_lm, n, att_w, ctc_w, len_bonus, list_tok,
                            list_score, list_psi, list_slot, out_state, stream);
 }
+int masr_test_ctc_align_no_trace(const float* logits, int64_t ld, const int32_t* enc_lens, const int32_t* targets, const int32_t* tgt_off,
+                                 const int32_t* tgt_len, int B, int Tp, int C, int blank, int maxL, void* work, int64_t work_bytes, int32_t* frames,
+                                 int32_t* start, int32_t* end, float* score, void* stream) {
+    return mk_ctc_align(logits, (long)ld, enc_lens, targets, tgt_off, tgt_len, B, Tp, C, blank, maxL, work, work_bytes, frames, start, end, score,
+                        (hipStream_t)stream, false);
+}
 int masr_test_attn_decode(const uint16_t* q, int64_t ldq, const uint16_t* k, const uint16_t* v, int64_t ldk, int64_t kv_batch_stride,
                           const uint16_t* knew, const uint16_t* vnew, int64_t ldnew, const int32_t* step, const int32_t* klens, uint16_t* o,
                           int64_t ldo, int B, int H, int hd, int Tk_cap, int rows_per_utt, const int32_t* src, int64_t ld_src, int64_t src_flip,

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, MasrSpecaugPolicy, check, check_beam_args, check_lm_args, lib, nbest_lists
+from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -437,6 +437,27 @@ class MasrEngine:
         self._last_x = xs
         return out if raw else nbest_lists(*out)
 
+    def ctc_align(self, xs: torch.Tensor, ilens, ys, olens, raw: bool = False):
+        """CTC forced alignment of each utterance's transcript on the CTC head (masr_recog_ctc_align; needs a hybrid model): one
+        encoder pass, the head GEMM, one Viterbi sweep over the T/4 frames.  ys: per-utterance token lists / tensors without sos / eos, olens
+        their lengths.  Returns per utterance (score, [(token, start, end), ...], frames list), start / end / frames in ENCODER frames (4 input
+        frames each); an infeasible utterance has score -inf and empty lists (raw: the device tensors frames [B, T // 4], start / end
+        [B, maxL], score [B] instead)."""
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        ol = torch.as_tensor(olens, dtype=torch.int64).cpu().contiguous()
+        ys = [torch.as_tensor(y, dtype=torch.int64).reshape(-1) for y in ys]
+        check_target_lengths(ys, ol.tolist())
+        # each transcript cut to its olens[b] (a row of a padded tensor may be longer): the library reads olens[b] tokens per utterance
+        ys = [y[:max(int(n), 0)] for y, n in zip(ys, ol.tolist())]
+        yf = torch.cat(ys + [torch.zeros(1, dtype=torch.int64)]).contiguous()      # (never empty: the pointer is never null)
+        maxL = max(int(ol.max()), 0)
+        self._decode_ws("masr_ctc_align_workspace_bytes", B, T, maxL)
+        out, ptrs = align_outputs(B, T // 4, maxL, self.device)
+        check(self._l.masr_recog_ctc_align(self.h, _ptr(xs), _ptr(il), B, T, _ptr(yf), _ptr(ol), maxL, *ptrs, self.stream()),
+              "masr_recog_ctc_align")
+        self._last_x = xs
+        return out if raw else align_lists(*out, [y.tolist() for y in ys], ol.tolist())
+
     @staticmethod
     def _rescore_weights(att_w, ctc_w):
         att_w, ctc_w = float(att_w), float(ctc_w)
@@ -519,6 +540,15 @@ class MasrEngine:
         into the workspace: (head logits fp32 [B, T // 4, ld], enc_lens int32 [B])"""
         lp, ep, ld = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(self._l.masr_test_ctc_beam_logits(self.h, B, T, K, C.byref(lp), C.byref(ld), C.byref(ep)), "masr_test_ctc_beam_logits")
+        base, n = self.ws.data_ptr(), B * (T // 4) * ld.value * 4
+        logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
+        return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)
+
+    def last_ctc_align_logits(self, B, T, maxL):
+        """test hook (include/masr_test.h masr_test_ctc_align_logits): what the last ctc_align of this (B, T, maxL) aligned to, as views into
+        the workspace: (head logits fp32 [B, T // 4, ld], enc_lens int32 [B])"""
+        lp, ep, ld = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._l.masr_test_ctc_align_logits(self.h, B, T, maxL, C.byref(lp), C.byref(ld), C.byref(ep)), "masr_test_ctc_align_logits")
         base, n = self.ws.data_ptr(), B * (T // 4) * ld.value * 4
         logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
         return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)

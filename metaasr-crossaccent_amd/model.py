@@ -135,6 +135,12 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_ctc_beam(xs_pad, ilens, beam_size, nbest)
 
+    def ctc_align(self, xs_pad, ilens, ys, olens):
+        """CTC forced alignment of each utterance's transcript on the CTC head (masr_recog_ctc_align, hybrid models only): per utterance
+        (score, [(token, start, end), ...], frames list) in encoder frames (4 input frames each)"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.ctc_align(xs_pad, ilens, ys, olens)
+
     def lm_ctc_beam_decode(self, xs_pad, ilens, beam_size, lm, lm_weight=0.3, len_bonus=0.0, nbest=1):
         """CTC prefix beam search with the n-gram LM `lm` and a per-token bonus fused in (masr_recog_ctc_beam_lm, hybrid models only): per
         utterance a list of at most nbest (token list, fused score, acoustic score), best first"""

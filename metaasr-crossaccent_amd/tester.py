@@ -30,6 +30,13 @@ anything is decoded.  Tester.MODES is the table of them:
                  the step ratios as for `beam`, with ctc_w > 0 required (absent or 0: ValueError, that search is `lm_beam`); lm_w (0.3),
                  len_bonus (0, finite, any sign), nbest (1, in [1, beam_size]).  No path or a BLSTM raises NotImplementedError, a
                  transformer without a CTC head ValueError.
+  ctc_align      masr_recog_ctc_align (BLSTM-CTC: masr_ctc_align per utterance), the CTC forced alignment of DESIGN 5.9: no search, so no
+                 solver.beam_decode block is read.  Each test utterance's REFERENCE transcript is aligned to the frames of the CTC output
+                 layer, and one line per utterance is appended to `<decode_dir>/ctc-ali` (no best-hyp is written):
+                 "<ref ids> TAB <start:end of each token, space separated> TAB <repr of the path's log-probability as a Python float>",
+                 start and end (one past the last) in ENCODER frames -- one encoder frame is 4 input frames on both models.  An utterance
+                 with too few frames for its transcript gets an empty middle field and -inf.  `--resume` counts the lines of ctc-ali.
+                 Needs a CTC output layer (a transformer without one: ValueError).
 The LM modes build the LM once per Tester and (path, <s> id, </s> id)."""
 import math
 from pathlib import Path
@@ -66,7 +73,7 @@ class Tester:
             self.decode_dir.mkdir(parents=True)
             self.prev_decode_step = -1
         else:
-            with open(Path(self.decode_dir, 'best-hyp')) as f:
+            with open(Path(self.decode_dir, 'ctc-ali' if self.decode_mode == 'ctc_align' else 'best-hyp')) as f:
                 self.prev_decode_step = sum(1 for _ in f)
 
     def load_data(self):
@@ -121,12 +128,22 @@ class Tester:
             self.write_hyp(y.tolist(), self.trim(pred.tolist()))
         return True
 
-    def write_hyp(self, y, hyp):
-        if getattr(self, '_skip_lines', 0) > 0:                  # utterance already in best-hyp (resumed inside a batch)
+    def _append(self, name, *fields):
+        if getattr(self, '_skip_lines', 0) > 0:                  # utterance already in the file (resumed inside a batch)
             self._skip_lines -= 1
             return
-        with open(Path(self.decode_dir, 'best-hyp'), 'a') as fout:
-            fout.write("{}\t{}\n".format(" ".join(str(i) for i in y), " ".join(str(i) for i in hyp)))
+        with open(Path(self.decode_dir, name), 'a') as fout:
+            fout.write("\t".join(fields) + "\n")
+
+    def write_hyp(self, y, hyp):
+        self._append('best-hyp', " ".join(str(i) for i in y), " ".join(str(i) for i in hyp))
+
+    def batch_ctc_align(self, xs, ilens, ys, olens):
+        """ctc-ali: the reference transcript, each token's start:end in encoder frames, the path's log-probability"""
+        ys = [y[:int(n)] for y, n in zip(ys, olens)]
+        for y, (score, segs, _) in zip(ys, self.asr_model.ctc_align(xs, ilens, ys, olens)):
+            self._append('ctc-ali', " ".join(str(i) for i in y.tolist()), " ".join(f"{st}:{en}" for _, st, en in segs), repr(float(score)))
+        return True
 
     # ------------------------------------------------------------------ settings: what the modes' vetting shares
     def _beam_size(self):
@@ -222,6 +239,10 @@ class Tester:
         if self.model_name != 'blstm':
             self._need_ctc_head('ctc_beam', "beam or greedy")
 
+    def _ctc_align_settings(self):
+        if self.model_name != 'blstm':
+            self._need_ctc_head('ctc_align', "greedy or beam to decode instead")
+
     def _rescore_settings(self):
         if self.model_name == 'blstm':
             raise NotImplementedError("rescore: attention rescoring needs the transformer's decoder, the BLSTM has none; "
@@ -284,7 +305,8 @@ class Tester:
         return self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
 
     # mode -> (its settings function, (Tester, xs, ilens) -> the best hypothesis of each utterance, Tester -> what the start-up line names);
-    # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself
+    # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself; nor has ctc_align, which reads the
+    # references too and writes ctc-ali (batch_ctc_align)
     MODES = {
         'greedy': (None, None, lambda t: "greedy decoding"),
         'beam': (_beam_settings,
@@ -306,6 +328,7 @@ class Tester:
                        lambda t, xs, il: [n[0][0] for n in t.asr_model.lm_rescore_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest,
                                                                                          t.att_weight, t.ctc_weight)],
                        lambda t: f"attention rescoring of the LM-fused CTC beam (beam {t.beam_size})"),
+        'ctc_align': (_ctc_align_settings, None, lambda t: "CTC forced alignment of the reference transcripts"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
                               xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],
@@ -332,7 +355,9 @@ class Tester:
                 continue
             self._skip_lines = done - seen if seen < done else 0
             xs, ilens, ys, olens = self.eval_set.materialize(idxs)
-            if best_hyps is None:
+            if self.decode_mode == 'ctc_align':
+                self.batch_ctc_align(xs, ilens, ys, olens)
+            elif best_hyps is None:
                 self.batch_greedy_decode(xs, ilens, ys, olens)
             else:
                 for hyp, y in zip(best_hyps(self, xs, ilens), ys):
