@@ -29,6 +29,11 @@ int masr_test_attention_dropout(const uint16_t* q, const uint16_t* k, const uint
 /* the NT GEMM with any combination of its fused epilogue stages (tools/bench_gemm_epi.py: what each stage costs per launch) */
 int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, const float* bias, int relu,
                        float drop_p, const float* residual, const uint16_t* mask, float* C32, uint16_t* C16, void* stream);
+/* ... with the two stages the entry above does not pass: the positional encoding pe fp32 [pe_period][N] added to row m as pe[m % pe_period]
+ * (null: none; the vgg2enc launch: bias + pe, fp32 and bf16 output) and accumulation into the fp32 output (C32 += result; the memory gradient
+ * summed over decoder layers); C32 with row pitch ldc and/or C16 with row pitch ldc16 */
+int masr_test_gemm_pe_acc(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, const float* bias,
+                          const float* pe, int pe_period, int accumulate, float* C32, int64_t ldc, uint16_t* C16, int64_t ldc16, void* stream);
 /* the decode's few-row GEMM (decode.hip skinny_gemm_kernel, the launch of every decoder Linear of masr_recog / masr_recog_beam):
  * C[M][N] = epi(A[M][K] W[N][K]^T) with bias, ReLU, fp32 residual [M][N], fp32 and/or bf16 output (tools/bench_beam.py: against the NT GEMM) */
 int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,

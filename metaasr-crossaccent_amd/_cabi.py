@@ -133,6 +133,7 @@ _SIGS = {
     "masr_test_gemm_dropout": (i32, [vp, i64, vp, i64, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp, i64, vp]),
     "masr_test_attention_dropout": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_gemm_epi": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp]),
+    "masr_test_gemm_pe_acc": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, i64, vp, i64, vp]),
     "masr_test_skinny_gemm": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "masr_test_ctc_prefix": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "masr_test_ctc_beam_logits": (i32, [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp)]),

@@ -90,6 +90,13 @@ __device__ __forceinline__ void dropout_scale4(uint32_t seed, uint32_t site, uin
     s[0] = (a & 0xFFFFu) < thr ? 0.0f : inv_keep; s[1] = (a >> 16) < thr ? 0.0f : inv_keep;
     s[2] = (b & 0xFFFFu) < thr ? 0.0f : inv_keep; s[3] = (b >> 16) < thr ? 0.0f : inv_keep;
 }
+// ... for a caller that KNOWS idx0 is even and keeps key = dropout_key(seed, site), thr = dropout_thr(p) over its loop: the two hash words and
+// nothing else (left to the compiler, the odd branch above is if-converted: a third word and two funnel shifts per call whatever the parity)
+__device__ __forceinline__ void dropout_scale4_even(uint32_t key, uint32_t thr, uint32_t idx0, float inv_keep, float (&s)[4]) {
+    const uint32_t p0 = idx0 >> 1, a = dropout_word(key, p0), b = dropout_word(key, p0 + 1);
+    s[0] = (a & 0xFFFFu) < thr ? 0.0f : inv_keep; s[1] = (a >> 16) < thr ? 0.0f : inv_keep;
+    s[2] = (b & 0xFFFFu) < thr ? 0.0f : inv_keep; s[3] = (b >> 16) < thr ? 0.0f : inv_keep;
+}
 
 #define HIP_CHECK_RET(expr)                                                        \
     do {                                                                           \

@@ -124,6 +124,186 @@ __device__ __forceinline__ long crow(const GemmArgs& g, int m) {
 enum { E_BIAS = 1, E_PE = 2, E_RELU = 4, E_MASK = 8, E_DROP = 16, E_RES = 32, E_ACC = 64, E_C32 = 128, E_C16 = 256 };
 #define HAS(flag, runtime) (EPI >= 0 ? bool(EPI & (flag)) : bool(runtime))
 
+// ---- the strips of one staged tile: optional inputs, arithmetic, stores (see gemm_epilogue)
+// FAST: an interior tile of a launch whose every stream takes the vector path (decided per workgroup from launch-uniform values, see
+// epi_fast): no bounds tests, no scalar fall-backs, one scalar base per stream (the tile's corner) and 32-bit element offsets inside the tile
+// that advance by a scalar row step per strip.  Otherwise the tile takes the general path: any edge, any alignment, 64-bit addresses.
+// DROP: 0 = no dropout, 1 = dropout with even element indices only (N even: two hash words per four outputs), -1 = decided at run time.
+// The arithmetic is the same in every form, zero signs included.  With its stage switched off, a specialised (EPI >= 0) epilogue used to
+// add a literal 0.f in its place; those adds turn a -0 (a dropped negative value) into +0 and cannot be folded.  Residual and accumulate
+// are never both on in a specialised epilogue, and then everything those adds do to the result is done by ONE `+ 0.f` at the point of
+// the residual add: a stage that is off before it changes at most the sign of a zero that reaches it.
+template <int BM, int BN, int EPI, int NT, bool FAST, int DROP>
+__device__ __forceinline__ void epi_strips(const GemmArgs& g, const float* ct, const int m0, const int n0, const long out_delta) {
+    // Every product rounds before the add behind it.  Without the pragma the specialised forms may fuse x * keep-scale + residual into one
+    // fma (one rounding instead of two): bias + dropout + residual would then differ from the general form, from the run-time form and
+    // from tests/test_hip_gemm_epilogue_exact.py in the last bit.
+#pragma clang fp contract(off)
+    static_assert(!FAST || (EPI >= 0 && DROP >= 0), "the fast path is for specialised epilogues");
+    // (residual AND accumulate run as the run-time form: with both on nothing adds a literal zero behind the dropout, so the single `+ 0.f`
+    // below would not stand for the adds of the stages that are off in front of it)
+    static_assert(EPI < 0 || !((EPI & E_RES) && (EPI & E_ACC)), "no specialised epilogue has residual and accumulate");
+    constexpr int LDC = BN + 4;
+    // A thread owns strips of SW columns.  The epilogue is bound by the NUMBER of vector-memory wave-instructions (one
+    // texture addresser per CU, ~70 cycles each whatever their width), so epilogues with 16-bit streams (bf16 output, ReLU
+    // mask) use 8-column strips = 16 bytes per lane; pure fp32 epilogues keep 4 columns (same instruction count, fewer LDS
+    // bank conflicts on the staged tile).  All optional inputs of a thread's strips are fetched BEFORE the first store:
+    // a load after a store may alias it as far as the compiler knows, so a load-compute-store loop pays one full memory
+    // round trip per strip (8 to 16 per tile; the masked dgrad GEMMs ran 3x longer than their unmasked twins).  Strips are
+    // therefore handled in batches of four: loads of the batch, then its arithmetic and stores.
+    constexpr int SW = (EPI >= 0 && (EPI & (E_C16 | E_MASK))) ? 8 : 4;
+    constexpr int CS = BN / SW, NCH = BM * CS / NT, RS = NT / CS;       // strip i of a thread is RS rows below strip i - 1
+    static_assert(NCH >= 1, "tile too small for this many threads");
+    static_assert(NT % CS == 0, "a thread's strips must share their columns");
+    const int tid = threadIdx.x, row0 = tid / CS, cs = (tid % CS) * SW, n = n0 + cs;
+    if (!FAST && n >= g.N) return;
+    const bool f_bias = HAS(E_BIAS, g.bias), f_pe = HAS(E_PE, g.pe), f_relu = HAS(E_RELU, g.relu), f_mask = HAS(E_MASK, g.mask);
+    const bool f_drop = DROP >= 0 ? DROP > 0 : (HAS(E_DROP, g.drop_p > 0.f) && g.drop_p > 0.f);
+    const bool f_res = HAS(E_RES, g.residual);
+    const bool f_acc = HAS(E_ACC, g.accumulate), f_c32 = HAS(E_C32, g.C32), f_c16 = HAS(E_C16, g.C16);
+    const int nv = FAST ? SW : (g.N - n < SW ? g.N - n : SW);   // valid columns of this thread's strip
+    const float inv_keep = f_drop ? 1.0f / (1.0f - g.drop_p) : 1.0f;
+    const uint32_t seed = (f_drop && g.seed_ptr) ? *g.seed_ptr : g.seed;
+    const uint32_t dkey = dropout_key(seed, g.site), dthr = dropout_thr(g.drop_p);
+    // dropout index m N + n of strip 0 (mod 2^32: what the cut 64-bit product gives), N RS further per strip
+    const uint32_t didx = (uint32_t)(m0 + row0) * (uint32_t)g.N + (uint32_t)n, dstep = (uint32_t)RS * (uint32_t)g.N;
+    auto ldf = [](const float* p, float (&o)[SW]) {
+#pragma unroll
+        for (int h = 0; h < SW / 4; ++h) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * h);
+            o[4 * h] = t[0]; o[4 * h + 1] = t[1]; o[4 * h + 2] = t[2]; o[4 * h + 3] = t[3];
+        }
+    };
+    float bv[SW];
+    if (FAST) { if (f_bias) ldf(g.bias + n, bv); }
+    else {
+#pragma unroll
+        for (int e = 0; e < SW; ++e) bv[e] = (f_bias && e < nv) ? g.bias[n + e] : 0.f;
+    }
+    // vector paths need a full strip and aligned rows (n is a multiple of SW by construction)
+    constexpr int A16 = SW - 1;                                  // bf16 strip = SW * 2 bytes: leading dimension multiple of SW
+    const bool v_c32 = FAST || (nv == SW && f_c32 && !((g.ldc | out_delta | g.cseg_stride) & 3) && !((uintptr_t)g.C32 & 15));
+    const bool v_res = FAST || (nv == SW && f_res && !(g.ldres & 3) && !((uintptr_t)g.residual & 15));
+    const bool v_c16 = FAST || (nv == SW && f_c16 && !(g.ldc16 & A16) && !((uintptr_t)g.C16 & (2 * SW - 1)));
+    const bool v_msk = FAST || (nv == SW && f_mask && !(g.ldmask & A16) && !((uintptr_t)g.mask & (2 * SW - 1)));
+    const bool v_pe = FAST || (nv == SW && f_pe && !(g.N & 3) && !((uintptr_t)g.pe & 15));
+    // FAST: row pitches fit 22 bits (epi_fast), so an element offset inside the tile fits 32
+    const float* const res_b = FAST && f_res ? g.residual + (long)m0 * g.ldres + n0 : nullptr;
+    const bf16* const msk_b = FAST && f_mask ? g.mask + (long)m0 * g.ldmask + n0 : nullptr;
+    float* const c32_b = FAST && f_c32 ? g.C32 + out_delta + crow(g, m0) + n0 : nullptr;   // (a tile never straddles two row segments)
+    bf16* const c16_b = FAST && f_c16 ? g.C16 + (long)m0 * g.ldc16 + n0 : nullptr;
+    const unsigned ur = (unsigned)row0, uc = (unsigned)cs;
+    const unsigned res_o = ur * (unsigned)g.ldres + uc, res_s = RS * (unsigned)g.ldres;
+    const unsigned msk_o = ur * (unsigned)g.ldmask + uc, msk_s = RS * (unsigned)g.ldmask;
+    const unsigned c32_o = ur * (unsigned)g.ldc + uc, c32_s = RS * (unsigned)g.ldc;
+    const unsigned c16_o = ur * (unsigned)g.ldc16 + uc, c16_s = RS * (unsigned)g.ldc16;
+    // strips are handled NB at a time (the batch's inputs must fit the registers the accumulators just vacated)
+    constexpr int NB = NCH < 4 ? NCH : 4;
+#pragma unroll
+    for (int i0 = 0; i0 < NCH; i0 += NB) {
+    // ---- phase 1: every optional input of the batch
+    float rs[NB][SW], old[NB][SW], pev[NB][SW], mk[NB][SW];
+#pragma unroll
+    for (int ii = 0; ii < NB; ++ii) {
+        const int i = ii, row = row0 + (i0 + ii) * RS, m = m0 + row;
+        const unsigned si = (unsigned)(i0 + ii);
+        if (!FAST) {
+#pragma unroll
+            for (int e = 0; e < SW; ++e) { rs[i][e] = 0.f; old[i][e] = 0.f; pev[i][e] = 0.f; mk[i][e] = 1.f; }
+            if (m >= g.M) continue;
+        }
+        if (f_res) {
+            const float* p = FAST ? res_b + (res_o + si * res_s) : g.residual + (long)m * g.ldres + n;
+            if (v_res) ldf(p, rs[i]);
+            else { for (int e = 0; e < nv; ++e) rs[i][e] = p[e]; }
+        }
+        if (f_pe) {
+            const float* p = g.pe + (long)(m % g.pe_period) * g.N + n;
+            if (v_pe) ldf(p, pev[i]);
+            else { for (int e = 0; e < nv; ++e) pev[i][e] = p[e]; }
+        }
+        if (f_mask) {
+            const bf16* p = FAST ? msk_b + (msk_o + si * msk_s) : g.mask + (long)m * g.ldmask + n;
+            if (v_msk) {
+                if constexpr (SW == 8) { const bf16x8 t = ld8(p); for (int e = 0; e < 8; ++e) mk[i][e] = (float)t[e]; }
+                else { const bf16x4 t = *reinterpret_cast<const bf16x4*>(p); for (int e = 0; e < 4; ++e) mk[i][e] = (float)t[e]; }
+            } else { for (int e = 0; e < nv; ++e) mk[i][e] = (float)p[e]; }
+        }
+        if (f_c32 && f_acc) {
+            const float* c32 = FAST ? c32_b + (c32_o + si * c32_s) : g.C32 + out_delta + crow(g, m) + n;
+            if (v_c32) ldf(c32, old[i]);
+            else { for (int e = 0; e < nv; ++e) old[i][e] = c32[e]; }
+        }
+    }
+    // ---- phase 2: arithmetic and stores
+#pragma unroll
+    for (int ii = 0; ii < NB; ++ii) {
+        const int i = ii, row = row0 + (i0 + ii) * RS, m = m0 + row;
+        const unsigned si = (unsigned)(i0 + ii);
+        if (!FAST && m >= g.M) continue;
+        float v[SW];
+        ldf(ct + row * LDC + cs, v);
+        float ks[SW];                                             // dropout keep-scales of the SW consecutive elements: one hash word per pair
+#pragma unroll
+        for (int h = 0; h < SW / 4; ++h) {
+            float k4[4] = {1.f, 1.f, 1.f, 1.f};
+            if (f_drop) {
+                if constexpr (DROP == 1) dropout_scale4_even(dkey, dthr, didx + si * dstep + 4 * h, inv_keep, k4);
+                else dropout_scale4(seed, g.site, didx + si * dstep + 4 * h, g.drop_p, inv_keep, k4);
+            }
+            ks[4 * h] = k4[0]; ks[4 * h + 1] = k4[1]; ks[4 * h + 2] = k4[2]; ks[4 * h + 3] = k4[3];
+        }
+#pragma unroll
+        for (int e = 0; e < SW; ++e) {
+            float x;
+            if constexpr (EPI < 0) x = v[e] + bv[e] + pev[i][e];
+            else {
+                x = v[e];
+                if (f_bias) x += bv[e];
+                if (f_pe) x += pev[i][e];
+            }
+            if (f_relu) x = fmaxf(x, 0.f);
+            if (f_mask) x = mk[i][e] > 0.f ? x * g.mask_scale : 0.f;
+            if (f_drop) x *= ks[e];
+            if constexpr (EPI < 0) v[e] = x + rs[i][e] + old[i][e];
+            else if constexpr (bool(EPI & E_RES)) v[e] = x + rs[i][e] + 0.f;
+            else if constexpr (bool(EPI & E_ACC)) v[e] = x + 0.f + old[i][e];
+            else v[e] = x + 0.f;
+        }
+        if (f_c32) {
+            float* c32 = FAST ? c32_b + (c32_o + si * c32_s) : g.C32 + out_delta + crow(g, m) + n;
+            if (v_c32) {
+#pragma unroll
+                for (int h = 0; h < SW / 4; ++h) *reinterpret_cast<f32x4*>(c32 + 4 * h) = f32x4{v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
+            } else { for (int e = 0; e < nv; ++e) c32[e] = v[e]; }
+        }
+        if (f_c16) {
+            bf16* p = FAST ? c16_b + (c16_o + si * c16_s) : g.C16 + (long)m * g.ldc16 + n;
+            if (v_c16) {
+                if constexpr (SW == 8) { bf16x8 t; for (int e = 0; e < 8; ++e) t[e] = (bf16)v[e]; st8(p, t); }
+                else { bf16x4 t; for (int e = 0; e < 4; ++e) t[e] = (bf16)v[e]; *reinterpret_cast<bf16x4*>(p) = t; }
+            } else { for (int e = 0; e < nv; ++e) p[e] = (bf16)v[e]; }
+        }
+    }
+    }
+}
+// whether the tile at (m0, n0) may take epi_strips' FAST path.  Everything here is uniform over the workgroup, and all but the two tile
+// bounds over the launch: full tile, every stream of the epilogue aligned for its vector access, row pitches that keep the offsets inside
+// a tile within 32 bits
+template <int BM, int BN, int EPI>
+__device__ __forceinline__ bool epi_fast(const GemmArgs& g, const int m0, const int n0, const long out_delta) {
+    constexpr int SW = (EPI & (E_C16 | E_MASK)) ? 8 : 4, A16 = SW - 1;
+    constexpr long PMAX = 1L << 22;                               // 128 rows x 2^22 elements x 4 bytes = 2^31
+    bool ok = m0 + BM <= g.M && n0 + BN <= g.N;
+    if (EPI & E_BIAS) ok = ok && !((uintptr_t)g.bias & 15);
+    if (EPI & E_C32) ok = ok && !((g.ldc | out_delta | g.cseg_stride) & 3) && !((uintptr_t)g.C32 & 15) && g.ldc >= 0 && g.ldc < PMAX;
+    if (EPI & E_RES) ok = ok && !(g.ldres & 3) && !((uintptr_t)g.residual & 15) && g.ldres >= 0 && g.ldres < PMAX;
+    if (EPI & E_C16) ok = ok && !(g.ldc16 & A16) && !((uintptr_t)g.C16 & (2 * SW - 1)) && g.ldc16 >= 0 && g.ldc16 < PMAX;
+    if (EPI & E_MASK) ok = ok && !(g.ldmask & A16) && !((uintptr_t)g.mask & (2 * SW - 1)) && g.ldmask >= 0 && g.ldmask < PMAX;
+    if (EPI & E_PE) ok = ok && !(g.N & 3) && !((uintptr_t)g.pe & 15);
+    return ok;
+}
+
 // ---- shared epilogue (see the comment inside): consumes the accumulators of one BM x BN tile
 // NT = threads that take part (512: the loader waves of gemm_ring_kernel store strips too; they hold no accumulators: has_acc false)
 template <int BM, int BN, int EPI, int NT = 256>
@@ -140,123 +320,32 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[BM
     // branches around loads serialise on s_waitcnt vmcnt(0) and used to dominate the small decoder GEMMs).
     float* ct = reinterpret_cast<float*>(smem);
     if (has_acc) {
+        const float alpha = g.alpha;
+        if (alpha != 1.f) {                                      // (a uniform branch: every Linear of the training step passes 1, and x * 1 = x)
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < FN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[i][j][r] *= alpha;
+        }
+        float* w = ct + (wm * WM + (lane >> 4) * 4) * LDC + wn * WN + (lane & 15);
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int j = 0; j < FN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    ct[(wm * WM + i * 16 + (lane >> 4) * 4 + r) * LDC + wn * WN + j * 16 + (lane & 15)] = acc[i][j][r] * g.alpha;
+                for (int r = 0; r < 4; ++r) w[(i * 16 + r) * LDC + j * 16] = acc[i][j][r];
     }
     __syncthreads();
-    // A thread owns strips of SW columns.  The epilogue is bound by the NUMBER of vector-memory wave-instructions (one
-    // texture addresser per CU, ~70 cycles each whatever their width), so epilogues with 16-bit streams (bf16 output, ReLU
-    // mask) use 8-column strips = 16 bytes per lane; pure fp32 epilogues keep 4 columns (same instruction count, fewer LDS
-    // bank conflicts on the staged tile).  All optional inputs of a thread's strips are fetched BEFORE the first store:
-    // a load after a store may alias it as far as the compiler knows, so a load-compute-store loop pays one full memory
-    // round trip per strip (8 to 16 per tile; the masked dgrad GEMMs ran 3x longer than their unmasked twins).  Strips are
-    // therefore handled in batches of four: loads of the batch, then its arithmetic and stores.
-    constexpr int SW = (EPI >= 0 && (EPI & (E_C16 | E_MASK))) ? 8 : 4;
-    constexpr int CS = BN / SW, NCH = BM * CS / NT;
-    static_assert(NCH >= 1, "tile too small for this many threads");
-    const int cs = (tid % CS) * SW, n = n0 + cs;
-    if (n >= g.N) return;
-    const bool f_bias = HAS(E_BIAS, g.bias), f_pe = HAS(E_PE, g.pe), f_relu = HAS(E_RELU, g.relu), f_mask = HAS(E_MASK, g.mask);
-    const bool f_drop = HAS(E_DROP, g.drop_p > 0.f) && g.drop_p > 0.f, f_res = HAS(E_RES, g.residual);
-    const bool f_acc = HAS(E_ACC, g.accumulate), f_c32 = HAS(E_C32, g.C32), f_c16 = HAS(E_C16, g.C16);
-    const int nv = g.N - n < SW ? g.N - n : SW;                 // valid columns of this thread's strip
-    const float inv_keep = f_drop ? 1.0f / (1.0f - g.drop_p) : 1.0f;
-    const uint32_t seed = (f_drop && g.seed_ptr) ? *g.seed_ptr : g.seed;
-    float bv[SW];
-#pragma unroll
-    for (int e = 0; e < SW; ++e) bv[e] = (f_bias && e < nv) ? g.bias[n + e] : 0.f;
-    // vector paths need a full strip and aligned rows (n is a multiple of SW by construction)
-    constexpr int A16 = SW - 1;                                  // bf16 strip = SW * 2 bytes: leading dimension multiple of SW
-    const bool v_c32 = nv == SW && f_c32 && !((g.ldc | out_delta | g.cseg_stride) & 3) && !((uintptr_t)g.C32 & 15);
-    const bool v_res = nv == SW && f_res && !(g.ldres & 3) && !((uintptr_t)g.residual & 15);
-    const bool v_c16 = nv == SW && f_c16 && !(g.ldc16 & A16) && !((uintptr_t)g.C16 & (2 * SW - 1));
-    const bool v_msk = nv == SW && f_mask && !(g.ldmask & A16) && !((uintptr_t)g.mask & (2 * SW - 1));
-    const bool v_pe = nv == SW && f_pe && !(g.N & 3) && !((uintptr_t)g.pe & 15);
-    auto ldf = [](const float* p, float (&o)[SW]) {
-#pragma unroll
-        for (int h = 0; h < SW / 4; ++h) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * h);
-            o[4 * h] = t[0]; o[4 * h + 1] = t[1]; o[4 * h + 2] = t[2]; o[4 * h + 3] = t[3];
-        }
-    };
-    // strips are handled NB at a time (the batch's inputs must fit the registers the accumulators just vacated)
-    constexpr int NB = NCH < 4 ? NCH : 4;
-#pragma unroll
-    for (int i0 = 0; i0 < NCH; i0 += NB) {
-    // ---- phase 1: every optional input of the batch
-    float rs[NB][SW], old[NB][SW], pev[NB][SW], mk[NB][SW];
-#pragma unroll
-    for (int ii = 0; ii < NB; ++ii) {
-        const int i = ii, row = (tid + (i0 + ii) * NT) / CS, m = m0 + row;
-#pragma unroll
-        for (int e = 0; e < SW; ++e) { rs[i][e] = 0.f; old[i][e] = 0.f; pev[i][e] = 0.f; mk[i][e] = 1.f; }
-        if (m >= g.M) continue;
-        if (f_res) {
-            const float* p = g.residual + (long)m * g.ldres + n;
-            if (v_res) ldf(p, rs[i]);
-            else { for (int e = 0; e < nv; ++e) rs[i][e] = p[e]; }
-        }
-        if (f_pe) {
-            const float* p = g.pe + (long)(m % g.pe_period) * g.N + n;
-            if (v_pe) ldf(p, pev[i]);
-            else { for (int e = 0; e < nv; ++e) pev[i][e] = p[e]; }
-        }
-        if (f_mask) {
-            const bf16* p = g.mask + (long)m * g.ldmask + n;
-            if (v_msk) {
-                if constexpr (SW == 8) { const bf16x8 t = ld8(p); for (int e = 0; e < 8; ++e) mk[i][e] = (float)t[e]; }
-                else { const bf16x4 t = *reinterpret_cast<const bf16x4*>(p); for (int e = 0; e < 4; ++e) mk[i][e] = (float)t[e]; }
-            } else { for (int e = 0; e < nv; ++e) mk[i][e] = (float)p[e]; }
-        }
-        if (f_c32 && f_acc) {
-            const float* c32 = g.C32 + out_delta + crow(g, m) + n;
-            if (v_c32) ldf(c32, old[i]);
-            else { for (int e = 0; e < nv; ++e) old[i][e] = c32[e]; }
+    if constexpr (EPI >= 0) {
+        if (epi_fast<BM, BN, EPI>(g, m0, n0, out_delta)) {
+            const bool drop = (EPI & E_DROP) && g.drop_p > 0.f;
+            if (!drop) return epi_strips<BM, BN, EPI, NT, true, 0>(g, ct, m0, n0, out_delta);
+            if (!(g.N & 1)) return epi_strips<BM, BN, EPI, NT, true, 1>(g, ct, m0, n0, out_delta);
         }
     }
-    // ---- phase 2: arithmetic and stores
-#pragma unroll
-    for (int ii = 0; ii < NB; ++ii) {
-        const int i = ii, row = (tid + (i0 + ii) * NT) / CS, m = m0 + row;
-        if (m >= g.M) continue;
-        float v[SW];
-        ldf(ct + row * LDC + cs, v);
-        float ks[SW];                                             // dropout keep-scales of the SW consecutive elements: one hash word per pair
-#pragma unroll
-        for (int h = 0; h < SW / 4; ++h) {
-            float k4[4] = {1.f, 1.f, 1.f, 1.f};
-            if (f_drop) dropout_scale4(seed, g.site, (uint32_t)((long)m * g.N + n + 4 * h), g.drop_p, inv_keep, k4);
-            ks[4 * h] = k4[0]; ks[4 * h + 1] = k4[1]; ks[4 * h + 2] = k4[2]; ks[4 * h + 3] = k4[3];
-        }
-#pragma unroll
-        for (int e = 0; e < SW; ++e) {
-            float x = v[e] + bv[e] + pev[i][e];
-            if (f_relu) x = fmaxf(x, 0.f);
-            if (f_mask) x = mk[i][e] > 0.f ? x * g.mask_scale : 0.f;
-            if (f_drop) x *= ks[e];
-            v[e] = x + rs[i][e] + old[i][e];
-        }
-        if (f_c32) {
-            float* c32 = g.C32 + out_delta + crow(g, m) + n;
-            if (v_c32) {
-#pragma unroll
-                for (int h = 0; h < SW / 4; ++h) *reinterpret_cast<f32x4*>(c32 + 4 * h) = f32x4{v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
-            } else { for (int e = 0; e < nv; ++e) c32[e] = v[e]; }
-        }
-        if (f_c16) {
-            bf16* p = g.C16 + (long)m * g.ldc16 + n;
-            if (v_c16) {
-                if constexpr (SW == 8) { bf16x8 t; for (int e = 0; e < 8; ++e) t[e] = (bf16)v[e]; st8(p, t); }
-                else { bf16x4 t; for (int e = 0; e < 4; ++e) t[e] = (bf16)v[e]; *reinterpret_cast<bf16x4*>(p) = t; }
-            } else { for (int e = 0; e < nv; ++e) p[e] = (bf16)v[e]; }
-        }
-    }
-    }
+    epi_strips<BM, BN, EPI, NT, false, -1>(g, ct, m0, n0, out_delta);
 }
 
 template <int BM, int BN, bool RM, int EPI>

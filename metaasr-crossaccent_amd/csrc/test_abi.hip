@@ -43,6 +43,13 @@ int masr_test_gemm_epi(const uint16_t* A, int64_t lda, const uint16_t* B, int64_
     g.C32 = C32; g.ldc = N; g.C16 = (bf16*)C16; g.ldc16 = N;
     return mk_gemm(g, (hipStream_t)stream);
 }
+int masr_test_gemm_pe_acc(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K, const float* bias, const float* pe,
+                          int pe_period, int accumulate, float* C32, int64_t ldc, uint16_t* C16, int64_t ldc16, void* stream) {
+    GemmArgs g = gemm_args();
+    g.A = (const bf16*)A; g.lda = lda; g.B = (const bf16*)B; g.ldb = ldb; g.M = M; g.N = N; g.K = K; g.bias = bias;
+    g.pe = pe; g.pe_period = pe_period; g.accumulate = accumulate; g.C32 = C32; g.ldc = ldc; g.C16 = (bf16*)C16; g.ldc16 = ldc16;
+    return mk_gemm(g, (hipStream_t)stream);
+}
 int masr_test_skinny_gemm(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int N, int K, const float* bias, int relu,
                           const float* residual, float* C32, uint16_t* C16, void* stream) {
     SkinnyArgs g{};
