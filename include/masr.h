@@ -308,6 +308,48 @@ int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, i
 int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
                        float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
 
+/* Shallow fusion of an LSTM language model into the attention beam.
+ * The LM is torch.nn.Embedding(C, E) -> torch.nn.LSTM(E, H, L) -> torch.nn.Linear(H, C) over the model's C output units with the model's ids;
+ * gate order i, f, g, o; no dropout.  1 <= E, H <= 2048, L in [1, 4], C in [2, 65535].  The start token is start_id in [0, C): 0 is this model's
+ * sos, C - 1 serves LMs trained with sos = eos.
+ * masr_nlm_create takes host arrays: embed fp32 [C][E]; per layer l, w_ih[l] [4H][in_l] (in_0 = E, else H), w_hh[l] [4H][H], b_ih[l] and b_hh[l]
+ * [4H]; lo_w [C][H], lo_b [C].  It builds the device weights on the current device and returns the handle; NULL + the masr_last_error text for a
+ * null array, a non-finite weight, a size out of range or start_id outside [0, C) -- all found on the host, before anything touches the device.
+ * Device layout and precision: bf16 operands (embedding rows, h, every weight matrix; per layer one matrix [4 Hp][INp + Hp] = W_ih | W_hh, with
+ * E and H padded up to multiples of 32 by zeros) with fp32 accumulation; fp32 gates, cell state c, bias fl(b_ih + b_hh), output bias and LM
+ * logits.  h is stored as bf16, the only form any consumer reads.  A padded unit's pre-activations are exactly 0, so its c and h stay exactly 0.
+ * masr_nlm_bytes: device bytes held.
+ * lm(c | h), the LM score of class c after hypothesis h: feed [start] + h from the zero state; y = the fp32 output row behind the last token;
+ * lm = (y_c - mx) - log_s with mx = max y and log_s = log sum exp(y - mx), composed as masr_recog_beam composes lp.  Every LM term is <= 0 and
+ * the beam's stop rule stays exact.
+ * masr_recog_beam_nlm: the search of masr_recog_beam (attention decoder alone, also on a hybrid model) with the per-step increment
+ *   f(c) = fl(lp(c) + fl(lm_w * lm(c | h))), no fused multiply-add,
+ * and everything else as masr_recog_beam_lm states it: the row lists by (f descending, class ascending), the selection, the stop rule, minlen /
+ * maxlen, the result layout, the bounds and messages; lm_w finite and >= 0; the LM's C must equal the model's odim; lm_w = 0 gives
+ * masr_recog_beam's scores bit for bit.  Every hypothesis row carries the LM's state (h, c) per layer, double-buffered by step parity: a row
+ * reads its parent's state of the step before and writes its own, so the state follows the beam's re-parenting without a copy.
+ * Needs a workspace of masr_beam_nlm_workspace_bytes(m, nlm, B, T, K, Lmax) = the beam's plus, with R = B * K, Cp = odim padded to 128, Hp = H
+ * padded to 32 and each entry rounded up to 256 bytes:
+ *   R * Cp * 4  (the fused rows)  +  R * Cp * 4  (the LM logits)  +  2 * L * R * Hp * 2  (h)  +  2 * L * R * Hp * 4  (c)
+ *   +  R * Hp * 2  (the top layer's new h once more, the output projection's operand at an address that does not depend on the step).
+ * The step is captured as its own hipGraph, keyed on the LM and lm_w as well: a call with another LM or weight captures anew.
+ * masr_nlm_score, model-free: the teacher-forced log-probability of R token sequences, tokens int32 [R][ld] and lens int32 [R] (device; every
+ * length in [0, ld], every token in [0, C - 1], vetted on the host after one synchronisation): logp_out[r] = the sum over i = 0 .. lens[r], in
+ * that order in fp32, of lm(target_i | tokens[r][0 .. i)), target_i = tokens[r][i] and, behind the last token, eos = C - 1.  It runs the beam's
+ * step kernels position by position with every row its own parent.  work: 256-byte aligned device memory of at least
+ * masr_nlm_score_work_bytes(nlm, R, ld) bytes (1 <= R <= 2^20, 0 <= ld <= 4096). */
+typedef struct masr_nlm masr_nlm;
+masr_nlm* masr_nlm_create(int C, int E, int H, int L, int start_id, const float* embed, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, const float* lo_w, const float* lo_b);
+void masr_nlm_destroy(masr_nlm* nlm);
+int64_t masr_nlm_bytes(const masr_nlm* nlm);
+int64_t masr_beam_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int Lmax);
+int masr_recog_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
+                        float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream);
+int64_t masr_nlm_score_work_bytes(const masr_nlm* nlm, int R, int ld);
+int masr_nlm_score(const masr_nlm* nlm, const int32_t* tokens, const int32_t* lens, int R, int ld, float* logp_out, void* work, int64_t work_bytes,
+                   void* stream);
+
 /* One-pass joint CTC/attention beam search with the n-gram LM, a length bonus and an N-best list (what ESPnet-style recipes decode
  * with).  It is masr_recog_beam_ctc with these differences; everything else (P = floor(3K/2), blank never, eos from minlen tokens on, -inf never
  * kept nor ended, minlen / maxlen, dead rows) is that search's:

@@ -262,6 +262,15 @@ int masr_test_mask_rows(float* x32, uint16_t* x16, const int32_t* lens, int B, i
 /* time sub-sampling.  dys == NULL: ys bf16 [B][Tout][C] = y bf16 [B][Tin][C] rows t' * sub (mk_subsample_rows, C % 8 == 0); else its backward
  * dy fp32 [B][Tin][C] = dys fp32 [B][Tout][C] at t % sub == 0, zero elsewhere (mk_subsample_rows_bwd, C % 4 == 0).  Tout == ceil(Tin / sub). */
 int masr_test_subsample_rows(const uint16_t* y, uint16_t* ys, const float* dys, float* dy, int B, int Tin, int Tout, int sub, int C, void* stream);
+/* one step of the LSTM LM's layer stack alone (nlm.hip: the L nlm_lstm_step launches and the output projection of masr_recog_beam_nlm's step) as
+ * step t >= 1 on R rows, K rows per utterance (R % K == 0).  t == 1: every row feeds the LM's start token from the zero state, tok / par are not
+ * read.  t > 1: row r feeds tok[r] (an id outside [0, C) reads as 0) and continues the state of row par[r] (null: r itself; outside the rows
+ * of r's utterance: r).  hstate bf16 / cstate fp32 [2][L][R][Hp], Hp = H padded to 32: the caller's previous states at parity (t - 1) & 1 are
+ * read, the new ones are written at parity t & 1.  score fp32 [R] (null: every row live): a row with -inf writes nothing.  logits fp32
+ * [R][ld], ld >= C: the LM logits of the live rows; logp (null: skipped) fp32 [R][ld]: their log_softmax as the beam composes it,
+ * (y - mx) - log_s.  Synchronises the stream. */
+int masr_test_nlm_step(const masr_nlm* nlm, int R, int K, int t, const int32_t* tok, const int32_t* par, const float* score, uint16_t* hstate,
+                       float* cstate, float* logits, int64_t ld, float* logp, void* stream);
 
 #ifdef __cplusplus
 }

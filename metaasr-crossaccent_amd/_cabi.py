@@ -84,6 +84,13 @@ _SIGS = {
     "masr_lm_bytes": (i64, [vp]),
     "masr_beam_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_nlm_create": (vp, [i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]),
+    "masr_nlm_destroy": (None, [vp]),
+    "masr_nlm_bytes": (i64, [vp]),
+    "masr_beam_nlm_workspace_bytes": (i64, [vp, vp, i32, i32, i32, i32]),
+    "masr_recog_beam_nlm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_nlm_score_work_bytes": (i64, [vp, i32, i32]),
+    "masr_nlm_score": (i32, [vp, vp, vp, i32, i32, vp, vp, i64, vp]),
     "masr_beam_ctc_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
     "masr_recog_beam_ctc_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
@@ -186,6 +193,7 @@ _SIGS = {
     "masr_test_tanh": (i32, [vp, vp, vp, vp, i64, vp]),
     "masr_test_mask_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "masr_test_subsample_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "masr_test_nlm_step": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_NAMES = ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "conv2_dgrad", "conv3_dgrad", "conv4_dgrad", "conv2_wgrad",
@@ -292,6 +300,16 @@ def check_lm_args(lm, lm_w, len_bonus):
     if getattr(lm, "h", None) is None:
         raise ValueError("lm must be a live NGramLM")
     return lm_w, len_bonus
+
+
+def check_nlm_args(nlm, lm_w):
+    """what the LSTM-LM-fused beam vets on the Python side -> lm_w as a float"""
+    lm_w = float(lm_w)
+    if not (math.isfinite(lm_w) and lm_w >= 0.0):
+        raise ValueError(f"lm_w must be finite and >= 0, got {lm_w}")
+    if getattr(nlm, "h", None) is None or not hasattr(nlm, "score"):
+        raise ValueError("lm must be a live LstmLM")
+    return lm_w
 
 
 def check(rc, what=""):

@@ -13,6 +13,7 @@
 
 #include "engine_internal.h"
 #include "lm.h"
+#include "nlm.h"
 #include "../../include/masr_test.h"
 
 // The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
@@ -143,6 +144,8 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   beam (masr_recog_beam): the decoder is planned for K*Lmax positions per utterance = Lmax slots for each of the B*K hypothesis
 //   rows, and the beam state follows
 //   LM fusion (masr_recog_beam_lm, lm): the beam's plan, then the fp32 fused rows [B*K][Cp]
+//   LSTM LM fusion (masr_recog_beam_nlm, nlm): the beam's plan, then the fused rows, the LM logits [B*K][Cp], the LM's states h bf16 and c fp32
+//   [2][L][B*K][Hp] each, and the top layer's new h [B*K][Hp]
 //   joint CTC/attention (masr_recog_beam_ctc, P = floor(3K/2) > 0): the row lists are P long, and the CTC head's logits [B*Tp][Cp], its
 //   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
 //   joint with LM, bonus and N-best (masr_recog_beam_ctc_lm, P > 0, lm, NB > 0): both of the above, then the candidates' LM terms [R][P], the
@@ -154,10 +157,11 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   second pass's scores
 //   CTC forced alignment (masr_recog_ctc_align, AL = maxL >= 0): one decoder position per utterance; the head's logits, the targets
 //   [B*maxL] with their offsets [B] and lengths [B], and the alignment's work buffer follow
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; int AL = -1; };
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; int AL = -1; const masr_nlm* nlm = nullptr; };
 struct DecodeBufs {
     BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
     float* lm_fused;                                                    // LM fusion: the rows' fused increments [R][Cp]
+    float* nlm_logits; bf16 *nlm_h, *nlm_htop; float* nlm_c;            // LSTM LM fusion: LM logits [R][Cp], states [2][L][R][Hp], top h [R][Hp]
     int *rs_tok, *rs_lens; float *rs_ctc, *rs_att, *rs_row_lp;          // rescoring: first-pass list [B][N][Tp] / [B][N] / [B][N], att [B*N], row terms [B*N*(Lmax+1)]
     int* al_tgt;                                                        // alignment: targets [B*maxL], then tgt_off [B], then tgt_len [B]
 };
@@ -174,7 +178,12 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
     a.list_tok = ar.get<int>((int64_t)R * W); a.list_score = ar.get<float>((int64_t)R * W);
     int* lens = ar.get<int>(2 * (int64_t)B); a.maxlen = lens; a.minlen = lens + B;
     a.fin = ar.get<int>(B); a.best_score = ar.get<float>(B); a.best_len = ar.get<int>(B); a.best_row = ar.get<int>(B);
-    if (d.lm) o.lm_fused = ar.get<float>((int64_t)R * m->Cp);
+    if (d.lm || d.nlm) o.lm_fused = ar.get<float>((int64_t)R * m->Cp);
+    if (d.nlm) {
+        o.nlm_logits = ar.get<float>((int64_t)R * m->Cp);
+        o.nlm_h = ar.get<bf16>(nlm_state_elems(d.nlm->dev, R)); o.nlm_c = ar.get<float>(nlm_state_elems(d.nlm->dev, R));
+        o.nlm_htop = ar.get<bf16>((int64_t)R * d.nlm->dev.Hp);
+    }
     if (!P) return o;
     a.P = P; a.Tp = Tp;
     o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
@@ -266,6 +275,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
                                    : d.NB ? "workspace too small (masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
                                    : d.lm ? "workspace too small (masr_beam_lm_workspace_bytes(B, T, K, Lmax))"
+                                   : d.nlm ? "workspace too small (masr_beam_nlm_workspace_bytes(nlm, B, T, K, Lmax))"
                                          : "workspace too small (masr_beam_workspace_bytes(B, T, K, Lmax))");
         return -2;
     }
@@ -331,20 +341,25 @@ static int ctc_head_logits(Ctx& c, float* ctc_logits) {
 static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
 
 // the four step beams' workspace queries: one predicate, and one message but for the N-best variant's (N < 0: no list)
-static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, int T, int K, int Lmax, bool joint, bool lm, int N = -1) {
+static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, int T, int K, int Lmax, bool joint, bool lm, int N = -1,
+                                   const masr_nlm* nlm = nullptr) {
     return decode_workspace_bytes(fn, m, shape_ok(B, T, K) && Lmax >= 1 && (N < 0 || (N >= 1 && N <= K)),
                                   N < 0 ? "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1" : "need B >= 1, T >= 4, 1 <= N <= K <= 64, Lmax >= 1", B, T,
-                                  DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0)});
+                                  DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0), -1, nlm});
 }
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
 // CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.  LM fusion (lm): the
 // fused top-K (lm.hip) in place of the row top-K.  Both (ba.N > 0): the fused pre-beam, the prefix scores with the LM term and
 // the bonus, the select with the N-best list; the weights are read from ba.wts, lm->w is not used.
+// LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last tokens and parent states (nlm.hip; it reads
+// only what the previous step's select wrote, so it sits in front of the decoder layers), and its fused top-K in place of the row top-K.
 struct LmStep { LmDev dev; float w; float* fused; };
-static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* lm = nullptr) {
+struct NlmStep { NlmDev dev; float w; NlmStepArgs args; float* logits; float* fused; };
+static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* lm = nullptr, const NlmStep* nlm = nullptr) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
+    if (nlm) CK(mk_nlm_step(nlm->dev, nlm->args, nlm->logits, m->Cp, s));
     CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
     if (ba.N) {
         CK(mk_beam_ctc_lm_prebeam(ba, lm->dev, a.logits, m->Cp, lm->fused, m->Cp, s));
@@ -358,18 +373,20 @@ static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* l
         CK(mk_beam_ctc_select(ba, s));                          // also advances *step_dev
         return 0;
     }
-    if (lm) CK(mk_beam_lm_topk(ba, lm->dev, lm->w, a.logits, m->Cp, lm->fused, m->Cp, s));
+    if (nlm) CK(mk_beam_nlm_topk(ba, nlm->w, a.logits, m->Cp, nlm->logits, m->Cp, nlm->fused, m->Cp, s));
+    else if (lm) CK(mk_beam_lm_topk(ba, lm->dev, lm->w, a.logits, m->Cp, lm->fused, m->Cp, s));
     else CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
     CK(mk_beam_select(ba, s));                                  // also advances *step_dev
     return 0;
 }
 
-// which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm) or masr_recog_beam_ctc_lm (joint, lm
-// and the N-best list); each has its own cached step graph
+// which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm), masr_recog_beam_ctc_lm (joint, lm
+// and the N-best list) or masr_recog_beam_nlm (nlm); each has its own cached step graph
 struct BeamMode {
     bool joint = false; float att_w = 0.f, ctc_w = 0.f;         // joint CTC/attention: the two weights
     const masr_lm* lm = nullptr; float lm_w = 0.f;              // n-gram LM fusion
     int N = 0; float len_bonus = 0.f;                           // N-best list (N > 0) and the bonus per emitted token
+    const masr_nlm* nlm = nullptr;                              // LSTM LM fusion (weighted by lm_w)
 };
 static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, const float* xs, const int64_t* ilens, int B, int T, int K,
                            float min_step_ratio, float max_step_ratio, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
@@ -392,7 +409,7 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, mode.joint ? beam_prebeam_width(K) : 0, false, 0, mode.lm != nullptr, mode.N},
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, mode.joint ? beam_prebeam_width(K) : 0, false, 0, mode.lm != nullptr, mode.N, -1, mode.nlm},
                                    &bufs);
       if (rc) return rc; }
     BeamArgs& ba = bufs.beam;
@@ -421,9 +438,17 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
         CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
         key[4] = mode.N;
     }
-    DecodeGraph& graph = mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
+    NlmStep ns{};
+    if (mode.nlm) {
+        ns.dev = mode.nlm->dev; ns.w = mode.lm_w; ns.logits = bufs.nlm_logits; ns.fused = bufs.lm_fused;
+        ns.args.step = ba.step; ns.args.R = ba.R; ns.args.K = ba.K; ns.args.tok_hist = ba.tok_hist; ns.args.par_hist = ba.par_hist;
+        ns.args.hist_stride = ba.R; ns.args.score = ba.score; ns.args.fin = ba.fin;
+        ns.args.hstate = bufs.nlm_h; ns.args.cstate = bufs.nlm_c; ns.args.htop = bufs.nlm_htop;
+        memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.nlm->serial;
+    }
+    DecodeGraph& graph = mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
     CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
-                 [&] { return beam_step(c, ba, bufs.step_qkv, mode.lm ? &ls : nullptr); }));
+                 [&] { return beam_step(c, ba, bufs.step_qkv, mode.lm ? &ls : nullptr, mode.nlm ? &ns : nullptr); }));
     if (mode.N) CK(mk_beam_backtrace_nbest(ba, tokens, lens, scores, s));
     else CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
@@ -527,6 +552,11 @@ int64_t masr_beam_ctc_workspace_bytes(const masr_model* m, int B, int T, int K, 
 int64_t masr_beam_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
     return beam_workspace_bytes("masr_beam_lm_workspace_bytes", m, B, T, K, Lmax, false, true);
 }
+int64_t masr_beam_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int Lmax) {
+    const char* fn = "masr_beam_nlm_workspace_bytes";
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    return beam_workspace_bytes(fn, m, B, T, K, Lmax, false, false, -1, nlm);
+}
 int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
     return beam_workspace_bytes("masr_beam_ctc_lm_workspace_bytes", m, B, T, K, Lmax, true, true, N);
 }
@@ -564,6 +594,19 @@ int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const 
     CK(check_model(fn, m));
     CK(check_lm(fn, m, lm, lm_w, nullptr));
     BeamMode mode; mode.lm = lm; mode.lm_w = lm_w;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
+                        float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
+    // LSTM LM shallow fusion into the attention beam (nlm.hip): masr_recog_beam with the LM's step in front of the decoder layers
+    // and the fused top-K in place of the row top-K
+    const char* fn = "masr_recog_beam_nlm";
+    CK(check_model(fn, m));
+    if (!nlm) return fail(fn, "null language model");
+    if (nlm->dev.C != m->C) return fail(fn, "the language model's classes differ from the model's odim");
+    CK(check_weight(fn, "lm_w", lm_w, false));
+    BeamMode mode; mode.nlm = nlm; mode.lm_w = lm_w;
     return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
 }
 

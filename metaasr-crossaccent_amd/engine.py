@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, lib, nbest_lists
+from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -388,6 +388,21 @@ class MasrEngine:
         out = self._outputs(B, ld=Lmax)
         check(self._l.masr_recog_beam_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), lm_w,
                                          *map(_ptr, out), self.stream()), "masr_recog_beam_lm")
+        self._last_x = xs
+        return self._best_lists(*out)
+
+    def recog_beam_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
+        """beam search with an LSTM LM fused in (masr_recog_beam_nlm): recog_beam's attention-only search with the per-step
+        increment log p_att(c | h) + lm_w * lm(c | h), every hypothesis carrying the LM's recurrent state.  nlm: an LstmLM (nlm.py) over this
+        model's odim classes; lm_w finite and >= 0.  Returns what recog_beam returns."""
+        K, _ = check_beam_args(beam_size)
+        lm_w = check_nlm_args(nlm, lm_w)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_nlm_workspace_bytes", nlm.h, B, T, K, Lmax)
+        out = self._outputs(B, ld=Lmax)
+        check(self._l.masr_recog_beam_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), lm_w,
+                                          *map(_ptr, out), self.stream()), "masr_recog_beam_nlm")
         self._last_x = xs
         return self._best_lists(*out)
 

@@ -121,6 +121,12 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_beam_lm(xs_pad, ilens, beam_size, lm, lm_weight, min_step_ratio, max_step_ratio)
 
+    def nlm_beam_decode(self, xs_pad, ilens, beam_size, nlm, lm_weight, min_step_ratio=0.0, max_step_ratio=1.0):
+        """beam search with shallow fusion of the LSTM LM `nlm` (an LstmLM; masr_recog_beam_nlm): (B token lists without sos / eos,
+        scores [B])"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_nlm(xs_pad, ilens, beam_size, nlm, lm_weight, min_step_ratio, max_step_ratio)
+
     def lm_joint_beam_decode(self, xs_pad, ilens, beam_size, lm, lm_weight=0.3, len_bonus=0.0, nbest=1, min_step_ratio=0.0, max_step_ratio=1.0,
                              att_weight=0.7, ctc_weight=0.3):
         """one-pass joint CTC/attention beam search with the n-gram LM `lm`, a per-token bonus and an N-best list (masr_recog_beam_ctc_lm,

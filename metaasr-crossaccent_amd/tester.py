@@ -20,6 +20,11 @@ anything is decoded.  Tester.MODES is the table of them:
                  the mode raises NotImplementedError (the reference asserts the path when its Tester is constructed); so does a BLSTM.
                  The LM is not fused into the joint beam by this mode: a hybrid model with ctc_w > 0 raises ValueError (that search is
                  `lm_joint_beam`); a plain model logs that ctc_w is ignored.
+  nlm_beam       masr_recog_beam_nlm, the attention beam with an LSTM LM fused in: `--lm_model_path` is read as a torch
+                 checkpoint of Embedding -> LSTM -> Linear over the output units (nlm.py has the two key layouts; tools/train_nlm.py
+                 writes one), weighted by lm_w (0.3); the step ratios as for `beam`; lm_start: sos | eos (sos) is the token the LM is
+                 started with (eos: LMs trained with sos = eos).  Without a path the mode raises NotImplementedError; so does a BLSTM.
+                 A hybrid model with ctc_w > 0 raises ValueError (set ctc_w: 0); a plain model logs that ctc_w is ignored.
   lm_ctc_beam    masr_recog_ctc_beam_lm (BLSTM-CTC: masr_ctc_beam_search_lm), `ctc_beam` with that LM and a per-token bonus fused into
                  the search: `--lm_model_path` as for `lm_beam`, lm_w (0.3), len_bonus (0, finite, any sign).  Refuses what
                  `ctc_beam` refuses, and a BLSTM whose blank is not id 0 (its slot serves as the LM's <s>).
@@ -162,10 +167,10 @@ class Tester:
             raise ValueError(f"solver.beam_decode.{key} must be finite and >= 0, got {bd.get(key, default)}")
         return w
 
-    def _lm_model_path(self):
+    def _lm_model_path(self, what="an ARPA n-gram file over the output units"):
         path = getattr(self.paras, 'lm_model_path', None)
         if path is None:
-            raise NotImplementedError(f"{self.decode_mode}: no language model given; pass --lm_model_path (an ARPA n-gram file over the output units)")
+            raise NotImplementedError(f"{self.decode_mode}: no language model given; pass --lm_model_path ({what})")
         return path
 
     def _need_ctc_head(self, mode, instead):
@@ -233,6 +238,35 @@ class Tester:
                                  "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
             logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
         logger.notice(f"LM shallow fusion: {self._load_lm(lm_path, self.sos_id, self.eos_id)}, lm_w = {self.lm_weight}")
+
+    def _load_nlm(self, path, start_id):
+        """self.nlm = the checkpoint as an LstmLM started with start_id, built once per Tester and (path, start_id)"""
+        key = (path, start_id)
+        if getattr(self, 'nlm', None) is None or getattr(self, '_nlm_key', None) != key:
+            from .nlm import LstmLM
+            self.nlm, self._nlm_key = LstmLM.load(path, start_id=start_id), key
+        return f"{path}, {self.nlm.L} x {self.nlm.H} LSTM on {self.nlm.E}-dim embeddings"
+
+    def _nlm_beam_settings(self):
+        lm_path = self._lm_model_path("a torch checkpoint of an LSTM LM over the output units")
+        if self.model_name == 'blstm':
+            raise NotImplementedError("nlm_beam: LM fusion is only implemented for the transformer's attention beam; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self._step_ratios(bd)
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        start = bd.get('lm_start', 'sos')
+        if start not in ('sos', 'eos'):
+            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
+        if self._weight(bd, 'ctc_w', 0.0) > 0.0:
+            if self.asr_model.engine.ctc_weight > 0.0:
+                raise ValueError(f"nlm_beam: the LSTM LM is not fused into the joint CTC/attention beam (beam_decode.ctc_w = {bd['ctc_w']}); "
+                                 "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
+            logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
+        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
+        if self.nlm.C != len(self.id2ch):
+            raise ValueError(f"nlm_beam: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        logger.notice(f"LSTM LM shallow fusion: {lm}, start token {start}, lm_w = {self.lm_weight}")
 
     def _ctc_beam_settings(self):
         self._beam_size()
@@ -315,6 +349,9 @@ class Tester:
         'lm_beam': (_lm_beam_settings,
                     lambda t, xs, il: t.asr_model.lm_beam_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.min_step_ratio, t.max_step_ratio)[0],
                     lambda t: f"beam decoding with LM fusion (beam {t.beam_size})"),
+        'nlm_beam': (_nlm_beam_settings,
+                     lambda t, xs, il: t.asr_model.nlm_beam_decode(xs, il, t.beam_size, t.nlm, t.lm_weight, t.min_step_ratio, t.max_step_ratio)[0],
+                     lambda t: f"beam decoding with LSTM LM fusion (beam {t.beam_size})"),
         'ctc_beam': (_ctc_beam_settings,
                      lambda t, xs, il: t._ctc_best(t.asr_model.ctc_beam_decode(xs, il, t.beam_size)),
                      lambda t: f"CTC prefix beam decoding (beam {t.beam_size})"),
