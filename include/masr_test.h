@@ -65,7 +65,7 @@ int masr_test_logits_f32(const float* y32, const float* W32, const float* bias, 
 /* the greedy decode's arg-max (decode.hip recog_argmax_step_kernel): out[(step[0] - 1) * B + b] = first maximal index of logits [b][:C]
  * (0 when no value is above -inf); the last row to finish sets step = {step[0] + 1, 0}.  step int32 [2] on the device */
 int masr_test_recog_argmax_step(int32_t* step, const float* logits, int64_t ld, int32_t* out, int B, int C, void* stream);
-/* one step t of the beam search's glue (beam.hip beam_row_topk_kernel + beam_select_kernel<false>) on R = B*K rows of caller-given fp32
+/* one step t of the beam search's glue (beam.hip beam_rows_kernel without an LM + beam_select_kernel<false>) on R = B*K rows of caller-given fp32
  * logits [R][ld].  In: minlen / maxlen [B].  In and out: score [R], fin [B], best_score / best_len / best_row [B], and row t-1 of the
  * token / parent history tok_hist_row / par_hist_row [R] (the entries the step does not write keep the caller's values).  Out: the rows'
  * lists list_tok / list_score [R][K] and the step pair step_out int32 [2].  All arrays on the device; synchronises the stream. */
@@ -199,7 +199,7 @@ int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t
 int masr_test_lm_score(const masr_lm* lm, const int32_t* ctx, int R, float* out, void* stream);
 /* the longest probe chain (slots examined) an insertion walked while the LM's tables were built; 1 = no n-gram ever met an occupied slot */
 int masr_test_lm_max_probe(const masr_lm* lm);
-/* the beam's LM step kernel alone (beam_lm_topk_kernel) at step t >= 1 on R = B*K rows of caller-given fp32 logits [R][ld] (C = the LM's classes
+/* the beam's row stage with the n-gram LM alone (beam.hip beam_rows_kernel, top-K) at step t >= 1 on R = B*K rows of caller-given fp32 logits [R][ld] (C = the LM's classes
  * <= ld): score fp32 [R] (-inf = dead row), minlen int32 [B], and the token / parent-row histories of the steps before, tok_hist / par_hist
  * int32 [t - 1][R] (null at t = 1; the kernel clamps what it reads).  Out: list_tok int32 / list_score fp32 [R][K].  The fused rows and the
  * step scalar are the entry's; no utterance is finished.  All arrays on the device; synchronises the stream. */
@@ -208,7 +208,7 @@ int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, c
 
 /* ---- the joint LM beam's step kernels alone (tests/test_hip_joint_lm_kernels.py).  All arrays on the device; each entry
  * synchronises the stream.
- * the fused pre-beam (lm.hip beam_ctc_lm_prebeam_kernel): masr_test_beam_lm_topk's inputs; P = floor(3K/2).  Out: pre_tok int32 / pre_lp / pre_lm
+ * the fused pre-beam (the same kernel, pre-beam): masr_test_beam_lm_topk's inputs; P = floor(3K/2).  Out: pre_tok int32 / pre_lp / pre_lm
  * fp32 [R][P] -- the row's P best classes by g (blank never, eos from minlen on; -1 / -inf / 0 past the end), their attention log-probs and
  * fl(lm_w * lm(c | h)).  A dead row's entries are left as the caller gave them. */
 int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,

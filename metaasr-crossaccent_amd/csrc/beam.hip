@@ -6,7 +6,10 @@
 //   beam_embed_step   row r: the embedding of its last token + pe[t-1]; its self-attention slot table (key j of row r lives in
 //                     cache row tab[r][j]) = its parent's table of the previous step, and tab[r][t-1] = r (the slot this step writes)
 //   ... decoder layers + fp32 logits (engine.hip) ...
-//   beam_row_topk     one wave per live row: fp32 log-softmax and the row's K best tokens (logit descending, token ascending)
+//   beam_rows         one wave per live row: fp32 log-softmax and the row's K best tokens (logit descending, token ascending).  The one
+//                     row stage of every step beam: an n-gram LM (masr_recog_beam_lm) or a row of LSTM-LM logits
+//                     (masr_recog_beam_nlm) adds its weighted term and the row is ranked by the fused increment; in the joint
+//                     beams it emits the P-long pre-beam for beam_ctc_prefix instead of the K-long list
 //   beam_select       one wave per utterance: K-way merge of the K sorted row lists -> the K best candidates (score descending,
 //                     parent rank ascending, then the row order above), ended / running bookkeeping, finished flag, step ticket
 // beam_backtrace runs once after the last step.
@@ -16,6 +19,7 @@
 // different logits is decided by the logit.  Hence K = 1 picks exactly the greedy arg-max (first maximal logit).
 #include "kernels.h"
 #include "search.h"
+#include "lm.h"
 
 namespace {
 
@@ -34,14 +38,11 @@ __global__ void beam_set_weights_kernel(float* w, float att_w, float ctc_w, floa
 // grid R, 256 threads
 __global__ __launch_bounds__(256) void beam_embed_step_kernel(BeamArgs a, const float* __restrict__ table, const float* __restrict__ pe,
                                                              float* __restrict__ y32, bf16* __restrict__ y16, int E) {
-    const int r = blockIdx.x, st = *a.step, u0 = (r / a.K) * a.K;
+    const int r = blockIdx.x, st = *a.step;
     int tok = a.sos, par = r;
-    if (st > 1) {
-        tok = a.tok_hist[(long)(st - 2) * a.R + r];
-        par = a.par_hist[(long)(st - 2) * a.R + r];
-        // rows of a finished utterance are not written any more; keep their reads in bounds (their results are never used)
-        if (tok < 0 || tok >= a.C) tok = a.sos;
-        if (par < u0 || par >= u0 + a.K) par = r;
+    if (st > 1) {                                                // (a finished utterance's rows: read in bounds, their results are never used)
+        const HistEntry h = hist_entry(a.tok_hist, a.par_hist, a.R, st - 1, r, a.C, a.K, a.sos);
+        tok = h.tok; par = h.par;
     }
     for (int e = threadIdx.x; e < E; e += 256) {
         const float v = table[(long)tok * E + e] + pe[(long)(st - 1) * E + e];
@@ -54,24 +55,104 @@ __global__ __launch_bounds__(256) void beam_embed_step_kernel(BeamArgs a, const 
     if (threadIdx.x == 0) cur[st - 1] = r;
 }
 
-// grid ceil(R / 4), 256 threads: one wave per row.  list_tok / list_score [R][K]: the row's K best extensions, token -1 past the end
-__global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
+// ---------------------------------------------------------------- the row stage: a row's logits -> its candidate list
+// The LM context of row r's hypothesis (st - 1 tokens), for the whole wave: token s of h is tok_hist[s - 1][row], row = the hypothesis's row
+// after step s; position 0 is sos.  Lane 0 walks the histories (hist_entry: clamped) and broadcasts; n <= order - 1, so no order the LM
+// lacks is ever indexed
+__device__ __forceinline__ LmCtx row_lm_context(const BeamArgs& a, const LmDev& lm, int r, int st, int lane) {
+    const int n = min(lm.order - 1, st);
+    int tok[LM_MAX_ORDER - 1];
+    int row = r;
+#pragma unroll
+    for (int i = 0; i < LM_MAX_ORDER - 1; ++i) {
+        int t = a.sos;
+        const int s = st - 1 - i;
+        if (lane == 0 && i < n && s >= 1) {
+            const HistEntry h = hist_entry(a.tok_hist, a.par_hist, a.R, s, row, a.C, a.K, a.sos);
+            t = h.tok; row = h.par;
+        }
+        tok[i] = __shfl(t, 0, 64);
+    }
+    return lm_context(lm, tok, n);
+}
+
+// Where the LM term of the row stage comes from.  row(..) does the wave's shared work for row r once and returns term(c) = lm(c | h), a
+// log-prob <= 0; the lanes call it for their classes (the n-gram's probes of a lane's ceil(C / 64) classes are independent loads)
+struct RowLmNone {                                               // no LM: nothing is fused
+    static constexpr bool FUSED = false;
+    __device__ auto row(const BeamArgs&, int, int, int) const { return [](int) { return 0.f; }; }
+};
+struct RowLmNgram {                                              // backoff n-gram tables (lm.h): the context from the history walk
+    static constexpr bool FUSED = true;
+    LmDev lm;
+    __device__ auto row(const BeamArgs& a, int r, int st, int lane) const {
+        return [&lm = lm, x = row_lm_context(a, lm, r, st, lane)](int c) { return lm_score(lm, x, c); };
+    }
+};
+struct RowLmLogits {                                             // a row of LM logits [R][ld] (the LSTM LM of nlm.hip): its log-softmax
+    static constexpr bool FUSED = true;
+    const float* y; long ld;
+    __device__ auto row(const BeamArgs& a, int r, int, int lane) const {
+        const float* yr = y + (long)r * ld;
+        return [yr, l = row_lse(yr, a.C, lane)](int c) { return (yr[c] - l.mx) - l.log_s; };
+    }
+};
+
+// grid ceil(R / 4), 256 threads: one wave per live row r (hypothesis h of st - 1 tokens, score ps).  lp(c) = (z_c - mx) - log_s of row_lse.
+// With an LM the lanes stride over the C classes and store the fused increment f(c) = fl(lp(c) + fl(lm_w * lm(c | h))) -- two roundings,
+// the one statement every LM-fused step beam composes it by -- to the row of the fp32 workspace fused [R][ldf]; the same wave reads it back
+// (8 KB at C = 2048: it stays in the L1 / L2 of its CU), so the stage is one launch.  row_top_n ranks the row by f, or without an LM by the
+// raw logit z (lp would merge logits that the rounding makes equal; the tie order is logit descending), class ascending.
+//   top-K (PRE false)   list_tok / list_score [R][K]: the K best classes, eos skipped below minlen, score fl(ps + f(c)) or fl(ps + lp(c)),
+//                       token -1 past the end; a dead row gets an empty list.  lm_w is the kernel argument (the step graph is keyed on it)
+//   pre-beam (PRE)      pre_tok [R][P]: the P best, blank never, eos skipped below minlen, -1 past the end; then the lanes share the P
+//                       entries: pre_lp = lp(c) and, with an LM, pre_lm = fl(lm_w * lm(c | h)), each computed again from its inputs (the
+//                       same expressions: the same bits), so no second [R][Cp] row is kept.  A dead row is left alone (the prefix kernel
+//                       gives it its empty list).  lm_w is a.wts[2]: no graph holds a weight of the joint LM beam
+template <class Lm, bool PRE>
+__global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a, Lm lm, float lm_w_arg, const float* __restrict__ logits, long ld,
+                                                       float* __restrict__ fused, long ldf) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.R) return;
     const int u = r / a.K, st = *a.step;
     if (a.fin[u]) return;
     const float ps = a.score[r];
-    int* lt = a.list_tok + (long)r * a.K;
-    float* ls = a.list_score + (long)r * a.K;
-    if (ps == NEG_INF) {                                         // dead row: an empty list
-        for (int i = lane; i < a.K; i += 64) { lt[i] = -1; ls[i] = NEG_INF; }
+    if (ps == NEG_INF) {                                         // dead row
+        if constexpr (!PRE)
+            for (int i = lane; i < a.K; i += 64) { a.list_tok[(long)r * a.K + i] = -1; a.list_score[(long)r * a.K + i] = NEG_INF; }
         return;
     }
+    const auto term = lm.row(a, r, st, lane);
     const float* z = logits + (long)r * ld;
     const bool no_eos = (st - 1) < a.minlen[u];                  // the hypothesis has st - 1 tokens
     const RowLse l = row_lse(z, a.C, lane);
-    row_top_n<false>(z, a.C, a.K, lane, [&](int c) { return no_eos && c == a.eos; },
-                     [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + ((z[c] - l.mx) - l.log_s); });
+    auto lp = [&](int c) { return (z[c] - l.mx) - l.log_s; };
+    auto skip = [&](int c) { return (PRE && c == 0) || (no_eos && c == a.eos); };
+    const float* rank = z;
+    float lm_w = 0.f;
+    if constexpr (Lm::FUSED) {
+        lm_w = PRE ? a.wts[2] : lm_w_arg;
+        float* fz = fused + (long)r * ldf;
+        for (int c = lane; c < a.C; c += 64) fz[c] = add_rn(lp(c), mul_rn(lm_w, term(c)));
+        __threadfence_block();                                   // lane 0 reads below what the other lanes of its wave stored
+        rank = fz;
+    }
+    if constexpr (PRE) {
+        int* pt = a.pre_tok + (long)r * a.P;
+        row_top_n<false>(rank, a.C, a.P, lane, skip, [&](int i, int c) { pt[i] = c; });
+        __threadfence_block();                                   // and the lanes read what lane 0 stored
+        for (int i = lane; i < a.P; i += 64) {
+            const int c = pt[i];
+            const bool ok = c > 0 && c < a.C;
+            a.pre_lp[(long)r * a.P + i] = ok ? lp(c) : NEG_INF;
+            if constexpr (Lm::FUSED) a.pre_lm[(long)r * a.P + i] = ok ? mul_rn(lm_w, term(c)) : 0.f;
+        }
+    } else {
+        int* lt = a.list_tok + (long)r * a.K;
+        float* ls = a.list_score + (long)r * a.K;
+        row_top_n<false>(rank, a.C, a.K, lane, skip,
+                         [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + (Lm::FUSED ? rank[c] : lp(c)); });
+    }
 }
 
 // K-way merge of an utterance's K sorted row lists by one wave (lane k = parent rank k): the n <= K best candidates, rank order, into the
@@ -253,22 +334,6 @@ __global__ __launch_bounds__(64) void beam_ctc_init_kernel(BeamArgs a) {
     }
 }
 
-// grid ceil(R / 4), 256 threads: one wave per live row.  pre_tok / pre_lp [R][P]: the row's P best tokens by logit (logit descending,
-// token ascending; blank never, eos once the hypothesis has minlen tokens), each with its fp32 attention log-prob; token -1 past the end
-__global__ __launch_bounds__(256) void beam_ctc_prebeam_kernel(BeamArgs a, const float* __restrict__ logits, long ld) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= a.R) return;
-    const int u = r / a.K, st = *a.step;
-    if (a.fin[u] || a.score[r] == NEG_INF) return;               // (the prefix kernel gives a dead row its empty list)
-    int* pt = a.pre_tok + (long)r * a.P;
-    float* pl = a.pre_lp + (long)r * a.P;
-    const float* z = logits + (long)r * ld;
-    const bool no_eos = (st - 1) < a.minlen[u];
-    const RowLse l = row_lse(z, a.C, lane);
-    row_top_n<false>(z, a.C, a.P, lane, [&](int c) { return c == 0 || (no_eos && c == a.eos); },
-                     [&](int i, int c) { pt[i] = c; pl[i] = c < 0 ? NEG_INF : (z[c] - l.mx) - l.log_s; });
-}
-
 // grid R, 128 threads: thread i runs the chain of the row's pre-beam candidate i (i < P <= 96), serial over the T_b frames.  The parent's
 // phi_t, r^b_t and x_t(blank) are staged in LDS by chunks of CTC_CH frames (every chain of the row shares them); the candidate's
 // (r^n_t, r^b_t) go to ctc_state[st & 1][r][t][i], so a wave's stores at one frame are contiguous.  Then the row's candidates are
@@ -389,6 +454,8 @@ __global__ __launch_bounds__(64) void beam_backtrace_nbest_kernel(BeamArgs a, in
 
 }  // namespace
 
+static int refuse(const char* fn, const char* why) { mk_set_error(fn, why); return -1; }
+
 int mk_beam_init(const BeamArgs& a, hipStream_t s) {
     const int n = a.R > a.B ? a.R : a.B;
     hipLaunchKernelGGL(beam_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
@@ -398,17 +465,44 @@ int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, f
     hipLaunchKernelGGL(beam_embed_step_kernel, dim3(a.R), dim3(256), 0, s, a, table, pe, y32, y16, E);
     return LAUNCH_OK();
 }
-int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_t s) {
-    hipLaunchKernelGGL(beam_row_topk_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, logits, ld);
+template <class Lm, bool PRE>
+static int launch_beam_rows(const BeamArgs& a, const Lm& src, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s) {
+    hipLaunchKernelGGL((beam_rows_kernel<Lm, PRE>), dim3((a.R + 3) / 4), dim3(256), 0, s, a, src, lm.lm_w, logits, ld, lm.fused, lm.ldf);
     return LAUNCH_OK();
 }
+int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s) {
+    const char* fn = "mk_beam_rows";
+    if (a.K < 1 || a.K > 64 || a.P < 0 || a.P > 96 || ld < a.C) return refuse(fn, "need 1 <= K <= 64, P <= 96, ld >= C");
+    const bool pre = a.P > 0;
+    if (!lm.ngram && !lm.lm_logits) {
+        const RowLmNone src{};
+        return pre ? launch_beam_rows<RowLmNone, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmNone, false>(a, src, lm, logits, ld, s);
+    }
+    if (!lm.fused || lm.ldf < a.C) return refuse(fn, "an LM needs the fused workspace, ldf >= C");
+    if (lm.ngram && lm.lm_logits) return refuse(fn, "one LM at most");
+    if (lm.lm_logits) {
+        if (pre) return refuse(fn, "the pre-beam takes no LM logits");      // (the one cell of the grid that no decode runs)
+        if (lm.ld_lm < a.C) return refuse(fn, "need ld_lm >= C");
+        return launch_beam_rows<RowLmLogits, false>(a, RowLmLogits{lm.lm_logits, lm.ld_lm}, lm, logits, ld, s);
+    }
+    if (lm.ngram->order < 1 || lm.ngram->order > LM_MAX_ORDER || lm.ngram->C != a.C) return refuse(fn, "need an LM of order 1 .. 4 over the beam's classes");
+    if (pre && (!a.wts || !a.pre_lm)) return refuse(fn, "the fused pre-beam needs the weights and the LM terms");
+    const RowLmNgram src{*lm.ngram};
+    return pre ? launch_beam_rows<RowLmNgram, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmNgram, false>(a, src, lm, logits, ld, s);
+}
 int mk_beam_select(const BeamArgs& a, hipStream_t s) {
-    if (a.K < 1 || a.K > 64) { mk_set_error("mk_beam_select", "beam size must be in [1, 64]"); return -1; }
-    hipLaunchKernelGGL(beam_select_kernel<false>, dim3(a.B), dim3(64), 0, s, a);
+    if (a.K < 1 || a.K > 64) return refuse("mk_beam_select", "beam size must be in [1, 64]");
+    if (a.P < 0 || a.P > 96 || (a.N && !a.P)) return refuse("mk_beam_select", "need P <= 96, and the joint beam (P >= 1) for an N-best list");
+    if (a.N && (a.N < 1 || a.N > a.K || !a.wts || !a.nb_score || !a.nb_len || !a.nb_row)) return refuse("mk_beam_select", "need 1 <= N <= K, the weights and the list");
+    if (a.N) hipLaunchKernelGGL(beam_select_nbest_kernel, dim3(a.B), dim3(64), 0, s, a);
+    else if (a.P) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(a.B), dim3(64), 0, s, a);
     return LAUNCH_OK();
 }
 int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
-    hipLaunchKernelGGL(beam_backtrace_kernel, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores);
+    if (a.N && (a.N < 1 || a.N > a.K || !a.nb_score || !a.nb_len || !a.nb_row)) return refuse("mk_beam_backtrace", "need 1 <= N <= K and the list");
+    if (a.N) hipLaunchKernelGGL(beam_backtrace_nbest_kernel, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores);
+    else hipLaunchKernelGGL(beam_backtrace_kernel, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores);
     return LAUNCH_OK();
 }
 
@@ -420,40 +514,15 @@ int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(beam_ctc_init_kernel, dim3(a.B), dim3(64), 0, s, a);
     return LAUNCH_OK();
 }
-int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s) {
-    hipLaunchKernelGGL(beam_ctc_prebeam_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, logits, ld);
-    return LAUNCH_OK();
-}
 int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s) {
-    if (a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_prefix", "pre-beam width must be in [1, 96]"); return -1; }
-    hipLaunchKernelGGL(beam_ctc_prefix_kernel<false>, dim3(a.R), dim3(128), 0, s, a);
+    if (a.P < 1 || a.P > 96) return refuse("mk_beam_ctc_prefix", "pre-beam width must be in [1, 96]");
+    if (a.N > 0 && (!a.wts || !a.pre_lm)) return refuse("mk_beam_ctc_prefix", "the LM variant needs the weights and the LM terms");
+    if (a.N > 0) hipLaunchKernelGGL(beam_ctc_prefix_kernel<true>, dim3(a.R), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL(beam_ctc_prefix_kernel<false>, dim3(a.R), dim3(128), 0, s, a);
     return LAUNCH_OK();
 }
-int mk_beam_ctc_prefix_lm(const BeamArgs& a, hipStream_t s) {
-    if (a.P < 1 || a.P > 96 || !a.wts || !a.pre_lm) { mk_set_error("mk_beam_ctc_prefix_lm", "need 1 <= P <= 96, the weights and the LM terms"); return -1; }
-    hipLaunchKernelGGL(beam_ctc_prefix_kernel<true>, dim3(a.R), dim3(128), 0, s, a);
-    return LAUNCH_OK();
-}
-int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s) {
-    if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96) { mk_set_error("mk_beam_ctc_select", "need 1 <= K <= 64, 1 <= P <= 96"); return -1; }
-    hipLaunchKernelGGL(beam_select_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
-    return LAUNCH_OK();
-}
-
 int mk_beam_set_weights(const BeamArgs& a, float att_w, float ctc_w, float lm_w, float len_bonus, hipStream_t s) {
-    if (!a.wts) { mk_set_error("mk_beam_set_weights", "null pointer"); return -1; }
+    if (!a.wts) return refuse("mk_beam_set_weights", "null pointer");
     hipLaunchKernelGGL(beam_set_weights_kernel, dim3(1), dim3(64), 0, s, const_cast<float*>(a.wts), att_w, ctc_w, lm_w, len_bonus);
-    return LAUNCH_OK();
-}
-int mk_beam_ctc_select_nbest(const BeamArgs& a, hipStream_t s) {
-    if (a.K < 1 || a.K > 64 || a.P < 1 || a.P > 96 || a.N < 1 || a.N > a.K || !a.wts || !a.nb_score || !a.nb_len || !a.nb_row) {
-        mk_set_error("mk_beam_ctc_select_nbest", "need 1 <= N <= K <= 64, 1 <= P <= 96, the weights and the list"); return -1;
-    }
-    hipLaunchKernelGGL(beam_select_nbest_kernel, dim3(a.B), dim3(64), 0, s, a);
-    return LAUNCH_OK();
-}
-int mk_beam_backtrace_nbest(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
-    if (a.N < 1 || a.N > a.K || !a.nb_score || !a.nb_len || !a.nb_row) { mk_set_error("mk_beam_backtrace_nbest", "need 1 <= N <= K and the list"); return -1; }
-    hipLaunchKernelGGL(beam_backtrace_nbest_kernel, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores);
     return LAUNCH_OK();
 }

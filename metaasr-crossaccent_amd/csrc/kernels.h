@@ -178,30 +178,35 @@ struct BeamArgs {
     float* nb_score; int *nb_len, *nb_row;     // [B][N] ended hypotheses, best first (best_* are not used): score, token count, row at step nb_len;
                                                // an empty slot holds -inf / -1 / the utterance's first row, and the empty slots are the last
 };
+// The LM of the row stage, if any (one at most): backoff n-gram tables (lm.h) or a row of LM logits per hypothesis row
+// (the LSTM LM, nlm.h).  Either one needs the fp32 workspace `fused`, where a row's fused increments stand while it is ranked
+struct LmDev;
+struct BeamRowLm {
+    const LmDev* ngram;                        // null: no n-gram LM
+    const float* lm_logits; long ld_lm;        // [R][ld_lm], null: no LM logits; lm(c) = their log-softmax
+    float* fused; long ldf;                    // [R][ldf]
+    float lm_w;                                // the LM weight of the top-K; the pre-beam reads a.wts[2]
+};
+// One step: mk_beam_embed_step, the decoder layers (engine), mk_beam_rows, in the joint beams mk_beam_ctc_prefix, and mk_beam_select.  Each
+// launcher picks its kernel by a.P (> 0: joint CTC/attention) and a.N (> 0: the joint LM beam with its N-best list):
+//   mk_beam_rows        logits [R][ld] -> P == 0: list_tok / list_score [R][K], the row's K best classes by the increment f(c); P > 0:
+//                       the pre-beam pre_tok / pre_lp (/ pre_lm) [R][P], the P best by f.  f(c) = lp(c), or with an LM
+//                       fl(lp(c) + fl(lm_w * lm(c | h))).  LM logits with P > 0 are refused: no decode runs that
+//   mk_beam_ctc_prefix  the prefix scores and the row sort of the pre-beam; N > 0: with the LM term and the length bonus, weights from a.wts
+//   mk_beam_select      the K-way merge; P > 0: the joint bookkeeping; N > 0: the N-best list and its stop rule.  Also advances step[0] once
+//                       all B utterances are done
+//   mk_beam_backtrace   once after the last step: tokens [B][Lmax], lens / scores [B]; N > 0: tokens [B][N][Lmax], lens / scores [B][N]
 int mk_beam_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s);
-int mk_beam_row_topk(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
-int mk_beam_select(const BeamArgs& a, hipStream_t s);                    // also advances step[0] once all B utterances are done
+int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s);
+int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
+int mk_beam_select(const BeamArgs& a, hipStream_t s);
 int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
-// joint CTC/attention beam (beam.hip): logits [B*Tp][ld] of the CTC head -> a.ctc_lp; the empty hypothesis's CTC state (after mk_beam_init);
-// per step the pre-beam, the prefix scores with the row sort, and the joint select (in place of mk_beam_row_topk / mk_beam_select)
+// once per joint decode: logits [B*Tp][ld] of the CTC head -> a.ctc_lp; the empty hypothesis's CTC state (after mk_beam_init); the joint LM
+// beam's four weights into a.wts (a plain launch in front of the step replays)
 int mk_beam_ctc_logsoftmax(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
 int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s);
-int mk_beam_ctc_prebeam(const BeamArgs& a, const float* logits, long ld, hipStream_t s);
-int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
-int mk_beam_ctc_select(const BeamArgs& a, hipStream_t s);                // also advances step[0]
-// joint beam with LM, bonus and N-best: the four weights into a.wts (a plain launch in front of the step replays); per step
-// mk_beam_ctc_lm_prebeam (lm.hip: the P best classes by g(c) = lp(c) + lm_w * lm(c | h), through the fp32 workspace fused [R][ldf]),
-// mk_beam_ctc_prefix_lm and mk_beam_ctc_select_nbest (also advances step[0]); mk_beam_backtrace_nbest: tokens [B][N][Lmax], lens / scores [B][N]
 int mk_beam_set_weights(const BeamArgs& a, float att_w, float ctc_w, float lm_w, float len_bonus, hipStream_t s);
-int mk_beam_ctc_prefix_lm(const BeamArgs& a, hipStream_t s);
-int mk_beam_ctc_select_nbest(const BeamArgs& a, hipStream_t s);
-int mk_beam_backtrace_nbest(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
-// n-gram LM shallow fusion (lm.hip, lm.h): in place of mk_beam_row_topk -- the row's K best classes by the fused increment
-// f(c) = lp(c) + lm_w * lm(c | h), through the fp32 workspace fused [R][ldf]; then mk_beam_select as ever
-struct LmDev;
-int mk_beam_lm_topk(const BeamArgs& a, const LmDev& lm, float lm_w, const float* logits, long ld, float* fused, long ldf, hipStream_t s);
-int mk_beam_ctc_lm_prebeam(const BeamArgs& a, const LmDev& lm, const float* logits, long ld, float* fused, long ldf, hipStream_t s);
 // out [R][C] = lm(c | ctx row) for every class; ctx int32 [R][order - 1], oldest first, -1 in front of a shorter context
 int mk_lm_score(const LmDev& lm, const int* ctx, int R, float* out, hipStream_t s);
 

@@ -46,7 +46,3 @@ inline int64_t nlm_state_elems(const NlmDev& d, int R) { return 2 * (int64_t)d.L
 int mk_nlm_step(const NlmDev& lm, const NlmStepArgs& a, float* logits, long ld, hipStream_t s);
 // out [R][ldo] = the log_softmax of logits [R][ld] over the C classes, (y - mx) - log_s of search.h row_lse
 int mk_nlm_logp(const float* logits, long ld, int R, int C, float* out, long ldo, hipStream_t s);
-// in place of mk_beam_row_topk: the row's K best classes by f(c) = fl(lp(c) + fl(lm_w * lm(c))), lm = the log_softmax of the row of
-// nlm_logits [R][ldn], through the fp32 workspace fused [R][ldf]; then mk_beam_select as ever
-struct BeamArgs;
-int mk_beam_nlm_topk(const BeamArgs& a, float lm_w, const float* logits, long ld, const float* nlm_logits, long ldn, float* fused, long ldf, hipStream_t s);

@@ -9,7 +9,7 @@
 // Per step (st read from the device scalar, so the launches are parameter-identical for every step and replay as one hipGraph):
 //   nlm_lstm_step   one launch per layer: gates = [x | h_par] [W_ih | W_hh]^T + b on MFMA, the cell in the epilogue
 //   skinny_gemm     the output projection of the top layer's new h -> fp32 LM logits [R][ld]   (decode.hip, no new kernel)
-//   beam_nlm_topk   beam_lm_topk with the LM term = log_softmax of that row
+//   beam_rows       the beams' row stage (beam.hip) with the LM term = log_softmax of that row
 #include <cmath>
 #include <cstring>
 #include <atomic>
@@ -26,20 +26,10 @@ namespace {
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
-// token and parent row of row r at step st, clamped as beam_embed_step clamps them: a stale entry can neither leave the class range nor
-// the utterance's rows
-__device__ __forceinline__ void nlm_row_source(const NlmStepArgs& a, const NlmDev& lm, int r, int st, int& tok, int& par) {
-    tok = lm.start_id; par = r;
-    if (st > 1) {
-        const long o = (long)(st - 2) * a.hist_stride + r;
-        tok = a.tok_hist[o];
-        if (tok < 0 || tok >= lm.C) tok = 0;
-        if (a.par_hist) {
-            const int u0 = (r / a.K) * a.K;
-            par = a.par_hist[o];
-            if (par < u0 || par >= u0 + a.K) par = r;
-        }
-    }
+// token and parent row of row r at step st (search.h hist_entry: clamped); an id outside the LM's classes reads as 0
+__device__ __forceinline__ HistEntry nlm_row_source(const NlmStepArgs& a, const NlmDev& lm, int r, int st) {
+    if (st <= 1) return {lm.start_id, r};
+    return hist_entry(a.tok_hist, a.par_hist, a.hist_stride, st - 1, r, lm.C, a.K, 0);
 }
 
 // Layer l of one step.  grid (Hp / 16, ceil(R / 16)), 256 threads: a workgroup owns 16 rows x 16 hidden units x the four gates, its four
@@ -56,8 +46,8 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     const int Hp = lm.Hp, INp = l ? Hp : lm.Ep, KT = INp + Hp;
     const long LS = (long)a.R * Hp;                              // one layer's states
     int row = r0 + (lane & 15); if (row > a.R - 1) row = a.R - 1;
-    int tok, par;
-    nlm_row_source(a, lm, row, st, tok, par);
+    const HistEntry src = nlm_row_source(a, lm, row, st);
+    const int tok = src.tok, par = src.par;
     const int ko = 8 * (lane >> 4);
     const bf16* __restrict__ x = (l ? a.hstate + ((long)cur * lm.L + (l - 1)) * LS + (long)row * Hp : lm.embed + (long)tok * lm.Ep) + ko;
     const bf16* __restrict__ hp = a.hstate + ((long)prv * lm.L + l) * LS + (long)par * Hp + ko;
@@ -93,8 +83,7 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     float z[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) z[g] = ((red[0][g][tm][tn] + red[1][g][tm][tn]) + (red[2][g][tm][tn] + red[3][g][tm][tn])) + lm.b[l][g * Hp + u];
-    nlm_row_source(a, lm, m, st, tok, par);
-    const float cp = st == 1 ? 0.f : a.cstate[((long)prv * lm.L + l) * LS + (long)par * Hp + u];
+    const float cp = st == 1 ? 0.f : a.cstate[((long)prv * lm.L + l) * LS + (long)nlm_row_source(a, lm, m, st).par * Hp + u];
     const float ig = sigm(z[0]), fg = sigm(z[1]), gg = tanhf(z[2]), og = sigm(z[3]);      // torch gate order i, f, g, o
     const float cn = fg * cp + ig * gg;
     const bf16 h = (bf16)(og * tanhf(cn));
@@ -102,32 +91,6 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     a.cstate[o] = cn;
     a.hstate[o] = h;
     if (l == lm.L - 1) a.htop[(long)m * Hp + u] = h;
-}
-
-// grid ceil(R / 4), 256 threads: one wave per live row.  beam_lm_topk_kernel (lm.hip) with the LM term read from the row of LM logits:
-// lm(c) = (y_c - mx) - log_s of row_lse, <= 0; f(c) = fl(lp(c) + fl(lm_w * lm(c))), two roundings, no fused multiply-add
-__global__ __launch_bounds__(256) void beam_nlm_topk_kernel(BeamArgs a, float lm_w, const float* __restrict__ logits, long ld,
-                                                           const float* __restrict__ nlm_logits, long ldn, float* __restrict__ fused, long ldf) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= a.R) return;
-    const int u = r / a.K, st = *a.step;
-    if (a.fin[u]) return;
-    const float ps = a.score[r];
-    int* lt = a.list_tok + (long)r * a.K;
-    float* ls = a.list_score + (long)r * a.K;
-    if (ps == NEG_INF) {                                         // dead row: an empty list
-        for (int i = lane; i < a.K; i += 64) { lt[i] = -1; ls[i] = NEG_INF; }
-        return;
-    }
-    const float* z = logits + (long)r * ld;
-    const float* y = nlm_logits + (long)r * ldn;
-    float* fz = fused + (long)r * ldf;
-    const bool no_eos = (st - 1) < a.minlen[u];                  // the hypothesis has st - 1 tokens
-    const RowLse l = row_lse(z, a.C, lane), ll = row_lse(y, a.C, lane);
-    for (int c = lane; c < a.C; c += 64) fz[c] = add_rn((z[c] - l.mx) - l.log_s, mul_rn(lm_w, (y[c] - ll.mx) - ll.log_s));
-    __threadfence_block();                                       // lane 0 reads below what the other lanes of its wave stored
-    row_top_n<false>(fz, a.C, a.K, lane, [&](int c) { return no_eos && c == a.eos; },
-                     [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + fz[c]; });
 }
 
 // grid ceil(R / 4), 256 threads: one wave per row
@@ -198,13 +161,6 @@ int mk_nlm_logp(const float* logits, long ld, int R, int C, float* out, long ldo
     hipLaunchKernelGGL(nlm_logp_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, ld, R, C, out, ldo);
     return LAUNCH_OK();
 }
-int mk_beam_nlm_topk(const BeamArgs& a, float lm_w, const float* logits, long ld, const float* nlm_logits, long ldn, float* fused, long ldf,
-                     hipStream_t s) {
-    if (a.K < 1 || a.K > 64 || ldn < a.C || ldf < a.C) { mk_set_error("mk_beam_nlm_topk", "need 1 <= K <= 64, ldn >= C, ldf >= C"); return -1; }
-    hipLaunchKernelGGL(beam_nlm_topk_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a, lm_w, logits, ld, nlm_logits, ldn, fused, ldf);
-    return LAUNCH_OK();
-}
-
 extern "C" {
 
 masr_nlm* masr_nlm_create(int C, int E, int H, int L, int start_id, const float* embed, const float* const* w_ih, const float* const* w_hh,

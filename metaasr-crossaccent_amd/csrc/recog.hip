@@ -348,36 +348,20 @@ static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, 
                                   DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0), -1, nlm});
 }
 
-// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  Joint
-// CTC/attention (ba.P > 0): pre-beam, prefix scores and the joint select in place of the row top-K and the select.  LM fusion (lm): the
-// fused top-K (lm.hip) in place of the row top-K.  Both (ba.N > 0): the fused pre-beam, the prefix scores with the LM term and
-// the bonus, the select with the N-best list; the weights are read from ba.wts, lm->w is not used.
-// LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last tokens and parent states (nlm.hip; it reads
-// only what the previous step's select wrote, so it sits in front of the decoder layers), and its fused top-K in place of the row top-K.
-struct LmStep { LmDev dev; float w; float* fused; };
-struct NlmStep { NlmDev dev; float w; NlmStepArgs args; float* logits; float* fused; };
-static int beam_step(Ctx& c, const BeamArgs& ba, bf16* step_qkv, const LmStep* lm = nullptr, const NlmStep* nlm = nullptr) {
+// One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  The launchers
+// pick their kernels by ba.P (joint CTC/attention: the pre-beam, the prefix scores, the joint select) and ba.N (the joint LM beam,
+// the prefix scores with the LM term and the bonus, the select with the N-best list; the weights are read from ba.wts), the row
+// stage by `lm`.  LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last tokens and parent states
+// (nlm.hip; it reads only what the previous step's select wrote, so it sits in front of the decoder layers) fill lm.lm_logits.
+static int beam_step(Ctx& c, const DecodeBufs& bufs, const BeamRowLm& lm, const masr_nlm* nlm, const NlmStepArgs& nlm_args) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
+    const BeamArgs& ba = bufs.beam;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
-    if (nlm) CK(mk_nlm_step(nlm->dev, nlm->args, nlm->logits, m->Cp, s));
-    CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
-    if (ba.N) {
-        CK(mk_beam_ctc_lm_prebeam(ba, lm->dev, a.logits, m->Cp, lm->fused, m->Cp, s));
-        CK(mk_beam_ctc_prefix_lm(ba, s));
-        CK(mk_beam_ctc_select_nbest(ba, s));                    // also advances *step_dev
-        return 0;
-    }
-    if (ba.P) {
-        CK(mk_beam_ctc_prebeam(ba, a.logits, m->Cp, s));
-        CK(mk_beam_ctc_prefix(ba, s));
-        CK(mk_beam_ctc_select(ba, s));                          // also advances *step_dev
-        return 0;
-    }
-    if (nlm) CK(mk_beam_nlm_topk(ba, nlm->w, a.logits, m->Cp, nlm->logits, m->Cp, nlm->fused, m->Cp, s));
-    else if (lm) CK(mk_beam_lm_topk(ba, lm->dev, lm->w, a.logits, m->Cp, lm->fused, m->Cp, s));
-    else CK(mk_beam_row_topk(ba, a.logits, m->Cp, s));
-    CK(mk_beam_select(ba, s));                                  // also advances *step_dev
-    return 0;
+    if (nlm) CK(mk_nlm_step(nlm->dev, nlm_args, bufs.nlm_logits, m->Cp, s));
+    CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, bufs.step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
+    CK(mk_beam_rows(ba, lm, a.logits, m->Cp, s));
+    if (ba.P) CK(mk_beam_ctc_prefix(ba, s));
+    return mk_beam_select(ba, s);                               // also advances *step_dev
 }
 
 // which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm), masr_recog_beam_ctc_lm (joint, lm
@@ -429,28 +413,28 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
         CK(mk_beam_ctc_init(ba, s));
         memcpy(key + 4, &mode.att_w, sizeof(float)); memcpy(key + 5, &mode.ctc_w, sizeof(float));
     }
-    LmStep ls{};
+    BeamRowLm rl{};
+    rl.lm_w = mode.N ? 0.f : mode.lm_w;                         // (the joint LM beam reads ba.wts: its graph holds no weight)
+    if (mode.lm || mode.nlm) { rl.fused = bufs.lm_fused; rl.ldf = m->Cp; }
     if (mode.lm) {
-        ls = LmStep{mode.lm->dev, mode.lm_w, bufs.lm_fused};
+        rl.ngram = &mode.lm->dev;
         memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.lm->serial;
     }
     if (mode.N) {
         CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
         key[4] = mode.N;
     }
-    NlmStep ns{};
+    NlmStepArgs na{};
     if (mode.nlm) {
-        ns.dev = mode.nlm->dev; ns.w = mode.lm_w; ns.logits = bufs.nlm_logits; ns.fused = bufs.lm_fused;
-        ns.args.step = ba.step; ns.args.R = ba.R; ns.args.K = ba.K; ns.args.tok_hist = ba.tok_hist; ns.args.par_hist = ba.par_hist;
-        ns.args.hist_stride = ba.R; ns.args.score = ba.score; ns.args.fin = ba.fin;
-        ns.args.hstate = bufs.nlm_h; ns.args.cstate = bufs.nlm_c; ns.args.htop = bufs.nlm_htop;
+        rl.lm_logits = bufs.nlm_logits; rl.ld_lm = m->Cp;
+        na.step = ba.step; na.R = ba.R; na.K = ba.K; na.tok_hist = ba.tok_hist; na.par_hist = ba.par_hist;
+        na.hist_stride = ba.R; na.score = ba.score; na.fin = ba.fin;
+        na.hstate = bufs.nlm_h; na.cstate = bufs.nlm_c; na.htop = bufs.nlm_htop;
         memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.nlm->serial;
     }
     DecodeGraph& graph = mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
-    CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed",
-                 [&] { return beam_step(c, ba, bufs.step_qkv, mode.lm ? &ls : nullptr, mode.nlm ? &ns : nullptr); }));
-    if (mode.N) CK(mk_beam_backtrace_nbest(ba, tokens, lens, scores, s));
-    else CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
+    CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed", [&] { return beam_step(c, bufs, rl, mode.nlm, na); }));
+    CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
     return 0;
 }
@@ -589,7 +573,7 @@ int masr_recog_beam_ctc(masr_model* m, const float* xs, const int64_t* ilens, in
 
 int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
                        float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
-    // n-gram LM shallow fusion into the attention beam (lm.hip): masr_recog_beam with the fused top-K in place of the row top-K
+    // n-gram LM shallow fusion into the attention beam: masr_recog_beam with the n-gram term fused into its row stage
     const char* fn = "masr_recog_beam_lm";
     CK(check_model(fn, m));
     CK(check_lm(fn, m, lm, lm_w, nullptr));
@@ -600,7 +584,7 @@ int masr_recog_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const 
 int masr_recog_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, float min_step_ratio,
                         float max_step_ratio, float lm_w, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
     // LSTM LM shallow fusion into the attention beam (nlm.hip): masr_recog_beam with the LM's step in front of the decoder layers
-    // and the fused top-K in place of the row top-K
+    // and its term fused into the row stage
     const char* fn = "masr_recog_beam_nlm";
     CK(check_model(fn, m));
     if (!nlm) return fail(fn, "null language model");

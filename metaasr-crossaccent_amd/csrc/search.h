@@ -26,7 +26,7 @@ __device__ __forceinline__ float log_add(float a, float b) {      // log(e^a + e
 
 // fl(a * b) and fl(a + b) that no later pass fuses into a multiply-add: under the default -ffp-contract the plain operators (and __fmul_rn /
 // __fadd_rn, which are the plain operators) were contracted in ctc_beam_sweep<true>, fma(lm_w, lm, len_bonus).  The LM-fused searches
-// (ctc_beam.hip, the joint LM beam of beam.hip / lm.hip) compose their scores from these two
+// (ctc_beam.hip, the row stage and the joint LM beam of beam.hip) compose their scores from these two
 __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;
@@ -48,7 +48,7 @@ __device__ __forceinline__ void wave_argmax_first(float& mx, int& am) {
 
 // Log-sum-exp of the row z[0 .. C) in two parts, lse = mx + log_s: strided max, wave_max, strided sum of __expf(z - mx), wave_sum,
 // __logf -- fp32 in that order.  The caller composes its log-prob, and the two compositions in use round differently:
-//   (z - mx) - log_s    beam_row_topk, beam_ctc_logsoftmax, beam_ctc_prebeam (beam.hip)
+//   (z - mx) - log_s    beam_rows, beam_ctc_logsoftmax (beam.hip)
 //   z - (mx + log_s)    ctc_beam_frames, and ctc_beam_sweep through the stored lse (ctc_beam.hip)
 // They may not be merged: the decoders' scores are pinned bit for bit to the written order, and the two kernels of ctc_beam.hip must
 // agree with each other (a class scores the same whether it is read from the frame's token set or gathered as a prefix's last token).
@@ -86,6 +86,20 @@ __device__ __forceinline__ void row_top_n(const float* z, int C, int N, int lane
             break;
         }
     }
+}
+
+// The step beams' histories, [step][stride]: token s >= 1 of the hypothesis that stands in row `row` after step s, and the row it stood in
+// after step s - 1 (par_hist null: the row itself).  Rows of a finished utterance are not written any more, so an entry may be stale: the
+// read is clamped -- a token outside [0, C) reads as `fallback`, a parent outside the K rows of the row's utterance as the row.  Every
+// kernel that walks the histories reads them through this (beam_embed_step and the n-gram context of beam.hip, nlm_lstm_step of nlm.hip)
+struct HistEntry { int tok, par; };
+__device__ __forceinline__ HistEntry hist_entry(const int* tok_hist, const int* par_hist, long stride, int s, int row, int C, int K, int fallback) {
+    const long o = (long)(s - 1) * stride + row;
+    const int u0 = (row / K) * K;
+    int tok = tok_hist[o], par = par_hist ? par_hist[o] : row;
+    if (tok < 0 || tok >= C) tok = fallback;
+    if (par < u0 || par >= u0 + K) par = row;
+    return {tok, par};
 }
 
 // Step ticket of a per-step kernel whose n blocks each end their part of step st: the last one to arrive resets the ticket and advances

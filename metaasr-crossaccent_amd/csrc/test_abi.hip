@@ -103,7 +103,7 @@ static int test_ctc_prefix(const char* fn, const float* lp, int C, int T, int la
     a.ctc_lp = lp; a.ctc_state = reinterpret_cast<float2*>(w + 256);
     a.pre_tok = const_cast<int*>(cand); a.pre_lp = const_cast<float*>(att_lp);
     a.list_tok = list_tok; a.list_score = list_score; a.list_psi = list_psi; a.list_slot = list_slot;
-    if (pre_lm) { a.pre_lm = const_cast<float*>(pre_lm); a.wts = flts + 4; a.att_w = a.ctc_w = 0.f; }      // (the LM kernel reads its weights from a.wts)
+    if (pre_lm) { a.N = 1; a.pre_lm = const_cast<float*>(pre_lm); a.wts = flts + 4; a.att_w = a.ctc_w = 0.f; }      // (N > 0: the LM kernel, which reads its weights from a.wts)
     int rc = 0;
     auto run = [&]() -> int {
         HIP_CHECK_RET(hipMemcpyAsync(ints, h_ints, sizeof h_ints, hipMemcpyHostToDevice, s));
@@ -112,7 +112,7 @@ static int test_ctc_prefix(const char* fn, const float* lp, int C, int T, int la
         if (last < 0) CK(mk_beam_ctc_init(a, s));            // (writes psi 0 and src 0: the empty hypothesis)
         else HIP_CHECK_RET(hipMemcpy2DAsync(a.ctc_state + plane, (size_t)n * sizeof(float2), parent, sizeof(float2), sizeof(float2), T,
                                             hipMemcpyDeviceToDevice, s));
-        CK(pre_lm ? mk_beam_ctc_prefix_lm(a, s) : mk_beam_ctc_prefix(a, s));
+        CK(mk_beam_ctc_prefix(a, s));
         HIP_CHECK_RET(hipMemcpyAsync(out_state, a.ctc_state + (st & 1) * plane, plane * sizeof(float2), hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipStreamSynchronize(s));
         return 0;
@@ -208,7 +208,7 @@ int masr_test_beam_step(int B, int K, int C, int sos, int eos, int t, const int3
         HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
-        CK(mk_beam_row_topk(a, logits, ld, s));
+        CK(mk_beam_rows(a, BeamRowLm{}, logits, ld, s));
         CK(mk_beam_select(a, s));
         HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
@@ -245,40 +245,12 @@ int masr_test_lm_max_probe(const masr_lm* lm) {
     if (!lm) { mk_set_error("masr_test_lm_max_probe", "null model"); return -1; }
     return lm->max_probe;
 }
-int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
-                           const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* list_tok, float* list_score, void* stream) {
-    const char* fn = "masr_test_beam_lm_topk";
-    if (!lm || !minlen || !logits || !score || !list_tok || !list_score || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
-    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
-    const int C = lm->dev.C;
-    if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
-    hipStream_t s = (hipStream_t)stream;
-    const int R = B * K;
-    char* w = nullptr;                                       // step[2] | fin [B] | fused [R][ld]
-    const size_t fin_off = 64, fused_off = (fin_off + sizeof(int) * (size_t)B + 255) & ~(size_t)255;
-    HIP_CHECK_RET(hipMalloc(&w, fused_off + sizeof(float) * (size_t)R * ld));
-    const int h_step[2] = {t, 0};
-    BeamArgs a{};
-    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen;
-    a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
-    a.list_tok = list_tok; a.list_score = list_score; a.fin = (int*)(w + fin_off);
-    auto run = [&]() -> int {
-        HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
-        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
-        CK(mk_beam_lm_topk(a, lm->dev, lm_w, logits, ld, (float*)(w + fused_off), ld, s));
-        HIP_CHECK_RET(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = run();
-    hipFree(w);
-    return rc;
-}
-// ---- the joint LM beam's step kernels (DESIGN 5.7)
-int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
-                               const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* pre_tok, float* pre_lp, float* pre_lm,
-                               void* stream) {
-    const char* fn = "masr_test_joint_lm_prebeam";
-    if (!lm || !minlen || !logits || !score || !pre_tok || !pre_lp || !pre_lm || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
+}  // extern "C"
+// masr_test_beam_lm_topk and masr_test_joint_lm_prebeam (out.P > 0): the row stage with the n-gram LM at step t on the caller's logits,
+// scores and histories.  `out` brings the entry's output arrays (and P); the rest of the beam's state is filled in here
+static int test_lm_rows(const char* fn, const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                        const float* score, const int32_t* tok_hist, const int32_t* par_hist, BeamArgs a, void* stream) {
+    if (!lm || !minlen || !logits || !score || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
     if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
     const int C = lm->dev.C;
     if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
@@ -288,21 +260,41 @@ int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int 
     const size_t wts_off = 64, fin_off = 128, fused_off = (fin_off + sizeof(int) * (size_t)B + 255) & ~(size_t)255;
     HIP_CHECK_RET(hipMalloc(&w, fused_off + sizeof(float) * (size_t)R * ld));
     const int h_step[2] = {t, 0};
-    BeamArgs a{};
-    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen; a.P = std::max(1, 3 * K / 2);
+    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen;
     a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
-    a.pre_tok = pre_tok; a.pre_lp = pre_lp; a.pre_lm = pre_lm; a.fin = (int*)(w + fin_off); a.wts = (float*)(w + wts_off);
+    a.fin = (int*)(w + fin_off); a.wts = (float*)(w + wts_off);
+    BeamRowLm rl{};
+    rl.ngram = &lm->dev; rl.fused = (float*)(w + fused_off); rl.ldf = ld; rl.lm_w = lm_w;
     auto run = [&]() -> int {
         HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
         HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
-        CK(mk_beam_set_weights(a, 0.f, 0.f, lm_w, 0.f, s));
-        CK(mk_beam_ctc_lm_prebeam(a, lm->dev, logits, ld, (float*)(w + fused_off), ld, s));
+        if (a.P) CK(mk_beam_set_weights(a, 0.f, 0.f, lm_w, 0.f, s));     // (the pre-beam reads its weight from the device)
+        CK(mk_beam_rows(a, rl, logits, ld, s));
         HIP_CHECK_RET(hipStreamSynchronize(s));
         return 0;
     };
     const int rc = run();
     hipFree(w);
     return rc;
+}
+extern "C" {
+int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                           const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* list_tok, float* list_score, void* stream) {
+    const char* fn = "masr_test_beam_lm_topk";
+    if (!list_tok || !list_score) { mk_set_error(fn, "null pointer"); return -1; }
+    BeamArgs out{};
+    out.list_tok = list_tok; out.list_score = list_score;
+    return test_lm_rows(fn, lm, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
+}
+// ---- the joint LM beam's step kernels (DESIGN 5.7)
+int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
+                               const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* pre_tok, float* pre_lp, float* pre_lm,
+                               void* stream) {
+    const char* fn = "masr_test_joint_lm_prebeam";
+    if (!pre_tok || !pre_lp || !pre_lm) { mk_set_error(fn, "null pointer"); return -1; }
+    BeamArgs out{};
+    out.P = std::max(1, 3 * K / 2); out.pre_tok = pre_tok; out.pre_lp = pre_lp; out.pre_lm = pre_lm;
+    return test_lm_rows(fn, lm, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
 }
 int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, const int32_t* list_tok,
                                 const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,
@@ -334,7 +326,7 @@ int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t
         HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         CK(mk_beam_set_weights(a, 0.f, 0.f, 0.f, len_bonus, s));
-        CK(mk_beam_ctc_select_nbest(a, s));
+        CK(mk_beam_select(a, s));
         HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
         HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));

@@ -448,7 +448,7 @@ def test_recog_argmax_step(L, B):
                                                [(int(got[st - 1, b]), int(want[st - 1, b])) for b in range(B) if got[st - 1, b] != want[st - 1, b]][:8])
 
 
-# ---------------------------------------------------------------- beam step glue (beam.hip beam_row_topk_kernel + beam_select_kernel<false>)
+# ---------------------------------------------------------------- beam step glue (beam.hip beam_rows_kernel without an LM + beam_select_kernel<false>)
 NEG = -np.inf
 SENT_TOK, SENT_SC, SENT_HIST = 12345, 777.0, -99
 

@@ -1,6 +1,6 @@
 """The step kernels of the joint beam with LM, bonus and N-best alone through include/masr_test.h:
   masr_test_joint_lm_prebeam   the fused pre-beam on random logits against numpy (as test_hip_lm_kernels.py checks beam_lm_topk), pre_lm bit
-                               for bit fl(lm_w * lm32)
+                               for bit fl(lm_w * lm32); and against masr_test_beam_lm_topk on the same inputs: one fused increment, bit for bit
   masr_test_ctc_prefix_lm      the prefix kernel with the LM term and the bonus: list_psi and the states to the tolerances of
                                test_hip_ctc_prefix_kernel.py, list_score bit for bit from the returned list_psi and the inputs in the written
                                order (a fused multiply-add shows here), and masr_test_ctc_prefix's output at pre_lm = 0, bonus = 0
@@ -46,7 +46,8 @@ def bits(a):
 
 
 # ---------------------------------------------------------------- the fused pre-beam
-def run_prebeam(L, C_, order, B, K, t, lm_w, seed, minlen_on):
+def prebeam_inputs(C_, order, B, K, t, seed, minlen_on):
+    """random logits (pad columns that would win every list), scores with one dead row, minlen, and histories over the LM's own tokens"""
     d, lm = toy(C_, order)
     rng = np.random.RandomState(seed)
     R, Pw, eos = B * K, max(1, 3 * K // 2), C_ - 1
@@ -63,6 +64,13 @@ def run_prebeam(L, C_, order, B, K, t, lm_w, seed, minlen_on):
     pool = sorted({w for g in d["grams"][min(1, order - 1)] for w in g if 0 < w < C_ - 1})
     tok_hist = np.array(pool, dtype=np.int32)[rng.randint(len(pool), size=(max(t - 1, 1), R))]
     par_hist = ((np.arange(R) // K * K)[None, :] + rng.randint(K, size=(max(t - 1, 1), R))).astype(np.int32)
+    return d, lm, z, score, dead, minlen, tok_hist, par_hist
+
+
+def run_prebeam(L, C_, order, B, K, t, lm_w, seed, minlen_on):
+    d, lm, z, score, dead, minlen, tok_hist, par_hist = prebeam_inputs(C_, order, B, K, t, seed, minlen_on)
+    R, Pw, eos = B * K, max(1, 3 * K // 2), C_ - 1
+    ld = z.shape[1]
     dz, ds, dm = torch.from_numpy(z).to(DEV), torch.from_numpy(score).to(DEV), torch.from_numpy(minlen).to(DEV)
     dt, dp = (torch.from_numpy(tok_hist).to(DEV), torch.from_numpy(par_hist).to(DEV)) if t > 1 else (None, None)
     pt = torch.full((R, Pw), -7, dtype=torch.int32, device=DEV)
@@ -123,6 +131,54 @@ def test_fused_prebeam(L, order, C_):
             n_pos += a; n_ok += b
     print(f"C = {C_}, order {order}: {n_ok} of {n_pos} pre-beam positions have neighbours > 1e-4 apart")
     assert n_ok >= 0.9 * n_pos, (n_ok, n_pos)
+
+
+@pytest.mark.parametrize("lm_w", [0.3, 0.7])                 # inexact products: at 0.5 or 2.0 a multiply-add and two roundings agree
+@pytest.mark.parametrize("C_, order, B, K, t", [(367, 3, 2, 64, 3), (12, 3, 3, 4, 2)])     # P = 96, 128 rows in two utterances; P = 6
+def test_topk_and_prebeam_compose_alike(L, C_, order, B, K, t, lm_w):
+    """The LM beam's top-K and the joint LM beam's pre-beam rank one row by the same f(c) = fl(lp(c) + fl(lm_w * lm(c | h))): on the same
+    inputs, with score +0 (list_score is then f itself) and minlen 0, every non-blank class of a row's K-list stands in its P-list
+    (P >= K + 1 and only blank is removed), list_score equals fl(pre_lp + pre_lm) bit for bit, and the common classes keep their order."""
+    d, lm, z, score, dead, minlen, tok_hist, par_hist = prebeam_inputs(C_, order, B, K, t, seed=7000 + C_ + K, minlen_on=False)
+    R, Pw, ld = B * K, 3 * K // 2, z.shape[1]
+    assert dead >= 0 and Pw >= K + 1
+    minlen[:] = 0
+    score[:] = 0.0
+    score[dead] = -np.inf
+    dz, ds, dm = torch.from_numpy(z).to(DEV), torch.from_numpy(score).to(DEV), torch.from_numpy(minlen).to(DEV)
+    dt, dp = torch.from_numpy(tok_hist).to(DEV), torch.from_numpy(par_hist).to(DEV)
+    lt = torch.full((R, K), -7, dtype=torch.int32, device=DEV)
+    ls = torch.full((R, K), float("nan"), device=DEV)
+    pt = torch.full((R, Pw), -7, dtype=torch.int32, device=DEV)
+    pl = torch.full((R, Pw), float("nan"), device=DEV)
+    pm = torch.full((R, Pw), float("nan"), device=DEV)
+    _cabi.check(L.masr_test_beam_lm_topk(lm.h, float(lm_w), B, K, t, P(dm), P(dz), ld, P(ds), P(dt), P(dp), P(lt), P(ls), S()), "masr_test_beam_lm_topk")
+    _cabi.check(L.masr_test_joint_lm_prebeam(lm.h, float(lm_w), B, K, t, P(dm), P(dz), ld, P(ds), P(dt), P(dp), P(pt), P(pl), P(pm), S()),
+                "masr_test_joint_lm_prebeam")
+    lt, ls, pt, pl, pm = lt.cpu().numpy(), ls.cpu().numpy(), pt.cpu().numpy(), pl.cpu().numpy(), pm.cpu().numpy()
+    n_cmp, missing, differ, disorder = 0, [], [], []
+    for r in range(R):
+        if r == dead:
+            continue
+        place = {int(c): i for i, c in enumerate(pt[r]) if c > 0}
+        common = [(i, int(c)) for i, c in enumerate(lt[r]) if c > 0]
+        assert len(common) >= K - 1, (r, lt[r])             # at most blank leaves the K-list
+        for i, c in common:
+            if c not in place:
+                missing.append((r, i, c))
+                continue
+            n_cmp += 1
+            f = F32(pl[r, place[c]]) + F32(pm[r, place[c]])
+            if bits(ls[r, i]) != bits(f):
+                differ.append((r, i, c, float(ls[r, i]), float(f)))
+        seq = [place[c] for _, c in common if c in place]
+        if seq != sorted(seq):
+            disorder.append((r, seq))
+    print(f"C = {C_}, K = {K}, lm_w = {lm_w}: {n_cmp} positions compared, {len(differ)} differ, {len(missing)} missing, {len(disorder)} rows out of order")
+    assert n_cmp >= (R - 1) * (K - 1), n_cmp
+    assert not missing, missing[:5]
+    assert not differ, (len(differ), n_cmp, differ[:5])
+    assert not disorder, disorder[:3]
 
 
 # ---------------------------------------------------------------- the prefix kernel with the LM term and the bonus

@@ -4,7 +4,7 @@ random-init weights, K = 1 / 4 / 10 / 20, N = 1 and N = K, with tools/bench_lm_b
 decode replays its step graph Lmax = T / 4 times whatever the stop rule decides, so ms per step = ms per decode / steps includes the
 encoder's share in all columns alike; the difference of two columns is the fused pre-beam, the LM prefix kernel and the N-best select
 against the joint beam's three step kernels.  For per-launch times run this under
-`rocprofv3 --kernel-trace --stats -- python tools/bench_joint_lm_beam.py` and read beam_ctc_lm_prebeam_kernel, beam_ctc_prefix_kernel and
+`rocprofv3 --kernel-trace --stats -- python tools/bench_joint_lm_beam.py` and read beam_rows_kernel, beam_ctc_prefix_kernel and
 beam_select_nbest_kernel in the stats.
 usage: python tools/bench_joint_lm_beam.py [B] [T] [n-grams in all]"""
 import json

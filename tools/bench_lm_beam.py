@@ -3,7 +3,7 @@ the hkust geometry, B = 16, T = 1000 (as tools/bench_beam.py), random-init weigh
 10^6 n-grams over the 367 classes (random n-grams with random log-probabilities: the kernel's work -- up to two table probes and the dense
 unigram per class -- does not depend on the values).  Both decodes replay all T / 4 steps (random weights never end a hypothesis early at
 lm_w = 0.3 with min_step_ratio = 1), so ms per step = ms per decode / steps includes the encoder's share in both columns alike; the
-difference of the two columns is beam_lm_topk against beam_row_topk.
+difference of the two columns is the row stage (beam_rows_kernel) with the n-gram LM against the one without.
 usage: python tools/bench_lm_beam.py [B] [T] [n-grams in all]"""
 import json
 import sys

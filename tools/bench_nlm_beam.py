@@ -2,8 +2,8 @@
 hkust geometry, B = 16, T = 1000 (as tools/bench_beam.py), random-init weights, K = 1 / 4 / 10 / 20, with a random 2 x 650 LSTM LM on
 650-dim embeddings over the 367 classes (the kernels' work does not depend on the values).  Both decodes replay all T / 4 steps (random
 weights never end a hypothesis early at lm_w = 0.3 with min_step_ratio = 1), so ms per step = ms per decode / steps includes the encoder's
-share in both columns alike; the difference of the two columns is the LM's L layer launches, its output projection and beam_nlm_topk against
-beam_row_topk.
+share in both columns alike; the difference of the two columns is the LM's L layer launches, its output projection and the row stage (beam_rows_kernel)
+with the LM logits against the one without.
 usage: python tools/bench_nlm_beam.py [B] [T] [H] [L]"""
 import json
 import sys
