@@ -377,6 +377,24 @@ int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, co
                            float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
                            void* stream);
 
+/* The same one-pass joint CTC/attention beam with the LSTM LM in place of the n-gram.  It is masr_recog_beam_ctc_lm word for word
+ * with one substitution: lm(c | h) is the LSTM LM's, as masr_recog_beam_nlm defines it (feed [start] + h from the zero state; lm = (y_c - mx) -
+ * log_s over the fp32 LM logits; every hypothesis row carries (h, c) per layer, double-buffered by step parity; a row reads its parent's state of
+ * the step before).  The pre-beam by g(c) = fl(lp(c) + fl(lm_w * lm(c | h))), P = floor(3K/2), blank never, eos from minlen tokens on, the
+ * five-rounding score, the N-best list, the bound stop rule and the result layout [B][N][Lmax] / [B][N] / [B][N] are that entry's.  Every LM term
+ * is <= 0, so the stop-rule argument of DESIGN 5.7 carries over.  lm_w = 0 gives masr_recog_beam_ctc_lm's result at lm_w = 0 bit for bit.
+ * -1 with a message, before any launch: everything masr_recog_beam_ctc_lm refuses, a null LSTM LM, an LM whose C is not the model's odim, lm_w
+ * negative or not finite, len_bonus not finite, N outside [1, K]; -2: a workspace below
+ * masr_beam_ctc_nlm_workspace_bytes(m, nlm, B, T, K, N, Lmax) = masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax) (its fused rows are shared)
+ * plus, with R = B * K, Cp = odim padded to 128, Hp = H padded to 32 and each entry rounded up to 256 bytes:
+ *   R * Cp * 4  (the LM logits)  +  2 * L * R * Hp * 2  (h)  +  2 * L * R * Hp * 4  (c)  +  R * Hp * 2  (the top layer's new h).
+ * The step is captured as its own hipGraph, keyed on (B, T, K, Lmax, N, the LM); the four weights are device values written before the replays,
+ * so a call with other weights replays the same graph and never an old value. */
+int64_t masr_beam_ctc_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int N, int Lmax);
+int masr_recog_beam_ctc_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int N,
+                            float min_step_ratio, float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens,
+                            int32_t* lens, float* scores, void* stream);
+
 /* CTC prefix beam search on the CTC head alone (hybrid models of masr_create_ctc): the encoder and the head GEMM of
  * masr_recog_beam_ctc, then masr_ctc_beam_search (below) on the head's fp32 logits with blank 0, eos = odim - 1, Tp = T / 4 and
  * enc_len = floor(ilens[b] / 4).  Result (device): tokens int32 [B][nbest][T/4], lens int32 [B][nbest], scores fp32 [B][nbest].  A model

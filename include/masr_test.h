@@ -214,6 +214,13 @@ int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, c
 int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
                                const float* score, const int32_t* tok_hist, const int32_t* par_hist, int32_t* pre_tok, float* pre_lp, float* pre_lm,
                                void* stream);
+/* the row stage with caller-given LM logit rows (the LSTM LM's place in masr_recog_beam_nlm and masr_recog_beam_ctc_nlm, DESIGN 5.10 / 5.11;
+ * tests/test_hip_nlm_joint_kernels.py): lm_logits fp32 [R][ld_lm] over C classes (2 <= C <= ld_lm, ld), the rest as masr_test_beam_lm_topk; no
+ * history is read.  lm(c) = the row's log-softmax.  pre_tok null: the top-K form, out list_tok int32 / list_score fp32 [R][K].  pre_tok given:
+ * the pre-beam form, out pre_tok int32 / pre_lp / pre_lm fp32 [R][P] as masr_test_joint_lm_prebeam gives them, P = floor(3K/2). */
+int masr_test_beam_nlm_rows(const float* lm_logits, int64_t ld_lm, float lm_w, int B, int K, int C, int t, const int32_t* minlen, const float* logits,
+                            int64_t ld, const float* score, int32_t* list_tok, float* list_score, int32_t* pre_tok, float* pre_lp, float* pre_lm,
+                            void* stream);
 /* masr_test_ctc_prefix through beam_ctc_prefix_kernel<LM>: pre_lm fp32 [n] the candidates' weighted LM terms, len_bonus added to a token's score
  * (not to eos's); list_score = fl(fl(fl(fl(score + fl(att_w lp)) + fl(ctc_w fl(psi - psi_par))) + pre_lm) + b) */
 int masr_test_ctc_prefix_lm(const float* lp, int C, int T, int last, const float* parent, float psi_par, float score, const int32_t* cand,

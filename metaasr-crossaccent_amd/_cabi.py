@@ -93,6 +93,8 @@ _SIGS = {
     "masr_nlm_score": (i32, [vp, vp, vp, i32, i32, vp, vp, i64, vp]),
     "masr_beam_ctc_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
     "masr_recog_beam_ctc_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "masr_beam_ctc_nlm_workspace_bytes": (i64, [vp, vp, i32, i32, i32, i32, i32]),
+    "masr_recog_beam_ctc_nlm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_ctc_beam_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "masr_recog_ctc_beam": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "masr_recog_ctc_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
@@ -153,6 +155,7 @@ _SIGS = {
     "masr_test_lm_max_probe": (i32, [vp]),
     "masr_test_beam_lm_topk": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_test_joint_lm_prebeam": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_beam_nlm_rows": (i32, [vp, i64, f32, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_ctc_prefix_lm": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
     "masr_test_beam_select_nbest": (i32, [i32, i32, i32, i32, i32, vp, f32] + [vp] * 15),
     "masr_test_attn_decode": (i32, [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, i64, vp]),
@@ -302,14 +305,16 @@ def check_lm_args(lm, lm_w, len_bonus):
     return lm_w, len_bonus
 
 
-def check_nlm_args(nlm, lm_w):
-    """what the LSTM-LM-fused beam vets on the Python side -> lm_w as a float"""
+def check_nlm_args(nlm, lm_w, len_bonus=None):
+    """what the LSTM-LM-fused beams vet on the Python side -> lm_w as a float; with a len_bonus (the joint beam) -> (lm_w, len_bonus)"""
     lm_w = float(lm_w)
     if not (math.isfinite(lm_w) and lm_w >= 0.0):
         raise ValueError(f"lm_w must be finite and >= 0, got {lm_w}")
+    if len_bonus is not None and not math.isfinite(float(len_bonus)):
+        raise ValueError(f"len_bonus must be finite, got {float(len_bonus)}")
     if getattr(nlm, "h", None) is None or not hasattr(nlm, "score"):
         raise ValueError("lm must be a live LstmLM")
-    return lm_w
+    return lm_w if len_bonus is None else (lm_w, float(len_bonus))
 
 
 def check(rc, what=""):

@@ -9,7 +9,8 @@
 //   beam_rows         one wave per live row: fp32 log-softmax and the row's K best tokens (logit descending, token ascending).  The one
 //                     row stage of every step beam: an n-gram LM (masr_recog_beam_lm) or a row of LSTM-LM logits
 //                     (masr_recog_beam_nlm) adds its weighted term and the row is ranked by the fused increment; in the joint
-//                     beams it emits the P-long pre-beam for beam_ctc_prefix instead of the K-long list
+//                     beams it emits the P-long pre-beam for beam_ctc_prefix instead of the K-long list, with either
+//                     LM's term in its ranking
 //   beam_select       one wave per utterance: K-way merge of the K sorted row lists -> the K best candidates (score descending,
 //                     parent rank ascending, then the row order above), ended / running bookkeeping, finished flag, step ticket
 // beam_backtrace runs once after the last step.
@@ -480,13 +481,16 @@ int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, lo
     }
     if (!lm.fused || lm.ldf < a.C) return refuse(fn, "an LM needs the fused workspace, ldf >= C");
     if (lm.ngram && lm.lm_logits) return refuse(fn, "one LM at most");
+    const bool pre_ok = !pre || (a.wts && a.pre_lm);
+    const char* pre_need = "the fused pre-beam needs the weights and the LM terms";
     if (lm.lm_logits) {
-        if (pre) return refuse(fn, "the pre-beam takes no LM logits");      // (the one cell of the grid that no decode runs)
         if (lm.ld_lm < a.C) return refuse(fn, "need ld_lm >= C");
-        return launch_beam_rows<RowLmLogits, false>(a, RowLmLogits{lm.lm_logits, lm.ld_lm}, lm, logits, ld, s);
+        if (!pre_ok) return refuse(fn, pre_need);
+        const RowLmLogits src{lm.lm_logits, lm.ld_lm};
+        return pre ? launch_beam_rows<RowLmLogits, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmLogits, false>(a, src, lm, logits, ld, s);
     }
     if (lm.ngram->order < 1 || lm.ngram->order > LM_MAX_ORDER || lm.ngram->C != a.C) return refuse(fn, "need an LM of order 1 .. 4 over the beam's classes");
-    if (pre && (!a.wts || !a.pre_lm)) return refuse(fn, "the fused pre-beam needs the weights and the LM terms");
+    if (!pre_ok) return refuse(fn, pre_need);
     const RowLmNgram src{*lm.ngram};
     return pre ? launch_beam_rows<RowLmNgram, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmNgram, false>(a, src, lm, logits, ld, s);
 }

@@ -124,6 +124,13 @@ static int check_lm(const char* fn, const masr_model* m, const masr_lm* lm, floa
     CK(check_weight(fn, "lm_w", lm_w, false));
     return !len_bonus || std::isfinite(*len_bonus) ? 0 : fail(fn, "len_bonus must be finite");
 }
+// the same for the LSTM LM
+static int check_nlm(const char* fn, const masr_model* m, const masr_nlm* nlm, float lm_w, const float* len_bonus) {
+    if (!nlm) return fail(fn, "null language model");
+    if (nlm->dev.C != m->C) return fail(fn, "the language model's classes differ from the model's odim");
+    CK(check_weight(fn, "lm_w", lm_w, false));
+    return !len_bonus || std::isfinite(*len_bonus) ? 0 : fail(fn, "len_bonus must be finite");
+}
 static int check_pointers(const char* fn, const float* xs, const int64_t* ilens, const int32_t* tokens, const int32_t* lens, const float* scores) {
     return xs && ilens && tokens && lens && scores ? 0 : fail(fn, "null pointer");
 }
@@ -150,6 +157,8 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   log-probs [B][C][Tp] and the candidates' prefix states [2][R][Tp][P] follow everything else
 //   joint with LM, bonus and N-best (masr_recog_beam_ctc_lm, P > 0, lm, NB > 0): both of the above, then the candidates' LM terms [R][P], the
 //   four weights and the N-best list [B][NB]
+//   joint with the LSTM LM (masr_recog_beam_ctc_nlm, P > 0, nlm, NB > 0): the joint LM beam's plan with the LSTM LM fusion's buffers behind
+//   the shared fused rows
 //   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
 //   buffer follow
 //   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
@@ -272,6 +281,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
                                    : d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : d.NB && d.nlm ? "workspace too small (masr_beam_ctc_nlm_workspace_bytes(nlm, B, T, K, N, Lmax))"
                                    : d.NB ? "workspace too small (masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
                                    : d.lm ? "workspace too small (masr_beam_lm_workspace_bytes(B, T, K, Lmax))"
@@ -340,7 +350,7 @@ static int ctc_head_logits(Ctx& c, float* ctc_logits) {
 
 static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's CTC_SCORING_RATIO 1.5
 
-// the four step beams' workspace queries: one predicate, and one message but for the N-best variant's (N < 0: no list)
+// the step beams' workspace queries: one predicate, and one message but for the N-best variant's (N < 0: no list)
 static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, int T, int K, int Lmax, bool joint, bool lm, int N = -1,
                                    const masr_nlm* nlm = nullptr) {
     return decode_workspace_bytes(fn, m, shape_ok(B, T, K) && Lmax >= 1 && (N < 0 || (N >= 1 && N <= K)),
@@ -350,9 +360,10 @@ static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, 
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  The launchers
 // pick their kernels by ba.P (joint CTC/attention: the pre-beam, the prefix scores, the joint select) and ba.N (the joint LM beam,
-// the prefix scores with the LM term and the bonus, the select with the N-best list; the weights are read from ba.wts), the row
-// stage by `lm`.  LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last tokens and parent states
-// (nlm.hip; it reads only what the previous step's select wrote, so it sits in front of the decoder layers) fill lm.lm_logits.
+// DESIGN 5.7 and, with the LSTM LM, 5.11: the prefix scores with the LM term and the bonus, the select with the N-best list; the weights are
+// read from ba.wts), the row stage by `lm`.  LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last
+// tokens and parent states (nlm.hip; it reads only what the previous step's select wrote, so it sits in front of the decoder layers) fill
+// lm.lm_logits.
 static int beam_step(Ctx& c, const DecodeBufs& bufs, const BeamRowLm& lm, const masr_nlm* nlm, const NlmStepArgs& nlm_args) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     const BeamArgs& ba = bufs.beam;
@@ -365,7 +376,8 @@ static int beam_step(Ctx& c, const DecodeBufs& bufs, const BeamRowLm& lm, const 
 }
 
 // which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm), masr_recog_beam_ctc_lm (joint, lm
-// and the N-best list) or masr_recog_beam_nlm (nlm); each has its own cached step graph
+// and the N-best list), masr_recog_beam_nlm (nlm) or masr_recog_beam_ctc_nlm (joint, nlm and the N-best list); each has its own cached step
+// graph
 struct BeamMode {
     bool joint = false; float att_w = 0.f, ctc_w = 0.f;         // joint CTC/attention: the two weights
     const masr_lm* lm = nullptr; float lm_w = 0.f;              // n-gram LM fusion
@@ -377,7 +389,7 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     // Beam search over the KV-cached decoder step (semantics: beam.hip and DESIGN 9).  maxlen / minlen per utterance from
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
     // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers; joint with
-    // LM: N and the serial number -- its four weights are device values written in front of the replays, no graph holds one) and
+    // either LM: N and the serial number -- its four weights are device values written in front of the replays, no graph holds one) and
     // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
     CK(check_beam_size(fn, K));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
@@ -420,10 +432,6 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
         rl.ngram = &mode.lm->dev;
         memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.lm->serial;
     }
-    if (mode.N) {
-        CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
-        key[4] = mode.N;
-    }
     NlmStepArgs na{};
     if (mode.nlm) {
         rl.lm_logits = bufs.nlm_logits; rl.ld_lm = m->Cp;
@@ -432,7 +440,11 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
         na.hstate = bufs.nlm_h; na.cstate = bufs.nlm_c; na.htop = bufs.nlm_htop;
         memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.nlm->serial;
     }
-    DecodeGraph& graph = mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
+    if (mode.N) {
+        CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
+        key[4] = mode.N;
+    }
+    DecodeGraph& graph = mode.nlm && mode.N ? m->joint_nlm_graph : mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
     CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed", [&] { return beam_step(c, bufs, rl, mode.nlm, na); }));
     CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
     m->have_acts = false;
@@ -544,6 +556,11 @@ int64_t masr_beam_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, 
 int64_t masr_beam_ctc_lm_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
     return beam_workspace_bytes("masr_beam_ctc_lm_workspace_bytes", m, B, T, K, Lmax, true, true, N);
 }
+int64_t masr_beam_ctc_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int N, int Lmax) {
+    const char* fn = "masr_beam_ctc_nlm_workspace_bytes";
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    return beam_workspace_bytes(fn, m, B, T, K, Lmax, true, false, N, nlm);
+}
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
     return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, shape_ok(B, T, K), "need B >= 1, T >= 4, 1 <= K <= 64", B, T, DecodeSpec{K, 0, 0, true});
 }
@@ -587,9 +604,7 @@ int masr_recog_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, con
     // and its term fused into the row stage
     const char* fn = "masr_recog_beam_nlm";
     CK(check_model(fn, m));
-    if (!nlm) return fail(fn, "null language model");
-    if (nlm->dev.C != m->C) return fail(fn, "the language model's classes differ from the model's odim");
-    CK(check_weight(fn, "lm_w", lm_w, false));
+    CK(check_nlm(fn, m, nlm, lm_w, nullptr));
     BeamMode mode; mode.nlm = nlm; mode.lm_w = lm_w;
     return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
 }
@@ -607,6 +622,23 @@ int masr_recog_beam_ctc_lm(masr_model* m, const masr_lm* lm, const float* xs, co
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "N", N, K));
     BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w; mode.lm = lm; mode.lm_w = lm_w; mode.N = N; mode.len_bonus = len_bonus;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_ctc_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float min_step_ratio,
+                            float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, int32_t* tokens, int32_t* lens, float* scores,
+                            void* stream) {
+    // masr_recog_beam_ctc_lm with the LSTM LM's term in the pre-beam and the score: the LM's step in front of the decoder layers,
+    // as in masr_recog_beam_nlm
+    const char* fn = "masr_recog_beam_ctc_nlm";
+    CK(check_model(fn, m));
+    CK(check_ctc_head(fn, m));
+    CK(check_weight(fn, "ctc_w", ctc_w, true));
+    CK(check_weight(fn, "att_w", att_w, false));
+    CK(check_nlm(fn, m, nlm, lm_w, &len_bonus));
+    CK(check_beam_size(fn, K));
+    CK(check_nbest(fn, "N", N, K));
+    BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w; mode.nlm = nlm; mode.lm_w = lm_w; mode.N = N; mode.len_bonus = len_bonus;
     return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
 }
 

@@ -247,12 +247,15 @@ int masr_test_lm_max_probe(const masr_lm* lm) {
 }
 }  // extern "C"
 // masr_test_beam_lm_topk and masr_test_joint_lm_prebeam (out.P > 0): the row stage with the n-gram LM at step t on the caller's logits,
-// scores and histories.  `out` brings the entry's output arrays (and P); the rest of the beam's state is filled in here
-static int test_lm_rows(const char* fn, const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
-                        const float* score, const int32_t* tok_hist, const int32_t* par_hist, BeamArgs a, void* stream) {
-    if (!lm || !minlen || !logits || !score || (t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
+// scores and histories.  `out` brings the entry's output arrays (and P); the rest of the beam's state is filled in here.
+// masr_test_beam_nlm_rows: the same with caller-given LM logit rows [R][ld_lm] over C classes in the n-gram's place (no history is read)
+static int test_lm_rows(const char* fn, const masr_lm* lm, const float* lm_logits, int64_t ld_lm, int C, float lm_w, int B, int K, int t,
+                        const int32_t* minlen, const float* logits, int64_t ld, const float* score, const int32_t* tok_hist, const int32_t* par_hist,
+                        BeamArgs a, void* stream) {
+    if ((!lm && !lm_logits) || !minlen || !logits || !score || (lm && t > 1 && (!tok_hist || !par_hist))) { mk_set_error(fn, "null pointer"); return -1; }
     if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
-    const int C = lm->dev.C;
+    if (lm) C = lm->dev.C;
+    else if (C < 2 || ld_lm < C) { mk_set_error(fn, "need C >= 2 and ld_lm >= C"); return -1; }
     if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
     hipStream_t s = (hipStream_t)stream;
     const int R = B * K;
@@ -264,7 +267,9 @@ static int test_lm_rows(const char* fn, const masr_lm* lm, float lm_w, int B, in
     a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
     a.fin = (int*)(w + fin_off); a.wts = (float*)(w + wts_off);
     BeamRowLm rl{};
-    rl.ngram = &lm->dev; rl.fused = (float*)(w + fused_off); rl.ldf = ld; rl.lm_w = lm_w;
+    if (lm) rl.ngram = &lm->dev;
+    else { rl.lm_logits = lm_logits; rl.ld_lm = ld_lm; }
+    rl.fused = (float*)(w + fused_off); rl.ldf = ld; rl.lm_w = lm_w;
     auto run = [&]() -> int {
         HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
         HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
@@ -284,7 +289,7 @@ int masr_test_beam_lm_topk(const masr_lm* lm, float lm_w, int B, int K, int t, c
     if (!list_tok || !list_score) { mk_set_error(fn, "null pointer"); return -1; }
     BeamArgs out{};
     out.list_tok = list_tok; out.list_score = list_score;
-    return test_lm_rows(fn, lm, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
+    return test_lm_rows(fn, lm, nullptr, 0, 0, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
 }
 // ---- the joint LM beam's step kernels
 int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int t, const int32_t* minlen, const float* logits, int64_t ld,
@@ -294,7 +299,23 @@ int masr_test_joint_lm_prebeam(const masr_lm* lm, float lm_w, int B, int K, int 
     if (!pre_tok || !pre_lp || !pre_lm) { mk_set_error(fn, "null pointer"); return -1; }
     BeamArgs out{};
     out.P = std::max(1, 3 * K / 2); out.pre_tok = pre_tok; out.pre_lp = pre_lp; out.pre_lm = pre_lm;
-    return test_lm_rows(fn, lm, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
+    return test_lm_rows(fn, lm, nullptr, 0, 0, lm_w, B, K, t, minlen, logits, ld, score, tok_hist, par_hist, out, stream);
+}
+// ---- the row stage with LM logits: pre_tok given = the pre-beam form, else top-K
+int masr_test_beam_nlm_rows(const float* lm_logits, int64_t ld_lm, float lm_w, int B, int K, int C, int t, const int32_t* minlen, const float* logits,
+                            int64_t ld, const float* score, int32_t* list_tok, float* list_score, int32_t* pre_tok, float* pre_lp, float* pre_lm,
+                            void* stream) {
+    const char* fn = "masr_test_beam_nlm_rows";
+    BeamArgs out{};
+    if (pre_tok) {
+        if (!pre_lp || !pre_lm) { mk_set_error(fn, "null pointer"); return -1; }
+        out.P = std::max(1, 3 * K / 2); out.pre_tok = pre_tok; out.pre_lp = pre_lp; out.pre_lm = pre_lm;
+    } else {
+        if (!list_tok || !list_score) { mk_set_error(fn, "null pointer"); return -1; }
+        out.list_tok = list_tok; out.list_score = list_score;
+    }
+    if (!lm_logits) { mk_set_error(fn, "null pointer"); return -1; }
+    return test_lm_rows(fn, nullptr, lm_logits, ld_lm, C, lm_w, B, K, t, minlen, logits, ld, score, nullptr, nullptr, out, stream);
 }
 int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, const int32_t* list_tok,
                                 const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,

@@ -425,6 +425,25 @@ class MasrEngine:
         self._last_x = xs
         return out if raw else nbest_lists(*out)
 
+    def recog_beam_ctc_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
+                           min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, att_weight: float = 0.7, ctc_weight: float = 0.3,
+                           raw: bool = False):
+        """recog_beam_ctc_lm with the LSTM LM `nlm` (an LstmLM over this model's odim classes) in the n-gram's place (masr_recog_beam_ctc_nlm,
+        DESIGN 5.11; needs a hybrid model): the LM's term in the pre-beam and in the score, every hypothesis carrying the LM's recurrent
+        state.  lm_w finite and >= 0, len_bonus finite of any sign, ctc_weight > 0, att_weight >= 0, nbest in [1, beam_size].  Returns what
+        recog_beam_ctc_lm returns: per utterance a list of at most nbest (token list, score), best first (raw: the device tensors)."""
+        K, N = check_beam_args(beam_size, nbest)
+        lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_ctc_nlm_workspace_bytes", nlm.h, B, T, K, N, Lmax)
+        out = self._outputs(B, N, ld=Lmax)
+        check(self._l.masr_recog_beam_ctc_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio), float(max_step_ratio),
+                                              float(att_weight), float(ctc_weight), lm_w, len_bonus, *map(_ptr, out), self.stream()),
+              "masr_recog_beam_ctc_nlm")
+        self._last_x = xs
+        return out if raw else nbest_lists(*out)
+
     def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
         head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first

@@ -135,6 +135,14 @@ class MyTransformer:
         return self.engine.recog_beam_ctc_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest, min_step_ratio, max_step_ratio,
                                              att_weight, ctc_weight)
 
+    def nlm_joint_beam_decode(self, xs_pad, ilens, beam_size, nlm, lm_weight=0.3, len_bonus=0.0, nbest=1, min_step_ratio=0.0, max_step_ratio=1.0,
+                              att_weight=0.7, ctc_weight=0.3):
+        """lm_joint_beam_decode with the LSTM LM `nlm` (an LstmLM) in the n-gram's place (masr_recog_beam_ctc_nlm, hybrid models only): per
+        utterance a list of at most nbest (token list, score), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_ctc_nlm(xs_pad, ilens, beam_size, nlm, lm_weight, len_bonus, nbest, min_step_ratio, max_step_ratio,
+                                              att_weight, ctc_weight)
+
     def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam, hybrid models only): per utterance a list of at most
         nbest (token list, score), best first"""

@@ -24,7 +24,8 @@ anything is decoded.  Tester.MODES is the table of them:
                  checkpoint of Embedding -> LSTM -> Linear over the output units (nlm.py has the two key layouts; tools/train_nlm.py
                  writes one), weighted by lm_w (0.3); the step ratios as for `beam`; lm_start: sos | eos (sos) is the token the LM is
                  started with (eos: LMs trained with sos = eos).  Without a path the mode raises NotImplementedError; so does a BLSTM.
-                 A hybrid model with ctc_w > 0 raises ValueError (set ctc_w: 0); a plain model logs that ctc_w is ignored.
+                 A hybrid model with ctc_w > 0 raises ValueError (set ctc_w: 0; the joint search with this LM is `nlm_joint_beam`); a
+                 plain model logs that ctc_w is ignored.
   lm_ctc_beam    masr_recog_ctc_beam_lm (BLSTM-CTC: masr_ctc_beam_search_lm), `ctc_beam` with that LM and a per-token bonus fused into
                  the search: `--lm_model_path` as for `lm_beam`, lm_w (0.3), len_bonus (0, finite, any sign).  Refuses what
                  `ctc_beam` refuses, and a BLSTM whose blank is not id 0 (its slot serves as the LM's <s>).
@@ -35,6 +36,12 @@ anything is decoded.  Tester.MODES is the table of them:
                  the step ratios as for `beam`, with ctc_w > 0 required (absent or 0: ValueError, that search is `lm_beam`); lm_w (0.3),
                  len_bonus (0, finite, any sign), nbest (1, in [1, beam_size]).  No path or a BLSTM raises NotImplementedError, a
                  transformer without a CTC head ValueError.
+  nlm_joint_beam masr_recog_beam_ctc_nlm, `lm_joint_beam` with the LSTM LM of `nlm_beam` in the n-gram's place: the LM's term in the
+                 pre-beam and the score, a per-token bonus and an N-best list whose best entry is written.  `--lm_model_path` and lm_start
+                 as for `nlm_beam`; att_w / ctc_w (ctc_w > 0 required: absent or 0 raises ValueError, that search is `nlm_beam`), the step
+                 ratios, lm_w (0.3), len_bonus (0, finite, any sign) and nbest (1, in [1, beam_size]) as for `lm_joint_beam`.  This is where a
+                 hybrid model that `nlm_beam` refuses for its ctc_w goes.  No path or a BLSTM raises NotImplementedError, a transformer
+                 without a CTC head ValueError, an LM over another number of classes ValueError.
   ctc_align      masr_recog_ctc_align (BLSTM-CTC: masr_ctc_align per utterance), the CTC forced alignment of DESIGN 5.9: no search, so no
                  solver.beam_decode block is read.  Each test utterance's REFERENCE transcript is aligned to the frames of the CTC output
                  layer, and one line per utterance is appended to `<decode_dir>/ctc-ali` (no best-hyp is written):
@@ -327,6 +334,32 @@ class Tester:
         logger.notice(f"Joint CTC/attention beam with LM: {lm}, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, lm_w = {self.lm_weight}, "
                       f"len_bonus = {self.len_bonus}, nbest = {self.nbest}")
 
+    def _nlm_joint_settings(self):
+        """_lm_joint_settings' search with _nlm_beam_settings' LM"""
+        lm_path = self._lm_model_path("a torch checkpoint of an LSTM LM over the output units")
+        if self.model_name == 'blstm':
+            raise NotImplementedError("nlm_joint_beam: the joint CTC/attention beam needs the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode ctc_beam or greedy")
+        bd = self._beam_size()
+        self._need_ctc_head('nlm_joint_beam', "nlm_beam, beam or greedy")
+        self._step_ratios(bd)
+        self.ctc_weight = self._weight(bd, 'ctc_w', 0.0)
+        if not self.ctc_weight > 0.0:
+            raise ValueError("nlm_joint_beam: solver.beam_decode.ctc_w must be > 0 (it is absent or 0); to fuse the LSTM LM into the attention "
+                             "beam alone use --decode_mode nlm_beam")
+        self.att_weight = self._weight(bd, 'att_w', 1.0 - self.ctc_weight)
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self._len_bonus(bd)
+        self._nbest(bd, 1)
+        start = bd.get('lm_start', 'sos')
+        if start not in ('sos', 'eos'):
+            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
+        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
+        if self.nlm.C != len(self.id2ch):
+            raise ValueError(f"nlm_joint_beam: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        logger.notice(f"Joint CTC/attention beam with LSTM LM: {lm}, start token {start}, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, "
+                      f"lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}, nbest = {self.nbest}")
+
     # ------------------------------------------------------------------ the decode modes
     def _ctc_best(self, lists):
         """the best entry of each N-best list of a CTC beam (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is
@@ -370,6 +403,10 @@ class Tester:
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
                               xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],
                           lambda t: f"joint CTC/attention beam decoding with LM fusion (beam {t.beam_size})"),
+        'nlm_joint_beam': (_nlm_joint_settings,
+                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.nlm_joint_beam_decode(
+                               xs, il, t.beam_size, t.nlm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],
+                           lambda t: f"joint CTC/attention beam decoding with LSTM LM fusion (beam {t.beam_size})"),
     }
 
     def exec(self):

@@ -1,5 +1,5 @@
 """What the decoder benchmark scripts share (bench_beam, bench_joint_beam, bench_ctc_beam, bench_lm_beam, bench_ctc_lm_beam,
-bench_joint_lm_beam, bench_rescore): the hkust geometry, an engine on it, the synthetic n-gram LM and the timing loop.  Importing it
+bench_joint_lm_beam, bench_nlm_joint_beam, bench_rescore): the hkust geometry, an engine on it, the synthetic n-gram LM and the timing loop.  Importing it
 runs nothing; the scripts put the repository root on sys.path first."""
 import time
 
