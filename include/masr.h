@@ -409,6 +409,17 @@ int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, in
 int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
                            float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream);
 
+/* masr_recog_ctc_beam with the LSTM LM fused into the search: the same encoder pass and head GEMM, then masr_ctc_beam_search_nlm
+ * (below) with blank 0 and eos = odim - 1; scores and am as masr_recog_ctc_beam_lm gives them.  One frame of the search is captured as a
+ * hipGraph of its own, keyed on (B, T, K, the LM) and replayed T / 4 times; lm_w and len_bonus are device values written before the replays,
+ * so a call with other weights replays the same graph and never an old value.  -1 with a message, before any launch: everything
+ * masr_recog_ctc_beam_lm refuses, a null LSTM LM, an LM whose C is not the model's odim; -2: a workspace below
+ * masr_ctc_beam_nlm_workspace_bytes(m, nlm, B, T, K) = masr_ctc_beam_workspace_bytes(B, T, K) with masr_ctc_beam_nlm_work_bytes(nlm, B, T / 4,
+ * odim, K) in the place of the plain search's work buffer. */
+int64_t masr_ctc_beam_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K);
+int masr_recog_ctc_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
+                            float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream);
+
 /* CTC forced alignment of each utterance's transcript on the CTC head (hybrid models of masr_create_ctc): the encoder and the head
  * GEMM of masr_recog_ctc_beam, then masr_ctc_align (below) on the head's fp32 logits with blank 0, Tp = T / 4 and enc_len = floor(ilens[b] / 4)
  * -- frames, start and end count ENCODER frames, one per 4 input frames.  ys_flat / olens are host int64 as masr_run_batch takes them: the
@@ -453,6 +464,15 @@ int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int
 int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
                           float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
                           int32_t* order, void* stream);
+/* masr_recog_rescore_lm with the LSTM LM search of masr_recog_ctc_beam_nlm(K, nbest = N, lm_w, len_bonus) as its first pass: c(b, n)
+ * is that pass's fused score, copied bit for bit into `ctc`; the second pass and the single host synchronisation are masr_recog_rescore's.
+ * -1 with a message, before any launch: everything masr_recog_rescore_lm refuses, a null LSTM LM, an LM whose C is not the model's odim;
+ * -2: a workspace below masr_rescore_nlm_workspace_bytes(m, nlm, B, T, K, N, Lmax) = masr_rescore_workspace_bytes(B, T, K, N, Lmax) with
+ * masr_ctc_beam_nlm_work_bytes(nlm, B, T / 4, odim, K) in the place of the first pass's work buffer. */
+int64_t masr_rescore_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int N, int Lmax);
+int masr_recog_rescore_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
+                           float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
+                           int32_t* order, void* stream);
 int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,
                        const int32_t* lens_in, const float* ctc_in, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att,
                        float* ctc, int32_t* order, void* stream);
@@ -590,6 +610,31 @@ int64_t masr_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K);
 int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                             const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
                             float* scores, float* am, void* stream);
+
+/* masr_ctc_beam_search_lm with the LSTM LM (masr_nlm_create) in the n-gram's place.  Model-free.  It is that search word for word
+ * with one substitution: lm(c | h) is the LSTM LM's, as masr_recog_beam_nlm defines it -- feed [start] + h from the zero state; lm = (y_c - mx) -
+ * log_s over the fp32 LM logits.  lmacc, the purely acoustic p_b / p_nb, S_t by acoustic logit alone, the merge test and the prefix hash, the
+ * ranking, the selection order, the end-of-utterance term, the final re-rank and the result layout (am included; enc_len 0: the empty prefix
+ * with am 0 and score fl(lm_w * lm(eos | ()))) are masr_ctc_beam_search_lm's.  Needs blank == 0, eos == C - 1, nlm->C == C <= 4096, lm_w finite
+ * and >= 0, len_bonus finite.
+ *   LM state   lmacc AND the LM's recurrent state of a prefix are functions of its token sequence alone: a prefix that is merged into keeps its
+ *              state and takes no LM step; one that leaves the beam and is created again gets the same bits from whichever parent produced
+ *              it (an LM step's result for a row depends neither on the row's index nor on the rows around it).
+ *   the search is frame-synchronous across launches: per frame one kernel runs every utterance's frame (the beam lives in the work buffer, by
+ *              parity), then the LM advances on the B * K rows -- a row that took a token steps from its parent's state, a row that stayed
+ *              copies its parent's state and log-softmax row.  All Tp frames are launched; an utterance past its enc_len idles.
+ * With lm_w == 0, tokens, lens, scores and am equal masr_ctc_beam_search_lm's at lm_w == 0 and the same len_bonus bit for bit (every LSTM lm is
+ * finite and <= 0, so DESIGN 5.6's signed-zero argument carries over); with len_bonus == 0 as well, masr_ctc_beam_search's.
+ * Every refusal returns -1 with its text in masr_last_error() before anything is launched: what masr_ctc_beam_search_lm refuses, a null LSTM LM,
+ * a work buffer that is not 256-byte aligned or below masr_ctc_beam_nlm_work_bytes(nlm, B, Tp, C, K) = masr_ctc_beam_work_bytes(B, Tp, C, K)
+ * plus, with R = B * K, Cp = C padded to 128, Hp = H padded to 32 and each entry rounded up to 256 bytes:
+ *   8 + 8  (the step word, the two weights)  +  5 * (2 * R * 4) + 2 * (2 * R * 8)  (the beam by parity: p_b, p_nb, lmacc, last, len; hash, parent
+ *   hash)  +  2 * B * 4  (live counts)  +  2 * (R * 4)  (the frame's token and parent row)  +  2 * L * R * Hp * 2  (h)  +  2 * L * R * Hp * 4  (c)
+ *   +  R * Hp * 2  (the top layer's new h)  +  R * Cp * 4  (the LM logits)  +  2 * R * Cp * 4  (the log-softmax rows by parity). */
+int64_t masr_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K);
+int masr_ctc_beam_search_nlm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                             const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
+                             float* scores, float* am, void* stream);
 
 /* CTC forced alignment: the single best alignment (Viterbi path) of a known transcript to the frames of a CTC output layer, model-free like
  * masr_ctc_loss and masr_ctc_beam_search.  logits and enc_lens as for masr_ctc_beam_search (row of utterance b, frame t at

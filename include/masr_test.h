@@ -278,6 +278,14 @@ int masr_test_subsample_rows(const uint16_t* y, uint16_t* ys, const float* dys, 
  * (y - mx) - log_s.  Synchronises the stream. */
 int masr_test_nlm_step(const masr_nlm* nlm, int R, int K, int t, const int32_t* tok, const int32_t* par, const float* score, uint16_t* hstate,
                        float* cstate, float* logits, int64_t ld, float* logp, void* stream);
+/* the same step in its carry form (nlm.h mk_nlm_step_carry: the LM advance of masr_ctc_beam_search_nlm, DESIGN 5.12;
+ * tests/test_hip_ctc_nlm_beam_kernel.py).  tok / par int32 [R]: tok[r] in [1, C - 2] is row r's token, anything else marks a stay; par[r] its
+ * parent row (outside the rows of r's utterance: r).  live int32 [2][R / K]: row r of utterance u is live when r - u * K < live[t & 1][u].  A token
+ * row equals masr_test_nlm_step's, bit for bit, and its log_softmax goes to logp[t & 1][r]; a stay row gets its parent's (h, c) of every layer
+ * and its parent's logp row of parity (t - 1) & 1; a dead row is left as the caller gave it.  logp fp32 [2][R][ld].  t == 1: every live row
+ * feeds the start token from the zero state.  Synchronises the stream. */
+int masr_test_nlm_step_carry(const masr_nlm* nlm, int R, int K, int t, const int32_t* tok, const int32_t* par, const int32_t* live, uint16_t* hstate,
+                             float* cstate, float* logits, int64_t ld, float* logp, void* stream);
 
 #ifdef __cplusplus
 }

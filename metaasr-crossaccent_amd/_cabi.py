@@ -103,6 +103,10 @@ _SIGS = {
     "masr_rescore_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
     "masr_recog_rescore": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_recog_rescore_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_ctc_beam_nlm_workspace_bytes": (i64, [vp, vp, i32, i32, i32]),
+    "masr_recog_ctc_beam_nlm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+    "masr_rescore_nlm_workspace_bytes": (i64, [vp, vp, i32, i32, i32, i32, i32]),
+    "masr_recog_rescore_nlm": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_rescore_nbest": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_edit_distance": (i64, [vp, i32, vp, i32]),
     "masr_blstm_create": (vp, [vp]),
@@ -132,6 +136,8 @@ _SIGS = {
     "masr_ctc_beam_search": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "masr_ctc_beam_lm_work_bytes": (i64, [i32, i32, i32, i32]),
     "masr_ctc_beam_search_lm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
+    "masr_ctc_beam_nlm_work_bytes": (i64, [vp, i32, i32, i32, i32]),
+    "masr_ctc_beam_search_nlm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_ctc_align_work_bytes": (i64, [i32, i32, i32]),
     "masr_ctc_align": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_profile_enable": (i32, [vp, i32]),
@@ -197,6 +203,7 @@ _SIGS = {
     "masr_test_mask_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "masr_test_subsample_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "masr_test_nlm_step": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "masr_test_nlm_step_carry": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_NAMES = ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "conv2_dgrad", "conv3_dgrad", "conv4_dgrad", "conv2_wgrad",

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import align_lists, align_outputs, align_targets, check, check_beam_args, check_lm_args, lib, nbest_lists
+from ._cabi import align_lists, align_outputs, align_targets, check, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -143,22 +143,31 @@ class BlstmEngine:
         forward with its check, then the search on last_logits() with a work tensor of this engine's own.  Returns per utterance a list
         of at most nbest (token list, score), best first.  With lm (an NGramLM over the odim classes, <s> in the blank's slot 0) the search
         is masr_ctc_beam_search_lm (lm_w finite and >= 0, len_bonus finite, blank 0) and the entries are
-        (token list, fused score, acoustic score)."""
+        (token list, fused score, acoustic score); with an LstmLM over the odim classes it is masr_ctc_beam_search_nlm, under
+        the same conditions and with the same entries."""
         K = int(K)
-        if lm is not None:
+        neural = lm is not None and hasattr(lm, "score")       # an LstmLM (nlm.py); anything else goes the n-gram's way
+        if neural:
+            lm_w, len_bonus = check_nlm_args(lm, lm_w, len_bonus)
+        elif lm is not None:
             lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
         K, N = check_beam_args(K, nbest)
         logits, lens = self.forward(xs, ilens)                 # (runs masr_blstm_check)
         B, Tp, Cc = logits.shape
-        need = int(self._l.masr_ctc_beam_work_bytes(B, Tp, Cc, K))
-        check(need if need < 0 else 0, "masr_ctc_beam_work_bytes")
+        if neural:
+            need = int(self._l.masr_ctc_beam_nlm_work_bytes(lm.h, B, Tp, Cc, K))
+            check(need if need < 0 else 0, "masr_ctc_beam_nlm_work_bytes")
+        else:
+            need = int(self._l.masr_ctc_beam_work_bytes(B, Tp, Cc, K))
+            check(need if need < 0 else 0, "masr_ctc_beam_work_bytes")
         if getattr(self, "_beam_work", None) is None or self._beam_work.numel() < need:
-            self._beam_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._beam_work = torch.empty(need, dtype=torch.uint8, device=self.device)     # (torch's allocations are 512-byte aligned)
         i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
         out = [torch.empty(B, N, Tp, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **f32)]      # tokens, lens, scores
         if lm is not None:
             out.append(torch.empty(B, N, **f32))                                                    # acoustic scores
-        fn, lm_args = ("masr_ctc_beam_search_lm", (lm.h, lm_w, len_bonus)) if lm is not None else ("masr_ctc_beam_search", ())
+        fn, lm_args = ("masr_ctc_beam_search", ()) if lm is None else ("masr_ctc_beam_search_nlm" if neural else "masr_ctc_beam_search_lm",
+                                                                       (lm.h, lm_w, len_bonus))
         check(getattr(self._l, fn)(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, *lm_args, _ptr(self._beam_work),
                                    self._beam_work.numel(), *map(_ptr, out), self.stream()), fn)
         return nbest_lists(*out)

@@ -20,11 +20,20 @@
 // (entry, class) pair issues its <= N - 1 first probes and the unigram load together and resolves them from the longest order down
 // (lm_score's order of additions); a merged pair needs no LM value, its target has one.  The tail adds fl(lm_w * lm(eos | h)) and re-ranks
 // the final beam.  ctc_beam_sweep<false> compiles to the sweep without any of it.
+//
+// masr_ctc_beam_search_nlm is the same search with an LSTM LM's term (nlm.h) in the n-gram's place.  That LM has state, so the
+// search runs frame by frame across launches: ctc_beam_frame runs ONE frame of every utterance on the beam kept in the work buffer, the LM's
+// carry step advances the B * K rows' states, and ctc_beam_tail writes the lists.  The frame's logic and the tail are one __device__ body each
+// (ctc_frame_step<M>, ctc_beam_tail<M>), written for all three LM modes.  The sweep does NOT run them yet: moved onto them it computed the
+// same bits but took 2.5 - 3 % longer at K >= 10 (DESIGN 5.12 has the figures), so its loop below stays as it was and the bodies serve the
+// per-frame kernels.
 #include <cmath>
 
 #include "kernels.h"
 #include "search.h"
+#include "host_util.h"
 #include "lm.h"
+#include "nlm.h"
 
 namespace {
 
@@ -113,6 +122,225 @@ __global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
     // (the row runs out on NaN rows only: P never exceeds the emittable classes)
     row_top_n<true>(z, a.C, a.P, lane, [&](int c) { return c == a.blank || c == a.eos; },
                     [&](int i, int c) { sc[i] = c; sl[i] = c < 0 ? NEG_INF : z[c] - lse; });
+}
+
+// The beam, the frame's candidates and the selection scratch of one utterance, in LDS.  M: 0 = no LM, 1 = the n-gram (ctc_beam_sweep<true>),
+// 2 = the LSTM LM (ctc_beam_frame); a mode holds only what it reads.  Candidate index of frame t: parent rank k, then stay (0)
+// or position j in S_t (1 + j): idx = k * (P + 1) + ..., so "score descending, index ascending" is the selection order of DESIGN 5.3.  sc
+// holds each candidate's ordered score, 0 = not a candidate (-inf, or an extension merged into a stay).  LM: the ordered score is that of
+// fl(score + lmacc(prefix)), lmx holds lmacc(h + c) of the extensions that are candidates.
+struct SwBase {
+    float pb[2][KMAX], pnb[2][KMAX];
+    int last[2][KMAX], len[2][KMAX];
+    unsigned long long hash[2][KMAX], phash[2][KMAX];
+    float tot[KMAX], stay_pb[KMAX], stay_pnb[KMAX], xl[KMAX];
+    int cls[KMAX], win[KMAX];
+    uint32_t sc[KMAX * (KMAX + 1)];
+    unsigned long long wmax[2][SW_WAVES];
+};
+struct SwLm { float lmacc[2][KMAX], lmx[KMAX * (KMAX + 1)]; };
+struct SwNgram { float bo[KMAX][LM_MAX_ORDER - 1]; unsigned long long ctx[2][KMAX]; int has[KMAX]; };
+template <int M> struct SwLds;
+template <> struct SwLds<0> : SwBase {};
+template <> struct SwLds<1> : SwBase, SwLm, SwNgram {};
+template <> struct SwLds<2> : SwBase, SwLm {};
+
+// the LM side of mode 2: the fp32 log-softmax rows of the utterance's K beam rows (row k of the CURRENT beam at logp + k * ldp), the two
+// weights and am [B][nbest]
+struct CtcNlmTerm { const float* logp; long ldp; float lm_w, len_bonus; float* am; };
+
+// lm(c | entry k of the current beam): the n-gram's lookups from the entry's packed context and its backoffs, or the LSTM LM's gather
+template <int M, class La>
+__device__ __forceinline__ float lm_term(const SwLds<M>& s, const La& la, int cur, int k, int c) {
+    if constexpr (M == 1) {
+        float bo[LM_MAX_ORDER - 1];
+#pragma unroll
+        for (int i = 0; i < LM_MAX_ORDER - 1; ++i) bo[i] = s.bo[k][i];
+        return lm_score_packed(la.lm, s.ctx[cur][k], ctx_len(la.lm, s.len[cur][k]), bo, s.has[k], c);
+    } else {
+        return la.logp[(long)k * la.ldp + c];
+    }
+}
+// lm(eos | entry k) at the end of the utterance
+template <int M, class La>
+__device__ __forceinline__ float lm_eos_term(const SwLds<M>& s, const La& la, int cur, int k, int eos) {
+    if constexpr (M == 1) {
+        const unsigned long long ctx = s.ctx[cur][k];
+        const int cn = ctx_len(la.lm, s.len[cur][k]);
+        float bo[LM_MAX_ORDER - 1];
+        const int has = ctx_backoffs(la.lm, ctx, cn, bo);
+        return lm_score_packed(la.lm, ctx, cn, bo, has, eos);
+    } else {
+        return la.logp[(long)k * la.ldp + eos];
+    }
+}
+
+// ONE frame (row = b * Tp + t) of one utterance's search, by its workgroup of 256 threads: the beam s.*[cur] of n entries -> s.*[cur ^ 1],
+// the frame's back-pointer records, and the number of entries kept.  s.win[r] stays the candidate index of the entry of rank r and s.cls the
+// frame's token set.  ctc_beam_sweep's loop body, statement for statement, with the LDS arrays as members of s.
+template <int M, class La>
+__device__ __forceinline__ int ctc_frame_step(SwLds<M>& s, const CtcBeamArgs& a, const La& la, long row, int cur, int n) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.K, P = a.P, P1 = P + 1;
+    const int nxt = cur ^ 1;
+    // the frame's token set, and every entry's not-extended candidate
+    if (tid < P) { s.cls[tid] = a.s_cls[row * P + tid]; s.xl[tid] = a.s_lp[row * P + tid]; }
+    if (tid < n) {
+        const float pb = s.pb[cur][tid], pnb = s.pnb[cur][tid];
+        const int last = s.last[cur][tid];
+        const float tot = log_add(pb, pnb);
+        s.tot[tid] = tot;
+        s.stay_pb[tid] = tot + a.xb[row];
+        s.stay_pnb[tid] = last < 0 ? NEG_INF : pnb + (a.logits[row * a.ld + last] - a.lse[row]);
+        if constexpr (M == 1) {
+            float bo[LM_MAX_ORDER - 1];
+            s.has[tid] = ctx_backoffs(la.lm, s.ctx[cur][tid], ctx_len(la.lm, s.len[cur][tid]), bo);
+#pragma unroll
+            for (int k = 0; k < LM_MAX_ORDER - 1; ++k) s.bo[tid][k] = bo[k];
+        }
+    }
+    __syncthreads();
+    const int ncand = n * P1;
+    for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+        const int k = idx / P1, j = idx % P1 - 1;
+        if (j < 0) continue;
+        const float v = (s.cls[j] == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
+        s.sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
+    }
+    __syncthreads();
+    // merge: the extension of k that is the beam entry k2 adds to k2's stay (at most one k per k2)
+    for (int p = tid; p < n * n; p += SW_THREADS) {
+        const int k = p / n, k2 = p % n;
+        if (s.len[cur][k2] != s.len[cur][k] + 1 || s.phash[cur][k2] != s.hash[cur][k]) continue;
+        const int c = s.last[cur][k2];
+        for (int j = 0; j < P; ++j) {
+            if (s.cls[j] != c) continue;
+            const float v = (c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
+            s.stay_pnb[k2] = log_add(s.stay_pnb[k2], v);
+            s.sc[k * P1 + 1 + j] = 0u;
+            break;
+        }
+    }
+    __syncthreads();
+    if (tid < n) {
+        float v = log_add(s.stay_pb[tid], s.stay_pnb[tid]);
+        if constexpr (M != 0) v = add_rn(v, s.lmacc[cur][tid]);
+        s.sc[tid * P1] = v == NEG_INF ? 0u : ord_f32(v);
+    }
+    if constexpr (M != 0) {
+        // the extensions still standing (finite, not merged: their class is a real one, never the -1 of a NaN row) get their LM term
+        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+            const int k = idx / P1, j = idx % P1 - 1;
+            if (j < 0 || !s.sc[idx]) continue;
+            const int c = s.cls[j];
+            if (c < 0) { s.sc[idx] = 0u; continue; }
+            const float lmv = lm_term<M>(s, la, cur, k, c);
+            const float acc = add_rn(s.lmacc[cur][k], add_rn(mul_rn(la.lm_w, lmv), la.len_bonus));
+            const float v = add_rn((c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j], acc);
+            s.lmx[idx] = acc;
+            s.sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
+        }
+    }
+    __syncthreads();
+    // the K best: arg-max rounds; a thread rescans its own candidates (idx = tid mod 256) only after it gave the winner
+    unsigned long long mine = 0;
+    for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+        const unsigned long long key = ((unsigned long long)s.sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+        if (s.sc[idx] && key > mine) mine = key;
+    }
+    int kept = 0;
+    for (int r = 0; r < K; ++r) {
+        const unsigned long long wm = wave_max_u64(mine);
+        if (lane == 0) s.wmax[r & 1][wave] = wm;
+        __syncthreads();
+        unsigned long long best = s.wmax[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < SW_WAVES; ++w) { const unsigned long long v = s.wmax[r & 1][w]; best = v > best ? v : best; }
+        if (best == 0) break;                                // uniform: nothing but -inf candidates is left
+        const int win = (int)(0xffffffffu - (uint32_t)best);
+        if (tid == 0) s.win[r] = win;
+        if (win % SW_THREADS == tid) {
+            s.sc[win] = 0u;
+            mine = 0;
+            for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+                const unsigned long long key = ((unsigned long long)s.sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+                if (s.sc[idx] && key > mine) mine = key;
+            }
+        }
+        kept = r + 1;
+    }
+    __syncthreads();
+    // the next beam, in rank order, and its back-pointer records: parent slot | (emitted class + 1) << 8  (0 = stay)
+    if (tid < kept) {
+        const int win = s.win[tid], k = win / P1, j = win % P1 - 1;
+        int rec = k;
+        if (j < 0) {
+            s.pb[nxt][tid] = s.stay_pb[k]; s.pnb[nxt][tid] = s.stay_pnb[k];
+            s.last[nxt][tid] = s.last[cur][k]; s.len[nxt][tid] = s.len[cur][k];
+            s.hash[nxt][tid] = s.hash[cur][k]; s.phash[nxt][tid] = s.phash[cur][k];
+            if constexpr (M != 0) s.lmacc[nxt][tid] = s.lmacc[cur][k];
+            if constexpr (M == 1) s.ctx[nxt][tid] = s.ctx[cur][k];
+        } else {
+            const int c = s.cls[j];
+            s.pb[nxt][tid] = NEG_INF;
+            s.pnb[nxt][tid] = (c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
+            s.last[nxt][tid] = c; s.len[nxt][tid] = s.len[cur][k] + 1;
+            s.hash[nxt][tid] = hash_push(s.hash[cur][k], c); s.phash[nxt][tid] = s.hash[cur][k];
+            if constexpr (M != 0) s.lmacc[nxt][tid] = s.lmx[win];
+            if constexpr (M == 1) s.ctx[nxt][tid] = ctx_push(s.ctx[cur][k], c);
+            rec |= (c + 1) << 8;
+        }
+        a.rec[row * K + tid] = rec;
+    }
+    __syncthreads();
+    return kept;
+}
+
+// The tail of a search: the N-best list of the final beam s.*[cur] of n entries.
+template <int M, class La>
+__device__ __forceinline__ void ctc_beam_tail(SwLds<M>& s, const CtcBeamArgs& a, const La& la, int b, int cur, int n, int Tb, int nbest,
+                                              int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
+    const int tid = threadIdx.x;
+    const int K = a.K, Tp = a.Tp;
+    // N-best list of the final beam: each live slot walks its records backwards (a prefix of len tokens meets exactly len emitting
+    // records on the way); everything behind a list's length is -1
+    // LM: final(h) = fl(fl(am + lmacc) + fl(lm_w * lm(eos | h))), and list position i is the entry of rank i by (final descending, beam rank
+    // ascending) -- ranked on the ordered bits, so the ranks are a permutation whatever the values
+    int* out = tokens + (long)b * nbest * Tp;
+    if constexpr (M != 0) {
+        if (tid < n) {
+            const float am = log_add(s.pb[cur][tid], s.pnb[cur][tid]);
+            const float fin = add_rn(add_rn(am, s.lmacc[cur][tid]), mul_rn(la.lm_w, lm_eos_term<M>(s, la, cur, tid, a.eos)));
+            s.tot[tid] = am; s.xl[tid] = fin; s.sc[tid] = ord_f32(fin);
+        }
+        __syncthreads();
+        if (tid < n) {
+            int rank = 0;
+            for (int j = 0; j < n; ++j) rank += s.sc[j] > s.sc[tid] || (s.sc[j] == s.sc[tid] && j < tid);
+            s.cls[rank] = tid;
+        }
+        __syncthreads();
+    }
+    if (tid < nbest) {
+        const bool live = tid < n;
+        const int src = M != 0 && live ? s.cls[tid] : tid;
+        int pos = live ? s.len[cur][src] : 0, slot = src;
+        s.win[tid] = pos;
+        lens[b * nbest + tid] = live ? pos : -1;
+        if constexpr (M != 0) {
+            scores[b * nbest + tid] = live ? s.xl[src] : NEG_INF;
+            la.am[b * nbest + tid] = live ? s.tot[src] : NEG_INF;
+        } else {
+            scores[b * nbest + tid] = live ? log_add(s.pb[cur][tid], s.pnb[cur][tid]) : NEG_INF;
+        }
+        for (int t = Tb - 1; t >= 0 && pos > 0; --t) {
+            const int rec = a.rec[((long)b * Tp + t) * K + slot];
+            if (rec >> 8) out[(long)tid * Tp + --pos] = (rec >> 8) - 1;
+            slot = rec & 0xff;
+        }
+    }
+    __syncthreads();
+    for (long i = tid; i < (long)nbest * Tp; i += SW_THREADS) if ((int)(i % Tp) >= s.win[i / Tp]) out[i] = -1;
 }
 
 // grid B, 256 threads.  Candidate index of frame t: parent rank k, then stay (0) or position j in S_t (1 + j): idx = k * (P + 1) + ...,
@@ -303,6 +531,74 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     for (long i = tid; i < (long)nbest * Tp; i += SW_THREADS) if ((int)(i % Tp) >= s_win[i / Tp]) out[i] = -1;
 }
 
+// ---- the LSTM LM search (masr_ctc_beam_search_nlm): frame-synchronous across launches.  The beam lives in the work buffer by
+// parity of the device step word st: the beam in front of frame t = st - 2 stands at parity (st - 1) & 1 -- where the LM's states and
+// log-softmax rows of step st - 1 stand (nlm.h) -- and the frame's kernel writes the next one to parity st & 1.
+__device__ __forceinline__ int clamp_live(int n, int K) { return n < 0 ? 0 : (n > K ? K : n); }
+__device__ __forceinline__ void nlm_beam_load(SwLds<2>& s, const CtcNlmArgs& q, long o, int cur, int i) {
+    s.pb[cur][i] = q.pb[o]; s.pnb[cur][i] = q.pnb[o]; s.last[cur][i] = q.last[o]; s.len[cur][i] = q.len[o];
+    s.hash[cur][i] = q.hash[o]; s.phash[cur][i] = q.phash[o]; s.lmacc[cur][i] = q.lmacc[o];
+}
+
+// grid B, 256 threads: the initial beam (the empty prefix in row 0 of every utterance) at parity 1, st = 1, the two weights, htop = 0
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_nlm_prepare_kernel(CtcNlmArgs q, int B, int K, float lm_w, float len_bonus, bf16* htop, long htop_n) {
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const long o = ((long)B + b) * K;
+        q.pb[o] = 0.f; q.pnb[o] = NEG_INF; q.last[o] = -1; q.len[o] = 0; q.hash[o] = HASH_EMPTY; q.phash[o] = 0; q.lmacc[o] = 0.f;
+        q.nlive[B + b] = 1; q.nlive[b] = 0;
+        if (b == 0) { q.step[0] = 1; q.step[1] = 0; q.wts[0] = lm_w; q.wts[1] = len_bonus; }
+    }
+    for (long i = (long)b * SW_THREADS + threadIdx.x; i < htop_n; i += (long)gridDim.x * SW_THREADS) htop[i] = (bf16)0.f;
+}
+
+// grid B, 256 threads: frame t = st - 2 of every utterance -- ctc_beam_sweep<true>'s frame with the LM term gathered from the log-softmax
+// row of the parent's beam row.  Besides the back-pointer record every kept entry leaves its parent row and its token (-1: a stay) for the LM's
+// carry step.  An utterance past its enc_len keeps its beam: every live row stays in its own row.
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_frame_kernel(CtcBeamArgs a, CtcNlmArgs q) {
+    __shared__ SwLds<2> s;
+    const int tid = threadIdx.x, b = blockIdx.x, K = a.K;
+    const int st = *q.step, t = st - 2, cur = (st - 1) & 1, nxt = st & 1;
+    const int Tb = clamp_len(a.enc_lens[b], a.Tp);
+    const long oc = ((long)cur * a.B + b) * K, on = ((long)nxt * a.B + b) * K, r0 = (long)b * K;
+    const int n = clamp_live(q.nlive[cur * a.B + b], K);
+    if (t < 0 || t >= Tb) {
+        if (tid < n) {
+            q.pb[on + tid] = q.pb[oc + tid]; q.pnb[on + tid] = q.pnb[oc + tid]; q.last[on + tid] = q.last[oc + tid]; q.len[on + tid] = q.len[oc + tid];
+            q.hash[on + tid] = q.hash[oc + tid]; q.phash[on + tid] = q.phash[oc + tid]; q.lmacc[on + tid] = q.lmacc[oc + tid];
+            q.tok[r0 + tid] = -1; q.par[r0 + tid] = (int)r0 + tid;
+        }
+        if (tid == 0) q.nlive[nxt * a.B + b] = n;
+        return;
+    }
+    if (tid < n) nlm_beam_load(s, q, oc + tid, cur, tid);
+    __syncthreads();
+    const CtcNlmTerm la{q.logp + ((long)cur * a.B * K + r0) * q.ldp, q.ldp, q.wts[0], q.wts[1], q.am};
+    const int kept = ctc_frame_step<2>(s, a, la, (long)b * a.Tp + t, cur, n);
+    if (tid < kept) {
+        q.pb[on + tid] = s.pb[nxt][tid]; q.pnb[on + tid] = s.pnb[nxt][tid]; q.last[on + tid] = s.last[nxt][tid]; q.len[on + tid] = s.len[nxt][tid];
+        q.hash[on + tid] = s.hash[nxt][tid]; q.phash[on + tid] = s.phash[nxt][tid]; q.lmacc[on + tid] = s.lmacc[nxt][tid];
+        const int win = s.win[tid], k = win / (a.P + 1), j = win % (a.P + 1) - 1;
+        q.tok[r0 + tid] = j < 0 ? -1 : s.cls[j];
+        q.par[r0 + tid] = (int)r0 + k;
+    }
+    if (tid == 0) q.nlive[nxt * a.B + b] = kept;
+}
+
+// grid B, 256 threads: the sweep's tail on the beam behind the last frame (parity (st - 1) & 1), the eos term from each live row's
+// log-softmax row
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_tail_kernel(CtcBeamArgs a, CtcNlmArgs q, int nbest, int* __restrict__ tokens,
+                                                                   int* __restrict__ lens, float* __restrict__ scores) {
+    __shared__ SwLds<2> s;
+    const int tid = threadIdx.x, b = blockIdx.x, K = a.K;
+    const int cur = (*q.step - 1) & 1;
+    const int n = clamp_live(q.nlive[cur * a.B + b], K);
+    if (tid < n) nlm_beam_load(s, q, ((long)cur * a.B + b) * K + tid, cur, tid);
+    __syncthreads();
+    const CtcNlmTerm la{q.logp + ((long)cur * a.B * K + (long)b * K) * q.ldp, q.ldp, q.wts[0], q.wts[1], q.am};
+    ctc_beam_tail<2>(s, a, la, b, cur, n, clamp_len(a.enc_lens[b], a.Tp), nbest, tokens, lens, scores);
+}
+
 long align256(long v) { return (v + 255) & ~255l; }
 int beam_width(int C, int K, int eos) { const int e = C - 1 - (eos >= 0 ? 1 : 0); return K < e ? K : e; }
 
@@ -314,9 +610,10 @@ int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K) {
     return 2 * align256(4 * rows) + 2 * align256(4 * rows * P) + align256(4 * rows * K);
 }
 
-// the checks and the two launches of both entry points; la: the LM side, or null
-static int ctc_beam_run(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
-                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, const CtcLmArgs* la, hipStream_t s) {
+// the argument checks of the three entry points; with_lm: an LM is fused (either kind), whose classes are lm_C
+static int ctc_beam_check(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                          const void* work, const int* tokens, const int* lens, const float* scores, bool with_lm, int lm_C, int lm_order, float lm_w,
+                          float len_bonus, const float* am) {
     if (!logits || !enc_lens || !work || !tokens || !lens || !scores) { mk_set_error(fn, "null pointer"); return -1; }
     if (B < 1 || Tp < 1) { mk_set_error(fn, "need B >= 1 and Tp >= 1"); return -1; }
     if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
@@ -324,21 +621,20 @@ static int ctc_beam_run(const char* fn, const float* logits, long ld, const int*
     if (C < 2 || C > 4096 || ld < C) { mk_set_error(fn, "need 2 <= C <= 4096 and ld >= C"); return -1; }
     if (blank < 0 || blank >= C) { mk_set_error(fn, "blank must be in [0, C)"); return -1; }
     if (eos < -1 || eos >= C || eos == blank) { mk_set_error(fn, "eos must be -1 or a class in [0, C) other than blank"); return -1; }
-    if (la) {
+    if (with_lm) {
         // the LM's ids are the model's: <s> shares the blank's slot 0 (never emitted), </s> is the last class
         if (blank != 0) { mk_set_error(fn, "blank must be 0 with a language model (class 0 is <s>)"); return -1; }
         if (eos != C - 1) { mk_set_error(fn, "eos must be C - 1 with a language model (the last class is </s>)"); return -1; }
-        if (la->lm.C != C) { mk_set_error(fn, "the language model's classes differ from C"); return -1; }
-        if (la->lm.order < 1 || la->lm.order > LM_MAX_ORDER) { mk_set_error(fn, "the language model's order must be in [1, 4]"); return -1; }
-        if (!(la->lm_w >= 0.f) || !std::isfinite(la->lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
-        if (!std::isfinite(la->len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
-        if (!la->am) { mk_set_error(fn, "null pointer"); return -1; }
+        if (lm_C != C) { mk_set_error(fn, "the language model's classes differ from C"); return -1; }
+        if (lm_order < 1 || lm_order > LM_MAX_ORDER) { mk_set_error(fn, "the language model's order must be in [1, 4]"); return -1; }
+        if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
+        if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
+        if (!am) { mk_set_error(fn, "null pointer"); return -1; }
     }
-    if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) {
-        mk_set_error(fn, la ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
-                            : "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned");
-        return -1;
-    }
+    return 0;
+}
+// the plain search's arrays, carved from the front of the work buffer
+static CtcBeamArgs ctc_beam_carve(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int blank, int eos, void* work) {
     CtcBeamArgs a{};
     a.logits = logits; a.ld = ld; a.enc_lens = enc_lens;
     a.B = B; a.Tp = Tp; a.C = C; a.K = K; a.P = beam_width(C, K, eos); a.blank = blank; a.eos = eos;
@@ -349,7 +645,25 @@ static int ctc_beam_run(const char* fn, const float* logits, long ld, const int*
     a.s_cls = (int*)w; w += align256(4 * rows * Pmax);
     a.s_lp = (float*)w; w += align256(4 * rows * Pmax);
     a.rec = (int*)w;
-    hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
+    return a;
+}
+static int ctc_beam_frames(const CtcBeamArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)(((long)a.B * a.Tp + 3) / 4)), dim3(256), 0, s, a);
+    return LAUNCH_OK();
+}
+
+// the checks and the two launches of the sweep's entry points; la: the LM side, or null
+static int ctc_beam_run(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, const CtcLmArgs* la, hipStream_t s) {
+    CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, la != nullptr, la ? la->lm.C : 0,
+                      la ? la->lm.order : 0, la ? la->lm_w : 0.f, la ? la->len_bonus : 0.f, la ? la->am : nullptr));
+    if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) {
+        mk_set_error(fn, la ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
+                            : "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned");
+        return -1;
+    }
+    const CtcBeamArgs a = ctc_beam_carve(logits, ld, enc_lens, B, Tp, C, K, blank, eos, work);
+    CK(ctc_beam_frames(a, s));
     if (la) hipLaunchKernelGGL(ctc_beam_sweep_kernel<true>, dim3(B), dim3(SW_THREADS), 0, s, a, *la, nbest, tokens, lens, scores);
     else hipLaunchKernelGGL(ctc_beam_sweep_kernel<false>, dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{}, nbest, tokens, lens, scores);
     return LAUNCH_OK();
@@ -370,4 +684,84 @@ int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int
     if (!lm) { mk_set_error(fn, "null language model"); return -1; }
     const CtcLmArgs la{lm->dev, lm_w, len_bonus, am};
     return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, &la, s);
+}
+
+// ---------------------------------------------------------------- the LSTM LM search
+// the work buffer: the plain search's arrays | step [2] | the two weights | the beam by parity [2][B][K]: p_b, p_nb, lmacc, last, len, hash,
+// parent hash | live counts [2][B] | token and parent row of the frame [R] each | the LM's h, c [2][L][R][Hp], top h [R][Hp], logits [R][Cp],
+// log-softmax rows [2][R][Cp]; R = B * K, Cp = C padded to 128, every entry rounded up to 256 bytes
+namespace {
+struct CtcNlmPlan { int64_t step, wts, pb, pnb, lmacc, last, len, hash, phash, nlive, tok, par, h, c, htop, logits, logp, total; long ldl; };
+CtcNlmPlan ctc_nlm_plan(const NlmDev& d, int B, int Tp, int C, int K) {
+    CtcNlmPlan p{};
+    const int64_t R = (int64_t)B * K;
+    p.ldl = (C + 127) / 128 * 128;
+    int64_t off = mk_ctc_beam_work_bytes(B, Tp, C, K);
+    auto take = [&](int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; };
+    p.step = take(8); p.wts = take(8);
+    p.pb = take(8 * R); p.pnb = take(8 * R); p.lmacc = take(8 * R); p.last = take(8 * R); p.len = take(8 * R);
+    p.hash = take(16 * R); p.phash = take(16 * R);
+    p.nlive = take(8 * (int64_t)B); p.tok = take(4 * R); p.par = take(4 * R);
+    p.h = take(nlm_state_elems(d, (int)R) * 2); p.c = take(nlm_state_elems(d, (int)R) * 4); p.htop = take(R * d.Hp * 2);
+    p.logits = take(R * p.ldl * 4); p.logp = take(2 * R * p.ldl * 4);
+    p.total = off;
+    return p;
+}
+}  // namespace
+
+int64_t mk_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K) {
+    const char* fn = "mk_ctc_beam_nlm_work_bytes";
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    if (mk_ctc_beam_work_bytes(B, Tp, C, K) < 0) return -1;
+    return ctc_nlm_plan(nlm->dev, B, Tp, C, K).total;
+}
+
+int mk_ctc_beam_nlm_begin(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                          const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, const int* tokens, const int* lens,
+                          const float* scores, float* am, CtcNlmRun* run, hipStream_t s) {
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, true, nlm->dev.C, 1, lm_w, len_bonus, am));
+    const NlmDev& d = nlm->dev;
+    const CtcNlmPlan p = ctc_nlm_plan(d, B, Tp, C, K);
+    if (work_bytes < p.total || ((uintptr_t)work & 255)) {
+        mk_set_error(fn, "work buffer too small (masr_ctc_beam_nlm_work_bytes(nlm, B, Tp, C, K)) or misaligned");
+        return -1;
+    }
+    CtcNlmRun& r = *run;
+    r = CtcNlmRun{};
+    r.a = ctc_beam_carve(logits, ld, enc_lens, B, Tp, C, K, blank, eos, work);
+    char* w = (char*)work;
+    CtcNlmArgs& q = r.q;
+    q.step = (int*)(w + p.step); q.wts = (float*)(w + p.wts);
+    q.pb = (float*)(w + p.pb); q.pnb = (float*)(w + p.pnb); q.lmacc = (float*)(w + p.lmacc); q.last = (int*)(w + p.last); q.len = (int*)(w + p.len);
+    q.hash = (unsigned long long*)(w + p.hash); q.phash = (unsigned long long*)(w + p.phash);
+    q.nlive = (int*)(w + p.nlive); q.tok = (int*)(w + p.tok); q.par = (int*)(w + p.par);
+    q.logp = (float*)(w + p.logp); q.ldp = p.ldl; q.am = am;
+    r.lm = d; r.logits = (float*)(w + p.logits); r.ldl = p.ldl;
+    NlmStepArgs& st = r.st;
+    st.step = q.step; st.R = B * K; st.K = K; st.tok_hist = q.tok; st.par_hist = q.par; st.hist_stride = 0; st.live = q.nlive;
+    st.hstate = (bf16*)(w + p.h); st.cstate = (float*)(w + p.c); st.htop = (bf16*)(w + p.htop);
+    CK(ctc_beam_frames(r.a, s));
+    hipLaunchKernelGGL(ctc_beam_nlm_prepare_kernel, dim3(B), dim3(SW_THREADS), 0, s, q, B, K, lm_w, len_bonus, st.htop, (long)st.R * d.Hp);
+    CK(LAUNCH_OK());
+    return mk_nlm_step_carry(d, st, r.logits, r.ldl, q.logp, q.ldp, q.step, s);          // LM step 1: [start] from the zero state
+}
+int mk_ctc_beam_nlm_frame(const CtcNlmRun& r, hipStream_t s) {
+    hipLaunchKernelGGL(ctc_beam_frame_kernel, dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q);
+    CK(LAUNCH_OK());
+    return mk_nlm_step_carry(r.lm, r.st, r.logits, r.ldl, r.q.logp, r.q.ldp, r.q.step, s);
+}
+int mk_ctc_beam_nlm_end(const CtcNlmRun& r, int nbest, int* tokens, int* lens, float* scores, hipStream_t s) {
+    hipLaunchKernelGGL(ctc_beam_tail_kernel, dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q, nbest, tokens, lens, scores);
+    return LAUNCH_OK();
+}
+
+int mk_ctc_beam_search_nlm(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                           const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int* tokens, int* lens, float* scores,
+                           float* am, hipStream_t s) {
+    CtcNlmRun r;
+    CK(mk_ctc_beam_nlm_begin("mk_ctc_beam_search_nlm", logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, nlm, lm_w, len_bonus, work, work_bytes,
+                             tokens, lens, scores, am, &r, s));
+    for (int t = 0; t < Tp; ++t) CK(mk_ctc_beam_nlm_frame(r, s));
+    return mk_ctc_beam_nlm_end(r, nbest, tokens, lens, scores, s);
 }

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "engine_internal.h"
+#include "nlm.h"
 
 static thread_local std::string g_err;
 void mk_set_error(const char* what, const char* detail) { g_err = std::string(what) + ": " + detail; }
@@ -252,7 +253,7 @@ void masr_destroy(masr_model* m) {
     if (m->h_stats) hipHostFree(m->h_stats);
     for (int i = 0; i < masr_model::RING; ++i) if (m->ring_ev[i]) { if (m->ring_used[i]) hipEventSynchronize(m->ring_ev[i]); hipEventDestroy(m->ring_ev[i]); }
     if (m->h_ring) hipHostFree(m->h_ring);
-    for (DecodeGraph* g : {&m->greedy_graph, &m->beam_graph, &m->joint_graph, &m->lm_graph, &m->joint_lm_graph, &m->nlm_graph, &m->joint_nlm_graph}) g->destroy();
+    for (DecodeGraph* g : {&m->greedy_graph, &m->beam_graph, &m->joint_graph, &m->lm_graph, &m->joint_lm_graph, &m->nlm_graph, &m->joint_nlm_graph, &m->ctc_nlm_graph}) g->destroy();
     for (auto& sg : m->step_graphs) { hipGraphExecDestroy(sg.e); hipGraphDestroy(sg.g); }
     for (auto& e : m->stage_ev) if (e) hipEventDestroy(e);
     for (auto& v : m->prof_ev) for (auto& p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -537,6 +538,13 @@ int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_
                             float* scores, float* am, void* stream) {
     return mk_ctc_beam_search_lm(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, work, work_bytes, tokens, lens, scores,
                                  am, (hipStream_t)stream);
+}
+int64_t masr_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K) { return mk_ctc_beam_nlm_work_bytes(nlm, B, Tp, C, K); }
+int masr_ctc_beam_search_nlm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                             const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
+                             float* scores, float* am, void* stream) {
+    return mk_ctc_beam_search_nlm(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, nlm, lm_w, len_bonus, work, work_bytes, tokens, lens, scores,
+                                  am, (hipStream_t)stream);
 }
 int64_t masr_ctc_align_work_bytes(int B, int Tp, int maxL) { return mk_ctc_align_work_bytes(B, Tp, maxL); }
 int masr_ctc_align(const float* logits, int64_t ld, const int32_t* enc_lens, const int32_t* targets, const int32_t* tgt_off, const int32_t* tgt_len,

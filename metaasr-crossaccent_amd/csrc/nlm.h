@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "kernels.h"
 
 constexpr int NLM_MAX_LAYERS = 4;
 constexpr int NLM_MAX_DIM = 2048;
@@ -39,6 +40,7 @@ struct NlmStepArgs {
     const int *tok_hist, *par_hist; long hist_stride;
     const float* score; const int* fin;
     bf16* hstate; float* cstate; bf16* htop;
+    const int* live;                         // the carry form only (mk_nlm_step_carry): live counts [2][R / K] by step parity
 };
 inline int64_t nlm_state_elems(const NlmDev& d, int R) { return 2 * (int64_t)d.L * R * d.Hp; }
 
@@ -46,3 +48,38 @@ inline int64_t nlm_state_elems(const NlmDev& d, int R) { return 2 * (int64_t)d.L
 int mk_nlm_step(const NlmDev& lm, const NlmStepArgs& a, float* logits, long ld, hipStream_t s);
 // out [R][ldo] = the log_softmax of logits [R][ld] over the C classes, (y - mx) - log_s of search.h row_lse
 int mk_nlm_logp(const float* logits, long ld, int R, int C, float* out, long ldo, hipStream_t s);
+
+// The carry form of the step, for a search whose rows mostly do NOT take a token (the CTC prefix beam).  The histories are one
+// slot per row (hist_stride 0): tok_hist[r] in [1, C - 2] is the row's token, anything else marks a STAY; par_hist[r] its parent row (outside
+// the K rows of r's utterance: r).  Row r of utterance u is live when r - u * K < live[(st & 1) * (R / K) + u].  At step st
+//   a token row computes from its parent's state at parity (st - 1) & 1 exactly as mk_nlm_step does, and its logits go through the
+//   log-softmax into logp[st & 1][r]  (logp fp32 [2][R][ldp]);
+//   a stay row copies its parent's (h, c) of every layer and its parent's logp row from parity (st - 1) & 1 to its own slot at st & 1;
+//   a dead row writes nothing.
+// A 16-row tile without a token row skips its reduction.  At st = 1 every live row feeds start_id from the zero state.  The last launch
+// advances *step (search.h step_ticket).
+int mk_nlm_step_carry(const NlmDev& lm, const NlmStepArgs& a, float* logits, long ld, float* logp, long ldp, int* step, hipStream_t s);
+
+// ---- the CTC prefix beam with the LSTM LM (ctc_beam.hip)
+struct CtcNlmArgs {
+    int* step;                               // [2] the step word st and its ticket: frame t runs at st = t + 2
+    float* wts;                              // lm_w, len_bonus
+    float *pb, *pnb, *lmacc; int *last, *len; unsigned long long *hash, *phash;      // the beam by parity [2][B][K]
+    int* nlive;                              // [2][B] live entries
+    int *tok, *par;                          // [R] the frame's token (-1: stay) and parent row of every kept entry
+    float* logp; long ldp;                   // [2][R][ldp] the rows' LM log-softmax
+    float* am;                               // [B][nbest]
+};
+struct CtcNlmRun { CtcBeamArgs a; CtcNlmArgs q; NlmStepArgs st; NlmDev lm; float* logits; long ldl; };
+int64_t mk_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K);
+// begin: the checks (-1 with the message under fn), the frames' log-sum-exp and token sets, the initial beam and LM step 1; frame: ONE frame
+// for every utterance, parameter-identical launches (the frame number is the device step word); end: the tail.  The operator below is begin,
+// Tp frames, end.
+int mk_ctc_beam_nlm_begin(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                          const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, const int* tokens, const int* lens,
+                          const float* scores, float* am, CtcNlmRun* run, hipStream_t s);
+int mk_ctc_beam_nlm_frame(const CtcNlmRun& r, hipStream_t s);
+int mk_ctc_beam_nlm_end(const CtcNlmRun& r, int nbest, int* tokens, int* lens, float* scores, hipStream_t s);
+int mk_ctc_beam_search_nlm(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                           const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int* tokens, int* lens, float* scores,
+                           float* am, hipStream_t s);

@@ -32,12 +32,28 @@ __device__ __forceinline__ HistEntry nlm_row_source(const NlmStepArgs& a, const 
     return hist_entry(a.tok_hist, a.par_hist, a.hist_stride, st - 1, r, lm.C, a.K, 0);
 }
 
+// the carry form's row (nlm.h mk_nlm_step_carry): token (-1: a stay), parent row, live.  Vetted: a token outside [1, C - 2] is a stay, a parent
+// outside the K rows of the row's utterance is the row
+struct CarrySrc { int tok, par; bool live; };
+__device__ __forceinline__ CarrySrc nlm_carry_source(const NlmStepArgs& a, const NlmDev& lm, int r, int st) {
+    const int u = r / a.K, u0 = u * a.K;
+    const bool live = r - u0 < a.live[(st & 1) * (a.R / a.K) + u];
+    if (st <= 1) return {lm.start_id, r, live};
+    int tok = a.tok_hist[r], par = a.par_hist[r];
+    if (tok < 1 || tok > lm.C - 2) tok = -1;
+    if (par < u0 || par >= u0 + a.K) par = r;
+    return {tok, par, live};
+}
+
 // Layer l of one step.  grid (Hp / 16, ceil(R / 16)), 256 threads: a workgroup owns 16 rows x 16 hidden units x the four gates, its four
 // waves split the reduction over INp + Hp (k = wave * 32 + 128 i) as skinny_gemm_kernel does and combine through LDS.  Operands go global
 // -> MFMA fragments directly (one 16-byte load per lane, operand and chunk): with <= 16 rows per tile there is no reuse to stage.  The A
 // row is embed[tok] (layer 0: the gather is the row index) or layer l - 1's new h of the row for the first INp columns, and layer l's h of
 // the PARENT row for the last Hp; a 32-wide chunk never straddles the two (INp % 32 == 0).  At st = 1 the state is zero: the recurrent half
 // is skipped (it would add exact zeros) and c_par = 0.
+// CARRY (mk_nlm_step_carry): a stay row copies its parent's (h, c), a dead row writes nothing, and a tile without a token row skips the
+// reduction -- the same 16 rows stand in every wave, so the vote is uniform over the workgroup.  A token row's arithmetic is the other form's.
+template <bool CARRY>
 __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepArgs a, int l) {
     __shared__ float red[4][4][16][17];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -46,8 +62,16 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     const int Hp = lm.Hp, INp = l ? Hp : lm.Ep, KT = INp + Hp;
     const long LS = (long)a.R * Hp;                              // one layer's states
     int row = r0 + (lane & 15); if (row > a.R - 1) row = a.R - 1;
-    const HistEntry src = nlm_row_source(a, lm, row, st);
-    const int tok = src.tok, par = src.par;
+    int tok, par;
+    bool work = true;
+    if constexpr (CARRY) {
+        const CarrySrc src = nlm_carry_source(a, lm, row, st);
+        work = __ballot(src.live && src.tok >= 0) != 0;
+        tok = src.tok < 0 ? 0 : src.tok; par = src.par;
+    } else {
+        const HistEntry src = nlm_row_source(a, lm, row, st);
+        tok = src.tok; par = src.par;
+    }
     const int ko = 8 * (lane >> 4);
     const bf16* __restrict__ x = (l ? a.hstate + ((long)cur * lm.L + (l - 1)) * LS + (long)row * Hp : lm.embed + (long)tok * lm.Ep) + ko;
     const bf16* __restrict__ hp = a.hstate + ((long)prv * lm.L + l) * LS + (long)par * Hp + ko;
@@ -57,7 +81,7 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int k = wave * 32;
+    int k = work ? wave * 32 : kend;
     for (; k + 128 < kend; k += 256) {                           // two chunks = ten independent loads in flight
         const bf16x8 a0 = ld8(k < INp ? x + k : hp + (k - INp)), a1 = ld8(k + 128 < INp ? x + k + 128 : hp + (k + 128 - INp));
         bf16x8 w0[4], w1[4];
@@ -78,18 +102,31 @@ __global__ __launch_bounds__(256) void nlm_lstm_step_kernel(NlmDev lm, NlmStepAr
     __syncthreads();
     const int tm = threadIdx.x >> 4, tn = threadIdx.x & 15, m = r0 + tm, u = u0 + tn;
     if (m >= a.R) return;
+    const long LO = ((long)cur * lm.L + l) * LS + (long)m * Hp + u;
+    if constexpr (CARRY) {
+        const CarrySrc sm = nlm_carry_source(a, lm, m, st);
+        if (!sm.live) return;
+        if (sm.tok < 0) {
+            const long po = ((long)prv * lm.L + l) * LS + (long)sm.par * Hp + u;
+            const bf16 h = a.hstate[po];
+            a.cstate[LO] = a.cstate[po];
+            a.hstate[LO] = h;
+            if (l == lm.L - 1) a.htop[(long)m * Hp + u] = h;
+            return;
+        }
+    }
     if (a.fin && a.fin[m / a.K]) return;
     if (a.score && a.score[m] == NEG_INF) return;               // dead row: its stale state is never a live row's parent
     float z[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) z[g] = ((red[0][g][tm][tn] + red[1][g][tm][tn]) + (red[2][g][tm][tn] + red[3][g][tm][tn])) + lm.b[l][g * Hp + u];
-    const float cp = st == 1 ? 0.f : a.cstate[((long)prv * lm.L + l) * LS + (long)nlm_row_source(a, lm, m, st).par * Hp + u];
+    const int mpar = CARRY ? nlm_carry_source(a, lm, m, st).par : nlm_row_source(a, lm, m, st).par;
+    const float cp = st == 1 ? 0.f : a.cstate[((long)prv * lm.L + l) * LS + (long)mpar * Hp + u];
     const float ig = sigm(z[0]), fg = sigm(z[1]), gg = tanhf(z[2]), og = sigm(z[3]);      // torch gate order i, f, g, o
     const float cn = fg * cp + ig * gg;
     const bf16 h = (bf16)(og * tanhf(cn));
-    const long o = ((long)cur * lm.L + l) * LS + (long)m * Hp + u;
-    a.cstate[o] = cn;
-    a.hstate[o] = h;
+    a.cstate[LO] = cn;
+    a.hstate[LO] = h;
     if (l == lm.L - 1) a.htop[(long)m * Hp + u] = h;
 }
 
@@ -100,6 +137,30 @@ __global__ __launch_bounds__(256) void nlm_logp_kernel(const float* __restrict__
     const float* y = logits + (long)r * ld;
     const RowLse l = row_lse(y, C, lane);
     for (int c = lane; c < C; c += 64) out[(long)r * ldo + c] = (y[c] - l.mx) - l.log_s;
+}
+
+// the carry form's last launch, grid ceil(R / 4), 256 threads: one wave per row.  A token row's log-softmax goes to logp[st & 1][r], a stay
+// row's is copied from its parent's row of the other parity, a dead row writes nothing; then the step advances
+__global__ __launch_bounds__(256) void nlm_logp_carry_kernel(NlmDev lm, NlmStepArgs a, const float* __restrict__ logits, long ld, float* __restrict__ logp,
+                                                            long ldp, int* step) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int st = *step;
+    if (r < a.R) {
+        const CarrySrc src = nlm_carry_source(a, lm, r, st);
+        if (src.live) {
+            float* out = logp + ((long)(st & 1) * a.R + r) * ldp;
+            if (src.tok < 0) {
+                const float* in = logp + ((long)((st & 1) ^ 1) * a.R + src.par) * ldp;
+                for (int c = lane; c < lm.C; c += 64) out[c] = in[c];
+            } else {
+                const float* y = logits + (long)r * ld;
+                const RowLse z = row_lse(y, lm.C, lane);
+                for (int c = lane; c < lm.C; c += 64) out[c] = (y[c] - z.mx) - z.log_s;
+            }
+        }
+    }
+    __syncthreads();                                             // every wave of the block has read the step
+    if (threadIdx.x == 0) step_ticket(step, st, gridDim.x);
 }
 
 // masr_nlm_score.  prepare, grid ceil(max(R * ld, R) / 256): hist[p][r] = tokens[r][p] (0 behind the row's length), out[r] = 0, step = 1
@@ -150,12 +211,27 @@ int mk_nlm_step(const NlmDev& lm, const NlmStepArgs& a, float* logits, long ld, 
         mk_set_error("mk_nlm_step", "need R, K >= 1, an LM of 1 .. 4 layers, ld >= C and the state buffers"); return -1;
     }
     for (int l = 0; l < lm.L; ++l) {
-        hipLaunchKernelGGL(nlm_lstm_step_kernel, dim3(lm.Hp / 16, (a.R + 15) / 16), dim3(256), 0, s, lm, a, l);
+        hipLaunchKernelGGL(nlm_lstm_step_kernel<false>, dim3(lm.Hp / 16, (a.R + 15) / 16), dim3(256), 0, s, lm, a, l);
         if (LAUNCH_OK()) return -1;
     }
     SkinnyArgs g{};
     g.A = a.htop; g.lda = lm.Hp; g.W = lm.lo; g.ldw = lm.Hp; g.M = a.R; g.N = lm.C; g.K = lm.Hp; g.bias = lm.lo_b; g.C32 = logits; g.ldc = ld;
     return mk_skinny_gemm(g, s);
+}
+int mk_nlm_step_carry(const NlmDev& lm, const NlmStepArgs& a, float* logits, long ld, float* logp, long ldp, int* step, hipStream_t s) {
+    if (a.R < 1 || a.K < 1 || a.R % a.K || lm.L < 1 || lm.L > NLM_MAX_LAYERS || lm.Hp % 32 || lm.Ep % 32 || ld < lm.C || ldp < lm.C || !a.hstate ||
+        !a.cstate || !a.htop || !a.step || !a.live || !a.tok_hist || !a.par_hist || !logp || step != a.step) {
+        mk_set_error("mk_nlm_step_carry", "need R a multiple of K >= 1, an LM of 1 .. 4 layers, ld, ldp >= C, the state buffers and the row records"); return -1;
+    }
+    for (int l = 0; l < lm.L; ++l) {
+        hipLaunchKernelGGL(nlm_lstm_step_kernel<true>, dim3(lm.Hp / 16, (a.R + 15) / 16), dim3(256), 0, s, lm, a, l);
+        if (LAUNCH_OK()) return -1;
+    }
+    SkinnyArgs g{};
+    g.A = a.htop; g.lda = lm.Hp; g.W = lm.lo; g.ldw = lm.Hp; g.M = a.R; g.N = lm.C; g.K = lm.Hp; g.bias = lm.lo_b; g.C32 = logits; g.ldc = ld;
+    CK(mk_skinny_gemm(g, s));
+    hipLaunchKernelGGL(nlm_logp_carry_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, lm, a, logits, ld, logp, ldp, step);
+    return LAUNCH_OK();
 }
 int mk_nlm_logp(const float* logits, long ld, int R, int C, float* out, long ldo, hipStream_t s) {
     hipLaunchKernelGGL(nlm_logp_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, ld, R, C, out, ldo);

@@ -160,7 +160,8 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   joint with the LSTM LM (masr_recog_beam_ctc_nlm, P > 0, nlm, NB > 0): the joint LM beam's plan with the LSTM LM fusion's buffers behind
 //   the shared fused rows
 //   CTC-only beam (masr_recog_ctc_beam, ctc_only): one decoder position per utterance; the head's logits [B*Tp][Cp] and the search's work
-//   buffer follow
+//   buffer follow -- with the LSTM LM (masr_recog_ctc_beam_nlm, nlm) the larger one of masr_ctc_beam_nlm_work_bytes, here and in the first
+//   pass of the rescoring plan
 //   attention rescoring (masr_recog_rescore / masr_rescore_nbest, N > 0): N * (Lmax + 1) decoder positions per utterance = the B*N hypotheses
 //   of up to Lmax tokens behind their sos; with a first pass (K > 0) the CTC-only beam's buffers and its N-best list follow, then the
 //   second pass's scores
@@ -207,10 +208,10 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
     a.nb_score = ar.get<float>((int64_t)B * d.NB); a.nb_len = ar.get<int>((int64_t)B * d.NB); a.nb_row = ar.get<int>((int64_t)B * d.NB);
     return o;
 }
-static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, int K) {
+static DecodeBufs plan_ctc_beam(const masr_model* m, Arena& ar, int B, int Tp, int K, const masr_nlm* nlm = nullptr) {
     DecodeBufs o{};
     o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
-    o.work_bytes = mk_ctc_beam_work_bytes(B, Tp, m->C, K);
+    o.work_bytes = nlm ? mk_ctc_beam_nlm_work_bytes(nlm, B, Tp, m->C, K) : mk_ctc_beam_work_bytes(B, Tp, m->C, K);
     o.work = ar.get<char>(o.work_bytes);
     return o;
 }
@@ -226,7 +227,7 @@ static DecodeBufs plan_rescore(const masr_model* m, Arena& ar, int B, int Tp, co
     DecodeBufs o{};
     const int64_t R = (int64_t)B * d.N;
     if (d.K) {
-        o = plan_ctc_beam(m, ar, B, Tp, d.K);
+        o = plan_ctc_beam(m, ar, B, Tp, d.K, d.nlm);
         o.rs_tok = ar.get<int>(R * Tp); o.rs_lens = ar.get<int>(R); o.rs_ctc = ar.get<float>(R);
     }
     o.rs_att = ar.get<float>(R); o.rs_row_lp = ar.get<float>(R * (d.Lmax + 1));
@@ -242,7 +243,7 @@ static DecodeBufs plan_decode(const masr_model* m, Arena& ar, Acts& a, int B, in
         return plan_ctc_align(m, ar, B, T / 4, d.AL);
     }
     plan_acts(m, ar, a, B, T, d.ctc_only ? 1 : d.K ? d.K * d.Lmax : Ldec, false);
-    return d.ctc_only ? plan_ctc_beam(m, ar, B, T / 4, d.K) : d.K ? plan_beam(m, ar, B, T / 4, d) : DecodeBufs{};
+    return d.ctc_only ? plan_ctc_beam(m, ar, B, T / 4, d.K, d.nlm) : d.K ? plan_beam(m, ar, B, T / 4, d) : DecodeBufs{};
 }
 // a decoder's workspace size; args_ok: B, T and the spec are in range (else the error `need`)
 static int64_t decode_workspace_bytes(const char* fn, const masr_model* m, bool args_ok, const char* need, int B, int T, const DecodeSpec& d) {
@@ -278,7 +279,9 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
     if (bufs) *bufs = planned;
     if (ar.off > m->ws_bytes) {
         mk_set_error("masr_recog", d.AL >= 0 ? "workspace too small (masr_ctc_align_workspace_bytes(B, T, maxL))"
+                                   : d.N && d.nlm ? "workspace too small (masr_rescore_nlm_workspace_bytes(nlm, B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
                                    : d.N ? "workspace too small (masr_rescore_workspace_bytes(B, T, K, N, Lmax), Lmax >= the longest hypothesis)"
+                                   : d.ctc_only && d.nlm ? "workspace too small (masr_ctc_beam_nlm_workspace_bytes(nlm, B, T, K))"
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
                                    : d.NB && d.nlm ? "workspace too small (masr_beam_ctc_nlm_workspace_bytes(nlm, B, T, K, N, Lmax))"
@@ -452,32 +455,44 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
 }
 
 // the CTC prefix beam over the head's logits of the encoder memory (ctc_beam.hip), with an LM the fused sweep: the first pass of
-// masr_recog_ctc_beam(_lm) and masr_recog_rescore(_lm)
-static int ctc_first_pass(Ctx& c, const DecodeBufs& bufs, int B, int Tp, int K, int N, const masr_lm* lm, float lm_w, float len_bonus, int32_t* tokens,
-                          int32_t* lens, float* scores, float* am) {
+// masr_recog_ctc_beam(_lm) and masr_recog_rescore(_lm).  With the LSTM LM the search is frame-synchronous: ONE frame is captured
+// as a hipGraph of its own and replayed Tp times (utterances past their enc_len idle through the rest).  Keyed on (B, T, K, the LM) and on
+// where the plan put what the frame's launches read (enc_lens, the logits, the work buffer); lm_w and len_bonus are device values written in
+// front of the replays, so a call with other weights replays the same graph and never an old value.
+static int ctc_first_pass(const char* fn, Ctx& c, const DecodeBufs& bufs, int B, int Tp, int K, int N, const masr_lm* lm, const masr_nlm* nlm, float lm_w,
+                          float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am) {
     masr_model* m = c.m; Acts& a = m->acts;
     CK(ctc_head_logits(c, bufs.ctc_logits));
+    if (nlm) {
+        CtcNlmRun run;
+        CK(mk_ctc_beam_nlm_begin(fn, bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, nlm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
+                                 tokens, lens, scores, am, &run, c.s));
+        const int key[6] = {B, Tp, K, (int)nlm->serial, (int)(((char*)a.enc_lens - (char*)m->ws) >> 2), (int)(((char*)bufs.ctc_logits - (char*)m->ws) >> 2)};
+        const void* const kp[3] = {m->ws, m->P, bufs.work};
+        CK(run_steps(m, m->ctc_nlm_graph, key, kp, Tp, c.s, fn, "stream capture of the CTC beam's frame failed", [&] { return mk_ctc_beam_nlm_frame(run, c.s); }));
+        return mk_ctc_beam_nlm_end(run, N, tokens, lens, scores, c.s);
+    }
     if (lm) return mk_ctc_beam_search_lm(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, lm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
                                          tokens, lens, scores, am, c.s);
     return mk_ctc_beam_search(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, bufs.work, bufs.work_bytes, tokens, lens, scores, c.s);
 }
 
 // masr_recog_ctc_beam (with_lm false) and masr_recog_ctc_beam_lm: one encoder pass, the head GEMM, one sweep over the T/4 frames
-static int recog_ctc_beam_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, float lm_w, float len_bonus, const float* xs,
+static int recog_ctc_beam_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, const masr_nlm* nlm, float lm_w, float len_bonus, const float* xs,
                                const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
     CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "nbest", nbest, K));
-    if (with_lm) CK(check_lm(fn, m, lm, lm_w, &len_bonus));
+    if (with_lm) CK(nlm ? check_nlm(fn, m, nlm, lm_w, &len_bonus) : check_lm(fn, m, lm, lm_w, &len_bonus));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (with_lm && !am) return fail(fn, "null pointer");
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true}, &bufs); if (rc) return rc; }
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true, 0, false, 0, -1, nlm}, &bufs); if (rc) return rc; }
     Ctx c{m, s, 0u, false, 0.f, 0.f};
-    CK(ctc_first_pass(c, bufs, B, T / 4, K, nbest, lm, lm_w, len_bonus, tokens, lens, scores, am));
+    CK(ctc_first_pass(fn, c, bufs, B, T / 4, K, nbest, lm, nlm, lm_w, len_bonus, tokens, lens, scores, am));
     m->have_acts = false;
     return 0;
 }
@@ -505,7 +520,7 @@ static int rescore_second_pass(Ctx& c, const DecodeBufs& bufs, const int* tok, l
 
 // masr_recog_rescore (with_lm false) and masr_recog_rescore_lm: the two-pass decode on one encoder pass; with an LM the first pass is the fused
 // search, its fused scores the c(b, n) of the second pass, and its acoustic totals land in the plan's scratch (rs_att, free until the second pass)
-static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, float lm_w, float len_bonus, const float* xs,
+static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, const masr_nlm* nlm, float lm_w, float len_bonus, const float* xs,
                               const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
                               float* att, float* ctc, int32_t* order, void* stream) {
     CK(check_model(fn, m));
@@ -513,7 +528,7 @@ static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "N", N, K));
     CK(check_rescore_weights(fn, att_w, ctc_w));
-    if (with_lm) CK(check_lm(fn, m, lm, lm_w, &len_bonus));
+    if (with_lm) CK(nlm ? check_nlm(fn, m, nlm, lm_w, &len_bonus) : check_lm(fn, m, lm, lm_w, &len_bonus));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (!att || !ctc || !order) return fail(fn, "null pointer");
     if (B <= 0 || T < 4) return fail(fn, "need B >= 1 and T >= 4");
@@ -523,10 +538,10 @@ static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lcap, 0, false, N}, &bufs); if (rc) return rc; }
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lcap, 0, false, N, false, 0, -1, nlm}, &bufs); if (rc) return rc; }
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     const int Tp = T / 4, R = B * N;
-    CK(ctc_first_pass(c, bufs, B, Tp, K, N, lm, lm_w, len_bonus, bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att));
+    CK(ctc_first_pass(fn, c, bufs, B, Tp, K, N, lm, nlm, lm_w, len_bonus, bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att));
     // the one host synchronisation of the decode: the list lengths decide how many positions the decoder pass has
     std::vector<int> h_lens(R);
     HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), bufs.rs_lens, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
@@ -563,6 +578,17 @@ int64_t masr_beam_ctc_nlm_workspace_bytes(const masr_model* m, const masr_nlm* n
 }
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
     return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, shape_ok(B, T, K), "need B >= 1, T >= 4, 1 <= K <= 64", B, T, DecodeSpec{K, 0, 0, true});
+}
+int64_t masr_ctc_beam_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K) {
+    const char* fn = "masr_ctc_beam_nlm_workspace_bytes";
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    return decode_workspace_bytes(fn, m, shape_ok(B, T, K), "need B >= 1, T >= 4, 1 <= K <= 64", B, T, DecodeSpec{K, 0, 0, true, 0, false, 0, -1, nlm});
+}
+int64_t masr_rescore_nlm_workspace_bytes(const masr_model* m, const masr_nlm* nlm, int B, int T, int K, int N, int Lmax) {
+    const char* fn = "masr_rescore_nlm_workspace_bytes";
+    if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
+    return decode_workspace_bytes(fn, m, shape_ok(B, T, K) && N >= 1 && N <= K && Lmax >= 0 && Lmax < MASR_PE_ROWS,
+                                  "need B >= 1, T >= 4, 1 <= N <= K <= 64, 0 <= Lmax < 3000", B, T, DecodeSpec{K, Lmax, 0, false, N, false, 0, -1, nlm});
 }
 int64_t masr_rescore_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
     return decode_workspace_bytes("masr_rescore_workspace_bytes", m, shape_ok(B, T, K) && N >= 1 && N <= K && Lmax >= 0 && Lmax < MASR_PE_ROWS,
@@ -645,13 +671,22 @@ int masr_recog_beam_ctc_nlm(masr_model* m, const masr_nlm* nlm, const float* xs,
 int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
                         float* scores, void* stream) {
     // CTC prefix beam search on the head alone (ctc_beam.hip)
-    return recog_ctc_beam_impl("masr_recog_ctc_beam", m, false, nullptr, 0.f, 0.f, xs, ilens, B, T, K, nbest, tokens, lens, scores, nullptr, stream);
+    return recog_ctc_beam_impl("masr_recog_ctc_beam", m, false, nullptr, nullptr, 0.f, 0.f, xs, ilens, B, T, K, nbest, tokens, lens, scores, nullptr, stream);
 }
 
 int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
                            float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
     // masr_recog_ctc_beam with the LM-fused sweep (ctc_beam.hip): the same plan, encoder pass and head GEMM
-    return recog_ctc_beam_impl("masr_recog_ctc_beam_lm", m, true, lm, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am, stream);
+    return recog_ctc_beam_impl("masr_recog_ctc_beam_lm", m, true, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am, stream);
+}
+
+int masr_recog_ctc_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
+                            float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
+    // masr_recog_ctc_beam with the LSTM LM's frame-synchronous search (ctc_beam.hip): the same encoder pass and head GEMM
+    const char* fn = "masr_recog_ctc_beam_nlm";
+    CK(check_model(fn, m));
+    if (!nlm) return fail(fn, "null language model");
+    return recog_ctc_beam_impl(fn, m, true, nullptr, nlm, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am, stream);
 }
 
 int masr_test_ctc_beam_logits(masr_model* m, int B, int T, int K, float** logits, int64_t* ld, int32_t** enc_lens) {
@@ -732,15 +767,24 @@ int masr_test_ctc_align_logits(masr_model* m, int B, int T, int maxL, float** lo
 
 int masr_recog_rescore(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens,
                        int32_t* lens, float* scores, float* att, float* ctc, int32_t* order, void* stream) {
-    return recog_rescore_impl("masr_recog_rescore", m, false, nullptr, 0.f, 0.f, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
+    return recog_rescore_impl("masr_recog_rescore", m, false, nullptr, nullptr, 0.f, 0.f, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order,
                               stream);
 }
 
 int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
                           float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
                           int32_t* order, void* stream) {
-    return recog_rescore_impl("masr_recog_rescore_lm", m, true, lm, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
+    return recog_rescore_impl("masr_recog_rescore_lm", m, true, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
                               order, stream);
+}
+
+int masr_recog_rescore_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,
+                           float len_bonus, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores, float* att, float* ctc,
+                           int32_t* order, void* stream) {
+    const char* fn = "masr_recog_rescore_nlm";
+    CK(check_model(fn, m));
+    if (!nlm) return fail(fn, "null language model");
+    return recog_rescore_impl(fn, m, true, nullptr, nlm, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc, order, stream);
 }
 
 int masr_rescore_nbest(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int N, const int32_t* tokens_in, int64_t ld_tok,

@@ -732,5 +732,31 @@ int masr_test_nlm_step(const masr_nlm* nlm, int R, int K, int t, const int32_t* 
     hipFree(w);
     return rc;
 }
+// the carry form of the same step (mk_nlm_step_carry)
+int masr_test_nlm_step_carry(const masr_nlm* nlm, int R, int K, int t, const int32_t* tok, const int32_t* par, const int32_t* live, uint16_t* hstate,
+                             float* cstate, float* logits, int64_t ld, float* logp, void* stream) {
+    const char* fn = "masr_test_nlm_step_carry";
+    if (!nlm || !hstate || !cstate || !logits || !logp || !tok || !par || !live) { mk_set_error(fn, "null pointer"); return -1; }
+    if (R < 1 || K < 1 || R % K || t < 1 || ld < nlm->dev.C || R > (1 << 20)) { mk_set_error(fn, "need 1 <= R <= 2^20, K >= 1, R % K == 0, t >= 1, ld >= C"); return -1; }
+    if (!test_al16(hstate)) { mk_set_error(fn, "operands must be 16-byte aligned"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    char* w = nullptr;                                       // step[2] | htop [R][Hp]
+    const size_t htop_off = 256, bytes = htop_off + sizeof(bf16) * (size_t)R * nlm->dev.Hp;
+    HIP_CHECK_RET(hipMalloc(&w, bytes));
+    const int h_step[2] = {t, 0};
+    NlmStepArgs a{};
+    a.step = (int*)w; a.R = R; a.K = K; a.tok_hist = tok; a.par_hist = par; a.hist_stride = 0; a.live = live;
+    a.hstate = (bf16*)hstate; a.cstate = cstate; a.htop = (bf16*)(w + htop_off);
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemsetAsync(w, 0, bytes, s));
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        CK(mk_nlm_step_carry(nlm->dev, a, logits, (long)ld, logp, (long)ld, (int*)w, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
 
 }  // extern "C"

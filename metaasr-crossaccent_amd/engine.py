@@ -471,6 +471,22 @@ class MasrEngine:
         self._last_x = xs
         return out if raw else nbest_lists(*out)
 
+    def recog_ctc_beam_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
+                           raw: bool = False):
+        """recog_ctc_beam_lm with the LSTM LM `nlm` (an LstmLM over this model's odim classes) in the n-gram's place
+        (masr_recog_ctc_beam_nlm): the search runs frame by frame, every beam row carrying the LM's recurrent state.  lm_w
+        finite and >= 0, len_bonus finite of any sign.  Returns what recog_ctc_beam_lm returns: per utterance a list of at most nbest
+        (token list, fused score, acoustic score), best first (raw: the device tensors tokens, lens, scores, am instead)."""
+        K, N = check_beam_args(beam_size, nbest)
+        lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_ctc_beam_nlm_workspace_bytes", nlm.h, B, T, K)
+        out = self._outputs(B, N, ld=T // 4, extra="f")
+        check(self._l.masr_recog_ctc_beam_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, *map(_ptr, out), self.stream()),
+              "masr_recog_ctc_beam_nlm")
+        self._last_x = xs
+        return out if raw else nbest_lists(*out)
+
     def ctc_align(self, xs: torch.Tensor, ilens, ys, olens, raw: bool = False):
         """CTC forced alignment of each utterance's transcript on the CTC head (masr_recog_ctc_align; needs a hybrid model): one
         encoder pass, the head GEMM, one Viterbi sweep over the T/4 frames.  ys: per-utterance token lists / tensors without sos / eos, olens
@@ -537,6 +553,21 @@ class MasrEngine:
         out = self._rescore_outputs(B, N, T // 4)
         check(self._l.masr_recog_rescore_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, att_w, ctc_w, *map(_ptr, out),
                                             self.stream()), "masr_recog_rescore_lm")
+        self._last_x = xs
+        return out if raw else self._rescore_lists(out)
+
+    def recog_rescore_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest=None,
+                          att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
+        """recog_rescore whose first pass is recog_ctc_beam_nlm's LSTM-LM-fused search (masr_recog_rescore_nlm): the `ctc` of an
+        entry is that pass's fused score.  Returns what recog_rescore returns."""
+        K, N = check_beam_args(beam_size, nbest)
+        att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
+        lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_rescore_nlm_workspace_bytes", nlm.h, B, T, K, N, T // 4)
+        out = self._rescore_outputs(B, N, T // 4)
+        check(self._l.masr_recog_rescore_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, att_w, ctc_w, *map(_ptr, out),
+                                             self.stream()), "masr_recog_rescore_nlm")
         self._last_x = xs
         return out if raw else self._rescore_lists(out)
 

@@ -167,6 +167,18 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_rescore_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest, att_weight, ctc_weight)
 
+    def nlm_ctc_beam_decode(self, xs_pad, ilens, beam_size, nlm, lm_weight=0.3, len_bonus=0.0, nbest=1):
+        """lm_ctc_beam_decode with the LSTM LM `nlm` (an LstmLM) in the n-gram's place (masr_recog_ctc_beam_nlm, hybrid models only): per
+        utterance a list of at most nbest (token list, fused score, acoustic score), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_ctc_beam_nlm(xs_pad, ilens, beam_size, nlm, lm_weight, len_bonus, nbest)
+
+    def nlm_rescore_decode(self, xs_pad, ilens, beam_size, nlm, lm_weight=0.3, len_bonus=0.0, nbest=None, att_weight=0.5, ctc_weight=0.5):
+        """attention rescoring of the LSTM-LM-fused CTC beam's nbest list (masr_recog_rescore_nlm, hybrid models only): rescore_decode with
+        nlm_ctc_beam_decode's search as the first pass"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_rescore_nlm(xs_pad, ilens, beam_size, nlm, lm_weight, len_bonus, nbest, att_weight, ctc_weight)
+
     def rescore_decode(self, xs_pad, ilens, beam_size, nbest=None, att_weight=0.5, ctc_weight=0.5):
         """attention rescoring (masr_recog_rescore, hybrid models only): the CTC prefix beam's nbest list re-ranked by
         att_weight * log p_att + ctc_weight * log p_ctc after one teacher-forced decoder pass; per utterance a list of

@@ -42,6 +42,12 @@ anything is decoded.  Tester.MODES is the table of them:
                  ratios, lm_w (0.3), len_bonus (0, finite, any sign) and nbest (1, in [1, beam_size]) as for `lm_joint_beam`.  This is where a
                  hybrid model that `nlm_beam` refuses for its ctc_w goes.  No path or a BLSTM raises NotImplementedError, a transformer
                  without a CTC head ValueError, an LM over another number of classes ValueError.
+  nlm_ctc_beam   masr_recog_ctc_beam_nlm (BLSTM-CTC: masr_ctc_beam_search_nlm), `lm_ctc_beam` with the LSTM LM of `nlm_beam` in the n-gram's
+                 place: the search runs frame by frame and every beam row carries the LM's state.  `--lm_model_path` and
+                 lm_start as for `nlm_beam`; beam_size, lm_w (0.3) and len_bonus (0, finite, any sign) as for `lm_ctc_beam`.  Refuses what
+                 `lm_ctc_beam` refuses (a BLSTM whose blank is not id 0 included), and an LM over another number of classes (ValueError).
+  nlm_rescore    masr_recog_rescore_nlm, `rescore` with `nlm_ctc_beam`'s search as its first pass: nbest, att_w and ctc_w as for `rescore`,
+                 the rest as for `nlm_ctc_beam`.  Refuses what `rescore` refuses (a BLSTM: NotImplementedError).
   ctc_align      masr_recog_ctc_align (BLSTM-CTC: masr_ctc_align per utterance), the CTC forced alignment of DESIGN 5.9: no search, so no
                  solver.beam_decode block is read.  Each test utterance's REFERENCE transcript is aligned to the frames of the CTC output
                  layer, and one line per utterance is appended to `<decode_dir>/ctc-ali` (no best-hyp is written):
@@ -314,6 +320,29 @@ class Tester:
         lm = self._load_lm(lm_path, 0, len(self.id2ch) - 1)         # <s> = 0 (the BLSTM's <blank> slot), </s> last
         logger.notice(f"LM-fused CTC beam: {lm}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
 
+    def _nlm_ctc_settings(self):
+        """nlm_ctc_beam and nlm_rescore: _lm_ctc_settings' searches with _nlm_beam_settings' LM"""
+        mode = self.decode_mode
+        lm_path = self._lm_model_path("a torch checkpoint of an LSTM LM over the output units")
+        if mode == 'nlm_rescore':
+            self._rescore_settings()                             # (BLSTM: NotImplementedError; no CTC head: ValueError; nbest, att_w, ctc_w)
+        else:
+            self._beam_size()
+            if self.model_name != 'blstm':
+                self._need_ctc_head(mode, "nlm_beam, beam or greedy")
+            elif self.blank_id != 0:
+                raise ValueError(f"decode_mode '{mode}' needs the blank at id 0 (the search never emits class 0), got {self.blank_id}")
+        bd = self.config['solver']['beam_decode']
+        self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+        self._len_bonus(bd)
+        start = bd.get('lm_start', 'sos')
+        if start not in ('sos', 'eos'):
+            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
+        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
+        if self.nlm.C != len(self.id2ch):
+            raise ValueError(f"{mode}: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        logger.notice(f"LSTM-LM-fused CTC beam: {lm}, start token {start}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
+
     def _lm_joint_settings(self):
         lm_path = self._lm_model_path()
         if self.model_name == 'blstm':
@@ -371,6 +400,11 @@ class Tester:
             return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus)
         return self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
 
+    def _nlm_ctc_beam_lists(self, xs, ilens):
+        if self.model_name == 'blstm':
+            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.nlm, self.lm_weight, self.len_bonus)
+        return self.asr_model.nlm_ctc_beam_decode(xs, ilens, self.beam_size, self.nlm, self.lm_weight, self.len_bonus)
+
     # mode -> (its settings function, (Tester, xs, ilens) -> the best hypothesis of each utterance, Tester -> what the start-up line names);
     # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself; nor has ctc_align, which reads the
     # references too and writes ctc-ali (batch_ctc_align)
@@ -398,6 +432,13 @@ class Tester:
                        lambda t, xs, il: [n[0][0] for n in t.asr_model.lm_rescore_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest,
                                                                                          t.att_weight, t.ctc_weight)],
                        lambda t: f"attention rescoring of the LM-fused CTC beam (beam {t.beam_size})"),
+        'nlm_ctc_beam': (_nlm_ctc_settings,
+                         lambda t, xs, il: t._ctc_best(t._nlm_ctc_beam_lists(xs, il)),
+                         lambda t: f"LSTM-LM-fused CTC prefix beam decoding (beam {t.beam_size})"),
+        'nlm_rescore': (_nlm_ctc_settings,
+                        lambda t, xs, il: [n[0][0] for n in t.asr_model.nlm_rescore_decode(xs, il, t.beam_size, t.nlm, t.lm_weight, t.len_bonus, t.nbest,
+                                                                                           t.att_weight, t.ctc_weight)],
+                        lambda t: f"attention rescoring of the LSTM-LM-fused CTC beam (beam {t.beam_size})"),
         'ctc_align': (_ctc_align_settings, None, lambda t: "CTC forced alignment of the reference transcripts"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
