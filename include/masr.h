@@ -636,6 +636,58 @@ int masr_ctc_beam_search_nlm(const float* logits, int64_t ld, const int32_t* enc
                              const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,
                              float* scores, float* am, void* stream);
 
+/* Contextual phrase biasing of the CTC prefix beam (the context graph of WeNet's CTC prefix beam search).
+ * The phrase list: P in [1, 65536] phrases of 1 .. 64 tokens each over the model's C in [3, 65535] classes, tokens in [1, C - 2] (no blank / sos, no
+ * eos).  masr_bias_create takes host arrays, phrase i = tokens[off[i] .. off[i + 1]); it builds a trie whose nodes are the distinct prefixes of
+ * the phrases (root = node 0, at most 2^20 nodes), as one open-addressing table of 16-byte slots (node, token) -> child with the n-gram tables'
+ * capacity, hash and probing, plus one byte revoke(u) per node, on the current device.  NULL + masr_last_error() for a null array, C or P out of
+ * range, a phrase of length 0 or above 64, a token outside [1, C - 2], a duplicate phrase or more than 2^20 nodes -- all found on the host, before
+ * anything touches the device.  masr_bias_bytes: device bytes held; masr_bias_nodes: the trie's nodes, the root included.
+ *   d(u) the depth of node u, e(u) the length of the longest phrase that is a prefix of, or equal to, u's string (0: none), revoke(u) = d(u) - e(u).
+ *   The state of a hypothesis is (u, n), n the credited tokens; () has (root, 0), and token c advances it:
+ *     v = child(u, c);  if v exists: (v, n + 1)
+ *     n = n - revoke(u);  v = child(root, c);  if v exists: (v, n + 1);  else (root, n)
+ *   and n_final(h) = n - revoke(u) at the end of the utterance.  n >= 0 always.  A phrase that is a proper prefix of a longer one keeps its tokens
+ *   when the longer match breaks.  There are no failure links: a broken match restarts at the root with the current token, so an overlapping
+ *   restart is missed on purpose (the phrase `a a b` is not found in `a a a b`).
+ * masr_ctc_beam_search_bias is masr_ctc_beam_search_lm word for word when lm is given and masr_ctc_beam_search when lm is null (lm_w and len_bonus
+ * are then ignored and no lmacc exists), except:
+ *   state      each entry also carries (u, n) of its prefix: an extension that is a candidate gets step(parent's state, c), a stay keeps its own,
+ *              a merged extension needs none.  The state is a function of the token sequence alone, so a prefix that is merged into, or leaves
+ *              the beam and is created again, has the same state whichever parent produced it.  p_b, p_nb, lmacc, S_t (by acoustic logit alone),
+ *              the merge test and the prefix hash are untouched.
+ *   ranking    a candidate scores fl(x + fl(bias_w * (float)n(prefix))), x = fl(acoustic + lmacc(prefix)) with the LM, the acoustic score without.
+ *              The count is provisional: a half-matched phrase is already boosted.  Every product and sum rounded on its own; selection order
+ *              unchanged.
+ *   the end    final(h) = fl(y + fl(bias_w * (float)n_final(h))), y = fl(fl(am + lmacc) + fl(lm_w * lm(eos | h))) with the LM, y = am without;
+ *              the final beam is re-ranked by (final descending, beam rank ascending) in both cases.
+ * Result (device): tokens, lens, scores (= final) and am as masr_ctc_beam_search_lm gives them (am also without an LM); nbias int32 [B][nbest] =
+ * n_final, -1 in slots that are not live; enc_len 0 gives the empty prefix with am 0 and nbias 0.
+ * Needs blank == 0 and eos == C - 1 with or without an LM, bias->C == C <= 4096, bias_w finite and >= 0.  -1 with a message before any launch:
+ * a null phrase list and everything the underlying search refuses.  The work buffer is masr_ctc_beam_bias_work_bytes(B, Tp, C, K) bytes (the
+ * plain search's size: the state lives on chip).  The LSTM LM search has no biasing. */
+typedef struct masr_bias masr_bias;
+masr_bias* masr_bias_create(int C, int P, const int32_t* tokens, const int64_t* off);
+void masr_bias_destroy(masr_bias* bias);
+int64_t masr_bias_bytes(const masr_bias* bias);
+int masr_bias_nodes(const masr_bias* bias);
+int64_t masr_ctc_beam_bias_work_bytes(int B, int Tp, int C, int K);
+int masr_ctc_beam_search_bias(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                              const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work, int64_t work_bytes,
+                              int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias, void* stream);
+/* Through the transformer (hybrid models): masr_recog_ctc_beam_bias runs the encoder pass and head GEMM of masr_recog_ctc_beam, then
+ * masr_ctc_beam_search_bias with blank 0 and eos = odim - 1 (lm may be null) in the workspace of masr_ctc_beam_workspace_bytes(B, T, K).
+ * masr_recog_rescore_bias is masr_recog_rescore_lm with that search as its first pass: c(b, n) is its final score, copied bit for bit into
+ * `ctc`; the second pass (not biased), the single host synchronisation and the workspace are masr_recog_rescore's.  -1 besides what
+ * masr_recog_ctc_beam / masr_recog_rescore refuse: a null phrase list, one whose C is not the model's odim, bias_w negative or not finite and,
+ * with an LM, what masr_recog_ctc_beam_lm refuses. */
+int masr_recog_ctc_beam_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K,
+                             int nbest, float lm_w, float len_bonus, float bias_w, int32_t* tokens, int32_t* lens, float* scores, float* am,
+                             int32_t* nbias, void* stream);
+int masr_recog_rescore_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K, int N,
+                            float lm_w, float len_bonus, float bias_w, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
+                            float* att, float* ctc, int32_t* order, void* stream);
+
 /* CTC forced alignment: the single best alignment (Viterbi path) of a known transcript to the frames of a CTC output layer, model-free like
  * masr_ctc_loss and masr_ctc_beam_search.  logits and enc_lens as for masr_ctc_beam_search (row of utterance b, frame t at
  * logits + (b * Tp + t) * ld, ld >= C; enc_lens device int32 [B], each clamped to [0, Tp]; frames past it and columns >= C are never read);

@@ -199,6 +199,13 @@ int masr_test_rescore_logits(masr_model* m, float** logits, int64_t* ld, int32_t
 int masr_test_lm_score(const masr_lm* lm, const int32_t* ctx, int R, float* out, void* stream);
 /* the longest probe chain (slots examined) an insertion walked while the LM's tables were built; 1 = no n-gram ever met an occupied slot */
 int masr_test_lm_max_probe(const masr_lm* lm);
+/* ---- contextual phrase biasing (bias.hip; tests/test_hip_bias_kernels.py)
+ * the automaton's step on `count` independent states (device int32 arrays): (nodes_out, n_out)[i] = step((nodes_in, n_in)[i], tokens[i]) by the
+ * __device__ function the sweep calls; a node outside the trie gives (-1, -1), a token outside [0, C) has no child.  Waits for the stream. */
+int masr_test_bias_step(const masr_bias* bias, const int32_t* nodes_in, const int32_t* n_in, const int32_t* tokens, int count, int32_t* nodes_out,
+                        int32_t* n_out, void* stream);
+/* the longest probe chain an insertion into the phrase table walked (slots examined) */
+int masr_test_bias_max_probe(const masr_bias* bias);
 /* the beam's row stage with the n-gram LM alone (beam.hip beam_rows_kernel, top-K) at step t >= 1 on R = B*K rows of caller-given fp32 logits [R][ld] (C = the LM's classes
  * <= ld): score fp32 [R] (-inf = dead row), minlen int32 [B], and the token / parent-row histories of the steps before, tok_hist / par_hist
  * int32 [t - 1][R] (null at t = 1; the kernel clamps what it reads).  Out: list_tok int32 / list_score fp32 [R][K].  The fused rows and the

@@ -82,6 +82,12 @@ _SIGS = {
     "masr_lm_create": (vp, [i32, i32, C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "masr_lm_destroy": (None, [vp]),
     "masr_lm_bytes": (i64, [vp]),
+    "masr_bias_create": (vp, [i32, i32, vp, vp]),
+    "masr_bias_destroy": (None, [vp]),
+    "masr_bias_bytes": (i64, [vp]),
+    "masr_bias_nodes": (i32, [vp]),
+    "masr_recog_ctc_beam_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "masr_recog_rescore_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_beam_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
     "masr_nlm_create": (vp, [i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]),
@@ -135,6 +141,8 @@ _SIGS = {
     "masr_ctc_beam_work_bytes": (i64, [i32, i32, i32, i32]),
     "masr_ctc_beam_search": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "masr_ctc_beam_lm_work_bytes": (i64, [i32, i32, i32, i32]),
+    "masr_ctc_beam_bias_work_bytes": (i64, [i32, i32, i32, i32]),
+    "masr_ctc_beam_search_bias": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, f32, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_ctc_beam_search_lm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_ctc_beam_nlm_work_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_ctc_beam_search_nlm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
@@ -159,6 +167,8 @@ _SIGS = {
     "masr_test_rescore_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]),
     "masr_test_lm_score": (i32, [vp, vp, i32, vp, vp]),
     "masr_test_lm_max_probe": (i32, [vp]),
+    "masr_test_bias_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
+    "masr_test_bias_max_probe": (i32, [vp]),
     "masr_test_beam_lm_topk": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_test_joint_lm_prebeam": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_beam_nlm_rows": (i32, [vp, i64, f32, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
@@ -284,6 +294,11 @@ def align_targets(ys, olens, device):
     off = [sum(max(n, 0) for n in ol[:b]) for b in range(len(ol))]
     i32 = dict(dtype=torch.int32, device=device)
     return torch.tensor(flat or [0], **i32), torch.tensor(off, **i32), torch.tensor(ol, **i32), max(ol + [0])
+
+
+def nbest_lists_bias(tok, lens, scores, am, nbias):
+    """device results of masr_ctc_beam_search_bias -> per utterance [(token list, final score, acoustic score, credited tokens), ...]"""
+    return [[(t, s, a, int(n)) for t, s, a, n in u] for u in nbest_lists(tok, lens, scores, am, nbias)]
 
 
 nbest_lists_lm = nbest_lists                                   # (the name the LM-fused searches' callers know)

@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import align_lists, align_outputs, align_targets, check, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists
+from ._cabi import align_lists, align_outputs, align_targets, check, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists, nbest_lists_bias
+from .bias import check_bias_args
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 
@@ -138,15 +139,21 @@ class BlstmEngine:
         check(self._l.masr_blstm_check(self.h, self.stream()), "masr_blstm_check")
         return self.last_logits()
 
-    def ctc_beam(self, xs, ilens, K, nbest=1, blank=0, lm=None, lm_w=0.0, len_bonus=0.0):
+    def ctc_beam(self, xs, ilens, K, nbest=1, blank=0, lm=None, lm_w=0.0, len_bonus=0.0, bias=None, bias_w=0.0):
         """CTC prefix beam search over the head's output (masr_ctc_beam_search; `blank` and eos = odim - 1 are never emitted): the
         forward with its check, then the search on last_logits() with a work tensor of this engine's own.  Returns per utterance a list
         of at most nbest (token list, score), best first.  With lm (an NGramLM over the odim classes, <s> in the blank's slot 0) the search
         is masr_ctc_beam_search_lm (lm_w finite and >= 0, len_bonus finite, blank 0) and the entries are
         (token list, fused score, acoustic score); with an LstmLM over the odim classes it is masr_ctc_beam_search_nlm, under
-        the same conditions and with the same entries."""
+        the same conditions and with the same entries.  With bias (a ContextBias over the odim classes) the search is
+        masr_ctc_beam_search_bias (bias_w finite and >= 0, blank 0, lm none or an NGramLM) and the entries are
+        (token list, final score, acoustic score, credited tokens)."""
         K = int(K)
         neural = lm is not None and hasattr(lm, "score")       # an LstmLM (nlm.py); anything else goes the n-gram's way
+        if bias is not None:
+            if neural:
+                raise NotImplementedError("contextual biasing is not fused into the LSTM LM search (DESIGN 5.13)")
+            bias_w = check_bias_args(bias, bias_w)
         if neural:
             lm_w, len_bonus = check_nlm_args(lm, lm_w, len_bonus)
         elif lm is not None:
@@ -164,8 +171,15 @@ class BlstmEngine:
             self._beam_work = torch.empty(need, dtype=torch.uint8, device=self.device)     # (torch's allocations are 512-byte aligned)
         i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
         out = [torch.empty(B, N, Tp, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **f32)]      # tokens, lens, scores
-        if lm is not None:
+        if lm is not None or bias is not None:
             out.append(torch.empty(B, N, **f32))                                                    # acoustic scores
+        if bias is not None:
+            out.append(torch.empty(B, N, **i32))                                                    # credited tokens
+            check(self._l.masr_ctc_beam_search_bias(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1,
+                                                    lm.h if lm is not None else None, lm_w if lm is not None else 0.0,
+                                                    len_bonus if lm is not None else 0.0, bias.h, bias_w, _ptr(self._beam_work),
+                                                    self._beam_work.numel(), *map(_ptr, out), self.stream()), "masr_ctc_beam_search_bias")
+            return nbest_lists_bias(*out)
         fn, lm_args = ("masr_ctc_beam_search", ()) if lm is None else ("masr_ctc_beam_search_nlm" if neural else "masr_ctc_beam_search_lm",
                                                                        (lm.h, lm_w, len_bonus))
         check(getattr(self._l, fn)(_ptr(logits), Cc, _ptr(lens), B, Tp, Cc, K, N, int(blank), self.odim - 1, *lm_args, _ptr(self._beam_work),
@@ -291,16 +305,18 @@ class MonoBLSTM:
 
     greedy_decode = __call__                                  # mono_blstm.py:63-64
 
-    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1, lm=None, lm_weight=0.0, len_bonus=0.0):
+    def ctc_beam_decode(self, xs_pad, ilens, beam_size, nbest=1, lm=None, lm_weight=0.0, len_bonus=0.0, bias=None, bias_weight=0.0):
         """CTC prefix beam search on the head (BlstmEngine.ctc_beam; the reference's own beam decoder is dead code); with lm,
-        the LM-fused search, entries (token list, fused score, acoustic score).
+        the LM-fused search, entries (token list, fused score, acoustic score); with bias (a ContextBias), the phrase-biased
+        search, entries (token list, final score, acoustic score, credited tokens).
         Each utterance is run alone, cut to its own length.  The VGG front end does not mask padded frames (as in the reference: behind
         the first conv they hold relu(bias), which the next convs read at the utterance's last frames), so in a padded batch an
         utterance's logits depend on the batch's length; alone, its hypotheses are a function of the utterance, whatever the batch size."""
         out = []
         for b, n in enumerate(torch.as_tensor(ilens).tolist()):
+            more = {} if bias is None else dict(bias=bias, bias_w=bias_weight)
             out += self.engine.ctc_beam(xs_pad[b:b + 1, :int(n)], [int(n)], beam_size, nbest, blank=self.blank_id, lm=lm, lm_w=lm_weight,
-                                        len_bonus=len_bonus)
+                                        len_bonus=len_bonus, **more)
         return out
 
     def ctc_align(self, xs_pad, ilens, ys, olens):

@@ -12,14 +12,17 @@
 // token, so "h + c is the beam entry h'" is  len(h') == len(h) + 1, parent_hash(h') == hash(h), last(h') == c.  Two different prefixes of
 // one beam with equal length and equal hash would be merged wrongly (DESIGN 5.3 has the odds).
 //
-// ctc_beam_sweep<true> is the same sweep with a backoff n-gram LM and a per-token bonus fused into the ranking (masr_ctc_beam_search_lm,
+// ctc_beam_sweep<true, false> is the same sweep with a backoff n-gram LM and a per-token bonus fused into the ranking (masr_ctc_beam_search_lm,
 // DESIGN 5.6).  p_b and p_nb stay purely acoustic; an entry also carries lmacc(h), the fp32 sum of its tokens' fl(fl(lm_w * lm(c | h)) +
 // len_bonus), and its LM context as one 64-bit word: the last <= 3 ids of [sos] + h as id + 1 in 16-bit fields, newest lowest -- the
 // order-k key of lm.h is a mask of it, so no record is walked for a context.  A candidate ranks by fl(acoustic score + lmacc(prefix)).
 // Per frame: every entry's <= N - 1 context backoffs are looked up once, next to the stay's gathers; after the merge, each surviving
 // (entry, class) pair issues its <= N - 1 first probes and the unigram load together and resolves them from the longest order down
 // (lm_score's order of additions); a merged pair needs no LM value, its target has one.  The tail adds fl(lm_w * lm(eos | h)) and re-ranks
-// the final beam.  ctc_beam_sweep<false> compiles to the sweep without any of it.
+// the final beam.  ctc_beam_sweep<false, false> compiles to the sweep without any of it.
+//
+// ctc_beam_sweep<LM, true> adds contextual phrase biasing (masr_ctc_beam_search_bias): each entry carries the state of the phrase
+// automaton of bias.h and ranks with fl(bias_w * credited tokens) added; the comment at the kernel has the rest.
 //
 // masr_ctc_beam_search_nlm is the same search with an LSTM LM's term (nlm.h) in the n-gram's place.  That LM has state, so the
 // search runs frame by frame across launches: ctc_beam_frame runs ONE frame of every utterance on the beam kept in the work buffer, the LM's
@@ -34,6 +37,7 @@
 #include "host_util.h"
 #include "lm.h"
 #include "nlm.h"
+#include "bias.h"
 
 namespace {
 
@@ -46,7 +50,7 @@ __device__ __forceinline__ unsigned long long hash_push(unsigned long long h, in
 }
 __device__ __forceinline__ int clamp_len(int n, int Tp) { return n < 0 ? 0 : (n > Tp ? Tp : n); }
 
-// ---- the LM side of ctc_beam_sweep<true>
+// ---- the LM side of ctc_beam_sweep<true, false>
 struct CtcLmArgs { LmDev lm; float lm_w, len_bonus; float* am; };      // am [B][nbest]: the acoustic totals
 
 constexpr unsigned long long CTX_MASK = (1ull << 48) - 1;
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
                     [&](int i, int c) { sc[i] = c; sl[i] = c < 0 ? NEG_INF : z[c] - lse; });
 }
 
-// The beam, the frame's candidates and the selection scratch of one utterance, in LDS.  M: 0 = no LM, 1 = the n-gram (ctc_beam_sweep<true>),
+// The beam, the frame's candidates and the selection scratch of one utterance, in LDS.  M: 0 = no LM, 1 = the n-gram (ctc_beam_sweep<true, false>),
 // 2 = the LSTM LM (ctc_beam_frame); a mode holds only what it reads.  Candidate index of frame t: parent rank k, then stay (0)
 // or position j in S_t (1 + j): idx = k * (P + 1) + ..., so "score descending, index ascending" is the selection order of DESIGN 5.3.  sc
 // holds each candidate's ordered score, 0 = not a candidate (-inf, or an extension merged into a stay).  LM: the ordered score is that of
@@ -347,8 +351,16 @@ __device__ __forceinline__ void ctc_beam_tail(SwLds<M>& s, const CtcBeamArgs& a,
 // so "score descending, index ascending" is the selection order of DESIGN 5.3.  s_sc holds each candidate's ordered score, 0 = not a
 // candidate (-inf, or an extension merged into a stay).  LM: the ordered score is that of fl(score + lmacc(prefix)), s_lmx holds lmacc(h + c)
 // of the extensions that are candidates, and la.am gets the acoustic totals.
-template <bool LM>
-__global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs a, CtcLmArgs la, int nbest, int* __restrict__ tokens,
+//
+// BIAS (masr_ctc_beam_search_bias): an entry also carries the phrase automaton's state (node, credited tokens n) of its prefix
+// (bias.h), a function of its tokens alone like lmacc and the context.  A candidate ranks by fl(x + fl(bias_w * n(prefix))), x the ordered
+// score above; the term is needed only while a candidate is scored, so no per-candidate array holds the stepped state: the <= K winners step
+// again from their parent when the next beam is written.  The tail revokes the unfinished match, final = fl(y + fl(bias_w * n_final)), and
+// re-ranks with or without an LM; without one la carries only am.
+struct CtcBiasArgs { BiasDev bias; float bias_w; int* nbias; };        // nbias [B][nbest]: n_final, -1 = no entry
+
+template <bool LM, bool BIAS>
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs a, CtcLmArgs la, CtcBiasArgs ba, int nbest, int* __restrict__ tokens,
                                                                     int* __restrict__ lens, float* __restrict__ scores) {
     __shared__ float s_pb[2][KMAX], s_pnb[2][KMAX];
     __shared__ int s_last[2][KMAX], s_len[2][KMAX];
@@ -361,6 +373,8 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     __shared__ float s_lmacc[2][KMAX], s_bo[KMAX][LM_MAX_ORDER - 1], s_lmx[KMAX * (KMAX + 1)];
     __shared__ unsigned long long s_ctx[2][KMAX];
     __shared__ int s_has[KMAX];
+    // BIAS only: the automaton's state per entry
+    __shared__ int s_bnode[2][KMAX], s_bn[2][KMAX];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     const int K = a.K, P = a.P, P1 = P + 1, Tp = a.Tp;
     const int Tb = clamp_len(a.enc_lens[b], Tp);
@@ -368,6 +382,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     if (tid == 0) {
         s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_hash[0][0] = HASH_EMPTY; s_phash[0][0] = 0;
         if constexpr (LM) { s_lmacc[0][0] = 0.f; s_ctx[0][0] = 1; }          // the context [sos]: sos = 0 as id + 1
+        if constexpr (BIAS) { s_bnode[0][0] = 0; s_bn[0][0] = 0; }
     }
     __syncthreads();
     for (int t = 0; t < Tb; ++t) {
@@ -415,6 +430,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
         if (tid < n) {
             float v = log_add(s_stay_pb[tid], s_stay_pnb[tid]);
             if constexpr (LM) v = add_rn(v, s_lmacc[cur][tid]);
+            if constexpr (BIAS) v = add_rn(v, mul_rn(ba.bias_w, (float)s_bn[cur][tid]));
             s_sc[tid * P1] = v == NEG_INF ? 0u : ord_f32(v);
         }
         if constexpr (LM) {
@@ -429,8 +445,25 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
                 for (int i = 0; i < LM_MAX_ORDER - 1; ++i) bo[i] = s_bo[k][i];
                 const float lmv = lm_score_packed(la.lm, s_ctx[cur][k], ctx_len(la.lm, s_len[cur][k]), bo, s_has[k], c);
                 const float acc = add_rn(s_lmacc[cur][k], add_rn(mul_rn(la.lm_w, lmv), la.len_bonus));
-                const float v = add_rn((c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j], acc);
+                float v = add_rn((c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j], acc);
+                if constexpr (BIAS) {
+                    int u = s_bnode[cur][k], nb = s_bn[cur][k];
+                    bias_step(ba.bias, u, nb, c);
+                    v = add_rn(v, mul_rn(ba.bias_w, (float)nb));
+                }
                 s_lmx[idx] = acc;
+                s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
+            }
+        } else if constexpr (BIAS) {
+            // the extensions still standing get the bias term of the state their token leads to
+            for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+                const int k = idx / P1, j = idx % P1 - 1;
+                if (j < 0 || !s_sc[idx]) continue;
+                const int c = s_cls[j];
+                if (c < 0) { s_sc[idx] = 0u; continue; }
+                int u = s_bnode[cur][k], nb = s_bn[cur][k];
+                bias_step(ba.bias, u, nb, c);
+                const float v = add_rn((c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j], mul_rn(ba.bias_w, (float)nb));
                 s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
             }
         }
@@ -472,6 +505,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
                 s_last[nxt][tid] = s_last[cur][k]; s_len[nxt][tid] = s_len[cur][k];
                 s_hash[nxt][tid] = s_hash[cur][k]; s_phash[nxt][tid] = s_phash[cur][k];
                 if constexpr (LM) { s_lmacc[nxt][tid] = s_lmacc[cur][k]; s_ctx[nxt][tid] = s_ctx[cur][k]; }
+                if constexpr (BIAS) { s_bnode[nxt][tid] = s_bnode[cur][k]; s_bn[nxt][tid] = s_bn[cur][k]; }
             } else {
                 const int c = s_cls[j];
                 s_pb[nxt][tid] = NEG_INF;
@@ -479,6 +513,11 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
                 s_last[nxt][tid] = c; s_len[nxt][tid] = s_len[cur][k] + 1;
                 s_hash[nxt][tid] = hash_push(s_hash[cur][k], c); s_phash[nxt][tid] = s_hash[cur][k];
                 if constexpr (LM) { s_lmacc[nxt][tid] = s_lmx[win]; s_ctx[nxt][tid] = ctx_push(s_ctx[cur][k], c); }
+                if constexpr (BIAS) {                               // the winner's step again, from its parent: the same bits as when it was scored
+                    int u = s_bnode[cur][k], nb = s_bn[cur][k];
+                    bias_step(ba.bias, u, nb, c);
+                    s_bnode[nxt][tid] = u; s_bn[nxt][tid] = nb;
+                }
                 rec |= (c + 1) << 8;
             }
             a.rec[row * K + tid] = rec;
@@ -490,15 +529,24 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     // records on the way); everything behind a list's length is -1
     // LM: final(h) = fl(fl(am + lmacc) + fl(lm_w * lm(eos | h))), and list position i is the entry of rank i by (final descending, beam rank
     // ascending) -- ranked on the ordered bits, so the ranks are a permutation whatever the values
+    // BIAS: final(h) = fl(y + fl(bias_w * n_final(h))), y the LM's final or, without one, am; s_bn becomes n_final
     int* out = tokens + (long)b * nbest * Tp;
-    if constexpr (LM) {
+    if constexpr (LM || BIAS) {
         if (tid < n) {
-            const unsigned long long ctx = s_ctx[cur][tid];
-            const int cn = ctx_len(la.lm, s_len[cur][tid]);
-            float bo[LM_MAX_ORDER - 1];
-            const int has = ctx_backoffs(la.lm, ctx, cn, bo);
             const float am = log_add(s_pb[cur][tid], s_pnb[cur][tid]);
-            const float fin = add_rn(add_rn(am, s_lmacc[cur][tid]), mul_rn(la.lm_w, lm_score_packed(la.lm, ctx, cn, bo, has, a.eos)));
+            float fin = am;
+            if constexpr (LM) {
+                const unsigned long long ctx = s_ctx[cur][tid];
+                const int cn = ctx_len(la.lm, s_len[cur][tid]);
+                float bo[LM_MAX_ORDER - 1];
+                const int has = ctx_backoffs(la.lm, ctx, cn, bo);
+                fin = add_rn(add_rn(am, s_lmacc[cur][tid]), mul_rn(la.lm_w, lm_score_packed(la.lm, ctx, cn, bo, has, a.eos)));
+            }
+            if constexpr (BIAS) {
+                const int nf = bias_final(ba.bias, s_bnode[cur][tid], s_bn[cur][tid]);
+                s_bn[cur][tid] = nf;
+                fin = add_rn(fin, mul_rn(ba.bias_w, (float)nf));
+            }
             s_tot[tid] = am; s_xl[tid] = fin; s_sc[tid] = ord_f32(fin);
         }
         __syncthreads();
@@ -511,11 +559,12 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     }
     if (tid < nbest) {
         const bool live = tid < n;
-        const int src = LM && live ? s_cls[tid] : tid;
+        const int src = (LM || BIAS) && live ? s_cls[tid] : tid;
         int pos = live ? s_len[cur][src] : 0, slot = src;
         s_win[tid] = pos;
         lens[b * nbest + tid] = live ? pos : -1;
-        if constexpr (LM) {
+        if constexpr (BIAS) ba.nbias[b * nbest + tid] = live ? s_bn[cur][src] : -1;
+        if constexpr (LM || BIAS) {
             scores[b * nbest + tid] = live ? s_xl[src] : NEG_INF;
             la.am[b * nbest + tid] = live ? s_tot[src] : NEG_INF;
         } else {
@@ -552,7 +601,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_nlm_prepare_kernel(CtcNlm
     for (long i = (long)b * SW_THREADS + threadIdx.x; i < htop_n; i += (long)gridDim.x * SW_THREADS) htop[i] = (bf16)0.f;
 }
 
-// grid B, 256 threads: frame t = st - 2 of every utterance -- ctc_beam_sweep<true>'s frame with the LM term gathered from the log-softmax
+// grid B, 256 threads: frame t = st - 2 of every utterance -- ctc_beam_sweep<true, false>'s frame with the LM term gathered from the log-softmax
 // row of the parent's beam row.  Besides the back-pointer record every kept entry leaves its parent row and its token (-1: a stay) for the LM's
 // carry step.  An utterance past its enc_len keeps its beam: every live row stays in its own row.
 __global__ __launch_bounds__(SW_THREADS) void ctc_beam_frame_kernel(CtcBeamArgs a, CtcNlmArgs q) {
@@ -654,18 +703,32 @@ static int ctc_beam_frames(const CtcBeamArgs& a, hipStream_t s) {
 
 // the checks and the two launches of the sweep's entry points; la: the LM side, or null
 static int ctc_beam_run(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
-                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, const CtcLmArgs* la, hipStream_t s) {
+                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, const CtcLmArgs* la, hipStream_t s,
+                        const CtcBiasArgs* ba = nullptr, float* am = nullptr) {
     CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, la != nullptr, la ? la->lm.C : 0,
                       la ? la->lm.order : 0, la ? la->lm_w : 0.f, la ? la->len_bonus : 0.f, la ? la->am : nullptr));
+    if (ba) {
+        // the phrase tokens are the model's classes 1 .. C - 2 whether an LM is fused or not
+        if (blank != 0) { mk_set_error(fn, "blank must be 0 with a phrase list (class 0 is no phrase token)"); return -1; }
+        if (eos != C - 1) { mk_set_error(fn, "eos must be C - 1 with a phrase list (the last class is no phrase token)"); return -1; }
+        if (ba->bias.C != C) { mk_set_error(fn, "the phrase list's classes differ from C"); return -1; }
+        if (!(ba->bias_w >= 0.f) || !std::isfinite(ba->bias_w)) { mk_set_error(fn, "bias_w must be finite and >= 0"); return -1; }
+        if (!am || !ba->nbias) { mk_set_error(fn, "null pointer"); return -1; }
+    }
     if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) {
-        mk_set_error(fn, la ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
-                            : "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned");
+        mk_set_error(fn, ba   ? "work buffer too small (masr_ctc_beam_bias_work_bytes(B, Tp, C, K)) or misaligned"
+                         : la ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
+                              : "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned");
         return -1;
     }
     const CtcBeamArgs a = ctc_beam_carve(logits, ld, enc_lens, B, Tp, C, K, blank, eos, work);
     CK(ctc_beam_frames(a, s));
-    if (la) hipLaunchKernelGGL(ctc_beam_sweep_kernel<true>, dim3(B), dim3(SW_THREADS), 0, s, a, *la, nbest, tokens, lens, scores);
-    else hipLaunchKernelGGL(ctc_beam_sweep_kernel<false>, dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{}, nbest, tokens, lens, scores);
+    if (ba) {
+        if (la) hipLaunchKernelGGL((ctc_beam_sweep_kernel<true, true>), dim3(B), dim3(SW_THREADS), 0, s, a, *la, *ba, nbest, tokens, lens, scores);
+        else hipLaunchKernelGGL((ctc_beam_sweep_kernel<false, true>), dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{LmDev{}, 0.f, 0.f, am}, *ba, nbest, tokens, lens, scores);
+    }
+    else if (la) hipLaunchKernelGGL((ctc_beam_sweep_kernel<true, false>), dim3(B), dim3(SW_THREADS), 0, s, a, *la, CtcBiasArgs{}, nbest, tokens, lens, scores);
+    else hipLaunchKernelGGL((ctc_beam_sweep_kernel<false, false>), dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{}, CtcBiasArgs{}, nbest, tokens, lens, scores);
     return LAUNCH_OK();
 }
 
@@ -684,6 +747,20 @@ int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int
     if (!lm) { mk_set_error(fn, "null language model"); return -1; }
     const CtcLmArgs la{lm->dev, lm_w, len_bonus, am};
     return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, &la, s);
+}
+
+// (the automaton's state lives in LDS too)
+int64_t mk_ctc_beam_bias_work_bytes(int B, int Tp, int C, int K) { return mk_ctc_beam_work_bytes(B, Tp, C, K); }
+
+int mk_ctc_beam_search_bias(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                            const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work, int64_t work_bytes,
+                            int* tokens, int* lens, float* scores, float* am, int* nbias, hipStream_t s) {
+    const char* fn = "mk_ctc_beam_search_bias";
+    if (!bias) { mk_set_error(fn, "null phrase list"); return -1; }
+    const CtcBiasArgs ba{bias->dev, bias_w, nbias};
+    if (!lm) return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, nullptr, s, &ba, am);
+    const CtcLmArgs la{lm->dev, lm_w, len_bonus, am};
+    return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, &la, s, &ba, am);
 }
 
 // ---------------------------------------------------------------- the LSTM LM search

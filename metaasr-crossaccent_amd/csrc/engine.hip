@@ -539,6 +539,13 @@ int masr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* enc_
     return mk_ctc_beam_search_lm(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, work, work_bytes, tokens, lens, scores,
                                  am, (hipStream_t)stream);
 }
+int64_t masr_ctc_beam_bias_work_bytes(int B, int Tp, int C, int K) { return mk_ctc_beam_bias_work_bytes(B, Tp, C, K); }
+int masr_ctc_beam_search_bias(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                              const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work, int64_t work_bytes,
+                              int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias, void* stream) {
+    return mk_ctc_beam_search_bias(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, bias, bias_w, work, work_bytes, tokens,
+                                   lens, scores, am, nbias, (hipStream_t)stream);
+}
 int64_t masr_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K) { return mk_ctc_beam_nlm_work_bytes(nlm, B, Tp, C, K); }
 int masr_ctc_beam_search_nlm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                              const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,

@@ -231,6 +231,16 @@ int64_t mk_ctc_beam_lm_work_bytes(int B, int Tp, int C, int K);
 int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                           const masr_lm* lm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int* tokens, int* lens, float* scores,
                           float* am, hipStream_t s);
+// the same search (lm null: the plain one) with contextual phrase biasing (bias.h): scores = fl(final + fl(bias_w * n_final)),
+// nbias int32 [B][nbest] = n_final (-1 = no entry), am written with or without an LM; blank 0 and eos C - 1 only
+struct masr_bias;
+struct BiasDev;
+int64_t mk_ctc_beam_bias_work_bytes(int B, int Tp, int C, int K);
+int mk_ctc_beam_search_bias(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                            const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work, int64_t work_bytes,
+                            int* tokens, int* lens, float* scores, float* am, int* nbias, hipStream_t s);
+// (nodes_out, n_out)[i] = bias_step((nodes_in, n_in)[i], tokens[i]) for count independent states (device arrays)
+int mk_bias_step(const BiasDev& d, const int* nodes_in, const int* n_in, const int* tokens, int count, int* nodes_out, int* n_out, hipStream_t s);
 
 // ---------------------------------------------------------------- CTC forced alignment (ctc_align.hip)
 // the best alignment of each utterance's transcript (targets[tgt_off[b] .. + tgt_len[b]), device arrays as mk_ctc_loss takes them) to its

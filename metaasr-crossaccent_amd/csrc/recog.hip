@@ -14,6 +14,7 @@
 #include "engine_internal.h"
 #include "lm.h"
 #include "nlm.h"
+#include "bias.h"
 #include "../../include/masr_test.h"
 
 // The decoder layers of one incremental decode step on `rows` query rows (greedy: one per utterance; beam: B*K hypotheses): input
@@ -118,6 +119,13 @@ static int check_weight(const char* fn, const char* name, float v, bool strict) 
     return fail(fn, (std::string(name) + " must be finite and " + (strict ? "> 0" : ">= 0")).c_str());
 }
 // LM fusion: the LM, its weight and, where the search has one (len_bonus != null), the per-token bonus
+// the biased first pass of masr_recog_ctc_beam_bias / masr_recog_rescore_bias: the phrase list, its weight, where n_final goes
+struct BiasPass { const masr_bias* bias = nullptr; float bias_w = 0.f; int32_t* nbias = nullptr; };
+static int check_bias(const char* fn, const masr_model* m, const masr_bias* bias, float bias_w) {
+    if (!bias) return fail(fn, "null phrase list");
+    if (bias->dev.C != m->C) return fail(fn, "the phrase list's classes differ from the model's odim");
+    return check_weight(fn, "bias_w", bias_w, false);
+}
 static int check_lm(const char* fn, const masr_model* m, const masr_lm* lm, float lm_w, const float* len_bonus) {
     if (!lm) return fail(fn, "null language model");
     if (lm->dev.C != m->C) return fail(fn, "the language model's classes differ from the model's odim");
@@ -460,9 +468,11 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
 // where the plan put what the frame's launches read (enc_lens, the logits, the work buffer); lm_w and len_bonus are device values written in
 // front of the replays, so a call with other weights replays the same graph and never an old value.
 static int ctc_first_pass(const char* fn, Ctx& c, const DecodeBufs& bufs, int B, int Tp, int K, int N, const masr_lm* lm, const masr_nlm* nlm, float lm_w,
-                          float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am) {
+                          float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, const BiasPass& bp = BiasPass{}) {
     masr_model* m = c.m; Acts& a = m->acts;
     CK(ctc_head_logits(c, bufs.ctc_logits));
+    if (bp.bias) return mk_ctc_beam_search_bias(bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, lm, lm_w, len_bonus, bp.bias, bp.bias_w,
+                                                bufs.work, bufs.work_bytes, tokens, lens, scores, am, bp.nbias, c.s);
     if (nlm) {
         CtcNlmRun run;
         CK(mk_ctc_beam_nlm_begin(fn, bufs.ctc_logits, m->Cp, a.enc_lens, B, Tp, m->C, K, N, 0, m->C - 1, nlm, lm_w, len_bonus, bufs.work, bufs.work_bytes,
@@ -479,20 +489,23 @@ static int ctc_first_pass(const char* fn, Ctx& c, const DecodeBufs& bufs, int B,
 
 // masr_recog_ctc_beam (with_lm false) and masr_recog_ctc_beam_lm: one encoder pass, the head GEMM, one sweep over the T/4 frames
 static int recog_ctc_beam_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, const masr_nlm* nlm, float lm_w, float len_bonus, const float* xs,
-                               const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
+                               const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream,
+                               const BiasPass* bp = nullptr) {
     CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "nbest", nbest, K));
     if (with_lm) CK(nlm ? check_nlm(fn, m, nlm, lm_w, &len_bonus) : check_lm(fn, m, lm, lm_w, &len_bonus));
+    if (bp) CK(check_bias(fn, m, bp->bias, bp->bias_w));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
-    if (with_lm && !am) return fail(fn, "null pointer");
+    if ((with_lm || bp) && !am) return fail(fn, "null pointer");
+    if (bp && !bp->nbias) return fail(fn, "null pointer");
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
     { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, 0, 0, true, 0, false, 0, -1, nlm}, &bufs); if (rc) return rc; }
     Ctx c{m, s, 0u, false, 0.f, 0.f};
-    CK(ctc_first_pass(fn, c, bufs, B, T / 4, K, nbest, lm, nlm, lm_w, len_bonus, tokens, lens, scores, am));
+    CK(ctc_first_pass(fn, c, bufs, B, T / 4, K, nbest, lm, nlm, lm_w, len_bonus, tokens, lens, scores, am, bp ? *bp : BiasPass{}));
     m->have_acts = false;
     return 0;
 }
@@ -522,13 +535,14 @@ static int rescore_second_pass(Ctx& c, const DecodeBufs& bufs, const int* tok, l
 // search, its fused scores the c(b, n) of the second pass, and its acoustic totals land in the plan's scratch (rs_att, free until the second pass)
 static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const masr_lm* lm, const masr_nlm* nlm, float lm_w, float len_bonus, const float* xs,
                               const int64_t* ilens, int B, int T, int K, int N, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
-                              float* att, float* ctc, int32_t* order, void* stream) {
+                              float* att, float* ctc, int32_t* order, void* stream, const BiasPass* bp = nullptr) {
     CK(check_model(fn, m));
     CK(check_ctc_head(fn, m));
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "N", N, K));
     CK(check_rescore_weights(fn, att_w, ctc_w));
     if (with_lm) CK(nlm ? check_nlm(fn, m, nlm, lm_w, &len_bonus) : check_lm(fn, m, lm, lm_w, &len_bonus));
+    if (bp) CK(check_bias(fn, m, bp->bias, bp->bias_w));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
     if (!att || !ctc || !order) return fail(fn, "null pointer");
     if (B <= 0 || T < 4) return fail(fn, "need B >= 1 and T >= 4");
@@ -541,7 +555,9 @@ static int recog_rescore_impl(const char* fn, masr_model* m, bool with_lm, const
     { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lcap, 0, false, N, false, 0, -1, nlm}, &bufs); if (rc) return rc; }
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     const int Tp = T / 4, R = B * N;
-    CK(ctc_first_pass(fn, c, bufs, B, Tp, K, N, lm, nlm, lm_w, len_bonus, bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att));
+    // (a biased first pass leaves its n_final in the row-term scratch, which like rs_att is free until the second pass: R <= R * (Lmax + 1))
+    const BiasPass first = bp ? BiasPass{bp->bias, bp->bias_w, (int32_t*)bufs.rs_row_lp} : BiasPass{};
+    CK(ctc_first_pass(fn, c, bufs, B, Tp, K, N, lm, nlm, lm_w, len_bonus, bufs.rs_tok, bufs.rs_lens, bufs.rs_ctc, bufs.rs_att, first));
     // the one host synchronisation of the decode: the list lengths decide how many positions the decoder pass has
     std::vector<int> h_lens(R);
     HIP_CHECK_RET(hipMemcpyAsync(h_lens.data(), bufs.rs_lens, sizeof(int) * (size_t)R, hipMemcpyDeviceToHost, s));
@@ -680,6 +696,15 @@ int masr_recog_ctc_beam_lm(masr_model* m, const masr_lm* lm, const float* xs, co
     return recog_ctc_beam_impl("masr_recog_ctc_beam_lm", m, true, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am, stream);
 }
 
+int masr_recog_ctc_beam_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K,
+                             int nbest, float lm_w, float len_bonus, float bias_w, int32_t* tokens, int32_t* lens, float* scores, float* am,
+                             int32_t* nbias, void* stream) {
+    // masr_recog_ctc_beam with the phrase-biased sweep (ctc_beam.hip), the n-gram LM fused in when one is given: the same plan
+    const BiasPass bp{bias, bias_w, nbias};
+    return recog_ctc_beam_impl("masr_recog_ctc_beam_bias", m, lm != nullptr, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, nbest, tokens, lens, scores, am,
+                               stream, &bp);
+}
+
 int masr_recog_ctc_beam_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, float lm_w,
                             float len_bonus, int32_t* tokens, int32_t* lens, float* scores, float* am, void* stream) {
     // masr_recog_ctc_beam with the LSTM LM's frame-synchronous search (ctc_beam.hip): the same encoder pass and head GEMM
@@ -776,6 +801,14 @@ int masr_recog_rescore_lm(masr_model* m, const masr_lm* lm, const float* xs, con
                           int32_t* order, void* stream) {
     return recog_rescore_impl("masr_recog_rescore_lm", m, true, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens, scores, att, ctc,
                               order, stream);
+}
+
+int masr_recog_rescore_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K, int N,
+                            float lm_w, float len_bonus, float bias_w, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
+                            float* att, float* ctc, int32_t* order, void* stream) {
+    const BiasPass bp{bias, bias_w, nullptr};
+    return recog_rescore_impl("masr_recog_rescore_bias", m, lm != nullptr, lm, nullptr, lm_w, len_bonus, xs, ilens, B, T, K, N, att_w, ctc_w, tokens, lens,
+                              scores, att, ctc, order, stream, &bp);
 }
 
 int masr_recog_rescore_nlm(masr_model* m, const masr_nlm* nlm, const float* xs, const int64_t* ilens, int B, int T, int K, int N, float lm_w,

@@ -8,6 +8,7 @@
 #include "host_util.h"
 #include "lm.h"
 #include "nlm.h"
+#include "bias.h"
 
 extern "C" {
 
@@ -244,6 +245,20 @@ int masr_test_lm_score(const masr_lm* lm, const int32_t* ctx, int R, float* out,
 int masr_test_lm_max_probe(const masr_lm* lm) {
     if (!lm) { mk_set_error("masr_test_lm_max_probe", "null model"); return -1; }
     return lm->max_probe;
+}
+// ---- contextual phrase biasing (bias.hip)
+int masr_test_bias_step(const masr_bias* bias, const int32_t* nodes_in, const int32_t* n_in, const int32_t* tokens, int count, int32_t* nodes_out,
+                        int32_t* n_out, void* stream) {
+    const char* fn = "masr_test_bias_step";
+    if (!bias || !nodes_in || !n_in || !tokens || !nodes_out || !n_out || count < 1) { mk_set_error(fn, "null pointer or count < 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_bias_step(bias->dev, nodes_in, n_in, tokens, count, nodes_out, n_out, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_bias_max_probe(const masr_bias* bias) {
+    if (!bias) { mk_set_error("masr_test_bias_max_probe", "null phrase list"); return -1; }
+    return bias->max_probe;
 }
 }  // extern "C"
 // masr_test_beam_lm_topk and masr_test_joint_lm_prebeam (out.P > 0): the row stage with the n-gram LM at step t on the caller's logits,

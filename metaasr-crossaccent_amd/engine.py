@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists
+from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists, nbest_lists_bias
+from .bias import check_bias_args
 
 MASR_TRAIN, MASR_EVAL = 1, 0
 CTC_HEAD = ("ctc.ctc_lo.weight", "ctc.ctc_lo.bias")           # parameters of the joint objective's CTC head (asr_model.ctc_weight > 0)
@@ -470,6 +471,39 @@ class MasrEngine:
               "masr_recog_ctc_beam_lm")
         self._last_x = xs
         return out if raw else nbest_lists(*out)
+
+    def recog_ctc_beam_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
+                            len_bonus: float = 0.0, nbest: int = 1, raw: bool = False):
+        """recog_ctc_beam with contextual phrase biasing (masr_recog_ctc_beam_bias): `bias` a ContextBias over this model's odim
+        classes, bias_w finite and >= 0; with lm (an NGramLM) the n-gram LM and the bonus are fused in as recog_ctc_beam_lm does, without
+        one lm_w and len_bonus are ignored.  Returns per utterance a list of at most nbest (token list, final score, acoustic score,
+        credited tokens), best first (raw: the device tensors tokens, lens, scores, am, nbias instead)."""
+        K, N = check_beam_args(beam_size, nbest)
+        bias_w = check_bias_args(bias, bias_w)
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus) if lm is not None else (0.0, 0.0)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
+        out = self._outputs(B, N, ld=T // 4, extra="fi")
+        check(self._l.masr_recog_ctc_beam_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus,
+                                               bias_w, *map(_ptr, out), self.stream()), "masr_recog_ctc_beam_bias")
+        self._last_x = xs
+        return out if raw else nbest_lists_bias(*out)
+
+    def recog_rescore_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
+                           len_bonus: float = 0.0, nbest=None, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
+        """recog_rescore whose first pass is recog_ctc_beam_bias's search (masr_recog_rescore_bias): the `ctc` of an entry is
+        that pass's final score; the attention pass is not biased.  Returns what recog_rescore returns."""
+        K, N = check_beam_args(beam_size, nbest)
+        att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
+        bias_w = check_bias_args(bias, bias_w)
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus) if lm is not None else (0.0, 0.0)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
+        out = self._rescore_outputs(B, N, T // 4)
+        check(self._l.masr_recog_rescore_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus,
+                                              bias_w, att_w, ctc_w, *map(_ptr, out), self.stream()), "masr_recog_rescore_bias")
+        self._last_x = xs
+        return out if raw else self._rescore_lists(out)
 
     def recog_ctc_beam_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                            raw: bool = False):

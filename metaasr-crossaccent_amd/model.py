@@ -167,6 +167,20 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_rescore_lm(xs_pad, ilens, beam_size, lm, lm_weight, len_bonus, nbest, att_weight, ctc_weight)
 
+    def bias_ctc_beam_decode(self, xs_pad, ilens, beam_size, bias, bias_weight=3.0, lm=None, lm_weight=0.3, len_bonus=0.0, nbest=1):
+        """CTC prefix beam search with the phrase list `bias` (a ContextBias) boosting its phrases (masr_recog_ctc_beam_bias, hybrid models
+        only), the n-gram LM `lm` fused in when one is given: per utterance a list of at most nbest (token list, final score, acoustic
+        score, credited tokens), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_ctc_beam_bias(xs_pad, ilens, beam_size, bias, bias_weight, lm, lm_weight, len_bonus, nbest)
+
+    def bias_rescore_decode(self, xs_pad, ilens, beam_size, bias, bias_weight=3.0, lm=None, lm_weight=0.3, len_bonus=0.0, nbest=None,
+                            att_weight=0.5, ctc_weight=0.5):
+        """attention rescoring of the phrase-biased CTC beam's nbest list (masr_recog_rescore_bias, hybrid models only): rescore_decode with
+        bias_ctc_beam_decode's search as the first pass"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_rescore_bias(xs_pad, ilens, beam_size, bias, bias_weight, lm, lm_weight, len_bonus, nbest, att_weight, ctc_weight)
+
     def nlm_ctc_beam_decode(self, xs_pad, ilens, beam_size, nlm, lm_weight=0.3, len_bonus=0.0, nbest=1):
         """lm_ctc_beam_decode with the LSTM LM `nlm` (an LstmLM) in the n-gram's place (masr_recog_ctc_beam_nlm, hybrid models only): per
         utterance a list of at most nbest (token list, fused score, acoustic score), best first"""

@@ -48,6 +48,14 @@ anything is decoded.  Tester.MODES is the table of them:
                  `lm_ctc_beam` refuses (a BLSTM whose blank is not id 0 included), and an LM over another number of classes (ValueError).
   nlm_rescore    masr_recog_rescore_nlm, `rescore` with `nlm_ctc_beam`'s search as its first pass: nbest, att_w and ctc_w as for `rescore`,
                  the rest as for `nlm_ctc_beam`.  Refuses what `rescore` refuses (a BLSTM: NotImplementedError).
+  bias_ctc_beam  masr_recog_ctc_beam_bias (BLSTM-CTC: masr_ctc_beam_search_bias), `ctc_beam` with contextual phrase biasing: the
+                 phrases of `--context_path` (one phrase per line as space-separated unit ids, blank lines skipped) are boosted by bias_w
+                 (3.0, finite and >= 0) per credited token.  Without a path the mode raises NotImplementedError; a bad file ValueError
+                 with its line number.  `--lm_model_path` is optional here: given, the n-gram LM is fused with lm_w / len_bonus as in
+                 `lm_ctc_beam`; absent, no LM is fused.  Refuses what `ctc_beam` refuses, and a BLSTM whose blank is not id 0.
+  bias_rescore   masr_recog_rescore_bias, `rescore` with `bias_ctc_beam`'s search as its first pass (the attention pass is not biased): nbest,
+                 att_w and ctc_w as for `rescore`, the rest as for `bias_ctc_beam`.  Refuses what `rescore` refuses (a BLSTM:
+                 NotImplementedError).
   ctc_align      masr_recog_ctc_align (BLSTM-CTC: masr_ctc_align per utterance), the CTC forced alignment of DESIGN 5.9: no search, so no
                  solver.beam_decode block is read.  Each test utterance's REFERENCE transcript is aligned to the frames of the CTC output
                  layer, and one line per utterance is appended to `<decode_dir>/ctc-ali` (no best-hyp is written):
@@ -389,6 +397,40 @@ class Tester:
         logger.notice(f"Joint CTC/attention beam with LSTM LM: {lm}, start token {start}, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, "
                       f"lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}, nbest = {self.nbest}")
 
+    def _load_bias(self, path):
+        """self.bias = the phrase file as a ContextBias over the output units, built once per Tester and path"""
+        if getattr(self, 'bias', None) is None or getattr(self, '_bias_key', None) != path:
+            from .bias import ContextBias
+            self.bias, self._bias_key = ContextBias.from_file(path, len(self.id2ch)), path
+        return f"{path}, {self.bias.phrases} phrases"
+
+    def _bias_ctc_settings(self):
+        """bias_ctc_beam and bias_rescore: ctc_beam's / rescore's settings, the phrase list, and lm_ctc_beam's LM when a path is given"""
+        mode = self.decode_mode
+        ctx_path = getattr(self.paras, 'context_path', None)
+        if ctx_path is None:
+            raise NotImplementedError(f"{mode}: no phrase list given; pass --context_path (one phrase per line as space-separated unit ids)")
+        if mode == 'bias_rescore':
+            self._rescore_settings()                             # (BLSTM: NotImplementedError; no CTC head: ValueError; nbest, att_w, ctc_w)
+        else:
+            self._beam_size()
+            if self.model_name != 'blstm':
+                self._need_ctc_head(mode, "beam or greedy")
+            elif self.blank_id != 0:
+                raise ValueError(f"decode_mode '{mode}' needs the blank at id 0 (the search never emits class 0), got {self.blank_id}")
+        bd = self.config['solver']['beam_decode']
+        self.bias_weight = self._weight(bd, 'bias_w', 3.0)
+        lm_path = getattr(self.paras, 'lm_model_path', None)
+        self.lm_weight, self.len_bonus = 0.0, 0.0
+        lm = "no LM"
+        if lm_path is not None:
+            self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+            self._len_bonus(bd)
+            lm = f"{self._load_lm(lm_path, 0, len(self.id2ch) - 1)}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}"
+        else:
+            self.lm = None
+        logger.notice(f"{mode}: phrase list {self._load_bias(ctx_path)}, bias_w = {self.bias_weight}; {lm}")
+
     # ------------------------------------------------------------------ the decode modes
     def _ctc_best(self, lists):
         """the best entry of each N-best list of a CTC beam (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is
@@ -404,6 +446,12 @@ class Tester:
         if self.model_name == 'blstm':
             return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.nlm, self.lm_weight, self.len_bonus)
         return self.asr_model.nlm_ctc_beam_decode(xs, ilens, self.beam_size, self.nlm, self.lm_weight, self.len_bonus)
+
+    def _bias_ctc_beam_lists(self, xs, ilens):
+        if self.model_name == 'blstm':
+            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus, bias=self.bias,
+                                                  bias_weight=self.bias_weight)
+        return self.asr_model.bias_ctc_beam_decode(xs, ilens, self.beam_size, self.bias, self.bias_weight, self.lm, self.lm_weight, self.len_bonus)
 
     # mode -> (its settings function, (Tester, xs, ilens) -> the best hypothesis of each utterance, Tester -> what the start-up line names);
     # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself; nor has ctc_align, which reads the
@@ -439,6 +487,13 @@ class Tester:
                         lambda t, xs, il: [n[0][0] for n in t.asr_model.nlm_rescore_decode(xs, il, t.beam_size, t.nlm, t.lm_weight, t.len_bonus, t.nbest,
                                                                                            t.att_weight, t.ctc_weight)],
                         lambda t: f"attention rescoring of the LSTM-LM-fused CTC beam (beam {t.beam_size})"),
+        'bias_ctc_beam': (_bias_ctc_settings,
+                          lambda t, xs, il: t._ctc_best(t._bias_ctc_beam_lists(xs, il)),
+                          lambda t: f"phrase-biased CTC prefix beam decoding (bias_ctc_beam, beam {t.beam_size}, {t.bias.phrases} phrases)"),
+        'bias_rescore': (_bias_ctc_settings,
+                         lambda t, xs, il: [n[0][0] for n in t.asr_model.bias_rescore_decode(xs, il, t.beam_size, t.bias, t.bias_weight, t.lm, t.lm_weight,
+                                                                                             t.len_bonus, t.nbest, t.att_weight, t.ctc_weight)],
+                         lambda t: f"attention rescoring of the phrase-biased CTC beam (bias_rescore, beam {t.beam_size}, {t.bias.phrases} phrases)"),
         'ctc_align': (_ctc_align_settings, None, lambda t: "CTC forced alignment of the reference transcripts"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
