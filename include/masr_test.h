@@ -294,6 +294,38 @@ int masr_test_nlm_step(const masr_nlm* nlm, int R, int K, int t, const int32_t* 
 int masr_test_nlm_step_carry(const masr_nlm* nlm, int R, int K, int t, const int32_t* tok, const int32_t* par, const int32_t* live, uint16_t* hstate,
                              float* cstate, float* logits, int64_t ld, float* logp, void* stream);
 
+/* ---- the flat optimiser passes and the operand-shadow kernels alone (optim.hip; tests/test_hip_optim_kernels.py, tests/test_hip_shadow_kernels.py).
+ * All arrays on the device unless said otherwise; each entry vets on the host what the kernel would index with, calls the launcher and
+ * synchronises the stream.
+ * the gradient norm (sumsq_kernel + sumsq_final, mk_sumsq) with a slab of the entry's own: out_norm[0] = sqrt(sum x[0 .. n)^2), accumulated in
+ * fp64.  Refuses n < 1 and an x that is not 16-byte aligned (the kernel reads float4 at every multiple of four floats). */
+int masr_test_sumsq(const float* x, int64_t n, float* out_norm, void* stream);
+/* clip + SGD (clip_sgd_kernel, mk_clip_sgd) on a caller-given device norm fp32 [1] (null: the unclipped step).  step_flags: bit 0 = the
+ * optimiser's first step (no buffer read), bit 1 = its last (no buffer written).  mom may be null only when momentum == 0 or both bits are set. */
+int masr_test_clip_sgd(float* p, const float* g, float* mom, int64_t n, const float* norm, float max_norm, float lr, float momentum, int nesterov,
+                       int step_flags, void* stream);
+/* acc += coef g / g *= coef with coef from the device norm (clip_axpy_kernel / clip_scale_kernel); nan_zero: a NaN norm leaves acc alone /
+ * zeroes g instead of spreading NaNs */
+int masr_test_clip_axpy(float* acc, const float* g, int64_t n, const float* norm, float max_norm, int nan_zero, void* stream);
+int masr_test_clip_scale(float* g, int64_t n, const float* norm, float max_norm, int nan_zero, void* stream);
+/* the Adam step the device skips under a NaN norm (adam_guarded_kernel, mk_adam_guarded): scalars A = (lr_a, t_a) when the launch before
+ * was applied, B = (lr_b, t_b) when it was skipped, as flags[slot ^ 1] says; flags int32 [2] on the device, slot 0 or 1; t_a, t_b >= 1 */
+int masr_test_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr_a, int t_a, float lr_b, int t_b, float b1, float b2,
+                           float eps, float weight_decay, int decoupled, const float* norm, int32_t* flags, int slot, void* stream);
+/* ONE launch of the shadow refresh (all_shadows_kernel, mk_all_shadows) over a caller-given job list, built as masr_bind builds its own
+ * (tile_start from the jobs' workgroup counts, in list order).  desc: HOST array of n_jobs rows {src, type, N, K, ldt, a0, a1} (type: 0 Linear
+ * [N][K] -> k16 [N][K], t16 [K][ldt]; 1 conv [CO = N][CI = K][3][3] -> wk, wd; 2 vgg2enc [E = N][C = a0][Dp = a1] -> wk [E][Dp C], its
+ * transpose [Dp C][E]; 3 copy of N floats); outs: HOST array of 2 n_jobs device pointers (job i: outs[2 i], outs[2 i + 1]; the second of a
+ * copy is not used).  P 16-byte aligned; a Linear job reads up to three floats in front of its rows and behind them.  Refuses n_jobs
+ * outside [1, 56], a type outside 0..3, a negative src, a Linear job with src < 4 or ldt < N, non-positive sizes, and a null output where
+ * the job's type writes one. */
+int masr_test_shadow_jobs(const float* P, int n_jobs, const int64_t* desc, void* const* outs, void* stream);
+/* the BLSTM engine's shadow passes: y bf16 [C][ldy] = x fp32 [R][C] transposed (ldy >= R; pads untouched); y bf16 [n] = x fp32 [n];
+ * w fp32 [CO][CI][3][3] -> wk bf16 [CO][tap CI + ci] and (wd may be null) wd bf16 [CI][(8 - tap) CO + co] */
+int masr_test_transpose_cast_bf16(const float* x, uint16_t* y, int R, int C, int64_t ldy, void* stream);
+int masr_test_cast_bf16(const float* x, uint16_t* y, int64_t n, void* stream);
+int masr_test_conv_weight_shadows(const float* w, uint16_t* wk, uint16_t* wd, int CO, int CI, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,15 @@ _SIGS = {
     "masr_test_subsample_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "masr_test_nlm_step": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
     "masr_test_nlm_step_carry": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "masr_test_sumsq": (i32, [vp, i64, vp, vp]),
+    "masr_test_clip_sgd": (i32, [vp, vp, vp, i64, vp, f32, f32, f32, i32, i32, vp]),
+    "masr_test_clip_axpy": (i32, [vp, vp, i64, vp, f32, i32, vp]),
+    "masr_test_clip_scale": (i32, [vp, i64, vp, f32, i32, vp]),
+    "masr_test_adam_guarded": (i32, [vp, vp, vp, vp, i64, f32, i32, f32, i32, f32, f32, f32, f32, i32, vp, vp, i32, vp]),
+    "masr_test_shadow_jobs": (i32, [vp, i32, vp, vp, vp]),
+    "masr_test_transpose_cast_bf16": (i32, [vp, vp, i32, i32, i64, vp]),
+    "masr_test_cast_bf16": (i32, [vp, vp, i64, vp]),
+    "masr_test_conv_weight_shadows": (i32, [vp, vp, vp, i32, i32, vp]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_NAMES = ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "conv2_dgrad", "conv3_dgrad", "conv4_dgrad", "conv2_wgrad",

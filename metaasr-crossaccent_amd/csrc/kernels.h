@@ -325,6 +325,8 @@ int mk_ls_ce(const float* logits, long ld, const int* gold, int rows, int C, flo
                float grad_w = 1.f);
 
 // ---------------------------------------------------------------- flat optimiser ops (optim.hip)
+// PRECONDITION: x is 16-byte aligned -- the kernel reads float4 at every multiple of four floats, whatever the pointer.  Every caller passes
+// an engine's flat gradient buffer, which masr_bind / masr_blstm_bind refuse unless it is 16-byte aligned.
 int mk_sumsq(const float* x, long n, float* slab, float* out_norm, hipStream_t s);       // out_norm[0] = sqrt(sum x^2)
 long mk_sumsq_slab_floats(long n);
 // coef = clip(max_norm / (norm+1e-6), <=1) (NaN propagates like torch.clamp)

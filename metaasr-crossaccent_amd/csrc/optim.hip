@@ -183,6 +183,13 @@ __global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restri
 // the same step on g = (((g0 + g1) + g2) + ...) * scale, the sum the meta loop used to build with one axpy pass per task and a
 // scale pass (same additions in the same order: bit-identical), read straight from the task slots' gradient buffers
 struct GradList { const float* g[8]; int n; float scale; };
+// sum * scale rounded on its own, as the scale pass stored it.  (__fmul_rn is a plain product to the compiler: left to -ffp-contract the
+// product was fused into the first-moment update's difference, fma(sum, scale, -m), and the step ended one ulp apart from scale + Adam on
+// ~1 element in 30 of m whenever the scale is no power of two; tests/test_hip_optim_kernels.py pins the equality)
+__device__ __forceinline__ float scaled_sum(float sum, float scale) {
+#pragma clang fp contract(off)
+    return sum * scale;
+}
 __global__ void adam_sum_kernel(float* __restrict__ p, GradList gl, float* __restrict__ m, float* __restrict__ v,
                                 long n, float step_size, float b1, float b2, float eps, float inv_sqrt_bc2, int vec) {
     auto one = [&](float& pp, float gg, float& mm, float& vv) {
@@ -190,12 +197,12 @@ __global__ void adam_sum_kernel(float* __restrict__ p, GradList gl, float* __res
         vv = b2 * vv + (1.f - b2) * gg * gg;
         pp = pp - step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
     };
-    flat_pass(n, vec, [&](long i) { float gg = 0.f + gl.g[0][i]; for (int k = 1; k < gl.n; ++k) gg += gl.g[k][i]; one(p[i], gg * gl.scale, m[i], v[i]); },
+    flat_pass(n, vec, [&](long i) { float gg = 0.f + gl.g[0][i]; for (int k = 1; k < gl.n; ++k) gg += gl.g[k][i]; one(p[i], scaled_sum(gg, gl.scale), m[i], v[i]); },
               [&](long i) { float4 pv = F4C(p)[i], mv = F4C(m)[i], vv = F4C(v)[i]; float4 gv = F4C(gl.g[0])[i];
                             gv.x = 0.f + gv.x; gv.y = 0.f + gv.y; gv.z = 0.f + gv.z; gv.w = 0.f + gv.w;
                             for (int k = 1; k < gl.n; ++k) { const float4 t = F4C(gl.g[k])[i]; gv.x += t.x; gv.y += t.y; gv.z += t.z; gv.w += t.w; }
-                            one(pv.x, gv.x * gl.scale, mv.x, vv.x); one(pv.y, gv.y * gl.scale, mv.y, vv.y);
-                            one(pv.z, gv.z * gl.scale, mv.z, vv.z); one(pv.w, gv.w * gl.scale, mv.w, vv.w);
+                            one(pv.x, scaled_sum(gv.x, gl.scale), mv.x, vv.x); one(pv.y, scaled_sum(gv.y, gl.scale), mv.y, vv.y);
+                            one(pv.z, scaled_sum(gv.z, gl.scale), mv.z, vv.z); one(pv.w, scaled_sum(gv.w, gl.scale), mv.w, vv.w);
                             F4P(p)[i] = pv; F4P(m)[i] = mv; F4P(v)[i] = vv; });
 }
 // out = ((g0 + g1) + ...) + g_{n-1}: the rank-local sum of a wave's task gradients, the payload of the wave's ONE all-reduce

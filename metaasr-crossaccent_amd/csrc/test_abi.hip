@@ -774,4 +774,131 @@ int masr_test_nlm_step_carry(const masr_nlm* nlm, int R, int K, int t, const int
     return rc;
 }
 
+// ---- the flat optimiser passes and the shadow kernels alone (optim.hip)
+static int test_flat_n(const char* fn, int64_t n) {
+    if (n < 1 || n > (int64_t)1 << 40) { mk_set_error(fn, "n outside [1, 2^40]"); return -1; }
+    return 0;
+}
+int masr_test_sumsq(const float* x, int64_t n, float* out_norm, void* stream) {
+    const char* fn = "masr_test_sumsq";
+    if (!x || !out_norm) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    if ((uintptr_t)x & 15) { mk_set_error(fn, "x must be 16-byte aligned (the kernel reads float4 at every multiple of four floats)"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    float* slab = nullptr;
+    HIP_CHECK_RET(hipMalloc(&slab, sizeof(float) * (size_t)mk_sumsq_slab_floats((long)n)));
+    auto run = [&]() -> int {
+        CK(mk_sumsq(x, (long)n, slab, out_norm, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(slab);
+    return rc;
+}
+int masr_test_clip_sgd(float* p, const float* g, float* mom, int64_t n, const float* norm, float max_norm, float lr, float momentum, int nesterov,
+                       int step_flags, void* stream) {
+    const char* fn = "masr_test_clip_sgd";
+    if (!p || !g) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    if (step_flags < 0 || step_flags > 3) { mk_set_error(fn, "step_flags outside 0..3"); return -1; }
+    if (!mom && momentum != 0.f && step_flags != 3) { mk_set_error(fn, "mom may be null only with momentum == 0 or step_flags == 3"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_clip_sgd(p, g, mom, (long)n, norm, max_norm, lr, momentum, nesterov, step_flags, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_clip_axpy(float* acc, const float* g, int64_t n, const float* norm, float max_norm, int nan_zero, void* stream) {
+    const char* fn = "masr_test_clip_axpy";
+    if (!acc || !g || !norm) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_clip_axpy(acc, g, (long)n, norm, max_norm, s, nan_zero != 0));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_clip_scale(float* g, int64_t n, const float* norm, float max_norm, int nan_zero, void* stream) {
+    const char* fn = "masr_test_clip_scale";
+    if (!g || !norm) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_clip_scale(g, (long)n, norm, max_norm, s, nan_zero != 0));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr_a, int t_a, float lr_b, int t_b, float b1, float b2,
+                           float eps, float weight_decay, int decoupled, const float* norm, int32_t* flags, int slot, void* stream) {
+    const char* fn = "masr_test_adam_guarded";
+    if (!p || !g || !m || !v || !norm || !flags) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    if (slot < 0 || slot > 1) { mk_set_error(fn, "slot must be 0 or 1"); return -1; }
+    if (t_a < 1 || t_b < 1) { mk_set_error(fn, "step numbers start at 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_adam_guarded(p, g, m, v, (long)n, lr_a, t_a, lr_b, t_b, b1, b2, eps, weight_decay, decoupled, norm, flags, slot, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_shadow_jobs(const float* P, int n_jobs, const int64_t* desc, void* const* outs, void* stream) {
+    const char* fn = "masr_test_shadow_jobs";
+    if (!P || !desc || !outs) { mk_set_error(fn, "null pointer"); return -1; }
+    if ((uintptr_t)P & 15) { mk_set_error(fn, "P must be 16-byte aligned"); return -1; }
+    if (n_jobs < 1 || n_jobs > SHADOW_JOBS_MAX) { mk_set_error(fn, "n_jobs outside [1, SHADOW_JOBS_MAX]"); return -1; }
+    ShadowJobs J{};
+    for (int i = 0; i < n_jobs; ++i) {
+        const int64_t* r = desc + 7 * (size_t)i;
+        const int64_t src = r[0], type = r[1], N = r[2], K = r[3], ldt = r[4], a0 = r[5], a1 = r[6];
+        void* p0 = outs[2 * i]; void* p1 = outs[2 * i + 1];
+        if (type < SH_LINEAR || type > SH_COPY32) { mk_set_error(fn, "job type outside 0..3"); return -1; }
+        if (src < 0) { mk_set_error(fn, "negative src"); return -1; }
+        const int64_t lim = 1 << 24;                             // (every product below stays far inside an int)
+        if (N < 1 || N > lim) { mk_set_error(fn, "non-positive (or oversized) N"); return -1; }
+        if (type == SH_LINEAR || type == SH_CONV) {
+            if (K < 1 || K > lim || N * K * 9 > 0x7fffffffLL) { mk_set_error(fn, "non-positive (or oversized) K"); return -1; }
+        }
+        if (type == SH_LINEAR) {
+            if (src < 4) { mk_set_error(fn, "a Linear job needs src >= 4 (the tile pass reads up to three floats in front of a row)"); return -1; }
+            if (ldt < N || ldt > lim) { mk_set_error(fn, "a Linear job needs ldt >= N"); return -1; }
+        }
+        if (type == SH_VGG2ENC) {
+            if (a0 < 1 || a1 < 1 || a0 > lim || a1 > lim || a0 * a1 > lim || N * a0 * a1 > 0x7fffffffLL) { mk_set_error(fn, "non-positive (or oversized) a0 / a1"); return -1; }
+        }
+        if (!p0 || (type != SH_COPY32 && !p1)) { mk_set_error(fn, "null output of a job that writes it"); return -1; }
+        ShadowDesc d{}; d.src = (long)src; d.type = (int)type; d.N = (int)N; d.K = (int)K; d.ldt = (int)ldt; d.a0 = (int)a0; d.a1 = (int)a1;
+        d.tile_start = J.blocks;
+        J.blocks += mk_shadow_blocks(d);
+        J.d[J.n] = d; J.p[2 * J.n] = (bf16*)p0; J.p[2 * J.n + 1] = (bf16*)p1; ++J.n;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_all_shadows(P, J, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_transpose_cast_bf16(const float* x, uint16_t* y, int R, int C, int64_t ldy, void* stream) {
+    const char* fn = "masr_test_transpose_cast_bf16";
+    if (!x || !y) { mk_set_error(fn, "null pointer"); return -1; }
+    if (R < 1 || C < 1 || ldy < R) { mk_set_error(fn, "need R, C >= 1 and ldy >= R"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_transpose_cast_bf16(x, (bf16*)y, R, C, (long)ldy, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_cast_bf16(const float* x, uint16_t* y, int64_t n, void* stream) {
+    const char* fn = "masr_test_cast_bf16";
+    if (!x || !y) { mk_set_error(fn, "null pointer"); return -1; }
+    CK(test_flat_n(fn, n));
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_cast_bf16(x, (bf16*)y, (long)n, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+int masr_test_conv_weight_shadows(const float* w, uint16_t* wk, uint16_t* wd, int CO, int CI, void* stream) {
+    const char* fn = "masr_test_conv_weight_shadows";
+    if (!w || !wk) { mk_set_error(fn, "null pointer"); return -1; }
+    if (CO < 1 || CI < 1 || (int64_t)CO * CI * 9 > 0x7fffffffLL) { mk_set_error(fn, "need CO, CI >= 1 and CO CI 9 < 2^31"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CK(mk_conv_weight_shadows(w, (bf16*)wk, (bf16*)wd, CO, CI, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // extern "C"
