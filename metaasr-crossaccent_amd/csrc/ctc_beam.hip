@@ -26,11 +26,16 @@
 //
 // masr_ctc_beam_search_nlm is the same search with an LSTM LM's term (nlm.h) in the n-gram's place.  That LM has state, so the
 // search runs frame by frame across launches: ctc_beam_frame runs ONE frame of every utterance on the beam kept in the work buffer, the LM's
-// carry step advances the B * K rows' states, and ctc_beam_tail writes the lists.  The frame's logic and the tail are one __device__ body each
-// (ctc_frame_step<M>, ctc_beam_tail<M>), written for all three LM modes.  The sweep does NOT run them yet: moved onto them it computed the
-// same bits but took 2.5 - 3 % longer at K >= 10 (DESIGN 5.12 has the figures), so its loop below stays as it was and the bodies serve the
-// per-frame kernels.
+// carry step advances the B * K rows' states, and ctc_beam_tail writes the lists.
+//
+// All of it is ONE kernel text, ctc_beam_kernel<M, BIAS, PH>: the frame logic (stay and extension scores, merge, K-best rounds, next beam
+// and records) and the tail (final re-rank, record walk, N-best list) are stated once, on separate __shared__ arrays with the frame loop in
+// the kernel -- the sweep's form, the fast one.  M is the LM (0 none, 1 the n-gram, 2 the LSTM LM's rows), PH what a launch
+// runs of it: ctc_beam_sweep<LM, BIAS> = <LM, BIAS, PH_SWEEP> starts from the empty prefix and runs every frame and the tail; ctc_beam_frame
+// = <2, false, PH_FRAME> loads the beam from the work buffer, runs one frame and stores it; ctc_beam_tail = <2, false, PH_TAIL> loads and
+// runs the tail.  The modes differ in lm(c | h) alone (one switch in the frame, one in the tail) and in what an entry carries.
 #include <cmath>
+#include <type_traits>
 
 #include "kernels.h"
 #include "search.h"
@@ -49,6 +54,7 @@ __device__ __forceinline__ unsigned long long hash_push(unsigned long long h, in
     return h ^ (h >> 29);
 }
 __device__ __forceinline__ int clamp_len(int n, int Tp) { return n < 0 ? 0 : (n > Tp ? Tp : n); }
+__device__ __forceinline__ int clamp_live(int n, int K) { return n < 0 ? 0 : (n > K ? K : n); }
 
 // ---- the LM side of ctc_beam_sweep<true, false>
 struct CtcLmArgs { LmDev lm; float lm_w, len_bonus; float* am; };      // am [B][nbest]: the acoustic totals
@@ -128,225 +134,12 @@ __global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
                     [&](int i, int c) { sc[i] = c; sl[i] = c < 0 ? NEG_INF : z[c] - lse; });
 }
 
-// The beam, the frame's candidates and the selection scratch of one utterance, in LDS.  M: 0 = no LM, 1 = the n-gram (ctc_beam_sweep<true, false>),
-// 2 = the LSTM LM (ctc_beam_frame); a mode holds only what it reads.  Candidate index of frame t: parent rank k, then stay (0)
-// or position j in S_t (1 + j): idx = k * (P + 1) + ..., so "score descending, index ascending" is the selection order of DESIGN 5.3.  sc
-// holds each candidate's ordered score, 0 = not a candidate (-inf, or an extension merged into a stay).  LM: the ordered score is that of
-// fl(score + lmacc(prefix)), lmx holds lmacc(h + c) of the extensions that are candidates.
-struct SwBase {
-    float pb[2][KMAX], pnb[2][KMAX];
-    int last[2][KMAX], len[2][KMAX];
-    unsigned long long hash[2][KMAX], phash[2][KMAX];
-    float tot[KMAX], stay_pb[KMAX], stay_pnb[KMAX], xl[KMAX];
-    int cls[KMAX], win[KMAX];
-    uint32_t sc[KMAX * (KMAX + 1)];
-    unsigned long long wmax[2][SW_WAVES];
-};
-struct SwLm { float lmacc[2][KMAX], lmx[KMAX * (KMAX + 1)]; };
-struct SwNgram { float bo[KMAX][LM_MAX_ORDER - 1]; unsigned long long ctx[2][KMAX]; int has[KMAX]; };
-template <int M> struct SwLds;
-template <> struct SwLds<0> : SwBase {};
-template <> struct SwLds<1> : SwBase, SwLm, SwNgram {};
-template <> struct SwLds<2> : SwBase, SwLm {};
-
-// the LM side of mode 2: the fp32 log-softmax rows of the utterance's K beam rows (row k of the CURRENT beam at logp + k * ldp), the two
-// weights and am [B][nbest]
-struct CtcNlmTerm { const float* logp; long ldp; float lm_w, len_bonus; float* am; };
-
-// lm(c | entry k of the current beam): the n-gram's lookups from the entry's packed context and its backoffs, or the LSTM LM's gather
-template <int M, class La>
-__device__ __forceinline__ float lm_term(const SwLds<M>& s, const La& la, int cur, int k, int c) {
-    if constexpr (M == 1) {
-        float bo[LM_MAX_ORDER - 1];
-#pragma unroll
-        for (int i = 0; i < LM_MAX_ORDER - 1; ++i) bo[i] = s.bo[k][i];
-        return lm_score_packed(la.lm, s.ctx[cur][k], ctx_len(la.lm, s.len[cur][k]), bo, s.has[k], c);
-    } else {
-        return la.logp[(long)k * la.ldp + c];
-    }
-}
-// lm(eos | entry k) at the end of the utterance
-template <int M, class La>
-__device__ __forceinline__ float lm_eos_term(const SwLds<M>& s, const La& la, int cur, int k, int eos) {
-    if constexpr (M == 1) {
-        const unsigned long long ctx = s.ctx[cur][k];
-        const int cn = ctx_len(la.lm, s.len[cur][k]);
-        float bo[LM_MAX_ORDER - 1];
-        const int has = ctx_backoffs(la.lm, ctx, cn, bo);
-        return lm_score_packed(la.lm, ctx, cn, bo, has, eos);
-    } else {
-        return la.logp[(long)k * la.ldp + eos];
-    }
-}
-
-// ONE frame (row = b * Tp + t) of one utterance's search, by its workgroup of 256 threads: the beam s.*[cur] of n entries -> s.*[cur ^ 1],
-// the frame's back-pointer records, and the number of entries kept.  s.win[r] stays the candidate index of the entry of rank r and s.cls the
-// frame's token set.  ctc_beam_sweep's loop body, statement for statement, with the LDS arrays as members of s.
-template <int M, class La>
-__device__ __forceinline__ int ctc_frame_step(SwLds<M>& s, const CtcBeamArgs& a, const La& la, long row, int cur, int n) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.K, P = a.P, P1 = P + 1;
-    const int nxt = cur ^ 1;
-    // the frame's token set, and every entry's not-extended candidate
-    if (tid < P) { s.cls[tid] = a.s_cls[row * P + tid]; s.xl[tid] = a.s_lp[row * P + tid]; }
-    if (tid < n) {
-        const float pb = s.pb[cur][tid], pnb = s.pnb[cur][tid];
-        const int last = s.last[cur][tid];
-        const float tot = log_add(pb, pnb);
-        s.tot[tid] = tot;
-        s.stay_pb[tid] = tot + a.xb[row];
-        s.stay_pnb[tid] = last < 0 ? NEG_INF : pnb + (a.logits[row * a.ld + last] - a.lse[row]);
-        if constexpr (M == 1) {
-            float bo[LM_MAX_ORDER - 1];
-            s.has[tid] = ctx_backoffs(la.lm, s.ctx[cur][tid], ctx_len(la.lm, s.len[cur][tid]), bo);
-#pragma unroll
-            for (int k = 0; k < LM_MAX_ORDER - 1; ++k) s.bo[tid][k] = bo[k];
-        }
-    }
-    __syncthreads();
-    const int ncand = n * P1;
-    for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-        const int k = idx / P1, j = idx % P1 - 1;
-        if (j < 0) continue;
-        const float v = (s.cls[j] == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
-        s.sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
-    }
-    __syncthreads();
-    // merge: the extension of k that is the beam entry k2 adds to k2's stay (at most one k per k2)
-    for (int p = tid; p < n * n; p += SW_THREADS) {
-        const int k = p / n, k2 = p % n;
-        if (s.len[cur][k2] != s.len[cur][k] + 1 || s.phash[cur][k2] != s.hash[cur][k]) continue;
-        const int c = s.last[cur][k2];
-        for (int j = 0; j < P; ++j) {
-            if (s.cls[j] != c) continue;
-            const float v = (c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
-            s.stay_pnb[k2] = log_add(s.stay_pnb[k2], v);
-            s.sc[k * P1 + 1 + j] = 0u;
-            break;
-        }
-    }
-    __syncthreads();
-    if (tid < n) {
-        float v = log_add(s.stay_pb[tid], s.stay_pnb[tid]);
-        if constexpr (M != 0) v = add_rn(v, s.lmacc[cur][tid]);
-        s.sc[tid * P1] = v == NEG_INF ? 0u : ord_f32(v);
-    }
-    if constexpr (M != 0) {
-        // the extensions still standing (finite, not merged: their class is a real one, never the -1 of a NaN row) get their LM term
-        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-            const int k = idx / P1, j = idx % P1 - 1;
-            if (j < 0 || !s.sc[idx]) continue;
-            const int c = s.cls[j];
-            if (c < 0) { s.sc[idx] = 0u; continue; }
-            const float lmv = lm_term<M>(s, la, cur, k, c);
-            const float acc = add_rn(s.lmacc[cur][k], add_rn(mul_rn(la.lm_w, lmv), la.len_bonus));
-            const float v = add_rn((c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j], acc);
-            s.lmx[idx] = acc;
-            s.sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
-        }
-    }
-    __syncthreads();
-    // the K best: arg-max rounds; a thread rescans its own candidates (idx = tid mod 256) only after it gave the winner
-    unsigned long long mine = 0;
-    for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-        const unsigned long long key = ((unsigned long long)s.sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
-        if (s.sc[idx] && key > mine) mine = key;
-    }
-    int kept = 0;
-    for (int r = 0; r < K; ++r) {
-        const unsigned long long wm = wave_max_u64(mine);
-        if (lane == 0) s.wmax[r & 1][wave] = wm;
-        __syncthreads();
-        unsigned long long best = s.wmax[r & 1][0];
-#pragma unroll
-        for (int w = 1; w < SW_WAVES; ++w) { const unsigned long long v = s.wmax[r & 1][w]; best = v > best ? v : best; }
-        if (best == 0) break;                                // uniform: nothing but -inf candidates is left
-        const int win = (int)(0xffffffffu - (uint32_t)best);
-        if (tid == 0) s.win[r] = win;
-        if (win % SW_THREADS == tid) {
-            s.sc[win] = 0u;
-            mine = 0;
-            for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-                const unsigned long long key = ((unsigned long long)s.sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
-                if (s.sc[idx] && key > mine) mine = key;
-            }
-        }
-        kept = r + 1;
-    }
-    __syncthreads();
-    // the next beam, in rank order, and its back-pointer records: parent slot | (emitted class + 1) << 8  (0 = stay)
-    if (tid < kept) {
-        const int win = s.win[tid], k = win / P1, j = win % P1 - 1;
-        int rec = k;
-        if (j < 0) {
-            s.pb[nxt][tid] = s.stay_pb[k]; s.pnb[nxt][tid] = s.stay_pnb[k];
-            s.last[nxt][tid] = s.last[cur][k]; s.len[nxt][tid] = s.len[cur][k];
-            s.hash[nxt][tid] = s.hash[cur][k]; s.phash[nxt][tid] = s.phash[cur][k];
-            if constexpr (M != 0) s.lmacc[nxt][tid] = s.lmacc[cur][k];
-            if constexpr (M == 1) s.ctx[nxt][tid] = s.ctx[cur][k];
-        } else {
-            const int c = s.cls[j];
-            s.pb[nxt][tid] = NEG_INF;
-            s.pnb[nxt][tid] = (c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k]) + s.xl[j];
-            s.last[nxt][tid] = c; s.len[nxt][tid] = s.len[cur][k] + 1;
-            s.hash[nxt][tid] = hash_push(s.hash[cur][k], c); s.phash[nxt][tid] = s.hash[cur][k];
-            if constexpr (M != 0) s.lmacc[nxt][tid] = s.lmx[win];
-            if constexpr (M == 1) s.ctx[nxt][tid] = ctx_push(s.ctx[cur][k], c);
-            rec |= (c + 1) << 8;
-        }
-        a.rec[row * K + tid] = rec;
-    }
-    __syncthreads();
-    return kept;
-}
-
-// The tail of a search: the N-best list of the final beam s.*[cur] of n entries.
-template <int M, class La>
-__device__ __forceinline__ void ctc_beam_tail(SwLds<M>& s, const CtcBeamArgs& a, const La& la, int b, int cur, int n, int Tb, int nbest,
-                                              int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
-    const int tid = threadIdx.x;
-    const int K = a.K, Tp = a.Tp;
-    // N-best list of the final beam: each live slot walks its records backwards (a prefix of len tokens meets exactly len emitting
-    // records on the way); everything behind a list's length is -1
-    // LM: final(h) = fl(fl(am + lmacc) + fl(lm_w * lm(eos | h))), and list position i is the entry of rank i by (final descending, beam rank
-    // ascending) -- ranked on the ordered bits, so the ranks are a permutation whatever the values
-    int* out = tokens + (long)b * nbest * Tp;
-    if constexpr (M != 0) {
-        if (tid < n) {
-            const float am = log_add(s.pb[cur][tid], s.pnb[cur][tid]);
-            const float fin = add_rn(add_rn(am, s.lmacc[cur][tid]), mul_rn(la.lm_w, lm_eos_term<M>(s, la, cur, tid, a.eos)));
-            s.tot[tid] = am; s.xl[tid] = fin; s.sc[tid] = ord_f32(fin);
-        }
-        __syncthreads();
-        if (tid < n) {
-            int rank = 0;
-            for (int j = 0; j < n; ++j) rank += s.sc[j] > s.sc[tid] || (s.sc[j] == s.sc[tid] && j < tid);
-            s.cls[rank] = tid;
-        }
-        __syncthreads();
-    }
-    if (tid < nbest) {
-        const bool live = tid < n;
-        const int src = M != 0 && live ? s.cls[tid] : tid;
-        int pos = live ? s.len[cur][src] : 0, slot = src;
-        s.win[tid] = pos;
-        lens[b * nbest + tid] = live ? pos : -1;
-        if constexpr (M != 0) {
-            scores[b * nbest + tid] = live ? s.xl[src] : NEG_INF;
-            la.am[b * nbest + tid] = live ? s.tot[src] : NEG_INF;
-        } else {
-            scores[b * nbest + tid] = live ? log_add(s.pb[cur][tid], s.pnb[cur][tid]) : NEG_INF;
-        }
-        for (int t = Tb - 1; t >= 0 && pos > 0; --t) {
-            const int rec = a.rec[((long)b * Tp + t) * K + slot];
-            if (rec >> 8) out[(long)tid * Tp + --pos] = (rec >> 8) - 1;
-            slot = rec & 0xff;
-        }
-    }
-    __syncthreads();
-    for (long i = tid; i < (long)nbest * Tp; i += SW_THREADS) if ((int)(i % Tp) >= s.win[i / Tp]) out[i] = -1;
-}
-
+// ---- the search: ONE kernel text for the five searches.  M: 0 = no LM, 1 = the n-gram (la is a CtcLmArgs), 2 = the LSTM LM, whose rows and
+// beam live in the work buffer (la is nlm.h's CtcNlmArgs).  PH: what of the text a launch runs --
+//   PH_SWEEP  the empty prefix, all frames 0 .. Tb - 1, the tail                                          (M = 0, 1: one launch per call)
+//   PH_FRAME  the beam of parity (st - 1) & 1 from the work buffer, the ONE frame t = st - 2, the beam to parity st & 1 with each kept
+//             entry's parent row and token (-1: a stay) for the LM's carry step; with t outside [0, Tb) every live row stays in its own row
+//   PH_TAIL   the beam of parity (st - 1) & 1, the tail                                                   (M = 2: st is the device step word)
 // grid B, 256 threads.  Candidate index of frame t: parent rank k, then stay (0) or position j in S_t (1 + j): idx = k * (P + 1) + ...,
 // so "score descending, index ascending" is the selection order of DESIGN 5.3.  s_sc holds each candidate's ordered score, 0 = not a
 // candidate (-inf, or an extension merged into a stay).  LM: the ordered score is that of fl(score + lmacc(prefix)), s_lmx holds lmacc(h + c)
@@ -359,9 +152,15 @@ __device__ __forceinline__ void ctc_beam_tail(SwLds<M>& s, const CtcBeamArgs& a,
 // re-ranks with or without an LM; without one la carries only am.
 struct CtcBiasArgs { BiasDev bias; float bias_w; int* nbias; };        // nbias [B][nbest]: n_final, -1 = no entry
 
-template <bool LM, bool BIAS>
-__global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs a, CtcLmArgs la, CtcBiasArgs ba, int nbest, int* __restrict__ tokens,
-                                                                    int* __restrict__ lens, float* __restrict__ scores) {
+enum { PH_SWEEP, PH_FRAME, PH_TAIL };
+template <int M> using CtcLmSide = std::conditional_t<M == 2, CtcNlmArgs, CtcLmArgs>;
+
+template <int M, bool BIAS, int PH>
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, CtcLmSide<M> la, CtcBiasArgs ba, int nbest, int* __restrict__ tokens,
+                                                              int* __restrict__ lens, float* __restrict__ scores) {
+    static_assert((M == 2) == (PH != PH_SWEEP), "the LSTM LM's search runs frame by frame, the others in one sweep");
+    static_assert(!(M == 2 && BIAS), "biasing the LSTM LM search needs the automaton's state per entry in the work buffer (DESIGN 5.13): not built");
+    constexpr bool LM = M != 0;
     __shared__ float s_pb[2][KMAX], s_pnb[2][KMAX];
     __shared__ int s_last[2][KMAX], s_len[2][KMAX];
     __shared__ unsigned long long s_hash[2][KMAX], s_phash[2][KMAX];
@@ -370,7 +169,9 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     __shared__ uint32_t s_sc[KMAX * (KMAX + 1)];
     __shared__ unsigned long long s_wmax[2][SW_WAVES];
     // LM only (unreferenced, hence not allocated, without it)
-    __shared__ float s_lmacc[2][KMAX], s_bo[KMAX][LM_MAX_ORDER - 1], s_lmx[KMAX * (KMAX + 1)];
+    __shared__ float s_lmacc[2][KMAX], s_lmx[KMAX * (KMAX + 1)];
+    // the n-gram only: an entry's packed context and its backoffs
+    __shared__ float s_bo[KMAX][LM_MAX_ORDER - 1];
     __shared__ unsigned long long s_ctx[2][KMAX];
     __shared__ int s_has[KMAX];
     // BIAS only: the automaton's state per entry
@@ -378,14 +179,44 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     const int K = a.K, P = a.P, P1 = P + 1, Tp = a.Tp;
     const int Tb = clamp_len(a.enc_lens[b], Tp);
-    int cur = 0, n = 1;
-    if (tid == 0) {
+    int cur = 0, n = 1, t0 = 0, t1 = Tb;                             // the beam s_*[cur] of n entries; the frames to run
+    // the LM's two weights, and mode 2's step word and log-softmax rows of this utterance's K beam rows (row k at logp + k * ldp)
+    float lm_w = 0.f, len_bonus = 0.f;
+    int st = 0;
+    const float* logp = nullptr;
+    if constexpr (M == 1) { lm_w = la.lm_w; len_bonus = la.len_bonus; }
+    if constexpr (M == 2) {
+        st = *la.step;
+        const int par = (st - 1) & 1;
+        lm_w = la.wts[0]; len_bonus = la.wts[1];
+        logp = la.logp + ((long)par * a.B + b) * K * la.ldp;
+        const long o = ((long)par * a.B + b) * K + tid;
+        n = clamp_live(la.nlive[par * a.B + b], K);
+        if (tid < n) {
+            s_pb[0][tid] = la.pb[o]; s_pnb[0][tid] = la.pnb[o]; s_last[0][tid] = la.last[o]; s_len[0][tid] = la.len[o];
+            s_hash[0][tid] = la.hash[o]; s_phash[0][tid] = la.phash[o]; s_lmacc[0][tid] = la.lmacc[o];
+        }
+        t0 = st - 2; t1 = PH == PH_FRAME && t0 >= 0 && t0 < Tb ? t0 + 1 : t0;
+    } else if (tid == 0) {
         s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_hash[0][0] = HASH_EMPTY; s_phash[0][0] = 0;
         if constexpr (LM) { s_lmacc[0][0] = 0.f; s_ctx[0][0] = 1; }          // the context [sos]: sos = 0 as id + 1
         if constexpr (BIAS) { s_bnode[0][0] = 0; s_bn[0][0] = 0; }
     }
     __syncthreads();
-    for (int t = 0; t < Tb; ++t) {
+    // The two helpers take what they read by value and capture nothing (the LDS arrays are static): a capture of cur by reference compiles
+    // to other code, with more registers.
+    // the score of h + c for entry k of the beam s_*[cur], c = S_t[j]
+    auto ext = [](int cur, int c, int k, int j) { return (c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j]; };
+    // a thread's best candidate: its key (ordered score, then the smaller index), 0 = none left
+    auto scan = [](int tid, int ncand) {
+        unsigned long long m = 0;
+        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
+            const unsigned long long key = ((unsigned long long)s_sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+            if (s_sc[idx] && key > m) m = key;
+        }
+        return m;
+    };
+    for (int t = t0; PH != PH_TAIL && t < t1; ++t) {
         const long row = (long)b * Tp + t;
         const int nxt = cur ^ 1;
         // the frame's token set, and every entry's not-extended candidate
@@ -397,7 +228,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
             s_tot[tid] = tot;
             s_stay_pb[tid] = tot + a.xb[row];
             s_stay_pnb[tid] = last < 0 ? NEG_INF : pnb + (a.logits[row * a.ld + last] - a.lse[row]);
-            if constexpr (LM) {
+            if constexpr (M == 1) {
                 float bo[LM_MAX_ORDER - 1];
                 s_has[tid] = ctx_backoffs(la.lm, s_ctx[cur][tid], ctx_len(la.lm, s_len[cur][tid]), bo);
 #pragma unroll
@@ -409,7 +240,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
         for (int idx = tid; idx < ncand; idx += SW_THREADS) {
             const int k = idx / P1, j = idx % P1 - 1;
             if (j < 0) continue;
-            const float v = (s_cls[j] == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+            const float v = ext(cur, s_cls[j], k, j);
             s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
         }
         __syncthreads();
@@ -420,7 +251,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
             const int c = s_last[cur][k2];
             for (int j = 0; j < P; ++j) {
                 if (s_cls[j] != c) continue;
-                const float v = (c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+                const float v = ext(cur, c, k, j);
                 s_stay_pnb[k2] = log_add(s_stay_pnb[k2], v);
                 s_sc[k * P1 + 1 + j] = 0u;
                 break;
@@ -433,47 +264,41 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
             if constexpr (BIAS) v = add_rn(v, mul_rn(ba.bias_w, (float)s_bn[cur][tid]));
             s_sc[tid * P1] = v == NEG_INF ? 0u : ord_f32(v);
         }
-        if constexpr (LM) {
+        if constexpr (LM || BIAS) {
             // the extensions still standing (finite, not merged: their class is a real one, never the -1 of a NaN row) get their LM term
+            // and the bias term of the state their token leads to
             for (int idx = tid; idx < ncand; idx += SW_THREADS) {
                 const int k = idx / P1, j = idx % P1 - 1;
                 if (j < 0 || !s_sc[idx]) continue;
                 const int c = s_cls[j];
                 if (c < 0) { s_sc[idx] = 0u; continue; }
-                float bo[LM_MAX_ORDER - 1];
+                float acc = 0.f, bo[LM_MAX_ORDER - 1];         // (bo is declared out here: in a scope of its own the LM sweeps compile to other code)
+                if constexpr (LM) {
+                    // lm(c | entry k): the n-gram's lookups from the entry's packed context and its backoffs, or the LSTM LM's gather
+                    float lmv;
+                    if constexpr (M == 1) {
 #pragma unroll
-                for (int i = 0; i < LM_MAX_ORDER - 1; ++i) bo[i] = s_bo[k][i];
-                const float lmv = lm_score_packed(la.lm, s_ctx[cur][k], ctx_len(la.lm, s_len[cur][k]), bo, s_has[k], c);
-                const float acc = add_rn(s_lmacc[cur][k], add_rn(mul_rn(la.lm_w, lmv), la.len_bonus));
-                float v = add_rn((c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j], acc);
+                        for (int i = 0; i < LM_MAX_ORDER - 1; ++i) bo[i] = s_bo[k][i];
+                        lmv = lm_score_packed(la.lm, s_ctx[cur][k], ctx_len(la.lm, s_len[cur][k]), bo, s_has[k], c);
+                    } else {
+                        lmv = logp[(long)k * la.ldp + c];
+                    }
+                    acc = add_rn(s_lmacc[cur][k], add_rn(mul_rn(lm_w, lmv), len_bonus));
+                }
+                float v = ext(cur, c, k, j);
+                if constexpr (LM) v = add_rn(v, acc);
                 if constexpr (BIAS) {
                     int u = s_bnode[cur][k], nb = s_bn[cur][k];
                     bias_step(ba.bias, u, nb, c);
                     v = add_rn(v, mul_rn(ba.bias_w, (float)nb));
                 }
-                s_lmx[idx] = acc;
-                s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
-            }
-        } else if constexpr (BIAS) {
-            // the extensions still standing get the bias term of the state their token leads to
-            for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-                const int k = idx / P1, j = idx % P1 - 1;
-                if (j < 0 || !s_sc[idx]) continue;
-                const int c = s_cls[j];
-                if (c < 0) { s_sc[idx] = 0u; continue; }
-                int u = s_bnode[cur][k], nb = s_bn[cur][k];
-                bias_step(ba.bias, u, nb, c);
-                const float v = add_rn((c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j], mul_rn(ba.bias_w, (float)nb));
+                if constexpr (LM) s_lmx[idx] = acc;
                 s_sc[idx] = v == NEG_INF ? 0u : ord_f32(v);
             }
         }
         __syncthreads();
         // the K best: arg-max rounds; a thread rescans its own candidates (idx = tid mod 256) only after it gave the winner
-        unsigned long long mine = 0;
-        for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-            const unsigned long long key = ((unsigned long long)s_sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
-            if (s_sc[idx] && key > mine) mine = key;
-        }
+        unsigned long long mine = scan(tid, ncand);
         int kept = 0;
         for (int r = 0; r < K; ++r) {
             const unsigned long long wm = wave_max_u64(mine);
@@ -485,14 +310,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
             if (best == 0) break;                                // uniform: nothing but -inf candidates is left
             const int win = (int)(0xffffffffu - (uint32_t)best);
             if (tid == 0) s_win[r] = win;
-            if (win % SW_THREADS == tid) {
-                s_sc[win] = 0u;
-                mine = 0;
-                for (int idx = tid; idx < ncand; idx += SW_THREADS) {
-                    const unsigned long long key = ((unsigned long long)s_sc[idx] << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
-                    if (s_sc[idx] && key > mine) mine = key;
-                }
-            }
+            if (win % SW_THREADS == tid) { s_sc[win] = 0u; mine = scan(tid, ncand); }
             kept = r + 1;
         }
         __syncthreads();
@@ -504,15 +322,17 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
                 s_pb[nxt][tid] = s_stay_pb[k]; s_pnb[nxt][tid] = s_stay_pnb[k];
                 s_last[nxt][tid] = s_last[cur][k]; s_len[nxt][tid] = s_len[cur][k];
                 s_hash[nxt][tid] = s_hash[cur][k]; s_phash[nxt][tid] = s_phash[cur][k];
-                if constexpr (LM) { s_lmacc[nxt][tid] = s_lmacc[cur][k]; s_ctx[nxt][tid] = s_ctx[cur][k]; }
+                if constexpr (LM) s_lmacc[nxt][tid] = s_lmacc[cur][k];
+                if constexpr (M == 1) s_ctx[nxt][tid] = s_ctx[cur][k];
                 if constexpr (BIAS) { s_bnode[nxt][tid] = s_bnode[cur][k]; s_bn[nxt][tid] = s_bn[cur][k]; }
             } else {
                 const int c = s_cls[j];
                 s_pb[nxt][tid] = NEG_INF;
-                s_pnb[nxt][tid] = (c == s_last[cur][k] ? s_pb[cur][k] : s_tot[k]) + s_xl[j];
+                s_pnb[nxt][tid] = ext(cur, c, k, j);
                 s_last[nxt][tid] = c; s_len[nxt][tid] = s_len[cur][k] + 1;
                 s_hash[nxt][tid] = hash_push(s_hash[cur][k], c); s_phash[nxt][tid] = s_hash[cur][k];
-                if constexpr (LM) { s_lmacc[nxt][tid] = s_lmx[win]; s_ctx[nxt][tid] = ctx_push(s_ctx[cur][k], c); }
+                if constexpr (LM) s_lmacc[nxt][tid] = s_lmx[win];
+                if constexpr (M == 1) s_ctx[nxt][tid] = ctx_push(s_ctx[cur][k], c);
                 if constexpr (BIAS) {                               // the winner's step again, from its parent: the same bits as when it was scored
                     int u = s_bnode[cur][k], nb = s_bn[cur][k];
                     bias_step(ba.bias, u, nb, c);
@@ -524,6 +344,21 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
         }
         __syncthreads();
         cur = nxt; n = kept;
+        if constexpr (PH == PH_FRAME) break;                    // one frame per launch: said here, the compiler drops the loop's registers
+    }
+    if constexpr (PH == PH_FRAME) {
+        // the beam behind the frame to parity st & 1; s_win and s_cls are still the frame's, if one ran
+        const long o = ((long)(st & 1) * a.B + b) * K + tid, r0 = (long)b * K;
+        if (tid < n) {
+            la.pb[o] = s_pb[cur][tid]; la.pnb[o] = s_pnb[cur][tid]; la.last[o] = s_last[cur][tid]; la.len[o] = s_len[cur][tid];
+            la.hash[o] = s_hash[cur][tid]; la.phash[o] = s_phash[cur][tid]; la.lmacc[o] = s_lmacc[cur][tid];
+            const bool ran = t1 > t0;
+            const int j = ran ? s_win[tid] % P1 - 1 : -1;
+            la.tok[r0 + tid] = j < 0 ? -1 : s_cls[j];
+            la.par[r0 + tid] = (int)r0 + (ran ? s_win[tid] / P1 : tid);
+        }
+        if (tid == 0) la.nlive[(st & 1) * a.B + b] = n;
+        return;
     }
     // N-best list of the final beam: each live slot walks its records backwards (a prefix of len tokens meets exactly len emitting
     // records on the way); everything behind a list's length is -1
@@ -536,11 +371,16 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
             const float am = log_add(s_pb[cur][tid], s_pnb[cur][tid]);
             float fin = am;
             if constexpr (LM) {
-                const unsigned long long ctx = s_ctx[cur][tid];
-                const int cn = ctx_len(la.lm, s_len[cur][tid]);
-                float bo[LM_MAX_ORDER - 1];
-                const int has = ctx_backoffs(la.lm, ctx, cn, bo);
-                fin = add_rn(add_rn(am, s_lmacc[cur][tid]), mul_rn(la.lm_w, lm_score_packed(la.lm, ctx, cn, bo, has, a.eos)));
+                // lm(eos | entry tid): the frame's switch, the context's backoffs looked up here (the backoffs, the sum, then the lookups:
+                // the order the n-gram sweep has always been compiled in)
+                unsigned long long ctx = 0;
+                int cn = 0, has = 0;
+                float bo[LM_MAX_ORDER - 1], lme;
+                if constexpr (M == 1) { ctx = s_ctx[cur][tid]; cn = ctx_len(la.lm, s_len[cur][tid]); has = ctx_backoffs(la.lm, ctx, cn, bo); }
+                const float y = add_rn(am, s_lmacc[cur][tid]);
+                if constexpr (M == 1) lme = lm_score_packed(la.lm, ctx, cn, bo, has, a.eos);
+                else lme = logp[(long)tid * la.ldp + a.eos];
+                fin = add_rn(y, mul_rn(lm_w, lme));
             }
             if constexpr (BIAS) {
                 const int nf = bias_final(ba.bias, s_bnode[cur][tid], s_bn[cur][tid]);
@@ -582,12 +422,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_sweep_kernel(CtcBeamArgs 
 
 // ---- the LSTM LM search (masr_ctc_beam_search_nlm): frame-synchronous across launches.  The beam lives in the work buffer by
 // parity of the device step word st: the beam in front of frame t = st - 2 stands at parity (st - 1) & 1 -- where the LM's states and
-// log-softmax rows of step st - 1 stand (nlm.h) -- and the frame's kernel writes the next one to parity st & 1.
-__device__ __forceinline__ int clamp_live(int n, int K) { return n < 0 ? 0 : (n > K ? K : n); }
-__device__ __forceinline__ void nlm_beam_load(SwLds<2>& s, const CtcNlmArgs& q, long o, int cur, int i) {
-    s.pb[cur][i] = q.pb[o]; s.pnb[cur][i] = q.pnb[o]; s.last[cur][i] = q.last[o]; s.len[cur][i] = q.len[o];
-    s.hash[cur][i] = q.hash[o]; s.phash[cur][i] = q.phash[o]; s.lmacc[cur][i] = q.lmacc[o];
-}
+// log-softmax rows of step st - 1 stand (nlm.h) -- and the frame's launch writes the next one to parity st & 1.
 
 // grid B, 256 threads: the initial beam (the empty prefix in row 0 of every utterance) at parity 1, st = 1, the two weights, htop = 0
 __global__ __launch_bounds__(SW_THREADS) void ctc_beam_nlm_prepare_kernel(CtcNlmArgs q, int B, int K, float lm_w, float len_bonus, bf16* htop, long htop_n) {
@@ -599,53 +434,6 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_nlm_prepare_kernel(CtcNlm
         if (b == 0) { q.step[0] = 1; q.step[1] = 0; q.wts[0] = lm_w; q.wts[1] = len_bonus; }
     }
     for (long i = (long)b * SW_THREADS + threadIdx.x; i < htop_n; i += (long)gridDim.x * SW_THREADS) htop[i] = (bf16)0.f;
-}
-
-// grid B, 256 threads: frame t = st - 2 of every utterance -- ctc_beam_sweep<true, false>'s frame with the LM term gathered from the log-softmax
-// row of the parent's beam row.  Besides the back-pointer record every kept entry leaves its parent row and its token (-1: a stay) for the LM's
-// carry step.  An utterance past its enc_len keeps its beam: every live row stays in its own row.
-__global__ __launch_bounds__(SW_THREADS) void ctc_beam_frame_kernel(CtcBeamArgs a, CtcNlmArgs q) {
-    __shared__ SwLds<2> s;
-    const int tid = threadIdx.x, b = blockIdx.x, K = a.K;
-    const int st = *q.step, t = st - 2, cur = (st - 1) & 1, nxt = st & 1;
-    const int Tb = clamp_len(a.enc_lens[b], a.Tp);
-    const long oc = ((long)cur * a.B + b) * K, on = ((long)nxt * a.B + b) * K, r0 = (long)b * K;
-    const int n = clamp_live(q.nlive[cur * a.B + b], K);
-    if (t < 0 || t >= Tb) {
-        if (tid < n) {
-            q.pb[on + tid] = q.pb[oc + tid]; q.pnb[on + tid] = q.pnb[oc + tid]; q.last[on + tid] = q.last[oc + tid]; q.len[on + tid] = q.len[oc + tid];
-            q.hash[on + tid] = q.hash[oc + tid]; q.phash[on + tid] = q.phash[oc + tid]; q.lmacc[on + tid] = q.lmacc[oc + tid];
-            q.tok[r0 + tid] = -1; q.par[r0 + tid] = (int)r0 + tid;
-        }
-        if (tid == 0) q.nlive[nxt * a.B + b] = n;
-        return;
-    }
-    if (tid < n) nlm_beam_load(s, q, oc + tid, cur, tid);
-    __syncthreads();
-    const CtcNlmTerm la{q.logp + ((long)cur * a.B * K + r0) * q.ldp, q.ldp, q.wts[0], q.wts[1], q.am};
-    const int kept = ctc_frame_step<2>(s, a, la, (long)b * a.Tp + t, cur, n);
-    if (tid < kept) {
-        q.pb[on + tid] = s.pb[nxt][tid]; q.pnb[on + tid] = s.pnb[nxt][tid]; q.last[on + tid] = s.last[nxt][tid]; q.len[on + tid] = s.len[nxt][tid];
-        q.hash[on + tid] = s.hash[nxt][tid]; q.phash[on + tid] = s.phash[nxt][tid]; q.lmacc[on + tid] = s.lmacc[nxt][tid];
-        const int win = s.win[tid], k = win / (a.P + 1), j = win % (a.P + 1) - 1;
-        q.tok[r0 + tid] = j < 0 ? -1 : s.cls[j];
-        q.par[r0 + tid] = (int)r0 + k;
-    }
-    if (tid == 0) q.nlive[nxt * a.B + b] = kept;
-}
-
-// grid B, 256 threads: the sweep's tail on the beam behind the last frame (parity (st - 1) & 1), the eos term from each live row's
-// log-softmax row
-__global__ __launch_bounds__(SW_THREADS) void ctc_beam_tail_kernel(CtcBeamArgs a, CtcNlmArgs q, int nbest, int* __restrict__ tokens,
-                                                                   int* __restrict__ lens, float* __restrict__ scores) {
-    __shared__ SwLds<2> s;
-    const int tid = threadIdx.x, b = blockIdx.x, K = a.K;
-    const int cur = (*q.step - 1) & 1;
-    const int n = clamp_live(q.nlive[cur * a.B + b], K);
-    if (tid < n) nlm_beam_load(s, q, ((long)cur * a.B + b) * K + tid, cur, tid);
-    __syncthreads();
-    const CtcNlmTerm la{q.logp + ((long)cur * a.B * K + (long)b * K) * q.ldp, q.ldp, q.wts[0], q.wts[1], q.am};
-    ctc_beam_tail<2>(s, a, la, b, cur, n, clamp_len(a.enc_lens[b], a.Tp), nbest, tokens, lens, scores);
 }
 
 long align256(long v) { return (v + 255) & ~255l; }
@@ -701,40 +489,44 @@ static int ctc_beam_frames(const CtcBeamArgs& a, hipStream_t s) {
     return LAUNCH_OK();
 }
 
-// the checks and the two launches of the sweep's entry points; la: the LM side, or null
+template <bool LM, bool BIAS>
+static void ctc_beam_sweep(const CtcBeamArgs& a, const CtcLmArgs& la, const CtcBiasArgs& ba, int nbest, int* tokens, int* lens, float* scores, hipStream_t s) {
+    hipLaunchKernelGGL((ctc_beam_kernel<LM ? 1 : 0, BIAS, PH_SWEEP>), dim3(a.B), dim3(SW_THREADS), 0, s, a, la, ba, nbest, tokens, lens, scores);
+}
+
+// the checks and the two launches of the sweep's entry points.  lm / bias: an n-gram LM / a phrase list is fused; without one its struct is
+// empty, but for la.am, which the biased search without an LM writes too
 static int ctc_beam_run(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
-                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, const CtcLmArgs* la, hipStream_t s,
-                        const CtcBiasArgs* ba = nullptr, float* am = nullptr) {
-    CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, la != nullptr, la ? la->lm.C : 0,
-                      la ? la->lm.order : 0, la ? la->lm_w : 0.f, la ? la->len_bonus : 0.f, la ? la->am : nullptr));
-    if (ba) {
+                        void* work, int64_t work_bytes, int* tokens, int* lens, float* scores, bool lm, const CtcLmArgs& la, bool bias,
+                        const CtcBiasArgs& ba, hipStream_t s) {
+    CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, lm, la.lm.C, la.lm.order, la.lm_w,
+                      la.len_bonus, la.am));
+    if (bias) {
         // the phrase tokens are the model's classes 1 .. C - 2 whether an LM is fused or not
         if (blank != 0) { mk_set_error(fn, "blank must be 0 with a phrase list (class 0 is no phrase token)"); return -1; }
         if (eos != C - 1) { mk_set_error(fn, "eos must be C - 1 with a phrase list (the last class is no phrase token)"); return -1; }
-        if (ba->bias.C != C) { mk_set_error(fn, "the phrase list's classes differ from C"); return -1; }
-        if (!(ba->bias_w >= 0.f) || !std::isfinite(ba->bias_w)) { mk_set_error(fn, "bias_w must be finite and >= 0"); return -1; }
-        if (!am || !ba->nbias) { mk_set_error(fn, "null pointer"); return -1; }
+        if (ba.bias.C != C) { mk_set_error(fn, "the phrase list's classes differ from C"); return -1; }
+        if (!(ba.bias_w >= 0.f) || !std::isfinite(ba.bias_w)) { mk_set_error(fn, "bias_w must be finite and >= 0"); return -1; }
+        if (!la.am || !ba.nbias) { mk_set_error(fn, "null pointer"); return -1; }
     }
     if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) {
-        mk_set_error(fn, ba   ? "work buffer too small (masr_ctc_beam_bias_work_bytes(B, Tp, C, K)) or misaligned"
-                         : la ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
+        mk_set_error(fn, bias ? "work buffer too small (masr_ctc_beam_bias_work_bytes(B, Tp, C, K)) or misaligned"
+                         : lm ? "work buffer too small (masr_ctc_beam_lm_work_bytes(B, Tp, C, K)) or misaligned"
                               : "work buffer too small (masr_ctc_beam_work_bytes(B, Tp, C, K)) or misaligned");
         return -1;
     }
     const CtcBeamArgs a = ctc_beam_carve(logits, ld, enc_lens, B, Tp, C, K, blank, eos, work);
     CK(ctc_beam_frames(a, s));
-    if (ba) {
-        if (la) hipLaunchKernelGGL((ctc_beam_sweep_kernel<true, true>), dim3(B), dim3(SW_THREADS), 0, s, a, *la, *ba, nbest, tokens, lens, scores);
-        else hipLaunchKernelGGL((ctc_beam_sweep_kernel<false, true>), dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{LmDev{}, 0.f, 0.f, am}, *ba, nbest, tokens, lens, scores);
-    }
-    else if (la) hipLaunchKernelGGL((ctc_beam_sweep_kernel<true, false>), dim3(B), dim3(SW_THREADS), 0, s, a, *la, CtcBiasArgs{}, nbest, tokens, lens, scores);
-    else hipLaunchKernelGGL((ctc_beam_sweep_kernel<false, false>), dim3(B), dim3(SW_THREADS), 0, s, a, CtcLmArgs{}, CtcBiasArgs{}, nbest, tokens, lens, scores);
+    static constexpr decltype(&ctc_beam_sweep<false, false>) sweep[2][2] = {{ctc_beam_sweep<false, false>, ctc_beam_sweep<false, true>},
+                                                                            {ctc_beam_sweep<true, false>, ctc_beam_sweep<true, true>}};
+    sweep[lm][bias](a, la, ba, nbest, tokens, lens, scores, s);
     return LAUNCH_OK();
 }
 
 int mk_ctc_beam_search(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos, void* work,
                        int64_t work_bytes, int* tokens, int* lens, float* scores, hipStream_t s) {
-    return ctc_beam_run("mk_ctc_beam_search", logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, nullptr, s);
+    return ctc_beam_run("mk_ctc_beam_search", logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, false,
+                        CtcLmArgs{}, false, CtcBiasArgs{}, s);
 }
 
 // (the LM state lives in LDS: the work buffer is the plain search's)
@@ -745,8 +537,8 @@ int mk_ctc_beam_search_lm(const float* logits, long ld, const int* enc_lens, int
                           float* am, hipStream_t s) {
     const char* fn = "mk_ctc_beam_search_lm";
     if (!lm) { mk_set_error(fn, "null language model"); return -1; }
-    const CtcLmArgs la{lm->dev, lm_w, len_bonus, am};
-    return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, &la, s);
+    return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, true,
+                        CtcLmArgs{lm->dev, lm_w, len_bonus, am}, false, CtcBiasArgs{}, s);
 }
 
 // (the automaton's state lives in LDS too)
@@ -757,10 +549,8 @@ int mk_ctc_beam_search_bias(const float* logits, long ld, const int* enc_lens, i
                             int* tokens, int* lens, float* scores, float* am, int* nbias, hipStream_t s) {
     const char* fn = "mk_ctc_beam_search_bias";
     if (!bias) { mk_set_error(fn, "null phrase list"); return -1; }
-    const CtcBiasArgs ba{bias->dev, bias_w, nbias};
-    if (!lm) return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, nullptr, s, &ba, am);
-    const CtcLmArgs la{lm->dev, lm_w, len_bonus, am};
-    return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, &la, s, &ba, am);
+    return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, lm != nullptr,
+                        lm ? CtcLmArgs{lm->dev, lm_w, len_bonus, am} : CtcLmArgs{LmDev{}, 0.f, 0.f, am}, true, CtcBiasArgs{bias->dev, bias_w, nbias}, s);
 }
 
 // ---------------------------------------------------------------- the LSTM LM search
@@ -824,12 +614,12 @@ int mk_ctc_beam_nlm_begin(const char* fn, const float* logits, long ld, const in
     return mk_nlm_step_carry(d, st, r.logits, r.ldl, q.logp, q.ldp, q.step, s);          // LM step 1: [start] from the zero state
 }
 int mk_ctc_beam_nlm_frame(const CtcNlmRun& r, hipStream_t s) {
-    hipLaunchKernelGGL(ctc_beam_frame_kernel, dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q);
+    hipLaunchKernelGGL((ctc_beam_kernel<2, false, PH_FRAME>), dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q, CtcBiasArgs{}, 0, nullptr, nullptr, nullptr);
     CK(LAUNCH_OK());
     return mk_nlm_step_carry(r.lm, r.st, r.logits, r.ldl, r.q.logp, r.q.ldp, r.q.step, s);
 }
 int mk_ctc_beam_nlm_end(const CtcNlmRun& r, int nbest, int* tokens, int* lens, float* scores, hipStream_t s) {
-    hipLaunchKernelGGL(ctc_beam_tail_kernel, dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q, nbest, tokens, lens, scores);
+    hipLaunchKernelGGL((ctc_beam_kernel<2, false, PH_TAIL>), dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, r.q, CtcBiasArgs{}, nbest, tokens, lens, scores);
     return LAUNCH_OK();
 }
 
