@@ -1460,14 +1460,31 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
 // all tiles of the workgroup and is written once; a fixed-order slab reduce makes the result deterministic.
 constexpr int W2_PS = 80, W2_LDY = 80;   // 160-B rows: tr-reads conflict-free
 constexpr int W2_TOTAL_WG = 256;    // one persistent workgroup per CU (see mk_conv3x3_wgrad)
+// The x operand of step (slab kc, tap row dyi) is two half-fragments, rho = rps kc + dyi and rho + hd (conv3x3_wgrad2_kernel: read_h); steps run in
+// groups u = 3 kc + dyi of three column shifts.  The first group that multiplies half rho -- the one that reads it from LDS; -1: nobody does.
+constexpr int w2_first_use(int rho, int rps, int hd) {
+    for (int u = 0; u < 12; ++u) {
+        const int lo = rps * (u / 3) + u % 3;
+        if (lo == rho || lo + hd == rho) return u;
+    }
+    return -1;
+}
+// LDS reads of step s = 9 kc + 3 dyi + dxj: its two halves, where it is the first to multiply them (0 behind the last step)
+constexpr int w2_nread(int s, int rps, int hd) {
+    if (s >= 36) return 0;
+    const int rho = rps * (s / 9) + s % 9 / 3;
+    return (w2_first_use(rho, rps, hd) == s / 3) + (w2_first_use(rho + hd, rps, hd) == s / 3);
+}
 
 // W2_TW: tile width in pixels (16, or 8 for maps whose width pads badly to 16); tile = 128 pixels
 // POOLED: the dy tile comes from ConvWgradArgs::dy_pooled + pool_idx: a thread fetches ONE pooled cell x 8 channels (16 B + 8 B of codes) and
 // stages the four positions of its window (4 + 0 instead of 4 x 16-byte loads per thread and tile)
-template <int CIN, int COUT, int W2_TW, bool POOLED = false>
+// BUF: the staging waves fetch through buffer descriptors (see Stage below); false for tensors of 4 GB and more
+template <int CIN, int COUT, int W2_TW, bool POOLED = false, bool BUF = true>
 __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, int nwg, int ntiles, int tiles_x, int tiles_y) {
     constexpr int W2_TH = 128 / W2_TW, W2_PH = W2_TH + 2, W2_PW = W2_TW + 2, RPS = 32 / W2_TW;      // RPS = pixel rows per 32-pixel slab
     constexpr int KTOT = 9 * CIN;
+    constexpr int W2_HD = 16 / W2_TW, W2_NHALF = 3 * RPS + 3 + W2_HD;   // x half-fragments: distance between a fragment's two, and how many a tile has per column shift
     constexpr int NPCH = (W2_PH * W2_PW * 8 + 255) / 256;   // patch chunks per thread (6)
     constexpr int NDCH = W2_TH * W2_TW * 8 / 256;           // dy chunks per thread (4)
     // one workgroup per CU: TWO tile buffers -- the next tile is written to LDS at the start of a tile's MFMA phase instead of behind
@@ -1477,15 +1494,26 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     __shared__ __attribute__((aligned(16))) bf16 dyt_[NB * DYT_EL];
 
     // 512 threads in two roles -- waves 0-3 multiply (wave w: input channels 16 w ..), waves 4-7 fetch and stage the next tile; each SIMD
-    // holds one wave of each role, so a tile's ~220 vector instructions of staging (pooled-dy expansion, zero fill, LDS stores, address
-    // arithmetic) and its load waits run BESIDE the MFMAs instead of in front of them in the same wave.  tid = index inside the role.
+    // holds one wave of each role, so a tile's ~120 vector instructions of staging (pooled-dy expansion, bias partials, LDS stores, offsets
+    // and range tests) and its load waits run BESIDE the MFMAs instead of in front of them in the same wave.  tid = index inside the role.
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const bool producer = threadIdx.x >= 256;
     const int cs = blockIdx.y % (CIN / 64), ch = blockIdx.y / (CIN / 64);
     const int H = a.H, W = a.W;
 
     // one tile's fetch, in registers between request and staging (TWO of them are kept in flight)
+    // BUF (every tensor of the launch below 4 GB: the launcher's test): the fetch is BUFFER loads through one descriptor per tensor over exactly
+    // its bytes, and a chunk outside the image -- left, right, top, bottom (columns -1 and W lie INSIDE the tensor's bytes: the range test stays),
+    // the rows behind a ragged last tile, a tile past the end of the walk -- carries an offset past the descriptor's end: the hardware returns
+    // zeros and the staging stores what arrived.  Without BUF the chunk is read at a clamped address and zeroed by selects at staging time
+    // (okp / okd: one bit per chunk).
     struct Stage { bf16x8 pr[NPCH], dr[NDCH]; uint2 pcode; unsigned okp, okd; };
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    constexpr unsigned OOB = 0xFFFFFFF0u;
+    const unsigned dy_el = (unsigned)a.B * (POOLED ? (H / 2) * (W / 2) : H * W) * COUT;          // dy as it is stored (used with BUF only)
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.in), 0, (unsigned)a.B * H * W * CIN * 2u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(POOLED ? a.dy_pooled : a.dy), 0, dy_el * 2u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rcd = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.pool_idx), 0, POOLED ? dy_el : 0u, 0x00020000);
     // Per-thread constants of the tile fetch: chunk i of the patch is pixel (ppi, ppj) relative to the tile origin (t0, d0) and sits prel
     // elements behind that pixel's address; per tile only the origin (wave-uniform: scalar ALU) and two range tests per chunk remain.  (With
     // the divisions, 64-bit multiplies and selects of the first version the fetch cost ~200 vector instructions per tile, which a lone
@@ -1512,6 +1540,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     int wt = blockIdx.x, wx = wt % tiles_x, wy = (wt / tiles_x) % tiles_y, wb = wt / (tiles_x * tiles_y);
     const int sx = nwg % tiles_x, sy = (nwg / tiles_x) % tiles_y, sb = nwg / (tiles_x * tiles_y);
     const int lx = (ntiles - 1) % tiles_x, ly = ((ntiles - 1) / tiles_x) % tiles_y, lb = (ntiles - 1) / (tiles_x * tiles_y);
+    auto bld8 = [](__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); };
     auto load_tile = [&](Stage& S, int tile) {
         (void)tile;                                                     // (== wt: callers walk first, first + nwg, ... in order)
         const bool past = wt >= ntiles;
@@ -1520,32 +1549,40 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
         { const int c = wx >= tiles_x; wx -= c ? tiles_x : 0; wy += sy + c; }
         { const int c = wy >= tiles_y; wy -= c ? tiles_y : 0; wb += sb + c; }
         const int t0 = ty * W2_TH, d0 = tx * W2_TW;
-        const bf16* in_o = a.in + (((long)b * H + t0) * W + d0) * CIN + cs * 64;             // the tile's origin pixel (always inside the map)
+        const int t0r = BUF && past ? 1 << 28 : t0;                     // BUF: a tile past the end of the walk lies outside the image as a whole
+        const long xo = (((long)b * H + t0) * W + d0) * CIN + cs * 64;  // the tile's origin pixel (always inside the map)
         S.okp = 0; S.okd = 0;
 #pragma unroll
         for (int i = 0; i < NPCH; ++i) {
-            const bool ok = (unsigned)(t0 + ppi[i]) < (unsigned)H && (unsigned)(d0 + ppj[i]) < (unsigned)W;
-            if (ok) S.okp |= 1u << i;
-            S.pr[i] = ld8(in_o + (ok ? prel[i] : (tid & 7) * 8));
+            const bool ok = (unsigned)(t0r + ppi[i]) < (unsigned)H && (unsigned)(d0 + ppj[i]) < (unsigned)W;
+            if constexpr (BUF) S.pr[i] = bld8(rin, ok ? ((unsigned)xo + (unsigned)prel[i]) * 2u : OOB);
+            else { if (ok) S.okp |= 1u << i; S.pr[i] = ld8(a.in + xo + (ok ? prel[i] : (tid & 7) * 8)); }
         }
         if constexpr (POOLED) {
-            const int t2 = t0 / 2 + pp_r, d2 = d0 / 2 + pp_c;
+            const int t2 = t0r / 2 + pp_r, d2 = d0 / 2 + pp_c;
             const bool ok = t2 < H2 && d2 < W2p;                            // (floor mode: the cropped last row / column gets no gradient)
-            if (ok) S.okd = 1u;
-            // (origin cell of the tile: inside the pooled map unless the map's last row / column is the cropped one -- then ok is false for
-            // every cell of the tile and the clamped origin is read)
-            const int t2o = t0 / 2 < H2 ? t0 / 2 : H2 - 1, d2o = d0 / 2 < W2p ? d0 / 2 : W2p - 1;
-            const long po = (((long)b * H2 + t2o) * W2p + d2o) * COUT + ch * 64;
-            const int rel = ok ? pprel : (tid & 7) * 8;
-            S.dr[0] = ld8(a.dy_pooled + po + rel);
-            S.pcode = *reinterpret_cast<const uint2*>(a.pool_idx + po + rel);
+            if constexpr (BUF) {
+                // (one element offset for both streams: 0x7FFFFFF8 is past the codes' end and, as bytes, past the gradient's)
+                const unsigned e = ok ? (unsigned)((((long)b * H2 + t0 / 2) * W2p + d0 / 2) * COUT + ch * 64) + (unsigned)pprel : OOB / 2u;
+                S.dr[0] = bld8(rdy, e * 2u);
+                S.pcode = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rcd, e, 0, 0));
+            } else {
+                if (ok) S.okd = 1u;
+                // (origin cell of the tile: inside the pooled map unless the map's last row / column is the cropped one -- then ok is false for
+                // every cell of the tile and the clamped origin is read)
+                const int t2o = t0 / 2 < H2 ? t0 / 2 : H2 - 1, d2o = d0 / 2 < W2p ? d0 / 2 : W2p - 1;
+                const long po = (((long)b * H2 + t2o) * W2p + d2o) * COUT + ch * 64;
+                const int rel = ok ? pprel : (tid & 7) * 8;
+                S.dr[0] = ld8(a.dy_pooled + po + rel);
+                S.pcode = *reinterpret_cast<const uint2*>(a.pool_idx + po + rel);
+            }
         } else {
-            const bf16* dy_o = a.dy + (((long)b * H + t0) * W + d0) * COUT + ch * 64;
+            const long yo = (((long)b * H + t0) * W + d0) * COUT + ch * 64;
 #pragma unroll
             for (int i = 0; i < NDCH; ++i) {
-                const bool ok = t0 + dpi[i] < H && d0 + dpj[i] < W;
-                if (ok) S.okd |= 1u << i;
-                S.dr[i] = ld8(dy_o + (ok ? drel[i] : (tid & 7) * 8));
+                const bool ok = t0r + dpi[i] < H && d0 + dpj[i] < W;
+                if constexpr (BUF) S.dr[i] = bld8(rdy, ok ? ((unsigned)yo + (unsigned)drel[i]) * 2u : OOB);
+                else { if (ok) S.okd |= 1u << i; S.dr[i] = ld8(a.dy + yo + (ok ? drel[i] : (tid & 7) * 8)); }
             }
         }
     };
@@ -1557,26 +1594,25 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
 #pragma unroll
         for (int i = 0; i < NPCH; ++i) {
             const int c = tid + i * 256;
-            if (c < W2_PH * W2_PW * 8) st8(patch + (c >> 3) * W2_PS + (c & 7) * 8, (S.okp >> i) & 1 ? S.pr[i] : zero8());
+            if (c < W2_PH * W2_PW * 8) st8(patch + (c >> 3) * W2_PS + (c & 7) * 8, BUF || ((S.okp >> i) & 1) ? S.pr[i] : zero8());
         }
         if constexpr (POOLED) {
+            // the four window positions of the cell on packed dwords (unpool_expand); their OR is the gradient where a code is 0..3 and +0 where
+            // it is 4 -- what the bias partial adds
             const int pp = tid >> 3, pr2 = pp / (W2_TW / 2), pc2 = pp % (W2_TW / 2);
-            bf16x8 o[4];
+            u32x4 o[4];
+            unpool_expand(__builtin_bit_cast(u32x4, BUF || S.okd ? S.dr[0] : zero8()), S.pcode, o);
+            const bf16x8 v = __builtin_bit_cast(bf16x8, o[0] | o[1] | o[2] | o[3]);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned cj = ((j < 4 ? S.pcode.x : S.pcode.y) >> (8 * (j & 3))) & 0xffu;
-                const bf16 gj = S.okd ? S.dr[0][j] : (bf16)0.f;
+            for (int j = 0; j < 8; ++j) csum[j] = fmaf(dbm, (float)v[j], csum[j]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) o[k][j] = cj == (unsigned)k ? gj : (bf16)0.f;
-                csum[j] = fmaf(dbm, cj < 4u ? (float)gj : 0.f, csum[j]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) st8(dyt + ((2 * pr2 + (k >> 1)) * W2_TW + 2 * pc2 + (k & 1)) * W2_LDY + (tid & 7) * 8, o[k]);
+            for (int k = 0; k < 4; ++k)
+                st8(dyt + ((2 * pr2 + (k >> 1)) * W2_TW + 2 * pc2 + (k & 1)) * W2_LDY + (tid & 7) * 8, __builtin_bit_cast(bf16x8, o[k]));
         } else {
 #pragma unroll
         for (int i = 0; i < NDCH; ++i) {
             const int c = tid + i * 256;
-            const bf16x8 v = (S.okd >> i) & 1 ? S.dr[i] : zero8();
+            const bf16x8 v = BUF || ((S.okd >> i) & 1) ? S.dr[i] : zero8();
             st8(dyt + (c >> 3) * W2_LDY + (c & 7) * 8, v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) csum[j] = fmaf(dbm, (float)v[j], csum[j]);
@@ -1585,8 +1621,9 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     };
 
     // wave w owns input channels 16w .. 16w+15 x all 64 output channels x 9 taps: the four dy fragments of a pixel slab are
-    // tap-independent (read once per slab), only ONE x fragment is read per tap: 26 transposing reads per 36 MFMAs
-    // (the 2 x 2 wave grid needed 40)
+    // tap-independent (read once per slab) and every HALF of an x fragment is read once per tile (the fragments of neighbouring taps and
+    // slabs overlap by a half): 62 transposing reads per 144 MFMAs on the 16-wide tile, 83 on the 8-wide one (whole fragments per tap: 104;
+    // the 2 x 2 wave grid needed 160)
     typedef __attribute__((address_space(3))) bf16x4 lds_b4;
     const int g = lane >> 4, q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
     const float dbm1 = do_db ? 1.f : 0.f;
@@ -1602,20 +1639,14 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
             af[fm][4] = hi[0]; af[fm][5] = hi[1]; af[fm][6] = hi[2]; af[fm][7] = hi[3];
         }
     };
-    auto read_b = [&](const bf16* patch, int kc, int tap) {
-        const int dyi = tap / 3, dxj = tap % 3;
-        const int pi = 4 * g + q;                               // pixel of the slab's first half this lane addresses
-        const bf16* b0 = patch + ((RPS * kc + pi / W2_TW + dyi) * W2_PW + pi % W2_TW + dxj) * W2_PS + wave * 16 + p4;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)b0);
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(b0 + (16 / W2_TW) * W2_PW * W2_PS));
-        bf16x8 bfr;
-        bfr[0] = lo[0]; bfr[1] = lo[1]; bfr[2] = lo[2]; bfr[3] = lo[3];
-        bfr[4] = hi[0]; bfr[5] = hi[1]; bfr[6] = hi[2]; bfr[7] = hi[3];
-        return bfr;
+    // Half-fragment rho of the x operand at column shift dxj: 16 pixels x this wave's 16 channels (two VGPRs).  Step (slab kc, tap (dyi, dxj))
+    // multiplies the halves rho = RPS kc + dyi (K slots 0-3) and rho + W2_HD (K slots 4-7): on the 16-wide tile half rho is patch row rho, on the
+    // 8-wide one the row pair {rho, rho + 1}.
+    // hb: the lane's element of half 0 at shift 0 (pixel 4 g + q of the half) -- every half is that address plus a constant, the read's offset field
+    const int hb = (((4 * g + q) / W2_TW) * W2_PW + (4 * g + q) % W2_TW) * W2_PS + wave * 16 + p4;
+    auto read_h = [&](const bf16* patch_hb, int rho, int dxj) {
+        return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(patch_hb + (rho * W2_PW + dxj) * W2_PS));
     };
-    // wave w owns input channels 16w .. 16w+15 x all 64 output channels x 9 taps: the four dy fragments of a pixel slab are
-    // tap-independent (read once per slab), only ONE x fragment is read per tap: 26 transposing reads per 36 MFMAs
-    // (the 2 x 2 wave grid needed 40)
     // The partial slab is written in REGISTER order -- element ((tap * 4 + fm) * 256 + thread) * 4 + r of this (64-ci, 64-co) block's 36 864 --
     // 36 sixteen-byte stores per lane, a kilobyte per wave-instruction (in [co][tap][ci] order the same 147 KB left as 144 dword stores per
     // lane in 64-byte pieces, at the end of the launch with every CU storing at once); conv3x3_wgrad_reduce_body un-permutes (folds.h)
@@ -1672,30 +1703,41 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
                 for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
             __syncthreads();
             for (int it = 0; it < niter; ++it) {
-                const bf16* patch = patch_ + (it & 1) * PATCH_EL;
+                const bf16* patch = patch_ + (it & 1) * PATCH_EL + hb;
                 const bf16* dyt = dyt_ + (it & 1) * DYT_EL;
                 // 36 steps (4 pixel slabs x 9 taps) of one x fragment x four dy fragments.  One wave per SIMD multiplies, so nobody else
-                // covers the LDS latency: the x fragments run THREE steps ahead through a ring of four (one step = 4 MFMAs = 64 cycles; at
-                // one step ahead every tap waited ~a step for its fragment), the dy fragments of the next slab arrive during tap 4.
-                // The order is pinned (left alone the scheduler folds the ring into read-and-use-at-once).
-                bf16x8 af[2][4], br[4];
+                // covers the LDS latency: the x halves arrive THREE steps ahead of the first step that multiplies them (one step = 4 MFMAs =
+                // 64 cycles; at one step ahead every tap waited ~a step for its fragment) and stay in registers until the last one has (hw:
+                // a window of at most W2_NHALF halves per column shift, restarted with every tile -- tiles alternate LDS buffers), the dy
+                // fragments of the next slab arrive during tap 4.  The order is pinned (left alone the scheduler folds the read-ahead into
+                // read-and-use-at-once).
+                bf16x8 af[2][4];
+                bf16x4 hw[W2_NHALF][3];
                 read_a(dyt, 0, af[0]);
-#pragma unroll
-                for (int t = 0; t < 3; ++t) br[t] = read_b(patch, 0, t);
-                __builtin_amdgcn_sched_group_barrier(0x100, 14, 0);
+                // the halves step s_ is the first to multiply (w2_first_use: step group s_ / 3 = 3 kc + dyi)
+#define CW_READ(s_)                                                                                                                  \
+                {                                                                                                                    \
+                    constexpr int sr_ = (s_) < 36 ? (s_) : 0, rho_ = RPS * (sr_ / 9) + (sr_ % 9) / 3, dx_ = sr_ % 3;                   \
+                    if constexpr ((s_) < 36 && w2_first_use(rho_, RPS, W2_HD) == sr_ / 3) hw[rho_][dx_] = read_h(patch, rho_, dx_);   \
+                    if constexpr ((s_) < 36 && w2_first_use(rho_ + W2_HD, RPS, W2_HD) == sr_ / 3) hw[rho_ + W2_HD][dx_] = read_h(patch, rho_ + W2_HD, dx_); \
+                }
+                CW_READ(0) CW_READ(1) CW_READ(2)
+                __builtin_amdgcn_sched_group_barrier(0x100, 8 + w2_nread(0, RPS, W2_HD) + w2_nread(1, RPS, W2_HD) + w2_nread(2, RPS, W2_HD), 0);
 #define CW_STEP(s_)                                                                                                                  \
                 {                                                                                                                    \
-                    constexpr int kc_ = (s_) / 9, tap_ = (s_) % 9;                                                                   \
-                    if ((s_) + 3 < 36) br[((s_) + 3) & 3] = read_b(patch, ((s_) + 3) / 9, ((s_) + 3) % 9);                              \
+                    constexpr int kc_ = (s_) / 9, tap_ = (s_) % 9, rho_ = RPS * kc_ + tap_ / 3;                                       \
+                    CW_READ((s_) + 3)                                                                                                \
                     if (tap_ == 4 && kc_ < 3) read_a(dyt, kc_ + 1, af[(kc_ + 1) & 1]);                                                \
-                    _Pragma("unroll") for (int fm = 0; fm < 4; ++fm) acc[tap_][fm] = mma16(af[kc_ & 1][fm], br[(s_) & 3], acc[tap_][fm]); \
-                    __builtin_amdgcn_sched_group_barrier(0x100, ((s_) + 3 < 36 ? 2 : 0) + (tap_ == 4 && kc_ < 3 ? 8 : 0), 0);         \
+                    const bf16x8 bf_ = __builtin_shufflevector(hw[rho_][tap_ % 3], hw[rho_ + W2_HD][tap_ % 3], 0, 1, 2, 3, 4, 5, 6, 7); \
+                    _Pragma("unroll") for (int fm = 0; fm < 4; ++fm) acc[tap_][fm] = mma16(af[kc_ & 1][fm], bf_, acc[tap_][fm]);     \
+                    __builtin_amdgcn_sched_group_barrier(0x100, w2_nread((s_) + 3, RPS, W2_HD) + (tap_ == 4 && kc_ < 3 ? 8 : 0), 0);   \
                     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                               \
                 }
                 CW_STEP(0) CW_STEP(1) CW_STEP(2) CW_STEP(3) CW_STEP(4) CW_STEP(5) CW_STEP(6) CW_STEP(7) CW_STEP(8)
                 CW_STEP(9) CW_STEP(10) CW_STEP(11) CW_STEP(12) CW_STEP(13) CW_STEP(14) CW_STEP(15) CW_STEP(16) CW_STEP(17)
                 CW_STEP(18) CW_STEP(19) CW_STEP(20) CW_STEP(21) CW_STEP(22) CW_STEP(23) CW_STEP(24) CW_STEP(25) CW_STEP(26)
                 CW_STEP(27) CW_STEP(28) CW_STEP(29) CW_STEP(30) CW_STEP(31) CW_STEP(32) CW_STEP(33) CW_STEP(34) CW_STEP(35)
+#undef CW_READ
 #undef CW_STEP
                 __syncthreads();
             }
@@ -2031,10 +2073,18 @@ int mk_conv3x3_wgrad(const ConvWgradArgs& a, hipStream_t s, int phase) {
     const Wgrad2Grid wg = wgrad2_grid(a);
     const int tw = wg.tw, tiles_x = wg.tiles_x, tiles_y = wg.tiles_y, ntiles = wg.ntiles, nwg = wg.nwg;
     const dim3 grid(nwg, (a.CIN / 64) * (a.COUT / 64));
+    // the staging fetches through 4 GB buffer descriptors (one per tensor); a larger tensor takes the instance with plain loads and zero selects
+    const long px = (long)a.B * a.H * a.W;
+    const bool buf = px * (a.CIN > a.COUT ? a.CIN : a.COUT) * 2 < (1L << 32) - 65536;
+#define W2T(CI, CO, TW_, PL)                                                                                                            \
+    do {                                                                                                                                \
+        if (buf) hipLaunchKernelGGL((conv3x3_wgrad2_kernel<CI, CO, TW_, PL, true>), grid, dim3(512), 0, s, a, nwg, ntiles, tiles_x, tiles_y);  \
+        else hipLaunchKernelGGL((conv3x3_wgrad2_kernel<CI, CO, TW_, PL, false>), grid, dim3(512), 0, s, a, nwg, ntiles, tiles_x, tiles_y);     \
+    } while (0)
 #define W2(CI, CO, PL)                                                                                                                  \
     do {                                                                                                                                \
-        if (tw == 8) hipLaunchKernelGGL((conv3x3_wgrad2_kernel<CI, CO, 8, PL>), grid, dim3(512), 0, s, a, nwg, ntiles, tiles_x, tiles_y);  \
-        else hipLaunchKernelGGL((conv3x3_wgrad2_kernel<CI, CO, 16, PL>), grid, dim3(512), 0, s, a, nwg, ntiles, tiles_x, tiles_y);         \
+        if (tw == 8) W2T(CI, CO, 8, PL);                                                                                                \
+        else W2T(CI, CO, 16, PL);                                                                                                       \
     } while (0)
     const bool pooled = a.dy_pooled && a.pool_idx;
     if (!pooled && !a.dy) { mk_set_error("mk_conv3x3_wgrad", "dy missing"); return -1; }
@@ -2049,6 +2099,7 @@ int mk_conv3x3_wgrad(const ConvWgradArgs& a, hipStream_t s, int phase) {
     else if (a.CIN == 256 && a.COUT == 256) W2(256, 256, false);
     else { mk_set_error("mk_conv3x3_wgrad", "unsupported channel counts"); return -1; }
 #undef W2
+#undef W2T
     const int n = a.COUT * 9 * a.CIN + a.COUT;
     if (phase != 1) hipLaunchKernelGGL(conv3x3_wgrad_reduce, dim3((n + 63) / 64), dim3(256), 0, s, a.slab, nwg, a.dw, a.db, a.CIN, a.COUT);
     return hipGetLastError() == hipSuccess ? 0 : -1;
