@@ -688,6 +688,41 @@ int masr_recog_rescore_bias(masr_model* m, const masr_lm* lm, const masr_bias* b
                             float lm_w, float len_bonus, float bias_w, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
                             float* att, float* ctc, int32_t* order, void* stream);
 
+/* Contextual phrase biasing of the attention beam and the joint beam.  A hypothesis of these searches is one token sequence on one
+ * path (prefixes are never merged), so each live row carries the state (u, n) of its hypothesis, starting at (root, 0).  For a hypothesis h of
+ * st - 1 tokens in state (u, n) and a class c at step st:
+ *     (u', n') = the state behind token c (above; classes 0 and eos have no child, so they yield (root, n - revoke(u)))
+ *     dn(h, c) = n' - n, an integer in [-63, 1];  if c != eos and st >= maxlen: dn -= revoke(u')   (the hypothesis ends as it is at this step)
+ *     b(h, c)  = fl(bias_w * (float)dn(h, c))                                                       (one rounding)
+ * The credit is provisional: a half-matched phrase is already boosted, a broken match gives its unearned tokens back, and so does the end of the
+ * hypothesis (eos or maxlen).  lm may be NULL in both entries (lm_w is then ignored).
+ * masr_recog_beam_bias is masr_recog_beam_lm with the row increment g(c) = fl(f(c) + b(h, c)); f is that entry's fused increment, or lp(c)
+ * without an LM.  A row's list is its K best by (g descending, class ascending), eos skipped below minlen; a candidate scores fl(s(h) + g(c)); the
+ * merge, the ended / running bookkeeping and the result layout are masr_recog_beam's.  Stop: nothing runs, st >= maxlen, or best_ended >=
+ * fl(run_best + fl((float)(maxlen - st) * bias_w)) -- a running hypothesis gains at most bias_w per further token and every other term is <= 0.
+ * nbias int32 [B] (device) = n_final of the returned hypothesis.  At bias_w = 0 with an LM tokens and scores equal masr_recog_beam_lm's at the
+ * same lm_w bit for bit; with lm NULL they equal masr_recog_beam's except where rounding ties the lp of two different logits of one row: the
+ * plain beam ranks a row by the logit, this one by lp (class ascending among equal lp), as masr_recog_beam_lm does at lm_w = 0.  The step graph
+ * is keyed on the LM, lm_w, the list and bias_w.
+ * masr_recog_beam_ctc_bias is masr_recog_beam_ctc_lm with these differences: the pre-beam ranks the P candidates by g(c) as above (so a phrase
+ * token is rescued into the pre-beam); the score is that entry's five-rounding sum followed by + b(h, c) as a sixth rounding (with lm NULL the LM
+ * term is the constant +0.f, added in the same place); the stop bound is fl(run_best + fl((float)(maxlen - st) * fl(max(len_bonus, 0) + bias_w))).
+ * nbias int32 [B][N], -1 in an empty slot.  bias_w is a device value next to the four weights: the graph is keyed on the LM, N and the list, and
+ * a call with another bias_w replays it and never an old value.  At bias_w = 0 with an LM the result equals masr_recog_beam_ctc_lm's bit for bit.
+ * -1 with a message, before any launch, outputs unwritten: everything masr_recog_beam_lm / masr_recog_beam_ctc_lm refuse except a null LM, a null
+ * list, a list whose C is not the model's odim, bias_w negative or not finite, a null nbias; -2: a workspace below
+ * masr_beam_bias_workspace_bytes(B, T, K, Lmax) = masr_beam_lm_workspace_bytes plus the states [2][B*K] (8 bytes each), or below
+ * masr_beam_ctc_bias_workspace_bytes(B, T, K, N, Lmax) = masr_beam_ctc_lm_workspace_bytes plus the states and the bias terms [B*K][P] (each
+ * entry rounded up to 256 bytes).  The LSTM-LM beams (masr_recog_beam_nlm, masr_recog_beam_ctc_nlm, masr_recog_ctc_beam_nlm) have no biasing. */
+int64_t masr_beam_bias_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax);
+int masr_recog_beam_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K,
+                         float min_step_ratio, float max_step_ratio, float lm_w, float bias_w, int32_t* tokens, int32_t* lens, float* scores,
+                         int32_t* nbias, void* stream);
+int64_t masr_beam_ctc_bias_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax);
+int masr_recog_beam_ctc_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K, int N,
+                             float min_step_ratio, float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, float bias_w,
+                             int32_t* tokens, int32_t* lens, float* scores, int32_t* nbias, void* stream);
+
 /* CTC forced alignment: the single best alignment (Viterbi path) of a known transcript to the frames of a CTC output layer, model-free like
  * masr_ctc_loss and masr_ctc_beam_search.  logits and enc_lens as for masr_ctc_beam_search (row of utterance b, frame t at
  * logits + (b * Tp + t) * ld, ld >= C; enc_lens device int32 [B], each clamped to [0, Tp]; frames past it and columns >= C are never read);

@@ -242,6 +242,28 @@ int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t
                                 int32_t* fin, float* nb_score, int32_t* nb_len, int32_t* nb_row, int32_t* tok_hist_row, int32_t* par_hist_row,
                                 int32_t* step_out, void* stream);
 
+/* ---- the phrase-biased step kernels alone (tests/test_hip_bias_beam_kernels.py).  All arrays on the device; each entry synchronises
+ * the stream.
+ * the biased row stage (beam_rows_kernel<Lm, PRE, true>) at step t on masr_test_beam_lm_topk's inputs (lm may be NULL: f = lp; C = the list's
+ * classes) plus maxlen int32 [B] and state_in int32 [R][2] = (node, credited tokens) of every row's PARENT row at step t - 1 (indexed by the parent
+ * row as par_hist names it; null at t = 1; a node outside the trie is refused).  Out: state_out int32 [R][2], the state of every live row's
+ * hypothesis (dead rows: zero).  pre_tok null: the top-K form, list_tok int32 / list_score fp32 [R][K].  pre_tok given: the pre-beam form, pre_tok
+ * int32 / pre_lp / pre_lm / pre_b fp32 [R][P], P = floor(3K/2); lm_w and bias_w are then read from the device as the decode reads them. */
+int masr_test_beam_bias_rows(const masr_lm* lm, const masr_bias* bias, float lm_w, float bias_w, int B, int K, int t, const int32_t* minlen,
+                             const int32_t* maxlen, const float* logits, int64_t ld, const float* score, const int32_t* tok_hist, const int32_t* par_hist,
+                             const int32_t* state_in, int32_t* state_out, int32_t* list_tok, float* list_score, int32_t* pre_tok, float* pre_lp,
+                             float* pre_lm, float* pre_b, void* stream);
+/* one step t of the attention beam's select with the stop bound of bias_w (beam_select_kernel<false, true>) on caller-given sorted row lists
+ * list_tok / list_score [B*K][K]; sos 0, eos = C - 1; the other arguments as masr_test_beam_step's */
+int masr_test_beam_select_bias(int B, int K, int C, int t, const int32_t* maxlen, float bias_w, const int32_t* list_tok, const float* list_score,
+                               float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* tok_hist_row,
+                               int32_t* par_hist_row, int32_t* step_out, void* stream);
+/* masr_test_beam_select_nbest through beam_select_nbest_kernel<true>: the stop bound allows fl(max(len_bonus, 0) + bias_w) per further token */
+int masr_test_beam_select_nbest_bias(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, float bias_w, const int32_t* list_tok,
+                                     const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,
+                                     int32_t* fin, float* nb_score, int32_t* nb_len, int32_t* nb_row, int32_t* tok_hist_row, int32_t* par_hist_row,
+                                     int32_t* step_out, void* stream);
+
 /* ---- the BLSTM path's LSTM kernels alone (lstm.hip, lstm_rec.hip; tests/test_hip_lstm_kernels.py).  Rows are batch-first (b * T + t), the gate
  * axis is unit-major (row / column u * 4 + g, g in torch's order i, f, g, o), index 0 / 1 = forward / reverse direction, KP = H rounded up to a
  * multiple of 32.  Each entry vets on the host what the kernel would index with, calls the launcher and synchronises the stream.

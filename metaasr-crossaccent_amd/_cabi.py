@@ -87,6 +87,10 @@ _SIGS = {
     "masr_bias_bytes": (i64, [vp]),
     "masr_bias_nodes": (i32, [vp]),
     "masr_recog_ctc_beam_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "masr_beam_bias_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
+    "masr_recog_beam_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
+    "masr_beam_ctc_bias_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32]),
+    "masr_recog_beam_ctc_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
     "masr_recog_rescore_bias": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "masr_beam_lm_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_recog_beam_lm": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
@@ -169,6 +173,9 @@ _SIGS = {
     "masr_test_lm_max_probe": (i32, [vp]),
     "masr_test_bias_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "masr_test_bias_max_probe": (i32, [vp]),
+    "masr_test_beam_bias_rows": (i32, [vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_beam_select_bias": (i32, [i32, i32, i32, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "masr_test_beam_select_nbest_bias": (i32, [i32, i32, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_beam_lm_topk": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_test_joint_lm_prebeam": (i32, [vp, f32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "masr_test_beam_nlm_rows": (i32, [vp, i64, f32, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),

@@ -10,7 +10,8 @@
 //                     row stage of every step beam: an n-gram LM (masr_recog_beam_lm) or a row of LSTM-LM logits
 //                     (masr_recog_beam_nlm) adds its weighted term and the row is ranked by the fused increment; in the joint
 //                     beams it emits the P-long pre-beam for beam_ctc_prefix instead of the K-long list, with either
-//                     LM's term in its ranking
+//                     LM's term in its ranking.  With a phrase list it also advances the row's automaton state and adds the
+//                     phrase term to the increment
 //   beam_select       one wave per utterance: K-way merge of the K sorted row lists -> the K best candidates (score descending,
 //                     parent rank ascending, then the row order above), ended / running bookkeeping, finished flag, step ticket
 // beam_backtrace runs once after the last step.
@@ -21,6 +22,8 @@
 #include "kernels.h"
 #include "search.h"
 #include "lm.h"
+#include "bias.h"
+#include <type_traits>
 
 namespace {
 
@@ -34,6 +37,10 @@ __global__ void beam_init_kernel(BeamArgs a) {
 // one thread: the joint LM beam's weights, read by its step kernels from the device
 __global__ void beam_set_weights_kernel(float* w, float att_w, float ctc_w, float lm_w, float len_bonus) {
     if (blockIdx.x == 0 && threadIdx.x == 0) { w[0] = att_w; w[1] = ctc_w; w[2] = lm_w; w[3] = len_bonus; }
+}
+// one thread: the biased joint beam's fifth weight, behind the four
+__global__ void beam_set_bias_w_kernel(float* w, float bias_w) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) w[4] = bias_w;
 }
 
 // grid R, 256 threads
@@ -99,6 +106,47 @@ struct RowLmLogits {                                             // a row of LM 
     }
 };
 
+// Contextual phrase biasing of the step beams.  A kernel takes what it needs of the list as RowBias, or, where nothing is biased,
+// the empty NoBias -- the unbiased instantiations keep the argument list and the code they had.
+struct NoBias {};
+struct RowBias {
+    BiasDev dev;
+    int2* state;                                                 // [2][R] (node, credited tokens) of row r's hypothesis, step parity
+    float* pre_b;                                                // [R][P] beside pre_lm: b(h, c) of the pre-beam's candidates (joint beam)
+    float bias_w;                                                // the top-K's weight (its step graph is keyed on it); the pre-beam reads a.wts[4]
+};
+template <bool BIAS, class T = RowBias> using bias_arg = std::conditional_t<BIAS, T, NoBias>;
+
+// Once per row: lane 0 takes the state of the row's parent (the other parity; the root at step 1) over the row's last token and stores it in
+// this step's parity; the wave gets the node.  A hypothesis of these beams is one token sequence on one path, so its state follows the
+// re-parenting as the LSTM LM's does.  A node outside the trie (only a caller of the test entry could set one) reads as the root
+__device__ __forceinline__ int row_bias_state(const BeamArgs& a, const RowBias& b, int r, int st, int lane) {
+    int u = 0;
+    if (lane == 0) {
+        int n = 0;
+        if (st > 1) {
+            const HistEntry h = hist_entry(a.tok_hist, a.par_hist, a.R, st - 1, r, a.C, a.K, a.sos);
+            const int2 p = b.state[(long)((st - 1) & 1) * a.R + h.par];
+            u = p.x < 0 || p.x >= b.dev.nodes ? 0 : p.x; n = p.y;
+            bias_step(b.dev, u, n, h.tok);
+        }
+        b.state[(long)(st & 1) * a.R + r] = make_int2(u, n);
+    }
+    return __shfl(u, 0, 64);
+}
+// dn(h, c) = n' - n of bias_step from node u (rv = revoke[u]) over class c, in [-63, 1]: at most two probes.  ends: the hypothesis h + c ends as
+// it is (a token at the last step), so what the new node has not earned is given back as well
+__device__ __forceinline__ int row_bias_dn(const BiasDev& d, int u, int rv, int c, bool ends) {
+    int v = bias_child(d, u, c), dn = 1;
+    if (v < 0) {
+        dn = -rv;
+        v = u != 0 ? bias_child(d, 0, c) : -1;
+        if (v >= 0) dn += 1; else v = 0;
+    }
+    if (ends) dn -= (int)d.revoke[v];
+    return dn;
+}
+
 // grid ceil(R / 4), 256 threads: one wave per live row r (hypothesis h of st - 1 tokens, score ps).  lp(c) = (z_c - mx) - log_s of row_lse.
 // With an LM the lanes stride over the C classes and store the fused increment f(c) = fl(lp(c) + fl(lm_w * lm(c | h))) -- two roundings,
 // the one statement every LM-fused step beam composes it by -- to the row of the fp32 workspace fused [R][ldf]; the same wave reads it back
@@ -110,9 +158,12 @@ struct RowLmLogits {                                             // a row of LM 
 //                       entries: pre_lp = lp(c) and, with an LM, pre_lm = fl(lm_w * lm(c | h)), each computed again from its inputs (the
 //                       same expressions: the same bits), so no second [R][Cp] row is kept.  A dead row is left alone (the prefix kernel
 //                       gives it its empty list).  lm_w is a.wts[2]: no graph holds a weight of the joint LM beam
-template <class Lm, bool PRE>
+// BIAS: the row's automaton state is advanced once (row_bias_state), and the increment the row is ranked by becomes
+// g(c) = fl(f(c) + b(h, c)), b = fl(bias_w * (float)dn(h, c)), f = lp without an LM -- the fused row is then needed without an LM too, and a
+// row without one ranks by lp, not by the logit.  The pre-beam also leaves pre_b = b(h, c), and without an LM pre_lm = +0
+template <class Lm, bool PRE, bool BIAS>
 __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a, Lm lm, float lm_w_arg, const float* __restrict__ logits, long ld,
-                                                       float* __restrict__ fused, long ldf) {
+                                                       float* __restrict__ fused, long ldf, bias_arg<BIAS> bias) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.R) return;
     const int u = r / a.K, st = *a.step;
@@ -131,10 +182,21 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a, Lm lm, float
     auto skip = [&](int c) { return (PRE && c == 0) || (no_eos && c == a.eos); };
     const float* rank = z;
     float lm_w = 0.f;
-    if constexpr (Lm::FUSED) {
-        lm_w = PRE ? a.wts[2] : lm_w_arg;
+    if constexpr (Lm::FUSED) lm_w = PRE ? a.wts[2] : lm_w_arg;
+    auto f = [&](int c) { if constexpr (Lm::FUSED) return add_rn(lp(c), mul_rn(lm_w, term(c))); else return lp(c); };
+    int bu = 0, brv = 0; float bias_w = 0.f; bool last = false;
+    if constexpr (BIAS) {
+        bu = row_bias_state(a, bias, r, st, lane);
+        brv = (int)bias.dev.revoke[bu];
+        bias_w = PRE ? a.wts[4] : bias.bias_w;
+        last = st >= a.maxlen[u];
+    }
+    auto b = [&](int c) {                                        // (BIAS only)
+        if constexpr (BIAS) return mul_rn(bias_w, (float)row_bias_dn(bias.dev, bu, brv, c, last && c != a.eos)); else return 0.f;
+    };
+    if constexpr (Lm::FUSED || BIAS) {
         float* fz = fused + (long)r * ldf;
-        for (int c = lane; c < a.C; c += 64) fz[c] = add_rn(lp(c), mul_rn(lm_w, term(c)));
+        for (int c = lane; c < a.C; c += 64) { if constexpr (BIAS) fz[c] = add_rn(f(c), b(c)); else fz[c] = f(c); }
         __threadfence_block();                                   // lane 0 reads below what the other lanes of its wave stored
         rank = fz;
     }
@@ -147,12 +209,14 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(BeamArgs a, Lm lm, float
             const bool ok = c > 0 && c < a.C;
             a.pre_lp[(long)r * a.P + i] = ok ? lp(c) : NEG_INF;
             if constexpr (Lm::FUSED) a.pre_lm[(long)r * a.P + i] = ok ? mul_rn(lm_w, term(c)) : 0.f;
+            else if constexpr (BIAS) a.pre_lm[(long)r * a.P + i] = 0.f;
+            if constexpr (BIAS) bias.pre_b[(long)r * a.P + i] = ok ? b(c) : 0.f;
         }
     } else {
         int* lt = a.list_tok + (long)r * a.K;
         float* ls = a.list_score + (long)r * a.K;
         row_top_n<false>(rank, a.C, a.K, lane, skip,
-                         [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + (Lm::FUSED ? rank[c] : lp(c)); });
+                         [&](int i, int c) { lt[i] = c; ls[i] = c < 0 ? NEG_INF : ps + (Lm::FUSED || BIAS ? rank[c] : lp(c)); });
     }
 }
 
@@ -191,8 +255,10 @@ __device__ __forceinline__ int beam_merge_lists(const BeamArgs& a, int r0, int l
 
 // grid B, 64 threads (one wave).  JOINT (masr_recog_beam_ctc): the row lists are P long, sorted by joint score, and a kept candidate also
 // takes its prefix score and the place of its CTC state
-template <bool JOINT>
-__global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
+// BIAS: a running hypothesis can still gain bias_w per further token, so the stop compares with the bound
+// fl(run_best + fl((float)(maxlen - st) * bias_w))
+template <bool JOINT, bool BIAS>
+__global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a, bias_arg<BIAS, float> bias_w) {
     __shared__ float s_score[64];
     __shared__ int s_tok[64], s_par[64];
     __shared__ float s_psi[JOINT ? 64 : 1];
@@ -227,7 +293,8 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
             }
             a.best_score[u] = bs; a.best_len[u] = bl; a.best_row[u] = br;
             // log-probabilities are <= 0: no running hypothesis can overtake an ended one that is at least as good
-            if (j == 0 || st >= maxlen || bs >= run_best) a.fin[u] = 1;
+            if constexpr (BIAS) { if (j == 0 || st >= maxlen || bs >= add_rn(run_best, mul_rn((float)(maxlen - st), bias_w))) a.fin[u] = 1; }
+            else if (j == 0 || st >= maxlen || bs >= run_best) a.fin[u] = 1;
         }
     }
     if (lane == 0) step_ticket(a.step, st, a.B);                 // the last utterance to finish advances the step
@@ -239,7 +306,9 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
 // by rank computation: old entry l moves to l + #{new with a larger score}, new entry e to e + #{old with a score >= its own} -- an old entry
 // ended at an earlier step and wins a tie.  Positions >= N fall off; empty slots (len -1) stay the last.
 // Stop: nothing runs, st >= maxlen, or the list is full and its N-th score >= fl(run_best + fl((maxlen - st) * max(len_bonus, 0))): every
-// other increment is <= 0, so no running hypothesis can still enter the list.
+// other increment is <= 0, so no running hypothesis can still enter the list.  BIAS: the gain per token is at most
+// fl(max(len_bonus, 0) + bias_w), bias_w = a.wts[4].
+template <bool BIAS>
 __global__ __launch_bounds__(64) void beam_select_nbest_kernel(BeamArgs a) {
     __shared__ float s_score[64], s_psi[64];
     __shared__ int s_tok[64], s_par[64], s_slot[64];
@@ -293,7 +362,9 @@ __global__ __launch_bounds__(64) void beam_select_nbest_kernel(BeamArgs a) {
             bool done = nrun == 0 || st >= maxlen;
             if (!done && total == N) {
                 const float run_best = s_score[__ffsll((long long)m_run) - 1];      // the first running candidate: the best one
-                done = s_ms[N - 1] >= add_rn(run_best, mul_rn((float)(maxlen - st), fmaxf(a.wts[3], 0.f)));
+                float gain = fmaxf(a.wts[3], 0.f);
+                if constexpr (BIAS) gain = add_rn(gain, a.wts[4]);
+                done = s_ms[N - 1] >= add_rn(run_best, mul_rn((float)(maxlen - st), gain));
             }
             if (done) a.fin[u] = 1;
         }
@@ -340,10 +411,10 @@ __global__ __launch_bounds__(64) void beam_ctc_init_kernel(BeamArgs a) {
 // (r^n_t, r^b_t) go to ctc_state[st & 1][r][t][i], so a wave's stores at one frame are contiguous.  Then the row's candidates are
 // sorted by (joint score descending, pre-beam position ascending) into list_tok / list_score / list_psi / list_slot.
 // LM (masr_recog_beam_ctc_lm): the same chains; the score takes the weights from a.wts and adds the pre-beam's weighted LM
-// term and, for a token, the length bonus -- five roundings, no multiply-add.
+// term and, for a token, the length bonus -- five roundings, no multiply-add.  BIAS: the pre-beam's b(h, c) is added as a sixth.
 constexpr int CTC_CH = 256;
-template <bool LM>
-__global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
+template <bool LM, bool BIAS>
+__global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a, bias_arg<BIAS, const float*> pre_b) {
     __shared__ float s_phi[CTC_CH], s_rbp[CTC_CH], s_xb[CTC_CH];
     __shared__ unsigned long long s_key[128];
     const int r = blockIdx.x, i = threadIdx.x, u = r / a.K, P = a.P;
@@ -400,6 +471,7 @@ __global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
         if constexpr (LM) {
             js = add_rn(add_rn(ps, mul_rn(a.wts[0], a.pre_lp[lo + i])), mul_rn(a.wts[1], d));
             js = add_rn(add_rn(js, a.pre_lm[lo + i]), c == a.eos ? 0.f : a.wts[3]);
+            if constexpr (BIAS) js = add_rn(js, pre_b[lo + i]);
         } else {
             js = __fadd_rn(__fadd_rn(ps, __fmul_rn(a.att_w, a.pre_lp[lo + i])), __fmul_rn(a.ctc_w, d));
         }
@@ -417,8 +489,18 @@ __global__ __launch_bounds__(128) void beam_ctc_prefix_kernel(BeamArgs a) {
     if (i < P && i >= nv) { a.list_tok[lo + i] = -1; a.list_score[lo + i] = NEG_INF; }
 }
 
-// grid B, 64 threads: tokens [B][Lmax] (-1 past the end), lens [B], scores [B] of the best ended hypothesis
-__global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
+// n_final of the n tokens at out: the automaton run forward from the root (one thread)
+__device__ __forceinline__ int bias_count(const BiasDev& d, const int* out, int n) {
+    int u = 0, cnt = 0;
+    for (int i = 0; i < n; ++i) bias_step(d, u, cnt, out[i]);
+    return bias_final(d, u, cnt);
+}
+struct BackBias { BiasDev dev; int* nbias; };
+
+// grid B, 64 threads: tokens [B][Lmax] (-1 past the end), lens [B], scores [B] of the best ended hypothesis; BIAS: nbias [B] = its n_final
+template <bool BIAS>
+__global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores,
+                                                            bias_arg<BIAS, BackBias> bb) {
     const int u = blockIdx.x;
     const int n = a.best_len[u];
     int* out = tokens + (long)u * a.Lmax;
@@ -431,12 +513,16 @@ __global__ __launch_bounds__(64) void beam_backtrace_kernel(BeamArgs a, int* __r
         }
         lens[u] = n;
         scores[u] = a.best_score[u];
+        if constexpr (BIAS) bb.nbias[u] = bias_count(bb.dev, out, n);
     }
 }
 
 // grid B * N, 64 threads: entry n of utterance u -> tokens [B][N][Lmax] (-1 past the end), lens / scores [B][N]; an empty slot: -1, -inf, all -1
-// and nothing is walked.  The walk stays inside the Lmax history rows and the utterance's K rows whatever the list holds.
-__global__ __launch_bounds__(64) void beam_backtrace_nbest_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores) {
+// and nothing is walked.  The walk stays inside the Lmax history rows and the utterance's K rows whatever the list holds.  BIAS: nbias [B][N] =
+// the entry's n_final, -1 in an empty slot
+template <bool BIAS>
+__global__ __launch_bounds__(64) void beam_backtrace_nbest_kernel(BeamArgs a, int* __restrict__ tokens, int* __restrict__ lens, float* __restrict__ scores,
+                                                                  bias_arg<BIAS, BackBias> bb) {
     const int e = blockIdx.x, u0 = (e / a.N) * a.K;
     const int n = min(a.nb_len[e], a.Lmax);
     int* out = tokens + (long)e * a.Lmax;
@@ -450,6 +536,7 @@ __global__ __launch_bounds__(64) void beam_backtrace_nbest_kernel(BeamArgs a, in
         }
         lens[e] = n < 0 ? -1 : n;
         scores[e] = n < 0 ? NEG_INF : a.nb_score[e];
+        if constexpr (BIAS) bb.nbias[e] = n < 0 ? -1 : bias_count(bb.dev, out, n);
     }
 }
 
@@ -467,19 +554,35 @@ int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, f
     return LAUNCH_OK();
 }
 template <class Lm, bool PRE>
-static int launch_beam_rows(const BeamArgs& a, const Lm& src, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s) {
-    hipLaunchKernelGGL((beam_rows_kernel<Lm, PRE>), dim3((a.R + 3) / 4), dim3(256), 0, s, a, src, lm.lm_w, logits, ld, lm.fused, lm.ldf);
+static int launch_beam_rows(const BeamArgs& a, const Lm& src, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s, const BeamBias* bias) {
+    const dim3 grid((a.R + 3) / 4), block(256);
+    if constexpr (!std::is_same_v<Lm, RowLmLogits>) if (bias) {     // (the LSTM-LM beams are not biased: no such instantiation)
+        const RowBias rb{*bias->dev, bias->state, bias->pre_b, bias->bias_w};
+        hipLaunchKernelGGL((beam_rows_kernel<Lm, PRE, true>), grid, block, 0, s, a, src, lm.lm_w, logits, ld, lm.fused, lm.ldf, rb);
+        return LAUNCH_OK();
+    }
+    hipLaunchKernelGGL((beam_rows_kernel<Lm, PRE, false>), grid, block, 0, s, a, src, lm.lm_w, logits, ld, lm.fused, lm.ldf, NoBias{});
     return LAUNCH_OK();
 }
-int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s) {
+// what the biased kernels of a step need beside the list: C, the state and, in the joint beam, the fifth weight and the bias terms
+static int check_beam_bias(const char* fn, const BeamArgs& a, const BeamBias* bias) {
+    if (!bias) return 0;
+    if (!bias->dev || bias->dev->C != a.C || bias->dev->nodes < 1 || !bias->dev->slots || !bias->dev->revoke) return refuse(fn, "need a phrase list over the beam's classes");
+    if (!bias->state || !a.maxlen) return refuse(fn, "biasing needs the state buffer and maxlen");
+    if (a.P && (!a.N || !a.wts || !a.pre_lm || !bias->pre_b)) return refuse(fn, "the biased pre-beam needs the N-best beam, the weights, the LM terms and the bias terms");
+    return 0;
+}
+int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s, const BeamBias* bias) {
     const char* fn = "mk_beam_rows";
     if (a.K < 1 || a.K > 64 || a.P < 0 || a.P > 96 || ld < a.C) return refuse(fn, "need 1 <= K <= 64, P <= 96, ld >= C");
+    if (check_beam_bias(fn, a, bias)) return -1;
     const bool pre = a.P > 0;
+    if (bias && lm.lm_logits) return refuse(fn, "the LSTM-LM beams are not biased");
+    if ((bias || lm.ngram || lm.lm_logits) && (!lm.fused || lm.ldf < a.C)) return refuse(fn, "an LM or a phrase list needs the fused workspace, ldf >= C");
     if (!lm.ngram && !lm.lm_logits) {
         const RowLmNone src{};
-        return pre ? launch_beam_rows<RowLmNone, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmNone, false>(a, src, lm, logits, ld, s);
+        return pre ? launch_beam_rows<RowLmNone, true>(a, src, lm, logits, ld, s, bias) : launch_beam_rows<RowLmNone, false>(a, src, lm, logits, ld, s, bias);
     }
-    if (!lm.fused || lm.ldf < a.C) return refuse(fn, "an LM needs the fused workspace, ldf >= C");
     if (lm.ngram && lm.lm_logits) return refuse(fn, "one LM at most");
     const bool pre_ok = !pre || (a.wts && a.pre_lm);
     const char* pre_need = "the fused pre-beam needs the weights and the LM terms";
@@ -487,26 +590,36 @@ int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, lo
         if (lm.ld_lm < a.C) return refuse(fn, "need ld_lm >= C");
         if (!pre_ok) return refuse(fn, pre_need);
         const RowLmLogits src{lm.lm_logits, lm.ld_lm};
-        return pre ? launch_beam_rows<RowLmLogits, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmLogits, false>(a, src, lm, logits, ld, s);
+        return pre ? launch_beam_rows<RowLmLogits, true>(a, src, lm, logits, ld, s, nullptr) : launch_beam_rows<RowLmLogits, false>(a, src, lm, logits, ld, s, nullptr);
     }
     if (lm.ngram->order < 1 || lm.ngram->order > LM_MAX_ORDER || lm.ngram->C != a.C) return refuse(fn, "need an LM of order 1 .. 4 over the beam's classes");
     if (!pre_ok) return refuse(fn, pre_need);
     const RowLmNgram src{*lm.ngram};
-    return pre ? launch_beam_rows<RowLmNgram, true>(a, src, lm, logits, ld, s) : launch_beam_rows<RowLmNgram, false>(a, src, lm, logits, ld, s);
+    return pre ? launch_beam_rows<RowLmNgram, true>(a, src, lm, logits, ld, s, bias) : launch_beam_rows<RowLmNgram, false>(a, src, lm, logits, ld, s, bias);
 }
-int mk_beam_select(const BeamArgs& a, hipStream_t s) {
+int mk_beam_select(const BeamArgs& a, hipStream_t s, const BeamBias* bias) {
     if (a.K < 1 || a.K > 64) return refuse("mk_beam_select", "beam size must be in [1, 64]");
     if (a.P < 0 || a.P > 96 || (a.N && !a.P)) return refuse("mk_beam_select", "need P <= 96, and the joint beam (P >= 1) for an N-best list");
     if (a.N && (a.N < 1 || a.N > a.K || !a.wts || !a.nb_score || !a.nb_len || !a.nb_row)) return refuse("mk_beam_select", "need 1 <= N <= K, the weights and the list");
-    if (a.N) hipLaunchKernelGGL(beam_select_nbest_kernel, dim3(a.B), dim3(64), 0, s, a);
-    else if (a.P) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(a.B), dim3(64), 0, s, a);
+    if (bias && a.P && !a.N) return refuse("mk_beam_select", "the biased joint beam is the N-best one");
+    if (bias && !a.N) hipLaunchKernelGGL((beam_select_kernel<false, true>), dim3(a.B), dim3(64), 0, s, a, bias->bias_w);
+    else if (bias) hipLaunchKernelGGL(beam_select_nbest_kernel<true>, dim3(a.B), dim3(64), 0, s, a);
+    else if (a.N) hipLaunchKernelGGL(beam_select_nbest_kernel<false>, dim3(a.B), dim3(64), 0, s, a);
+    else if (a.P) hipLaunchKernelGGL((beam_select_kernel<true, false>), dim3(a.B), dim3(64), 0, s, a, NoBias{});
+    else hipLaunchKernelGGL((beam_select_kernel<false, false>), dim3(a.B), dim3(64), 0, s, a, NoBias{});
     return LAUNCH_OK();
 }
-int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s) {
+int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s, const BiasDev* bias, int* nbias) {
     if (a.N && (a.N < 1 || a.N > a.K || !a.nb_score || !a.nb_len || !a.nb_row)) return refuse("mk_beam_backtrace", "need 1 <= N <= K and the list");
-    if (a.N) hipLaunchKernelGGL(beam_backtrace_nbest_kernel, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores);
-    else hipLaunchKernelGGL(beam_backtrace_kernel, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores);
+    if (bias && !nbias) return refuse("mk_beam_backtrace", "null pointer");
+    if (bias) {
+        const BackBias bb{*bias, nbias};
+        if (a.N) hipLaunchKernelGGL(beam_backtrace_nbest_kernel<true>, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores, bb);
+        else hipLaunchKernelGGL(beam_backtrace_kernel<true>, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores, bb);
+    } else {
+        if (a.N) hipLaunchKernelGGL(beam_backtrace_nbest_kernel<false>, dim3(a.B * a.N), dim3(64), 0, s, a, tokens, lens, scores, NoBias{});
+        else hipLaunchKernelGGL(beam_backtrace_kernel<false>, dim3(a.B), dim3(64), 0, s, a, tokens, lens, scores, NoBias{});
+    }
     return LAUNCH_OK();
 }
 
@@ -518,15 +631,22 @@ int mk_beam_ctc_init(const BeamArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(beam_ctc_init_kernel, dim3(a.B), dim3(64), 0, s, a);
     return LAUNCH_OK();
 }
-int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s) {
+int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s, const float* pre_b) {
     if (a.P < 1 || a.P > 96) return refuse("mk_beam_ctc_prefix", "pre-beam width must be in [1, 96]");
     if (a.N > 0 && (!a.wts || !a.pre_lm)) return refuse("mk_beam_ctc_prefix", "the LM variant needs the weights and the LM terms");
-    if (a.N > 0) hipLaunchKernelGGL(beam_ctc_prefix_kernel<true>, dim3(a.R), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(beam_ctc_prefix_kernel<false>, dim3(a.R), dim3(128), 0, s, a);
+    if (pre_b && !a.N) return refuse("mk_beam_ctc_prefix", "the biased joint beam is the N-best one");
+    if (pre_b) hipLaunchKernelGGL((beam_ctc_prefix_kernel<true, true>), dim3(a.R), dim3(128), 0, s, a, pre_b);
+    else if (a.N > 0) hipLaunchKernelGGL((beam_ctc_prefix_kernel<true, false>), dim3(a.R), dim3(128), 0, s, a, NoBias{});
+    else hipLaunchKernelGGL((beam_ctc_prefix_kernel<false, false>), dim3(a.R), dim3(128), 0, s, a, NoBias{});
     return LAUNCH_OK();
 }
 int mk_beam_set_weights(const BeamArgs& a, float att_w, float ctc_w, float lm_w, float len_bonus, hipStream_t s) {
     if (!a.wts) return refuse("mk_beam_set_weights", "null pointer");
     hipLaunchKernelGGL(beam_set_weights_kernel, dim3(1), dim3(64), 0, s, const_cast<float*>(a.wts), att_w, ctc_w, lm_w, len_bonus);
+    return LAUNCH_OK();
+}
+int mk_beam_set_bias_weight(const BeamArgs& a, float bias_w, hipStream_t s) {
+    if (!a.wts) return refuse("mk_beam_set_bias_weight", "null pointer");
+    hipLaunchKernelGGL(beam_set_bias_w_kernel, dim3(1), dim3(64), 0, s, const_cast<float*>(a.wts), bias_w);
     return LAUNCH_OK();
 }

@@ -120,7 +120,7 @@ struct masr_model {
     // LM fusion: the beam's key + lm_w's bits + the LM's serial number; joint with LM: the beam's key + N + the LM's serial number (its
     // weights are device values, not part of the graph); LSTM LM fusion: the beam's key + lm_w's bits + that LM's serial number; joint with
     // the LSTM LM: the beam's key + N + that LM's serial number (weights on the device, as joint with LM)
-    DecodeGraph greedy_graph, beam_graph, joint_graph, lm_graph, joint_lm_graph, nlm_graph, joint_nlm_graph, ctc_nlm_graph;
+    DecodeGraph greedy_graph, beam_graph, joint_graph, lm_graph, joint_lm_graph, nlm_graph, joint_nlm_graph, ctc_nlm_graph, bias_graph, joint_bias_graph;
     struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
     bool prof = false;

@@ -172,7 +172,7 @@ struct BeamArgs {
     int* list_slot; float* list_psi;           // [R][P] beside list_tok / list_score: the candidate's chain slot and prefix score
     // joint decode with an n-gram LM, a length bonus and an N-best list (masr_recog_beam_ctc_lm; N = 0 and null otherwise).  The
     // four weights live on the device, so that a cached step graph never holds a value of theirs
-    const float* wts;                          // [4] att_w, ctc_w, lm_w, len_bonus (att_w / ctc_w above are not read)
+    const float* wts;                          // [4] att_w, ctc_w, lm_w, len_bonus (att_w / ctc_w above are not read); the biased beam: [5], bias_w last
     float* pre_lm;                             // [R][P] beside pre_tok / pre_lp: the weighted LM term fl(lm_w * lm(c | h))
     int N;                                     // entries of the N-best list, 1 <= N <= K
     float* nb_score; int *nb_len, *nb_row;     // [B][N] ended hypotheses, best first (best_* are not used): score, token count, row at step nb_len;
@@ -198,10 +198,25 @@ struct BeamRowLm {
 //   mk_beam_backtrace   once after the last step: tokens [B][Lmax], lens / scores [B]; N > 0: tokens [B][N][Lmax], lens / scores [B][N]
 int mk_beam_init(const BeamArgs& a, hipStream_t s);
 int mk_beam_embed_step(const BeamArgs& a, const float* table, const float* pe, float* y32, bf16* y16, int E, hipStream_t s);
-int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s);
-int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s);
-int mk_beam_select(const BeamArgs& a, hipStream_t s);
-int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s);
+// Contextual phrase biasing of the step beams (bias null / pre_b null: the unbiased kernels, as they were).  With it
+//   mk_beam_rows        advances each live row's automaton state and ranks by g(c) = fl(f(c) + fl(bias_w * dn(h, c))), f = lp without an LM;
+//                       the pre-beam also writes pre_b, and pre_lm = +0 without an LM.  LM logits with a list are refused
+//   mk_beam_ctc_prefix  adds pre_b as the sixth term of the score (the N-best beam only)
+//   mk_beam_select      stops on the bound that allows bias_w more per further token: the attention beam's from bias->bias_w, the N-best
+//                       beam's from a.wts[4] (mk_beam_set_bias_weight)
+//   mk_beam_backtrace   also writes nbias = n_final of every returned hypothesis ([B], or [B][N] with -1 in an empty slot)
+struct BiasDev;
+struct BeamBias {
+    const BiasDev* dev;
+    int2* state;                               // [2][R] (node, credited tokens), step parity
+    float* pre_b;                              // [R][P] beside pre_lm (joint beam)
+    float bias_w;                              // the attention beam's weight; the joint beam reads a.wts[4]
+};
+int mk_beam_rows(const BeamArgs& a, const BeamRowLm& lm, const float* logits, long ld, hipStream_t s, const BeamBias* bias = nullptr);
+int mk_beam_ctc_prefix(const BeamArgs& a, hipStream_t s, const float* pre_b = nullptr);
+int mk_beam_select(const BeamArgs& a, hipStream_t s, const BeamBias* bias = nullptr);
+int mk_beam_backtrace(const BeamArgs& a, int* tokens, int* lens, float* scores, hipStream_t s, const BiasDev* bias = nullptr, int* nbias = nullptr);
+int mk_beam_set_bias_weight(const BeamArgs& a, float bias_w, hipStream_t s);      // a.wts[4] (five floats then), behind mk_beam_set_weights
 // once per joint decode: logits [B*Tp][ld] of the CTC head -> a.ctc_lp; the empty hypothesis's CTC state (after mk_beam_init); the joint LM
 // beam's four weights into a.wts (a plain launch in front of the step replays)
 int mk_beam_ctc_logsoftmax(const BeamArgs& a, const float* logits, long ld, hipStream_t s);

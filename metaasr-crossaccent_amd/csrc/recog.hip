@@ -175,13 +175,17 @@ static bool shape_ok(int B, int T, int K) { return B > 0 && T >= 4 && K >= 1 && 
 //   second pass's scores
 //   CTC forced alignment (masr_recog_ctc_align, AL = maxL >= 0): one decoder position per utterance; the head's logits, the targets
 //   [B*maxL] with their offsets [B] and lengths [B], and the alignment's work buffer follow
-struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; int AL = -1; const masr_nlm* nlm = nullptr; };
+//   phrase biasing of either step beam (masr_recog_beam_bias, masr_recog_beam_ctc_bias, bias): the LM variant's plan -- the fused
+//   rows are needed without an LM too -- then the automaton states [2][R] and, in the joint beam, the candidates' bias terms [R][P]; the joint
+//   beam's weights are five
+struct DecodeSpec { int K = 0, Lmax = 0, P = 0; bool ctc_only = false; int N = 0; bool lm = false; int NB = 0; int AL = -1; const masr_nlm* nlm = nullptr; bool bias = false; };
 struct DecodeBufs {
     BeamArgs beam; bf16* step_qkv; float* ctc_logits; void* work; int64_t work_bytes;
     float* lm_fused;                                                    // LM fusion: the rows' fused increments [R][Cp]
     float* nlm_logits; bf16 *nlm_h, *nlm_htop; float* nlm_c;            // LSTM LM fusion: LM logits [R][Cp], states [2][L][R][Hp], top h [R][Hp]
     int *rs_tok, *rs_lens; float *rs_ctc, *rs_att, *rs_row_lp;          // rescoring: first-pass list [B][N][Tp] / [B][N] / [B][N], att [B*N], row terms [B*N*(Lmax+1)]
     int* al_tgt;                                                        // alignment: targets [B*maxL], then tgt_off [B], then tgt_len [B]
+    int2* bias_state; float* bias_pre;                                  // phrase biasing: states [2][R], the joint beam's bias terms [R][P]
 };
 
 static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const DecodeSpec& d) {
@@ -202,6 +206,7 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
         o.nlm_h = ar.get<bf16>(nlm_state_elems(d.nlm->dev, R)); o.nlm_c = ar.get<float>(nlm_state_elems(d.nlm->dev, R));
         o.nlm_htop = ar.get<bf16>((int64_t)R * d.nlm->dev.Hp);
     }
+    if (d.bias) o.bias_state = ar.get<int2>(2 * (int64_t)R);
     if (!P) return o;
     a.P = P; a.Tp = Tp;
     o.ctc_logits = ar.get<float>((int64_t)B * Tp * m->Cp);
@@ -212,7 +217,8 @@ static DecodeBufs plan_beam(const masr_model* m, Arena& ar, int B, int Tp, const
     a.list_slot = ar.get<int>((int64_t)R * P); a.list_psi = ar.get<float>((int64_t)R * P);
     if (!d.NB) return o;
     a.N = d.NB;
-    a.pre_lm = ar.get<float>((int64_t)R * P); a.wts = ar.get<float>(4);
+    a.pre_lm = ar.get<float>((int64_t)R * P); a.wts = ar.get<float>(d.bias ? 5 : 4);
+    if (d.bias) o.bias_pre = ar.get<float>((int64_t)R * P);
     a.nb_score = ar.get<float>((int64_t)B * d.NB); a.nb_len = ar.get<int>((int64_t)B * d.NB); a.nb_row = ar.get<int>((int64_t)B * d.NB);
     return o;
 }
@@ -292,6 +298,8 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
                                    : d.ctc_only && d.nlm ? "workspace too small (masr_ctc_beam_nlm_workspace_bytes(nlm, B, T, K))"
                                    : d.ctc_only ? "workspace too small (masr_ctc_beam_workspace_bytes(B, T, K))"
                                    : !d.K ? "workspace too small (masr_workspace_bytes(B, T, max(ilens)/4))"
+                                   : d.bias && d.NB ? "workspace too small (masr_beam_ctc_bias_workspace_bytes(B, T, K, N, Lmax))"
+                                   : d.bias ? "workspace too small (masr_beam_bias_workspace_bytes(B, T, K, Lmax))"
                                    : d.NB && d.nlm ? "workspace too small (masr_beam_ctc_nlm_workspace_bytes(nlm, B, T, K, N, Lmax))"
                                    : d.NB ? "workspace too small (masr_beam_ctc_lm_workspace_bytes(B, T, K, N, Lmax))"
                                    : d.P ? "workspace too small (masr_beam_ctc_workspace_bytes(B, T, K, Lmax))"
@@ -363,10 +371,10 @@ static int beam_prebeam_width(int K) { return 3 * K / 2; }         // ESPnet's C
 
 // the step beams' workspace queries: one predicate, and one message but for the N-best variant's (N < 0: no list)
 static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, int T, int K, int Lmax, bool joint, bool lm, int N = -1,
-                                   const masr_nlm* nlm = nullptr) {
+                                   const masr_nlm* nlm = nullptr, bool bias = false) {
     return decode_workspace_bytes(fn, m, shape_ok(B, T, K) && Lmax >= 1 && (N < 0 || (N >= 1 && N <= K)),
                                   N < 0 ? "need B >= 1, T >= 4, 1 <= K <= 64, Lmax >= 1" : "need B >= 1, T >= 4, 1 <= N <= K <= 64, Lmax >= 1", B, T,
-                                  DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0), -1, nlm});
+                                  DecodeSpec{K, Lmax, joint ? beam_prebeam_width(K) : 0, false, 0, lm, std::max(N, 0), -1, nlm, bias});
 }
 
 // One beam-search step on the B*K hypothesis rows (beam.hip).  Step-independent arguments throughout, like decode_step.  The launchers
@@ -375,15 +383,16 @@ static int64_t beam_workspace_bytes(const char* fn, const masr_model* m, int B, 
 // read from ba.wts), the row stage by `lm`.  LSTM LM fusion (nlm): the LM's layer stack and output projection on the rows' last
 // tokens and parent states (nlm.hip; it reads only what the previous step's select wrote, so it sits in front of the decoder layers) fill
 // lm.lm_logits.
-static int beam_step(Ctx& c, const DecodeBufs& bufs, const BeamRowLm& lm, const masr_nlm* nlm, const NlmStepArgs& nlm_args) {
+// Phrase biasing (bias): the row stage, the prefix scores and the select take their biased forms.
+static int beam_step(Ctx& c, const DecodeBufs& bufs, const BeamRowLm& lm, const masr_nlm* nlm, const NlmStepArgs& nlm_args, const BeamBias* bias = nullptr) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s;
     const BeamArgs& ba = bufs.beam;
     CK(mk_beam_embed_step(ba, m->P + m->embed_w, m->pe, a.y32[0], a.y16[0], m->E, s));
     if (nlm) CK(mk_nlm_step(nlm->dev, nlm_args, bufs.nlm_logits, m->Cp, s));
     CK(decode_layers(c, DecStepGeom{ba.R, ba.Lmax, ba.K, bufs.step_qkv, ba.tab, (long)ba.R * ba.Lmax}));
-    CK(mk_beam_rows(ba, lm, a.logits, m->Cp, s));
-    if (ba.P) CK(mk_beam_ctc_prefix(ba, s));
-    return mk_beam_select(ba, s);                               // also advances *step_dev
+    CK(mk_beam_rows(ba, lm, a.logits, m->Cp, s, bias));
+    if (ba.P) CK(mk_beam_ctc_prefix(ba, s, bias ? bias->pre_b : nullptr));
+    return mk_beam_select(ba, s, bias);                         // also advances *step_dev
 }
 
 // which beam decode: masr_recog_beam (nothing set), masr_recog_beam_ctc (joint), masr_recog_beam_lm (lm), masr_recog_beam_ctc_lm (joint, lm
@@ -394,6 +403,7 @@ struct BeamMode {
     const masr_lm* lm = nullptr; float lm_w = 0.f;              // n-gram LM fusion
     int N = 0; float len_bonus = 0.f;                           // N-best list (N > 0) and the bonus per emitted token
     const masr_nlm* nlm = nullptr;                              // LSTM LM fusion (weighted by lm_w)
+    const masr_bias* bias = nullptr; float bias_w = 0.f; int32_t* nbias = nullptr;      // phrase biasing; lm may then be null
 };
 static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, const float* xs, const int64_t* ilens, int B, int T, int K,
                            float min_step_ratio, float max_step_ratio, int32_t* tokens, int32_t* lens, float* scores, void* stream) {
@@ -401,9 +411,11 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     // enc_len = ilens / 4 as the ESPnet rule; the step is captured once per (B, T, K, Lmax, workspace, parameters; joint: the two
     // weights; LM fusion: lm_w and the LM's serial number, so that another LM or weight never replays this one's table pointers; joint with
     // either LM: N and the serial number -- its four weights are device values written in front of the replays, no graph holds one) and
-    // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.
+    // replayed Lmax times -- utterances that finish earlier idle through the remaining replays.  Phrase biasing: the third key pointer holds the
+    // list's serial number and, in the attention beam, the bits of bias_w (the joint beam's bias_w is a device value like its four weights).
     CK(check_beam_size(fn, K));
     CK(check_pointers(fn, xs, ilens, tokens, lens, scores));
+    if (mode.bias && !mode.nbias) return fail(fn, "null pointer");
     if (B <= 0) return fail(fn, "need B >= 1");
     std::vector<int> mx_len(B), mn_len(B);
     int Lmax = 0;
@@ -416,7 +428,7 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     hipStream_t s = (hipStream_t)stream;
     DecodeBufs bufs;
     int Ldec = 0;
-    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, mode.joint ? beam_prebeam_width(K) : 0, false, 0, mode.lm != nullptr, mode.N, -1, mode.nlm},
+    { const int rc = recog_prepare(m, xs, ilens, B, T, s, &Ldec, DecodeSpec{K, Lmax, mode.joint ? beam_prebeam_width(K) : 0, false, 0, mode.lm != nullptr || mode.bias != nullptr, mode.N, -1, mode.nlm, mode.bias != nullptr},
                                    &bufs);
       if (rc) return rc; }
     BeamArgs& ba = bufs.beam;
@@ -427,7 +439,7 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     Ctx c{m, s, 0u, false, 0.f, 0.f};
     CK(project_memory_kv(c));
     CK(mk_beam_init(ba, s));
-    int key[6] = {B, T, K, Lmax, 0, 0}; const void* const kp[3] = {m->ws, m->P, nullptr};
+    int key[6] = {B, T, K, Lmax, 0, 0}; const void* kp[3] = {m->ws, m->P, nullptr};
     if (mode.joint) {
         // once per decode: the CTC head over the memory, its log-softmax per frame, the empty hypothesis's state
         ba.att_w = mode.att_w; ba.ctc_w = mode.ctc_w; ba.enc_lens = a.enc_lens;
@@ -438,7 +450,7 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     }
     BeamRowLm rl{};
     rl.lm_w = mode.N ? 0.f : mode.lm_w;                         // (the joint LM beam reads ba.wts: its graph holds no weight)
-    if (mode.lm || mode.nlm) { rl.fused = bufs.lm_fused; rl.ldf = m->Cp; }
+    if (mode.lm || mode.nlm || mode.bias) { rl.fused = bufs.lm_fused; rl.ldf = m->Cp; }
     if (mode.lm) {
         rl.ngram = &mode.lm->dev;
         memcpy(key + 4, &mode.lm_w, sizeof(float)); key[5] = (int)mode.lm->serial;
@@ -454,10 +466,20 @@ static int recog_beam_impl(const char* fn, masr_model* m, const BeamMode& mode, 
     if (mode.N) {
         CK(mk_beam_set_weights(ba, mode.att_w, mode.ctc_w, mode.lm_w, mode.len_bonus, s));
         key[4] = mode.N;
+        if (!mode.lm && !mode.nlm) key[5] = 0;                  // (the biased joint beam without an LM: no weight in the key)
     }
-    DecodeGraph& graph = mode.nlm && mode.N ? m->joint_nlm_graph : mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
-    CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed", [&] { return beam_step(c, bufs, rl, mode.nlm, na); }));
-    CK(mk_beam_backtrace(ba, tokens, lens, scores, s));
+    BeamBias bb{};
+    if (mode.bias) {
+        bb.dev = &mode.bias->dev; bb.state = bufs.bias_state; bb.pre_b = bufs.bias_pre; bb.bias_w = mode.N ? 0.f : mode.bias_w;
+        uint32_t wbits = 0;
+        memcpy(&wbits, &bb.bias_w, sizeof wbits);
+        kp[2] = (const void*)(uintptr_t)(((uint64_t)mode.bias->serial << 32) | wbits);
+        if (mode.N) CK(mk_beam_set_bias_weight(ba, mode.bias_w, s));
+    }
+    const BeamBias* bias = mode.bias ? &bb : nullptr;
+    DecodeGraph& graph = mode.bias ? (mode.N ? m->joint_bias_graph : m->bias_graph) : mode.nlm && mode.N ? m->joint_nlm_graph : mode.nlm ? m->nlm_graph : mode.N ? m->joint_lm_graph : mode.joint ? m->joint_graph : mode.lm ? m->lm_graph : m->beam_graph;
+    CK(run_steps(m, graph, key, kp, Lmax, s, fn, "stream capture of the beam step failed", [&] { return beam_step(c, bufs, rl, mode.nlm, na, bias); }));
+    CK(mk_beam_backtrace(ba, tokens, lens, scores, s, mode.bias ? &mode.bias->dev : nullptr, mode.nbias));
     m->have_acts = false;
     return 0;
 }
@@ -592,6 +614,12 @@ int64_t masr_beam_ctc_nlm_workspace_bytes(const masr_model* m, const masr_nlm* n
     if (!nlm) { mk_set_error(fn, "null language model"); return -1; }
     return beam_workspace_bytes(fn, m, B, T, K, Lmax, true, false, N, nlm);
 }
+int64_t masr_beam_bias_workspace_bytes(const masr_model* m, int B, int T, int K, int Lmax) {
+    return beam_workspace_bytes("masr_beam_bias_workspace_bytes", m, B, T, K, Lmax, false, true, -1, nullptr, true);
+}
+int64_t masr_beam_ctc_bias_workspace_bytes(const masr_model* m, int B, int T, int K, int N, int Lmax) {
+    return beam_workspace_bytes("masr_beam_ctc_bias_workspace_bytes", m, B, T, K, Lmax, true, true, N, nullptr, true);
+}
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K) {
     return decode_workspace_bytes("masr_ctc_beam_workspace_bytes", m, shape_ok(B, T, K), "need B >= 1, T >= 4, 1 <= K <= 64", B, T, DecodeSpec{K, 0, 0, true});
 }
@@ -681,6 +709,37 @@ int masr_recog_beam_ctc_nlm(masr_model* m, const masr_nlm* nlm, const float* xs,
     CK(check_beam_size(fn, K));
     CK(check_nbest(fn, "N", N, K));
     BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w; mode.nlm = nlm; mode.lm_w = lm_w; mode.N = N; mode.len_bonus = len_bonus;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K,
+                         float min_step_ratio, float max_step_ratio, float lm_w, float bias_w, int32_t* tokens, int32_t* lens, float* scores,
+                         int32_t* nbias, void* stream) {
+    // contextual phrase biasing of the attention beam: masr_recog_beam(_lm) with the automaton's term in the row increment
+    const char* fn = "masr_recog_beam_bias";
+    CK(check_model(fn, m));
+    if (lm) CK(check_lm(fn, m, lm, lm_w, nullptr));
+    CK(check_bias(fn, m, bias, bias_w));
+    BeamMode mode; mode.lm = lm; mode.lm_w = lm ? lm_w : 0.f; mode.bias = bias; mode.bias_w = bias_w; mode.nbias = nbias;
+    return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
+}
+
+int masr_recog_beam_ctc_bias(masr_model* m, const masr_lm* lm, const masr_bias* bias, const float* xs, const int64_t* ilens, int B, int T, int K, int N,
+                             float min_step_ratio, float max_step_ratio, float att_w, float ctc_w, float lm_w, float len_bonus, float bias_w,
+                             int32_t* tokens, int32_t* lens, float* scores, int32_t* nbias, void* stream) {
+    // contextual phrase biasing of the joint beam: masr_recog_beam_ctc_lm with the automaton's term in the pre-beam and the score
+    const char* fn = "masr_recog_beam_ctc_bias";
+    CK(check_model(fn, m));
+    CK(check_ctc_head(fn, m));
+    CK(check_weight(fn, "ctc_w", ctc_w, true));
+    CK(check_weight(fn, "att_w", att_w, false));
+    if (lm) CK(check_lm(fn, m, lm, lm_w, &len_bonus));
+    else if (!std::isfinite(len_bonus)) return fail(fn, "len_bonus must be finite");
+    CK(check_bias(fn, m, bias, bias_w));
+    CK(check_beam_size(fn, K));
+    CK(check_nbest(fn, "N", N, K));
+    BeamMode mode; mode.joint = true; mode.att_w = att_w; mode.ctc_w = ctc_w; mode.lm = lm; mode.lm_w = lm ? lm_w : 0.f; mode.N = N; mode.len_bonus = len_bonus;
+    mode.bias = bias; mode.bias_w = bias_w; mode.nbias = nbias;
     return recog_beam_impl(fn, m, mode, xs, ilens, B, T, K, min_step_ratio, max_step_ratio, tokens, lens, scores, stream);
 }
 

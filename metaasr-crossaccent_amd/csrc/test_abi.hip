@@ -373,6 +373,136 @@ int masr_test_beam_select_nbest(int B, int K, int N, int C, int t, const int32_t
     hipFree(w);
     return rc;
 }
+static int test_read_ints(const int32_t* dev, size_t n, std::vector<int>& host, hipStream_t s);
+// ---- the phrase-biased step kernels alone (tests/test_hip_bias_beam_kernels.py)
+int masr_test_beam_bias_rows(const masr_lm* lm, const masr_bias* bias, float lm_w, float bias_w, int B, int K, int t, const int32_t* minlen,
+                             const int32_t* maxlen, const float* logits, int64_t ld, const float* score, const int32_t* tok_hist, const int32_t* par_hist,
+                             const int32_t* state_in, int32_t* state_out, int32_t* list_tok, float* list_score, int32_t* pre_tok, float* pre_lp,
+                             float* pre_lm, float* pre_b, void* stream) {
+    const char* fn = "masr_test_beam_bias_rows";
+    if (!bias || !minlen || !maxlen || !logits || !score || !state_out || (t > 1 && (!tok_hist || !par_hist || !state_in))) { mk_set_error(fn, "null pointer"); return -1; }
+    if (pre_tok ? (!pre_lp || !pre_lm || !pre_b) : (!list_tok || !list_score)) { mk_set_error(fn, "null pointer"); return -1; }
+    if (K < 1 || K > 64) { mk_set_error(fn, "beam size must be in [1, 64]"); return -1; }
+    const int C = bias->dev.C;
+    if (lm && lm->dev.C != C) { mk_set_error(fn, "the LM's classes differ from the list's"); return -1; }
+    if (B < 1 || t < 1 || ld < C || (int64_t)B * K > (1 << 20)) { mk_set_error(fn, "need B, t >= 1, ld >= C, B * K <= 2^20"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    if (t > 1) {                                             // every node the kernel starts from must be one of the trie's
+        std::vector<int> hs;
+        CK(test_read_ints(state_in, (size_t)2 * R, hs, s));
+        for (int r = 0; r < R; ++r) if (hs[2 * r] < 0 || hs[2 * r] >= bias->dev.nodes) { mk_set_error(fn, "state node outside the trie"); return -1; }
+    }
+    char* w = nullptr;                                       // step[2] | weights [5] | fin [B] | states [2][R] | fused [R][ld]
+    const size_t wts_off = 64, fin_off = 128, st_off = (fin_off + sizeof(int) * (size_t)B + 255) & ~(size_t)255;
+    const size_t fused_off = (st_off + sizeof(int2) * 2 * (size_t)R + 255) & ~(size_t)255;
+    HIP_CHECK_RET(hipMalloc(&w, fused_off + sizeof(float) * (size_t)R * ld));
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = (int*)w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.minlen = minlen; a.maxlen = maxlen;
+    a.tok_hist = const_cast<int*>(tok_hist); a.par_hist = const_cast<int*>(par_hist); a.score = const_cast<float*>(score);
+    a.fin = (int*)(w + fin_off); a.wts = (float*)(w + wts_off);
+    if (pre_tok) { a.P = std::max(1, 3 * K / 2); a.N = 1; a.pre_tok = pre_tok; a.pre_lp = pre_lp; a.pre_lm = pre_lm; }
+    else { a.list_tok = list_tok; a.list_score = list_score; }
+    BeamRowLm rl{};
+    if (lm) rl.ngram = &lm->dev;
+    rl.fused = (float*)(w + fused_off); rl.ldf = ld; rl.lm_w = lm_w;
+    int2* st = (int2*)(w + st_off);
+    const BeamBias bb{&bias->dev, st, pre_b, bias_w};
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemsetAsync(w, 0, fused_off, s));
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        if (t > 1) HIP_CHECK_RET(hipMemcpyAsync(st + (size_t)((t - 1) & 1) * R, state_in, sizeof(int2) * R, hipMemcpyDeviceToDevice, s));
+        if (a.P) { CK(mk_beam_set_weights(a, 0.f, 0.f, lm_w, 0.f, s)); CK(mk_beam_set_bias_weight(a, bias_w, s)); }
+        CK(mk_beam_rows(a, rl, logits, ld, s, &bb));
+        HIP_CHECK_RET(hipMemcpyAsync(state_out, st + (size_t)(t & 1) * R, sizeof(int2) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+int masr_test_beam_select_bias(int B, int K, int C, int t, const int32_t* maxlen, float bias_w, const int32_t* list_tok, const float* list_score,
+                               float* score, int32_t* fin, float* best_score, int32_t* best_len, int32_t* best_row, int32_t* tok_hist_row,
+                               int32_t* par_hist_row, int32_t* step_out, void* stream) {
+    const char* fn = "masr_test_beam_select_bias";
+    if (!maxlen || !list_tok || !list_score || !score || !fin || !best_score || !best_len || !best_row || !tok_hist_row || !par_hist_row || !step_out) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (K < 1 || K > 64 || B < 1 || C < 2 || t < 1) { mk_set_error(fn, "need 1 <= K <= 64, B, t >= 1, C >= 2"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    const size_t hist = (size_t)t * R * sizeof(int);
+    int* w = nullptr;                                        // step[2] | tok_hist [t][R] | par_hist [t][R]
+    HIP_CHECK_RET(hipMalloc(&w, 64 + 2 * hist));
+    int* tok_hist = w + 16;
+    int* par_hist = tok_hist + (size_t)t * R;
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.maxlen = maxlen;
+    a.tok_hist = tok_hist; a.par_hist = par_hist; a.score = score; a.fin = fin;
+    a.list_tok = const_cast<int*>(list_tok); a.list_score = const_cast<float*>(list_score);
+    a.best_score = best_score; a.best_len = best_len; a.best_row = best_row;
+    BeamBias bb{}; bb.bias_w = bias_w;
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_select(a, s, &bb));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
+int masr_test_beam_select_nbest_bias(int B, int K, int N, int C, int t, const int32_t* maxlen, float len_bonus, float bias_w, const int32_t* list_tok,
+                                     const float* list_score, const float* list_psi, const int32_t* list_slot, float* score, float* psi, int32_t* src,
+                                     int32_t* fin, float* nb_score, int32_t* nb_len, int32_t* nb_row, int32_t* tok_hist_row, int32_t* par_hist_row,
+                                     int32_t* step_out, void* stream) {
+    const char* fn = "masr_test_beam_select_nbest_bias";
+    if (!maxlen || !list_tok || !list_score || !list_psi || !list_slot || !score || !psi || !src || !fin || !nb_score || !nb_len || !nb_row ||
+        !tok_hist_row || !par_hist_row || !step_out) {
+        mk_set_error(fn, "null pointer"); return -1;
+    }
+    if (K < 1 || K > 64 || N < 1 || N > K) { mk_set_error(fn, "need 1 <= N <= K <= 64"); return -1; }
+    if (B < 1 || C < 2 || t < 1) { mk_set_error(fn, "need B, t >= 1, C >= 2"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * K;
+    const size_t hist = (size_t)t * R * sizeof(int);
+    int* w = nullptr;                                        // step[2] | weights [5] at int 16 | tok_hist [t][R] | par_hist [t][R]
+    HIP_CHECK_RET(hipMalloc(&w, 128 + 2 * hist));
+    int* tok_hist = w + 32;
+    int* par_hist = tok_hist + (size_t)t * R;
+    const int h_step[2] = {t, 0};
+    BeamArgs a{};
+    a.step = w; a.B = B; a.K = K; a.R = R; a.Lmax = t; a.C = C; a.sos = 0; a.eos = C - 1; a.maxlen = maxlen; a.P = std::max(1, 3 * K / 2); a.N = N;
+    a.tok_hist = tok_hist; a.par_hist = par_hist; a.score = score; a.psi = psi; a.src = src; a.fin = fin;
+    a.list_tok = const_cast<int*>(list_tok); a.list_score = const_cast<float*>(list_score);
+    a.list_psi = const_cast<float*>(list_psi); a.list_slot = const_cast<int*>(list_slot);
+    a.nb_score = nb_score; a.nb_len = nb_len; a.nb_row = nb_row; a.wts = reinterpret_cast<float*>(w + 16);
+    const BeamBias bb{};
+    auto run = [&]() -> int {
+        HIP_CHECK_RET(hipMemcpyAsync(w, h_step, sizeof h_step, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist + (size_t)(t - 1) * R, tok_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist + (size_t)(t - 1) * R, par_hist_row, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        CK(mk_beam_set_weights(a, 0.f, 0.f, 0.f, len_bonus, s));
+        CK(mk_beam_set_bias_weight(a, bias_w, s));
+        CK(mk_beam_select(a, s, &bb));
+        HIP_CHECK_RET(hipMemcpyAsync(tok_hist_row, tok_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(par_hist_row, par_hist + (size_t)(t - 1) * R, sizeof(int) * R, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(step_out, w, sizeof h_step, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = run();
+    hipFree(w);
+    return rc;
+}
 // ---- the training step's row kernels alone (tests/test_hip_train_row_kernels.py): each entry vets what the kernel would index with, fills the
 // launcher's arguments and calls it
 static int test_read_ints(const int32_t* dev, size_t n, std::vector<int>& host, hipStream_t s) {

@@ -489,6 +489,49 @@ class MasrEngine:
         self._last_x = xs
         return out if raw else nbest_lists_bias(*out)
 
+    def recog_beam_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
+                        min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, raw: bool = False):
+        """the attention beam with contextual phrase biasing (masr_recog_beam_bias): recog_beam's search -- with lm (an NGramLM)
+        recog_beam_lm's -- whose per-step increment also carries bias_w per token credited by the phrase automaton of `bias` (a ContextBias
+        over this model's odim classes); bias_w finite and >= 0, without an LM lm_w is ignored.  Returns (B token lists without sos / eos,
+        fp32 scores [B] on the host, credited tokens int32 [B] on the host); raw: the device tensors tokens, lens, scores, nbias instead."""
+        K, _ = check_beam_args(beam_size)
+        bias_w = check_bias_args(bias, bias_w)
+        lm_w, _ = check_lm_args(lm, lm_w, 0.0) if lm is not None else (0.0, 0.0)
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_bias_workspace_bytes", B, T, K, Lmax)
+        out = self._outputs(B, ld=Lmax, extra="i")
+        check(self._l.masr_recog_beam_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio),
+                                           float(max_step_ratio), lm_w, bias_w, *map(_ptr, out), self.stream()), "masr_recog_beam_bias")
+        self._last_x = xs
+        return out if raw else (*self._best_lists(*out[:3]), out[3].cpu())
+
+    def recog_beam_ctc_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
+                            len_bonus: float = 0.0, nbest: int = 1, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0,
+                            att_weight: float = 0.7, ctc_weight: float = 0.3, raw: bool = False):
+        """the one-pass joint CTC/attention beam with contextual phrase biasing (masr_recog_beam_ctc_bias; needs a hybrid model):
+        recog_beam_ctc_lm's search with the automaton's term in the pre-beam and in the score; lm may be None (no LM term; lm_w is ignored, the
+        bonus is kept).  Returns per utterance a list of at most nbest (token list, score, credited tokens), best first (raw: the device
+        tensors tokens [B, nbest, Lmax], lens, scores, nbias instead)."""
+        K, N = check_beam_args(beam_size, nbest)
+        bias_w = check_bias_args(bias, bias_w)
+        if lm is not None:
+            lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
+        else:
+            lm_w, len_bonus = 0.0, float(len_bonus)
+            if not math.isfinite(len_bonus):
+                raise ValueError(f"len_bonus must be finite, got {len_bonus}")
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
+        self._decode_ws("masr_beam_ctc_bias_workspace_bytes", B, T, K, N, Lmax)
+        out = self._outputs(B, N, ld=Lmax, extra="i")
+        check(self._l.masr_recog_beam_ctc_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio),
+                                               float(max_step_ratio), float(att_weight), float(ctc_weight), lm_w, len_bonus, bias_w,
+                                               *map(_ptr, out), self.stream()), "masr_recog_beam_ctc_bias")
+        self._last_x = xs
+        return out if raw else [[(t, sc, int(n)) for t, sc, n in u] for u in nbest_lists(*out)]
+
     def recog_rescore_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
                            len_bonus: float = 0.0, nbest=None, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
         """recog_rescore whose first pass is recog_ctc_beam_bias's search (masr_recog_rescore_bias): the `ctc` of an entry is

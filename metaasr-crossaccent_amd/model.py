@@ -174,6 +174,20 @@ class MyTransformer:
         assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
         return self.engine.recog_ctc_beam_bias(xs_pad, ilens, beam_size, bias, bias_weight, lm, lm_weight, len_bonus, nbest)
 
+    def bias_beam_decode(self, xs_pad, ilens, beam_size, bias, bias_weight=3.0, lm=None, lm_weight=0.3, min_step_ratio=0.0, max_step_ratio=1.0):
+        """the attention beam with the phrase list `bias` (a ContextBias) boosting its phrases (masr_recog_beam_bias), the n-gram LM `lm` fused
+        in when one is given: (B token lists without sos / eos, scores [B], credited tokens [B])"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_bias(xs_pad, ilens, beam_size, bias, bias_weight, lm, lm_weight, min_step_ratio, max_step_ratio)
+
+    def bias_joint_beam_decode(self, xs_pad, ilens, beam_size, bias, bias_weight=3.0, lm=None, lm_weight=0.3, len_bonus=0.0, nbest=1,
+                               min_step_ratio=0.0, max_step_ratio=1.0, att_weight=0.7, ctc_weight=0.3):
+        """the one-pass joint CTC/attention beam with the phrase list `bias` (masr_recog_beam_ctc_bias, hybrid models only), lm_joint_beam_decode's
+        search with or without its LM: per utterance a list of at most nbest (token list, score, credited tokens), best first"""
+        assert xs_pad.size(0) == ilens.size(0), "Batch size mismatch"
+        return self.engine.recog_beam_ctc_bias(xs_pad, ilens, beam_size, bias, bias_weight, lm, lm_weight, len_bonus, nbest, min_step_ratio,
+                                               max_step_ratio, att_weight, ctc_weight)
+
     def bias_rescore_decode(self, xs_pad, ilens, beam_size, bias, bias_weight=3.0, lm=None, lm_weight=0.3, len_bonus=0.0, nbest=None,
                             att_weight=0.5, ctc_weight=0.5):
         """attention rescoring of the phrase-biased CTC beam's nbest list (masr_recog_rescore_bias, hybrid models only): rescore_decode with

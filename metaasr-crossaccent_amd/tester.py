@@ -56,6 +56,14 @@ anything is decoded.  Tester.MODES is the table of them:
   bias_rescore   masr_recog_rescore_bias, `rescore` with `bias_ctc_beam`'s search as its first pass (the attention pass is not biased): nbest,
                  att_w and ctc_w as for `rescore`, the rest as for `bias_ctc_beam`.  Refuses what `rescore` refuses (a BLSTM:
                  NotImplementedError).
+  bias_beam      masr_recog_beam_bias, the attention beam (`beam`, with `--lm_model_path` `lm_beam`) with contextual phrase biasing (DESIGN
+                 5.14): `--context_path` and bias_w (3.0) as for `bias_ctc_beam`, the step ratios as for `beam`; `--lm_model_path` is optional
+                 (given: lm_w as for `lm_beam`).  Without a context path or on a BLSTM the mode raises NotImplementedError.  A hybrid model
+                 with ctc_w > 0 raises ValueError (that search is `bias_joint_beam`); a plain model logs that ctc_w is ignored.
+  bias_joint_beam masr_recog_beam_ctc_bias, `lm_joint_beam` with the same biasing, with or without its LM: att_w / ctc_w (ctc_w > 0
+                 required: absent or 0 raises ValueError, that search is `bias_beam`), the step ratios, len_bonus and nbest as for
+                 `lm_joint_beam`; `--context_path` and bias_w as above; `--lm_model_path` optional.  A BLSTM raises NotImplementedError, a
+                 transformer without a CTC head ValueError.  The LSTM-LM modes (`nlm_beam`, `nlm_joint_beam`, `nlm_ctc_beam`) are not biased.
   ctc_align      masr_recog_ctc_align (BLSTM-CTC: masr_ctc_align per utterance), the CTC forced alignment of DESIGN 5.9: no search, so no
                  solver.beam_decode block is read.  Each test utterance's REFERENCE transcript is aligned to the frames of the CTC output
                  layer, and one line per utterance is appended to `<decode_dir>/ctc-ali` (no best-hyp is written):
@@ -431,6 +439,45 @@ class Tester:
             self.lm = None
         logger.notice(f"{mode}: phrase list {self._load_bias(ctx_path)}, bias_w = {self.bias_weight}; {lm}")
 
+    def _bias_step_settings(self):
+        """bias_beam and bias_joint_beam: beam's / lm_joint_beam's settings, the phrase list, and lm_beam's LM when a path is given"""
+        mode = self.decode_mode
+        ctx_path = getattr(self.paras, 'context_path', None)
+        if ctx_path is None:
+            raise NotImplementedError(f"{mode}: no phrase list given; pass --context_path (one phrase per line as space-separated unit ids)")
+        if self.model_name == 'blstm':
+            raise NotImplementedError(f"{mode}: the attention and joint beams need the transformer's decoder, the BLSTM has none; "
+                                      "use --decode_mode bias_ctc_beam")
+        bd = self._beam_size()
+        self._step_ratios(bd)
+        ctc_w = self._weight(bd, 'ctc_w', 0.0)
+        if mode == 'bias_beam':
+            if ctc_w > 0.0:
+                if self.asr_model.engine.ctc_weight > 0.0:
+                    raise ValueError(f"bias_beam: this search is the attention beam alone (beam_decode.ctc_w = {bd['ctc_w']}); the phrase-biased "
+                                     "joint CTC/attention beam is --decode_mode bias_joint_beam, or set beam_decode.ctc_w: 0")
+                logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
+        else:
+            self._need_ctc_head(mode, "bias_beam, beam or greedy")
+            self.ctc_weight = ctc_w
+            if not ctc_w > 0.0:
+                raise ValueError("bias_joint_beam: solver.beam_decode.ctc_w must be > 0 (it is absent or 0); to bias the attention beam alone use "
+                                 "--decode_mode bias_beam")
+            self.att_weight = self._weight(bd, 'att_w', 1.0 - ctc_w)
+            self._nbest(bd, 1)
+        self.bias_weight = self._weight(bd, 'bias_w', 3.0)
+        lm_path = getattr(self.paras, 'lm_model_path', None)
+        self.lm_weight, self.len_bonus = 0.0, 0.0
+        if mode == 'bias_joint_beam':
+            self._len_bonus(bd)                                  # (the bonus needs no LM)
+        lm = "no LM"
+        if lm_path is not None:
+            self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+            lm = f"{self._load_lm(lm_path, self.sos_id, self.eos_id)}, lm_w = {self.lm_weight}"
+        else:
+            self.lm = None
+        logger.notice(f"{mode}: phrase list {self._load_bias(ctx_path)}, bias_w = {self.bias_weight}; {lm}")
+
     # ------------------------------------------------------------------ the decode modes
     def _ctc_best(self, lists):
         """the best entry of each N-best list of a CTC beam (the search never emits blank or eos, so the BLSTM's trim changes nothing; it is
@@ -494,6 +541,15 @@ class Tester:
                          lambda t, xs, il: [n[0][0] for n in t.asr_model.bias_rescore_decode(xs, il, t.beam_size, t.bias, t.bias_weight, t.lm, t.lm_weight,
                                                                                              t.len_bonus, t.nbest, t.att_weight, t.ctc_weight)],
                          lambda t: f"attention rescoring of the phrase-biased CTC beam (bias_rescore, beam {t.beam_size}, {t.bias.phrases} phrases)"),
+        'bias_beam': (_bias_step_settings,
+                      lambda t, xs, il: t.asr_model.bias_beam_decode(xs, il, t.beam_size, t.bias, t.bias_weight, t.lm, t.lm_weight, t.min_step_ratio,
+                                                                     t.max_step_ratio)[0],
+                      lambda t: f"phrase-biased beam decoding (bias_beam, beam {t.beam_size}, {t.bias.phrases} phrases)"),
+        'bias_joint_beam': (_bias_step_settings,
+                            lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.bias_joint_beam_decode(
+                                xs, il, t.beam_size, t.bias, t.bias_weight, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio,
+                                t.att_weight, t.ctc_weight)],
+                            lambda t: f"phrase-biased joint CTC/attention beam decoding (bias_joint_beam, beam {t.beam_size}, {t.bias.phrases} phrases)"),
         'ctc_align': (_ctc_align_settings, None, lambda t: "CTC forced alignment of the reference transcripts"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
