@@ -253,7 +253,7 @@ void masr_destroy(masr_model* m) {
     if (m->h_stats) hipHostFree(m->h_stats);
     for (int i = 0; i < masr_model::RING; ++i) if (m->ring_ev[i]) { if (m->ring_used[i]) hipEventSynchronize(m->ring_ev[i]); hipEventDestroy(m->ring_ev[i]); }
     if (m->h_ring) hipHostFree(m->h_ring);
-    for (DecodeGraph* g : {&m->greedy_graph, &m->beam_graph, &m->joint_graph, &m->lm_graph, &m->joint_lm_graph, &m->nlm_graph, &m->joint_nlm_graph, &m->ctc_nlm_graph, &m->bias_graph, &m->joint_bias_graph}) g->destroy();
+    for (DecodeGraph& g : m->decode_graphs) g.destroy();
     for (auto& sg : m->step_graphs) { hipGraphExecDestroy(sg.e); hipGraphDestroy(sg.g); }
     for (auto& e : m->stage_ev) if (e) hipEventDestroy(e);
     for (auto& v : m->prof_ev) for (auto& p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }

@@ -70,6 +70,8 @@ struct DecodeGraph {
         if (graph) hipGraphDestroy(graph);
     }
 };
+// the slots of masr_model::decode_graphs (the table there says which decoder takes which)
+enum GraphSlot { G_GREEDY, G_BEAM, G_JOINT, G_LM, G_NLM, G_JOINT_LM, G_JOINT_NLM, G_BIAS, G_JOINT_BIAS, G_CTC_NLM, G_COUNT };
 
 constexpr int KSPLIT_MAX = 8;                              // partial products of a k-split GEMM (Acts::part)
 constexpr int MASR_PE_ROWS = 3000;                         // rows of the positional-encoding table (masr_bind)
@@ -115,12 +117,24 @@ struct masr_model {
     std::vector<StepGraph> step_graphs; int last_key[4] = {0, 0, 0, -1}; const void* last_xs = nullptr; uint64_t graph_clock = 0;
     int64_t n_direct = 0, n_captured = 0, n_replayed = 0;  // masr_step_counters
     bool step_graphs_on = false;                           // masr_set_step_graphs
-    // cached step graphs of the three decoders, each keyed on its own shape (recog.hip run_steps): alternating decoders do not evict
-    // one another.  greedy {B, T, Ldec} + {ws, P, out}; beam {B, T, K, Lmax} + {ws, P}; joint: the beam's key + the two weights' bits;
-    // LM fusion: the beam's key + lm_w's bits + the LM's serial number; joint with LM: the beam's key + N + the LM's serial number (its
-    // weights are device values, not part of the graph); LSTM LM fusion: the beam's key + lm_w's bits + that LM's serial number; joint with
-    // the LSTM LM: the beam's key + N + that LM's serial number (weights on the device, as joint with LM)
-    DecodeGraph greedy_graph, beam_graph, joint_graph, lm_graph, joint_lm_graph, nlm_graph, joint_nlm_graph, ctc_nlm_graph, bias_graph, joint_bias_graph;
+    // cached step graphs of the decoders, one slot per decoder variant (recog.hip run_steps): alternating decoders do not evict one
+    // another.  A call whose key equals the slot's replays its graph, any other captures anew.  A weight that is in no key is a device value
+    // written in front of the replays.  The step beams' keys are written by recog.hip beam_graph_key alone; words 0-3 are B, T, K, Lmax and
+    // pointers 0-1 are ws, P:
+    //   slot           decoder                      word 4                          word 5             pointer 2
+    //   G_BEAM         attention beam               0                               0                  null
+    //   G_JOINT        joint                        bits of att_w                   bits of ctc_w      null
+    //   G_LM           n-gram LM                    bits of lm_w                    LM serial          null
+    //   G_NLM          LSTM LM                      bits of lm_w                    NLM serial         null
+    //   G_JOINT_LM     joint + n-gram LM (N-best)   N                               LM serial          null
+    //   G_JOINT_NLM    joint + LSTM LM (N-best)     N                               NLM serial         null
+    //   G_BIAS         biased attention beam        bits of lm_w with an LM, else 0 LM serial, else 0  bias serial << 32 | bits of bias_w
+    //   G_JOINT_BIAS   biased joint (N-best)        N                               LM serial, else 0  bias serial << 32
+    // and the two that are no step beam's, keyed where they run:
+    //   G_GREEDY       masr_recog                   words {B, T, Ldec, 0, 0, 0}, pointers {ws, P, out}
+    //   G_CTC_NLM      CTC beam + LSTM LM, a frame  words {B, T/4, K, NLM serial, the offsets of enc_lens and of the head's logits in ws, in
+    //                  (ctc_first_pass)             4-byte units}, pointers {ws, P, the search's work buffer}
+    DecodeGraph decode_graphs[G_COUNT];
     struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
     bool prof = false;
