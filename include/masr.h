@@ -85,7 +85,7 @@ int masr_run_batch(masr_model* m, const float* xs, const int64_t* ilens, const i
  * the host's enqueue time 6x and leaves the step time unchanged -- the step is GPU-bound -- hence off by default.
  * counters: out[0] = steps launched kernel by kernel, out[1] = graphs captured, out[2] = steps replayed from a graph, out[3] = k-split GEMM
  * launches of the last step launched or captured (0 = whole reductions).  Captured graphs hold the launch geometry of the settings they were
- * captured under: masr_set_concurrency / masr_set_ksplit / masr_set_split_wgrad_launches / masr_set_specaug drop them (after a device synchronisation). */
+ * captured under: masr_set_concurrency / masr_set_ksplit / masr_set_split_wgrad_launches / masr_set_specaug / masr_set_chunk drop them (after a device synchronisation). */
 void masr_set_step_graphs(masr_model* m, int on);
 /* The Linear weight gradients of a step are ONE launch (the decoder-row tiles fill the CUs the encoder-row tiles leave idle); on: two
  * launches, encoder rows then decoder rows (A/B; identical bits -- each element of dW is reduced by one workgroup either way). */
@@ -149,6 +149,36 @@ int masr_specaug(const float* xs, const int32_t* lens_dev, float* out, int B, in
 int masr_set_specaug(masr_model* m, const masr_specaug_policy* p);
 /* device view of the augmented batch of the last masr_run_batch(MASR_TRAIN) under a policy: fp32 [B][T][D].  -1 if that step did not augment. */
 int masr_specaug_last(masr_model* m, const float** xa, int* B, int* T, int* D);
+
+/* Extension (the reference's encoder always attends over the whole utterance): a chunk mask on the ENCODER's self-attention, WeNet's U2 recipe for a
+ * first pass that does not depend on audio behind a bounded look-ahead (YAML asr_model.chunk).  Under a chunk of c >= 1 encoder frames
+ * (an encoder frame is 4 input frames) query i sees key j iff
+ *   j < klen_b (the key-padding mask, as without a chunk)  and  j < (i / c + 1) * c  and  (left < 0 or j >= (i / c - left) * c)
+ * (integer division): its own chunk whole, `left` chunks before it (-1: all of them), nothing behind it.  c = 1, left = -1 is the causal mask;
+ * c >= the encoder length with left = -1 masks nothing.  A query row without a visible key -- only with left >= 0, and only a padding row whose window
+ * starts at or behind klen_b -- gives an attention output of exactly 0 and passes exactly 0 to every gradient (WeNet zeroes such rows behind its
+ * softmax).  The decoder's self-attention stays causal and its cross-attention stays full: the attention decoder is the second pass.
+ *   size     >= 0: the chunk in encoder frames; 0 = full context
+ *   left     >= -1: earlier chunks a query may see; -1 = all
+ *   dynamic  0 / 1: 1 = every TRAINING step draws its chunk (`size` then only serves the passes that do not train; `left` is not drawn)
+ * Which chunk is in force: masr_run_batch(MASR_EVAL) and every masr_recog* (greedy, the beams, the CTC beams, rescoring, ctc_align: each runs one encoder
+ * forward) always use `size`.  masr_run_batch(MASR_TRAIN) uses `size`, or with dynamic = 1 the draw of its step -- all integers, from the step's 32-bit
+ * seed as masr_specaug forms it (step_seed, the dropout key and hash word, uni(w, r) = (uint64(w) * r) >> 32), with Tp = the batch's encoder frames:
+ *   w = the dropout hash word of (the dropout key of (step_seed, site 0x43484E4B), 0);  r = 1 + uni(w, Tp - 1);
+ *   Tp < 2 or r > Tp / 2 (integer division): full context (chunk 0);  otherwise c = r % 25 + 1, in [1, 25].
+ * so about half of the steps train with full context and the others with a chunk of at most a second of audio (WeNet's rule), and a resumed run
+ * draws what the uninterrupted one would have (masr_dropout_state).  The step's chunk travels in the per-step upload beside the seed, so a captured
+ * step graph replays with the current one.  A model without a policy runs the kernels it ran before, bit for bit. */
+typedef struct masr_chunk_policy {
+    int32_t size, left, dynamic;
+} masr_chunk_policy;
+/* the model's policy (null or all-zero: off, the default).  Changing it drops captured step graphs; size < 0, left < -1 or dynamic outside {0, 1}
+ * returns -1 with a message and leaves the old policy in place. */
+int masr_set_chunk(masr_model* m, const masr_chunk_policy* p);
+/* the stateless draw above on the host, at the (seed, step) masr_dropout_state reports before the step: 0 (full context) or the chunk in [1, 25] */
+int masr_chunk_draw(uint64_t seed, uint64_t step, int Tp);
+/* *size = the chunk the last masr_run_batch or masr_recog* ran its encoder with (0 = full context).  -1 before the first one. */
+int masr_chunk_last(masr_model* m, int* size);
 
 /* nn.utils.clip_grad_norm_(parameters, max_norm) (fo_meta_interface.py:148-149,242-243): norm only */
 int masr_grad_norm(masr_model* m, void* stream);

@@ -163,6 +163,12 @@ int masr_test_layernorm(const float* x, const float* gamma, const float* beta, c
 int masr_test_attention_dropout_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o, uint16_t* dq, uint16_t* dk,
                                     uint16_t* dv, float* lse, const int32_t* klens, int B, int H, int Tq, int Tk, int hd, int causal, float drop_p,
                                     uint32_t seed, uint32_t site, void* stream);
+/* ... under a chunk mask (include/masr.h masr_chunk_policy; Tq == Tk, causal == 0): `chunk` / `left` by value, or the chunk read from device
+ * memory where chunk_dev is non-null (then `chunk` is not read; a 0 there is full context).  -1 with a message, before any launch, for a chunk
+ * together with causal, Tq != Tk, chunk < 0 or left < -1.  chunk = 0 with chunk_dev = null is masr_test_attention_dropout_bwd. */
+int masr_test_attention_chunk(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o, uint16_t* dq, uint16_t* dk,
+                              uint16_t* dv, float* lse, const int32_t* klens, int B, int H, int Tq, int Tk, int hd, int causal, float drop_p,
+                              uint32_t seed, uint32_t site, int chunk, int left, const int32_t* chunk_dev, void* stream);
 int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o,
                         uint16_t* dq, uint16_t* dk, uint16_t* dv, float* lse, float* delta, const int32_t* klens,
                         int B, int H, int Tq, int Tk, int hd, int causal, void* stream);

@@ -21,6 +21,10 @@ class MasrSpecaugPolicy(C.Structure):
                 ("time_masks", C.c_int32), ("time_width", C.c_int32), ("time_ratio", C.c_float)]
 
 
+class MasrChunkPolicy(C.Structure):
+    _fields_ = [("size", C.c_int32), ("left", C.c_int32), ("dynamic", C.c_int32)]
+
+
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _SIGS = {
     "masr_version": (C.c_int, []),
@@ -51,6 +55,9 @@ _SIGS = {
     "masr_specaug": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(MasrSpecaugPolicy), C.c_uint64, C.c_uint64, vp]),
     "masr_set_specaug": (i32, [vp, C.POINTER(MasrSpecaugPolicy)]),
     "masr_specaug_last": (i32, [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "masr_set_chunk": (i32, [vp, C.POINTER(MasrChunkPolicy)]),
+    "masr_chunk_draw": (i32, [C.c_uint64, C.c_uint64, i32]),
+    "masr_chunk_last": (i32, [vp, C.POINTER(i32)]),
     "masr_grad_norm": (i32, [vp, vp]),
     "masr_clip_sgd_step": (i32, [vp, vp, f32, f32, f32, i32, i32, vp]),
     "masr_clip_grads": (i32, [vp, f32, vp]),
@@ -209,6 +216,7 @@ _SIGS = {
     "masr_test_layernorm_slab_floats": (i64, [i32, i32]),
     "masr_test_layernorm": (i32, [vp] * 13 + [i32, i32, f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_attention_dropout_bwd": (i32, [vp] * 10 + [i32] * 6 + [f32, C.c_uint32, C.c_uint32, vp]),
+    "masr_test_attention_chunk": (i32, [vp] * 10 + [i32] * 6 + [f32, C.c_uint32, C.c_uint32, i32, i32, vp, vp]),
     "masr_test_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "masr_test_lstm_shadows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "masr_test_lstm_unperm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),

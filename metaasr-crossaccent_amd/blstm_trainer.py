@@ -34,6 +34,8 @@ class ReduceLROnPlateau:
 def get_trainer(cls, config, paras, id2accent):
     if config['asr_model'].get('specaug') is not None:          # SpecAugment lives in the transformer engine's training step (engine.py specaug_of)
         raise ValueError("asr_model.specaug: transformer only")
+    if config['asr_model'].get('chunk') is not None:            # the chunk mask lives in the transformer encoder's self-attention (engine.py chunk_of)
+        raise ValueError("asr_model.chunk: transformer only")
     logger.notice("BLSTM Trainer Init...")
 
     class BLSTMTrainer(cls):

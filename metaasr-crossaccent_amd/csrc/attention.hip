@@ -125,8 +125,28 @@ __device__ __forceinline__ void store_rows_t(const f32x4 (&acc)[HD / 16], float 
 __device__ __forceinline__ float fold_groups_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float fold_groups_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 
+// The chunk mask of AttnArgs (template parameter CH of every kernel below; the CH = false instantiations hold none of it).  Query i sees
+// the keys [lo(i), hi(i)); key j is seen by the queries [qlo(j), qhi(j)): j < (i/c + 1) c <=> i >= (j/c) c, and j >= (i/c - left) c <=>
+// i < (j/c + left + 1) c.  All four are non-decreasing, so a workgroup's block range and a wave's `full` test come from its end rows, and
+// the element tests compare against two per-lane bounds formed once in front of the loop (no division inside it).
+struct ChunkWin {
+    int c, left;
+    __device__ __forceinline__ explicit ChunkWin(const AttnArgs& a) {
+        const int cc = a.chunk_ptr ? *a.chunk_ptr : a.chunk;
+        c = cc > 0 && cc < (1 << 30) ? cc : (1 << 30);      // 0: full context (one chunk holds every row)
+        left = a.left;
+    }
+    __device__ __forceinline__ int hi(int i) const { return (i / c + 1) * c; }
+    __device__ __forceinline__ int lo(int i) const { const int ci = i / c - left; return left >= 0 && ci > 0 ? ci * c : 0; }
+    __device__ __forceinline__ int qlo(int j) const { return (j / c) * c; }
+    __device__ __forceinline__ int qhi(int j) const {
+        const long v = ((long)(j / c) + left + 1) * c;
+        return left >= 0 && v < 0x7fffffffL ? (int)v : 0x7fffffff;
+    }
+};
+
 // ---------------------------------------------------------------------------- forward
-template <int HD>
+template <int HD, bool CH>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     using C = Cfg<HD>;
     constexpr int LD = C::LD, KS = C::KS, DT = C::DT;
@@ -160,19 +180,27 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    int nkb = (Tk + BLK - 1) / BLK;
+    int nkb = (Tk + BLK - 1) / BLK, kb0 = 0;
     if (a.causal) { const int lim = (q0 + BLK - 1) / BLK + 1; if (lim < nkb) nkb = lim; }
+    int khi = 0, klo = 0, whi = 0, wlo = 0;                 // chunk mask: visible keys of query qi [klo, khi); of every row of the wave [wlo, whi)
+    if constexpr (CH) {
+        const ChunkWin w(a);
+        khi = w.hi(qi); klo = w.lo(qi); whi = w.hi(qrow0); wlo = w.lo(qrow0 + 15);
+        // key blocks behind the last row's last visible key and in front of the first row's first one are never loaded
+        const int kend = min(w.hi(min(q0 + BLK, Tq) - 1), Tk);
+        nkb = (kend + BLK - 1) / BLK; kb0 = w.lo(q0) / BLK;
+    }
 
     TileRegs<HD> tk, tv;
-    tk.fetch(kb_, a.ldk, 0, Tk, tid);
-    tv.fetch(vb, a.ldv, 0, Tk, tid);
+    tk.fetch(kb_, a.ldk, kb0 * BLK, Tk, tid);
+    tv.fetch(vb, a.ldv, kb0 * BLK, Tk, tid);
     __syncthreads();                                        // (the zero fill)
     tk.commit(sK[0], Tk, tid);
     tv.commit(sV[0], Tk, tid);
-    if (nkb > 1) { tk.fetch(kb_, a.ldk, BLK, Tk, tid); tv.fetch(vb, a.ldv, BLK, Tk, tid); }
+    if (kb0 + 1 < nkb) { tk.fetch(kb_, a.ldk, (kb0 + 1) * BLK, Tk, tid); tv.fetch(vb, a.ldv, (kb0 + 1) * BLK, Tk, tid); }
     __syncthreads();
-    for (int kb = 0; kb < nkb; ++kb) {
-        const bf16* cK = sK[kb & 1]; const bf16* cV = sV[kb & 1];
+    for (int kb = kb0; kb < nkb; ++kb) {
+        const bf16* cK = sK[(kb - kb0) & 1]; const bf16* cV = sV[(kb - kb0) & 1];
         f32x4 s[4];                                         // S^T: keys jt*16 + 4g + r of query qi
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
@@ -185,7 +213,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
         // still produce the one-hot softmax torch does).  The backward forms fl(s scale) - lse with lse = fl(m scale) + log l: the SAME rounded
         // product on both sides (__fmul_rn: never contracted into an FMA), exact at the maximum.
         // A block without a masked element (wave-uniform test) skips the per-element index arithmetic and compares.
-        const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qrow0);
+        bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qrow0);
+        if constexpr (CH) full = full && kb * BLK + BLK <= whi && kb * BLK >= wlo;      // (a statement of its own: folded into the expression above, the unmasked kernel's schedule moved)
         float mx = NEG;
         if (!full) {
 #pragma unroll
@@ -193,7 +222,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int kj = kb * BLK + jt * 16 + g4 + r;
-                    if (kj >= klen || (a.causal && kj > qi)) s[jt][r] = NEG;
+                    if (kj >= klen || (a.causal && kj > qi) || (CH && (kj >= khi || kj < klo))) s[jt][r] = NEG;
                 }
         }
 #pragma unroll
@@ -228,14 +257,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
             for (int dt = 0; dt < DT; ++dt) o[dt] = mma16(frag_tr<LD>(cV, m2 * 32, dt * 16, lane), pf, o[dt]);
         }
         if (kb + 1 < nkb) {
-            tk.commit(sK[(kb + 1) & 1], Tk, tid);           // (that buffer was last read in iteration kb-1: behind its barrier)
-            tv.commit(sV[(kb + 1) & 1], Tk, tid);
+            tk.commit(sK[(kb - kb0 + 1) & 1], Tk, tid);     // (that buffer was last read in iteration kb-1: behind its barrier)
+            tv.commit(sV[(kb - kb0 + 1) & 1], Tk, tid);
             if (kb + 2 < nkb) { tk.fetch(kb_, a.ldk, (kb + 2) * BLK, Tk, tid); tv.fetch(vb, a.ldv, (kb + 2) * BLK, Tk, tid); }
             __syncthreads();
         }
     }
-    if (qi < Tq && lane < 16) a.lse[((long)b * a.H + h) * Tq + qi] = __fmul_rn(m, scale) + __logf(l);
-    store_rows_t<HD>(o, 1.f / l, a.o + (long)b * Tq * a.ldo + h * HD, a.ldo, qrow0, Tq, lane);
+    if constexpr (CH) {
+        // a row without a visible key (a padding row whose window starts at or behind klen): l == 0 exactly, o = 0 and lse = 0, never 0 / 0
+        const bool any = l > 0.f;
+        if (qi < Tq && lane < 16) a.lse[((long)b * a.H + h) * Tq + qi] = any ? __fmul_rn(m, scale) + __logf(l) : 0.f;
+        store_rows_t<HD>(o, any ? 1.f / l : 0.f, a.o + (long)b * Tq * a.ldo + h * HD, a.ldo, qrow0, Tq, lane);
+    } else {
+        if (qi < Tq && lane < 16) a.lse[((long)b * a.H + h) * Tq + qi] = __fmul_rn(m, scale) + __logf(l);
+        store_rows_t<HD>(o, 1.f / l, a.o + (long)b * Tq * a.ldo + h * HD, a.ldo, qrow0, Tq, lane);
+    }
 }
 
 // ---------------------------------------------------------------------------- backward
@@ -247,7 +283,7 @@ template <int HD> struct BwdSmem {
     static constexpr size_t TILE = sizeof(bf16) * BLK * LD;
     static constexpr size_t BYTES = 4 * TILE + sizeof(float) * 4 * BLK;
 };
-template <int HD>
+template <int HD, bool CH>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx, char* smem) {
     using C = Cfg<HD>;
     constexpr int LD = C::LD, KS = C::KS, DT = C::DT;
@@ -287,19 +323,27 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    int nkb = (Tk + BLK - 1) / BLK;
+    int nkb = (Tk + BLK - 1) / BLK, kb0 = 0;
     if (a.causal) { const int lim = (q0 + BLK - 1) / BLK + 1; if (lim < nkb) nkb = lim; }
+    int khi = 0, klo = 0, whi = 0, wlo = 0;                 // chunk mask, as in attn_fwd_kernel
+    if constexpr (CH) {
+        const ChunkWin w(a);
+        khi = w.hi(qi); klo = w.lo(qi); whi = w.hi(qrow0); wlo = w.lo(qrow0 + 15);
+        const int kend = min(w.hi(min(q0 + BLK, Tq) - 1), Tk);
+        nkb = (kend + BLK - 1) / BLK; kb0 = w.lo(q0) / BLK;
+    }
     TileRegs<HD> tk, tv;
-    tk.fetch(kb_, a.ldk, 0, Tk, tid);
-    tv.fetch(vb, a.ldv, 0, Tk, tid);
+    tk.fetch(kb_, a.ldk, kb0 * BLK, Tk, tid);
+    tv.fetch(vb, a.ldv, kb0 * BLK, Tk, tid);
     __syncthreads();
     tk.commit(sKb[0], Tk, tid);
     tv.commit(sVb[0], Tk, tid);
-    if (nkb > 1) { tk.fetch(kb_, a.ldk, BLK, Tk, tid); tv.fetch(vb, a.ldv, BLK, Tk, tid); }
+    if (kb0 + 1 < nkb) { tk.fetch(kb_, a.ldk, (kb0 + 1) * BLK, Tk, tid); tv.fetch(vb, a.ldv, (kb0 + 1) * BLK, Tk, tid); }
     __syncthreads();
-    for (int kb = 0; kb < nkb; ++kb) {
-        const bf16* cK = sKb[kb & 1]; const bf16* cV = sVb[kb & 1];
-        const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qrow0) && qrow0 + 16 <= Tq;   // nothing masked (wave-uniform)
+    for (int kb = kb0; kb < nkb; ++kb) {
+        const bf16* cK = sKb[(kb - kb0) & 1]; const bf16* cV = sVb[(kb - kb0) & 1];
+        const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qrow0) && qrow0 + 16 <= Tq &&
+                          (!CH || (kb * BLK + BLK <= whi && kb * BLK >= wlo));   // nothing masked (wave-uniform)
         // two halves of 32 keys: dS^T (keys jt*16 + 4g + r of query qi) of a half lives in 8 registers between its two products
 #pragma unroll
         for (int m2 = 0; m2 < 2; ++m2) {
@@ -320,7 +364,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
                     float p = __builtin_amdgcn_exp2f((__fmul_rn(s[r], scale) - lse) * LOG2E);
                     if (!full) {
                         const int kj = kb * BLK + jt * 16 + g4 + r;
-                        if (kj >= klen || (a.causal && kj > qi) || qi >= Tq) p = 0.f;
+                        if (kj >= klen || (a.causal && kj > qi) || qi >= Tq || (CH && (kj >= khi || kj < klo))) p = 0.f;
                     }
                     ds[j2][r] = p * (dp[r] * k4[r] - dl) * scale;
                 }
@@ -330,8 +374,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
             for (int dt = 0; dt < DT; ++dt) dq[dt] = mma16(frag_tr<LD>(cK, m2 * 32, dt * 16, lane), df, dq[dt]);
         }
         if (kb + 1 < nkb) {
-            tk.commit(sKb[(kb + 1) & 1], Tk, tid);
-            tv.commit(sVb[(kb + 1) & 1], Tk, tid);
+            tk.commit(sKb[(kb - kb0 + 1) & 1], Tk, tid);
+            tv.commit(sVb[(kb - kb0 + 1) & 1], Tk, tid);
             if (kb + 2 < nkb) { tk.fetch(kb_, a.ldk, (kb + 2) * BLK, Tk, tid); tv.fetch(vb, a.ldv, (kb + 2) * BLK, Tk, tid); }
             __syncthreads();
         }
@@ -339,7 +383,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, const int bx
     store_rows_t<HD>(dq, 1.f, a.dq + (long)b * Tq * a.lddq + h * HD, a.lddq, qrow0, Tq, lane);
 }
 
-template <int HD>
+template <int HD, bool CH>
 __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int bx, char* smem) {
     using C = Cfg<HD>;
     constexpr int LD = C::LD, KS = C::KS, DT = C::DT;
@@ -374,8 +418,16 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-    const int nqb = (Tq + BLK - 1) / BLK;
-    const int qb0 = a.causal ? k0 / BLK : 0;
+    int nqb = (Tq + BLK - 1) / BLK;
+    int qb0 = a.causal ? k0 / BLK : 0;
+    int qhi = 0, qlo = 0, whi = 0, wlo = 0;                 // chunk mask: the queries that see key kj [qlo, qhi); that see every key of the wave [wlo, whi)
+    if constexpr (CH) {
+        const ChunkWin w(a);
+        qhi = w.qhi(kj); qlo = w.qlo(kj); whi = w.qhi(krow0); wlo = w.qlo(krow0 + 15);
+        // query blocks in front of the first query that sees the key tile and behind the last one are never loaded
+        const int qend = min(w.qhi(min(k0 + BLK, Tk) - 1), Tq);
+        nqb = (qend + BLK - 1) / BLK; qb0 = w.qlo(k0) / BLK;
+    }
     TileRegs<HD> tq, tdo;
     float nlse = 0.f, ndl = 0.f;       // lse (threads 0..63) / delta (threads 4r..4r+3: row r) of the next query block
     auto fetch_q = [&](int qbi) {
@@ -421,7 +473,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
         const int cur = (qbi - qb0) & 1;
         const bf16* cQ = sQb[cur]; const bf16* cDO = sDOb[cur];
         const float* cLse = sStat + cur * 2 * BLK; const float* cDl = cLse + BLK;
-        const bool full = krow0 + 16 <= klen && qbi * BLK + BLK <= Tq && (!a.causal || krow0 + 15 <= qbi * BLK);      // nothing masked (wave-uniform)
+        const bool full = krow0 + 16 <= klen && qbi * BLK + BLK <= Tq && (!a.causal || krow0 + 15 <= qbi * BLK) &&
+                          (!CH || (qbi * BLK >= wlo && qbi * BLK + BLK <= whi));      // nothing masked (wave-uniform)
         // two halves of 32 queries: P / dS (queries jt*16 + 4g + r of key kj) of a half live in 16 registers between the products
 #pragma unroll
         for (int m2 = 0; m2 < 2; ++m2) {
@@ -441,7 +494,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
                 for (int r = 0; r < 4; ++r) {
                     const int qi = qbi * BLK + jt * 16 + g4 + r;
                     float p = __builtin_amdgcn_exp2f((__fmul_rn(st[r], scale) - ls4[r]) * LOG2E);
-                    if (!full && (kj >= klen || (a.causal && kj > qi) || qi >= Tq)) p = 0.f;
+                    if (!full && (kj >= klen || (a.causal && kj > qi) || qi >= Tq || (CH && (qi < qlo || qi >= qhi)))) p = 0.f;
                     float ms = 1.f;
                     if (a.drop_p > 0.f) ms = dropout_scale(dseed, a.site, dbase + (uint32_t)qi * (uint32_t)Tk, a.drop_p, inv_keep);
                     pt[j2][r] = p * ms;
@@ -468,11 +521,11 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, const int b
 
 // dQ and dK/dV of one attention as ONE grid: blocks [0, nqb) own 64 query rows each, the rest 64 key rows each.  The two
 // halves are independent given delta, so they overlap instead of queueing as two launch-latency-bound kernels.
-template <int HD>
+template <int HD, bool CH>
 __global__ __launch_bounds__(256, 3) void attn_bwd_kernel(AttnArgs a, int nqb) {
     __shared__ __attribute__((aligned(16))) char smem[BwdSmem<HD>::BYTES];
-    if ((int)blockIdx.x < nqb) attn_bwd_dq_body<HD>(a, blockIdx.x, smem);
-    else attn_bwd_dkv_body<HD>(a, blockIdx.x - nqb, smem);
+    if ((int)blockIdx.x < nqb) attn_bwd_dq_body<HD, CH>(a, blockIdx.x, smem);
+    else attn_bwd_dkv_body<HD, CH>(a, blockIdx.x - nqb, smem);
 }
 
 // ============================================================================ head dim 64: tiles through an LDS-DMA ring
@@ -535,7 +588,7 @@ __device__ __forceinline__ void ring_wait(int n) {
 // twice the independent work -- but 256 one-wave-per-SIMD workgroups run their chains without anyone to overlap with (forward 12.7 -> 13.2 us).
 // EIGHT waves of one row tile each stream the same bytes per row and keep two chains per SIMD; four waves serve short sequences (the decoder's 37 tokens).
 constexpr int FWD_NST = 4, BWD_NST = 3, STAT_BLKS = 8;
-template <int NW, int RT>
+template <int NW, int RT, bool CH>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
     constexpr int HD = 64, KS = 2, DT = 4, NST = FWD_NST, BQ = 16 * NW * RT, NT = 64 * NW, LT = 2 * 512 / NT;
     __shared__ __attribute__((aligned(1024))) bf16 ring[NST][2][RTILE];              // [stage][K | V]
@@ -558,10 +611,21 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[rt][ks] = frag_global<HD>(qb, a.ldq, qrow0 + rt * 16, Tq, ks, lane);
 
-    int nkb = (Tk + BLK - 1) / BLK;
+    int nkb = (Tk + BLK - 1) / BLK, kb0 = 0;
     if (a.causal) { const int lim = (q0 + BQ - 1) / BLK + 1; if (lim < nkb) nkb = lim; }
-    auto issue = [&](int kb) { bf16* st = ring[kb % NST][0]; ring_issue<NT>(st, kb_, a.ldk, kb * BLK, Tk, tid); ring_issue<NT>(st + RTILE, vb, a.ldv, kb * BLK, Tk, tid); };
-    for (int t = 0; t < NST - 1 && t < nkb; ++t) issue(t);
+    int khi[RT], klo[RT], whi[RT], wlo[RT];                 // chunk mask, as in attn_fwd_kernel, per row tile
+    if constexpr (CH) {
+        const ChunkWin w(a);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int qr = qrow0 + rt * 16;
+            khi[rt] = w.hi(qr + (lane & 15)); klo[rt] = w.lo(qr + (lane & 15)); whi[rt] = w.hi(qr); wlo[rt] = w.lo(qr + 15);
+        }
+        const int kend = min(w.hi(min(q0 + BQ, Tq) - 1), Tk);
+        nkb = (kend + BLK - 1) / BLK; kb0 = w.lo(q0) / BLK;   // the ring starts at kb0: no stage of a skipped block is issued, waited for or read
+    }
+    auto issue = [&](int kb) { bf16* st = ring[(kb - kb0) % NST][0]; ring_issue<NT>(st, kb_, a.ldk, kb * BLK, Tk, tid); ring_issue<NT>(st + RTILE, vb, a.ldv, kb * BLK, Tk, tid); };
+    for (int t = 0; t < NST - 1 && kb0 + t < nkb; ++t) issue(kb0 + t);
 
     const float sc2 = scale * LOG2E;
     float m[RT], l[RT];                                     // of query qi (the same in the four lane groups); m in units of q.k
@@ -575,11 +639,11 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
         for (int dt = 0; dt < DT; ++dt) o[rt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-    for (int kb = 0; kb < nkb; ++kb) {
+    for (int kb = kb0; kb < nkb; ++kb) {
         ring_wait<LT>(nkb - 1 - kb < NST - 2 ? nkb - 1 - kb : NST - 2);
         __builtin_amdgcn_s_barrier();                       // block kb landed for every wave; stage (kb-1) % NST is no longer read
         if (kb + NST - 1 < nkb) issue(kb + NST - 1);
-        const bf16* cK = ring[kb % NST][0]; const bf16* cV = cK + RTILE;
+        const bf16* cK = ring[(kb - kb0) % NST][0]; const bf16* cV = cK + RTILE;
         f32x4 s[RT][4];
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
@@ -597,7 +661,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const int qr = qrow0 + rt * 16, qi = qr + (lane & 15);
-            const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qr);
+            const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qr) && (!CH || (kb * BLK + BLK <= whi[rt] && kb * BLK >= wlo[rt]));
             float mx = NEG;
             if (!full) {
 #pragma unroll
@@ -605,7 +669,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int kj = kb * BLK + jt * 16 + g4 + r;
-                        if (kj >= klen || (a.causal && kj > qi)) s[rt][jt][r] = NEG;
+                        if (kj >= klen || (a.causal && kj > qi) || (CH && (kj >= khi[rt] || kj < klo[rt]))) s[rt][jt][r] = NEG;
                     }
             }
 #pragma unroll
@@ -648,12 +712,18 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_ring_kernel(AttnArgs a) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int qi = qrow0 + rt * 16 + (lane & 15);
+        if constexpr (CH) {                                 // (a row without a visible key: o = 0, lse = 0 -- see attn_fwd_kernel)
+            const bool any = l[rt] > 0.f;
+            if (qi < Tq && lane < 16) a.lse[((long)b * a.H + h) * Tq + qi] = any ? __fmul_rn(m[rt], scale) + __logf(l[rt]) : 0.f;
+            store_rows_t<HD>(o[rt], any ? 1.f / l[rt] : 0.f, a.o + (long)b * Tq * a.ldo + h * HD, a.ldo, qrow0 + rt * 16, Tq, lane);
+            continue;
+        }
         if (qi < Tq && lane < 16) a.lse[((long)b * a.H + h) * Tq + qi] = __fmul_rn(m[rt], scale) + __logf(l[rt]);
         store_rows_t<HD>(o[rt], 1.f / l[rt], a.o + (long)b * Tq * a.ldo + h * HD, a.ldo, qrow0 + rt * 16, Tq, lane);
     }
 }
 
-template <int NW, int RT>
+template <int NW, int RT, bool CH>
 __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx, bf16* ringp) {
     constexpr int HD = 64, KS = 2, DT = 4, NST = BWD_NST, BQ = 16 * NW * RT, NT = 64 * NW, LT = 2 * 512 / NT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -688,10 +758,21 @@ __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx
         lse[rt] = qi < Tq ? a.lse[((long)b * a.H + h) * Tq + qi] : 0.f;
         dbase[rt] = (uint32_t)((((long)b * a.H + h) * Tq + qi) * Tk);
     }
-    int nkb = (Tk + BLK - 1) / BLK;
+    int nkb = (Tk + BLK - 1) / BLK, kb0 = 0;
     if (a.causal) { const int lim = (q0 + BQ - 1) / BLK + 1; if (lim < nkb) nkb = lim; }
-    auto issue = [&](int kb) { bf16* st = ringp + (kb % NST) * 2 * RTILE; ring_issue<NT>(st, kb_, a.ldk, kb * BLK, Tk, tid); ring_issue<NT>(st + RTILE, vb, a.ldv, kb * BLK, Tk, tid); };
-    for (int t = 0; t < NST - 1 && t < nkb; ++t) issue(t);
+    int khi[RT], klo[RT], whi[RT], wlo[RT];                 // chunk mask, as in attn_fwd_ring_kernel
+    if constexpr (CH) {
+        const ChunkWin w(a);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int qr = qrow0 + rt * 16;
+            khi[rt] = w.hi(qr + (lane & 15)); klo[rt] = w.lo(qr + (lane & 15)); whi[rt] = w.hi(qr); wlo[rt] = w.lo(qr + 15);
+        }
+        const int kend = min(w.hi(min(q0 + BQ, Tq) - 1), Tk);
+        nkb = (kend + BLK - 1) / BLK; kb0 = w.lo(q0) / BLK;
+    }
+    auto issue = [&](int kb) { bf16* st = ringp + ((kb - kb0) % NST) * 2 * RTILE; ring_issue<NT>(st, kb_, a.ldk, kb * BLK, Tk, tid); ring_issue<NT>(st + RTILE, vb, a.ldv, kb * BLK, Tk, tid); };
+    for (int t = 0; t < NST - 1 && kb0 + t < nkb; ++t) issue(kb0 + t);
     f32x4 dq[RT][DT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -700,11 +781,11 @@ __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx
         for (int dt = 0; dt < DT; ++dt) dq[rt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-    for (int kb = 0; kb < nkb; ++kb) {
+    for (int kb = kb0; kb < nkb; ++kb) {
         ring_wait<LT>(nkb - 1 - kb < NST - 2 ? nkb - 1 - kb : NST - 2);
         __builtin_amdgcn_s_barrier();
         if (kb + NST - 1 < nkb) issue(kb + NST - 1);
-        const bf16* cK = ringp + (kb % NST) * 2 * RTILE; const bf16* cV = cK + RTILE;
+        const bf16* cK = ringp + ((kb - kb0) % NST) * 2 * RTILE; const bf16* cV = cK + RTILE;
 #pragma unroll
         for (int m2 = 0; m2 < 2; ++m2) {
             f32x4 ds[RT][2];
@@ -717,7 +798,8 @@ __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     const int qr = qrow0 + rt * 16, qi = qr + (lane & 15);
-                    const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qr) && qr + 16 <= Tq;
+                    const bool full = kb * BLK + BLK <= klen && (!a.causal || kb * BLK + BLK - 1 <= qr) && qr + 16 <= Tq &&
+                                      (!CH || (kb * BLK + BLK <= whi[rt] && kb * BLK >= wlo[rt]));
                     f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
@@ -731,7 +813,7 @@ __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx
                         float p = __builtin_amdgcn_exp2f((__fmul_rn(s[r], scale) - lse[rt]) * LOG2E);
                         if (!full) {
                             const int kj = kb * BLK + jt * 16 + g4 + r;
-                            if (kj >= klen || (a.causal && kj > qi) || qi >= Tq) p = 0.f;
+                            if (kj >= klen || (a.causal && kj > qi) || qi >= Tq || (CH && (kj >= khi[rt] || kj < klo[rt]))) p = 0.f;
                         }
                         ds[rt][j2][r] = p * (dp[r] * k4[r] - dl[rt]) * scale;
                     }
@@ -752,7 +834,7 @@ __device__ __forceinline__ void attn_bwd_ring_dq(const AttnArgs& a, const int bx
     for (int rt = 0; rt < RT; ++rt) store_rows_t<HD>(dq[rt], 1.f, a.dq + (long)b * Tq * a.lddq + h * HD, a.lddq, qrow0 + rt * 16, Tq, lane);
 }
 
-template <int NW, int RT>
+template <int NW, int RT, bool CH>
 __device__ __forceinline__ void attn_bwd_ring_dkv(const AttnArgs& a, const int bx, bf16* ringp, float* sStat) {
     constexpr int HD = 64, KS = 2, DT = 4, NST = BWD_NST, BK = 16 * NW * RT, NT = 64 * NW, LT = 2 * 512 / NT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -786,8 +868,19 @@ __device__ __forceinline__ void attn_bwd_ring_dkv(const AttnArgs& a, const int b
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) { dk[rt][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[rt][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-    const int nqb = (Tq + BLK - 1) / BLK;
-    const int qb0 = a.causal ? k0 / BLK : 0;
+    int nqb = (Tq + BLK - 1) / BLK;
+    int qb0 = a.causal ? k0 / BLK : 0;
+    int qhi[RT], qlo[RT], whi[RT], wlo[RT];                 // chunk mask, as in attn_bwd_dkv_body, per row tile
+    if constexpr (CH) {
+        const ChunkWin w(a);
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const int kr = krow0 + rt * 16;
+            qhi[rt] = w.qhi(kr + (lane & 15)); qlo[rt] = w.qlo(kr + (lane & 15)); whi[rt] = w.qhi(kr); wlo[rt] = w.qlo(kr + 15);
+        }
+        const int qend = min(w.qhi(min(k0 + BK, Tk) - 1), Tq);
+        nqb = (qend + BLK - 1) / BLK; qb0 = w.qlo(k0) / BLK;   // the ring and the statistics groups start at qb0 and end at nqb
+    }
     auto issue = [&](int qbi) {
         bf16* st = ringp + ((qbi - qb0) % NST) * 2 * RTILE;
         ring_issue<NT>(st, qb, a.ldq, qbi * BLK, Tq, tid); ring_issue<NT>(st + RTILE, dob, a.lddo, qbi * BLK, Tq, tid);
@@ -860,7 +953,8 @@ __device__ __forceinline__ void attn_bwd_ring_dkv(const AttnArgs& a, const int b
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     const int kr = krow0 + rt * 16, kj = kr + (lane & 15);
-                    const bool full = kr + 16 <= klen && qbi * BLK + BLK <= Tq && (!a.causal || kr + 15 <= qbi * BLK);
+                    const bool full = kr + 16 <= klen && qbi * BLK + BLK <= Tq && (!a.causal || kr + 15 <= qbi * BLK) &&
+                                      (!CH || (qbi * BLK >= wlo[rt] && qbi * BLK + BLK <= whi[rt]));
                     f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f}, dpt = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
@@ -871,7 +965,7 @@ __device__ __forceinline__ void attn_bwd_ring_dkv(const AttnArgs& a, const int b
                     for (int r = 0; r < 4; ++r) {
                         const int qi = qbi * BLK + jt * 16 + g4 + r;
                         float p = __builtin_amdgcn_exp2f((__fmul_rn(st[r], scale) - ls4[r]) * LOG2E);
-                        if (!full && (kj >= klen || (a.causal && kj > qi) || qi >= Tq)) p = 0.f;
+                        if (!full && (kj >= klen || (a.causal && kj > qi) || qi >= Tq || (CH && (qi < qlo[rt] || qi >= qhi[rt])))) p = 0.f;
                         float ms = 1.f;
                         if (a.drop_p > 0.f) ms = dropout_scale(dseed, a.site, dbase[rt] + (uint32_t)qi * (uint32_t)Tk, a.drop_p, inv_keep);
                         pt[rt][j2][r] = p * ms;
@@ -899,26 +993,26 @@ __device__ __forceinline__ void attn_bwd_ring_dkv(const AttnArgs& a, const int b
         store_rows_t<HD>(dv[rt], 1.f, a.dv + (long)b * Tk * a.lddv + h * HD, a.lddv, krow0 + rt * 16, Tk, lane);
     }
 }
-template <int NW, int RQ, int RK>
+template <int NW, int RQ, int RK, bool CH>
 __global__ __launch_bounds__(64 * NW, (NW > 4 || RQ > 1 || RK > 1) ? 2 : 3) void attn_bwd_ring_kernel(AttnArgs a, int nqb) {
     __shared__ __attribute__((aligned(1024))) bf16 ring[BWD_NST * 2 * RTILE];
     __shared__ __attribute__((aligned(16))) float stat[2 * STAT_BLKS * BLK];
-    if ((int)blockIdx.x < nqb) attn_bwd_ring_dq<NW, RQ>(a, blockIdx.x, ring);
-    else attn_bwd_ring_dkv<NW, RK>(a, blockIdx.x - nqb, ring, stat);
+    if ((int)blockIdx.x < nqb) attn_bwd_ring_dq<NW, RQ, CH>(a, blockIdx.x, ring);
+    else attn_bwd_ring_dkv<NW, RK, CH>(a, blockIdx.x - nqb, ring, stat);
 }
 
-template <int HD>
+template <int HD, bool CH>
 int launch_fwd(const AttnArgs& a, hipStream_t s) {
     constexpr int long_min = 65;                             // sequences from this length on: 128-row workgroups (8 waves x 1 row tile)
     if (HD == 64) {
-        if (a.Tq < long_min) hipLaunchKernelGGL((attn_fwd_ring_kernel<4, 1>), dim3((a.Tq + 63) / 64, a.H, a.B), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((attn_fwd_ring_kernel<8, 1>), dim3((a.Tq + 127) / 128, a.H, a.B), dim3(512), 0, s, a);
+        if (a.Tq < long_min) hipLaunchKernelGGL((attn_fwd_ring_kernel<4, 1, CH>), dim3((a.Tq + 63) / 64, a.H, a.B), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((attn_fwd_ring_kernel<8, 1, CH>), dim3((a.Tq + 127) / 128, a.H, a.B), dim3(512), 0, s, a);
     } else {
-        hipLaunchKernelGGL(attn_fwd_kernel<HD>, dim3((a.Tq + BLK - 1) / BLK, a.H, a.B), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((attn_fwd_kernel<HD, CH>), dim3((a.Tq + BLK - 1) / BLK, a.H, a.B), dim3(256), 0, s, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-template <int HD>
+template <int HD, bool CH>
 int launch_bwd(const AttnArgs& a, hipStream_t s) {
     constexpr int long_min = 65;
     if (HD == 64) {
@@ -930,21 +1024,25 @@ int launch_bwd(const AttnArgs& a, hipStream_t s) {
             const int rq = lq ? 2 : 1, rk = lk ? 2 : 1;
             const int nqb = (a.Tq + 64 * rq - 1) / (64 * rq), nkb = (a.Tk + 64 * rk - 1) / (64 * rk);
             const dim3 grid(nqb + nkb, a.H, a.B);
-            if (rq == 2 && rk == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 2, 2>), grid, dim3(256), 0, s, a, nqb);
-            else if (rq == 1 && rk == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 1, 2>), grid, dim3(256), 0, s, a, nqb);
-            else if (rq == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 2, 1>), grid, dim3(256), 0, s, a, nqb);
-            else hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 1, 1>), grid, dim3(256), 0, s, a, nqb);
+            if (rq == 2 && rk == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 2, 2, CH>), grid, dim3(256), 0, s, a, nqb);
+            else if (rq == 1 && rk == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 1, 2, CH>), grid, dim3(256), 0, s, a, nqb);
+            else if (rq == 2) hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 2, 1, CH>), grid, dim3(256), 0, s, a, nqb);
+            else hipLaunchKernelGGL((attn_bwd_ring_kernel<4, 1, 1, CH>), grid, dim3(256), 0, s, a, nqb);
         }
     } else {
         const int nqb = (a.Tq + BLK - 1) / BLK, nkb = (a.Tk + BLK - 1) / BLK;
-        hipLaunchKernelGGL(attn_bwd_kernel<HD>, dim3(nqb + nkb, a.H, a.B), dim3(256), 0, s, a, nqb);
+        hipLaunchKernelGGL((attn_bwd_kernel<HD, CH>), dim3(nqb + nkb, a.H, a.B), dim3(256), 0, s, a, nqb);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+bool chunked(const AttnArgs& a) { return a.chunk > 0 || a.chunk_ptr != nullptr; }
 bool check(const AttnArgs& a) {
     if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7)) { mk_set_error("mk_attn", "row strides must be multiples of 8"); return false; }
     if (a.hd != 16 && a.hd != 32 && a.hd != 64) { mk_set_error("mk_attn", "head dim must be 16, 32 or 64"); return false; }
+    if (a.chunk < 0 || a.left < -1) { mk_set_error("mk_attn", "chunk mask: need chunk >= 0 and left >= -1"); return false; }
+    if (chunked(a) && a.causal) { mk_set_error("mk_attn", "chunk mask: not together with the causal mask"); return false; }
+    if (chunked(a) && a.Tq != a.Tk) { mk_set_error("mk_attn", "chunk mask: self-attention only (Tq == Tk)"); return false; }
     return true;
 }
 
@@ -952,14 +1050,16 @@ bool check(const AttnArgs& a) {
 
 int mk_attn_fwd(const AttnArgs& a, hipStream_t s) {
     if (!check(a)) return -1;
-    if (a.hd == 64) return launch_fwd<64>(a, s);
-    if (a.hd == 32) return launch_fwd<32>(a, s);
-    return launch_fwd<16>(a, s);
+    if (chunked(a)) return a.hd == 64 ? launch_fwd<64, true>(a, s) : a.hd == 32 ? launch_fwd<32, true>(a, s) : launch_fwd<16, true>(a, s);
+    if (a.hd == 64) return launch_fwd<64, false>(a, s);
+    if (a.hd == 32) return launch_fwd<32, false>(a, s);
+    return launch_fwd<16, false>(a, s);
 }
 int mk_attn_bwd(const AttnArgs& a, hipStream_t s) {
     if (!check(a)) return -1;
     if ((a.lddo & 7)) { mk_set_error("mk_attn_bwd", "lddo must be a multiple of 8"); return -1; }
-    if (a.hd == 64) return launch_bwd<64>(a, s);
-    if (a.hd == 32) return launch_bwd<32>(a, s);
-    return launch_bwd<16>(a, s);
+    if (chunked(a)) return a.hd == 64 ? launch_bwd<64, true>(a, s) : a.hd == 32 ? launch_bwd<32, true>(a, s) : launch_bwd<16, true>(a, s);
+    if (a.hd == 64) return launch_bwd<64, false>(a, s);
+    if (a.hd == 32) return launch_bwd<32, false>(a, s);
+    return launch_bwd<16, false>(a, s);
 }

@@ -367,6 +367,22 @@ int masr_set_specaug(masr_model* m, const masr_specaug_policy* p) {
     m->aug = q; m->aug_on = on;
     return 0;
 }
+int masr_chunk_draw(uint64_t seed, uint64_t step, int Tp) { return chunk_draw_of(step_seed_of(seed, step), Tp); }
+int masr_set_chunk(masr_model* m, const masr_chunk_policy* p) {
+    masr_chunk_policy q{0, -1, 0};
+    if (p) q = *p;
+    if (q.size < 0 || q.left < -1 || (q.dynamic != 0 && q.dynamic != 1)) { mk_set_error("masr_set_chunk", "need size >= 0, left >= -1, dynamic in {0, 1}"); return -1; }
+    const bool on = q.size > 0 || q.dynamic != 0;
+    if (!on) q = masr_chunk_policy{0, -1, 0};
+    if (on != m->chunk_on || memcmp(&q, &m->chunk, sizeof q)) drop_step_graphs(m);            // (chunk and left are kernel arguments of the captured launches)
+    m->chunk = q; m->chunk_on = on;
+    return 0;
+}
+int masr_chunk_last(masr_model* m, int* size) {
+    if (m->chunk_last < 0 || !size) { mk_set_error("masr_chunk_last", "no encoder forward yet (or a null pointer)"); return -1; }
+    *size = m->chunk_last;
+    return 0;
+}
 int masr_specaug_last(masr_model* m, const float** xa, int* B, int* T, int* D) {
     if (!m->have_acts || !m->aug_ran || !m->acts.xa) { mk_set_error("masr_specaug_last", "the last step did not augment (no policy, MASR_EVAL, or no step yet)"); return -1; }
     *xa = m->acts.xa; *B = m->acts.B; *T = m->acts.T; *D = m->acts.D;

@@ -27,7 +27,7 @@ struct Acts {
     int B, T, D, H2, W2, Tp, Dp, L, rows_e, rows_d;
     int *tok_in, *gold, *enc_lens, *step_dev;
     int *tok_order, *tok_start;             // decoder-input token positions sorted by token id + the C + 1 segment starts (embedding backward)
-    uint32_t* meta;                                        // [8] behind enc_lens, same upload: [0] dropout seed of the step, [1] 1/n_total (float bits)
+    uint32_t* meta;                                        // [8] behind enc_lens, same upload: [0] dropout seed of the step, [1] 1/n_total (float bits), [2] the step's chunk (masr_set_chunk; 0 = none)
     bf16* step_qkv;                                        // incremental decode: the newest position's q|k|v [B][3E]
     bf16 *a1, *p1, *a3, *p2;
     unsigned long long *a1_bits, *a3_bits;                           // ReLU mask of a1, one word per pixel (written by conv1's forward, read by conv2's fused dgrad)
@@ -102,6 +102,8 @@ struct masr_model {
     uint64_t seed = 0x1234; uint64_t step = 0;
     masr_specaug_policy aug{}; bool aug_on = false;        // masr_set_specaug
     bool aug_ran = false;                                  // the last masr_run_batch left its augmented batch in acts.xa (masr_specaug_last)
+    masr_chunk_policy chunk{0, -1, 0}; bool chunk_on = false;   // masr_set_chunk: the chunk mask of the encoder's self-attention
+    int chunk_last = -1;                                   // the chunk the last encoder forward ran with (masr_chunk_last; 0 = full context, -1 = none yet)
     Acts acts; bool have_acts = false;
     LnReduceGroup lng; int64_t ln_slab_used = 0;           // LayerNorm dgamma/dbeta partials, folded by one grouped launch
     bool split_wgrad = false;                              // masr_set_split_wgrad_launches
@@ -170,10 +172,24 @@ inline GemmArgs lin_fwd_args(const bf16* x, long ldx, const bf16* wk, int M, int
 inline uint32_t step_seed_of(uint64_t seed, uint64_t step) { return (uint32_t)(seed * 0x9E3779B97F4A7C15ull >> 32) + (uint32_t)step * 7919u; }
 // host check of a policy against the batch geometry it will run on; null, or what is wrong (engine.hip)
 const char* specaug_policy_error(const masr_specaug_policy& p, int D);
+// the chunk a dynamic policy's training step runs with, from the step's 32-bit seed (include/masr.h masr_chunk_policy; 0 = full context).
+// The hash of common.h (mix32, dropout_key, dropout_word) on the host: one word per step
+inline uint32_t host_mix32(uint32_t x) { x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16; return x; }
+inline int chunk_draw_of(uint32_t step_seed, int Tp) {
+    if (Tp < 2) return 0;
+    const uint32_t key = host_mix32(step_seed * 0x9E3779B1u + 0x43484E4Bu * 0x85EBCA77u + 0x632BE5ABu), w = host_mix32(0u ^ key);
+    const int r = 1 + (int)(((uint64_t)w * (uint64_t)(Tp - 1)) >> 32);
+    return r > Tp / 2 ? 0 : r % 25 + 1;
+}
 
 // seed_ptr / inv_ptr: non-null while a step is being captured into a graph -- the dropout seed and 1/n_total of the step
 // then live in device memory (Acts::meta, uploaded with the tokens), so one captured launch sequence serves every step
-struct Ctx { masr_model* m; hipStream_t s; uint32_t seed; bool train; float p_drop, p_pos; const uint32_t* seed_ptr = nullptr; const float* inv_ptr = nullptr; };
+// chunk / left / chunk_ptr: the chunk mask of the encoder's self-attention in this pass (masr_set_chunk; 0: none).  Training passes get it from
+// masr_run_batch -- chunk_ptr (Acts::meta + 2) under capture of a dynamic policy's step --, every other pass from forward_encoder itself.
+struct Ctx {
+    masr_model* m; hipStream_t s; uint32_t seed; bool train; float p_drop, p_pos; const uint32_t* seed_ptr = nullptr; const float* inv_ptr = nullptr;
+    int chunk = 0, left = -1; const int* chunk_ptr = nullptr;
+};
 
 inline int gemm(Ctx& c, const GemmArgs& g) {
     const int re = c.m->acts.rows_e;

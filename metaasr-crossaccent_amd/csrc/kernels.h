@@ -110,6 +110,11 @@ struct AttnArgs {
     int B, H, Tq, Tk, hd, causal;
     float drop_p; uint32_t seed, site;
     const uint32_t* seed_ptr;                    // non-null: the seed is read from device memory (graph-replayed steps)
+    // chunk mask (include/masr.h masr_chunk_policy; needs Tq == Tk and causal == 0): query i sees key j iff j < (i / c + 1) c and
+    // (left < 0 or j >= (i / c - left) c).  chunk = 0 and chunk_ptr = null: no mask, the kernels without it.  A chunk read as 0 from
+    // chunk_ptr is full context inside the masked kernels (a dynamic policy's step that drew none).
+    int chunk, left;
+    const int* chunk_ptr;                        // non-null: the chunk is read from device memory (graph-replayed steps)
 };
 int mk_attn_fwd(const AttnArgs& a, hipStream_t s);
 int mk_attn_bwd(const AttnArgs& a, hipStream_t s);

@@ -78,9 +78,10 @@ static int gemm_or_ksplit(Ctx& c, GemmArgs g, LnSumArgs* defer, const LnSumArgs&
 // nb: the attention's batches, rows_q = nb * Tq query rows
 int attn_block_fwd(Ctx& c, const Attn& at, const bf16* xq, int rows_q, int nb, int Tq, int Tk, bool self, bool causal, const int* klens,
                    bf16* qkv_or_q, bf16* kv, bf16* ao, float* lse, const float* resid, float* s_out, uint32_t site_p, uint32_t site_o,
-                   LnSumArgs* defer = nullptr) {
+                   LnSumArgs* defer = nullptr, bool chunk = false) {
     masr_model* m = c.m; const int E = m->E; const float* P = m->P;
     AttnArgs a{};
+    if (chunk) { a.chunk = c.chunk; a.left = c.left; a.chunk_ptr = c.chunk_ptr; }      // the encoder's self-attention under masr_set_chunk
     if (self) {
         GemmArgs g = lin_fwd_args(xq, E, at.in.k16, rows_q, 3 * E, E, P + at.in.b); g.C16 = qkv_or_q; g.ldc16 = 3 * E;
         CK(gemm(c, g));
@@ -159,6 +160,8 @@ int ffn_bwd(Ctx& c, const Lin& l1, const Lin& l2, const bf16* x16, const bf16* f
 int forward_encoder(Ctx& c, const float* xs) {
     masr_model* m = c.m; Acts& a = m->acts; hipStream_t s = c.s; const float* P = m->P;
     const int B = a.B, T = a.T, D = a.D, E = m->E;
+    // every pass that does not train (MASR_EVAL, the decoders) runs under the policy's own chunk; a training pass brings the step's along
+    if (!c.train) { c.chunk = m->chunk.size; c.left = m->chunk.left; c.chunk_ptr = nullptr; m->chunk_last = c.chunk; }
     uint32_t site = 1;
     {
         Prof p(m, MASR_PROF_CONV1_FWD, s);
@@ -188,7 +191,7 @@ int forward_encoder(Ctx& c, const float* xs) {
         EncAct& e = a.enc[l]; const EncL& w = m->enc[l];
         for (int i = 0; i < 4; ++i) e.site[i] = site++;
         CK(attn_block_fwd(c, w.sa, a.x16[l], a.rows_e, a.B, a.Tp, a.Tp, true, false, a.enc_lens, e.qkv, nullptr, e.ao, e.lse, a.x32[l], e.s1,
-                          e.site[0], e.site[1]));
+                          e.site[0], e.site[1], nullptr, true));
         CK(ln_fwd(c, w.n1, e.s1, e.x1_32, e.x1_16, e.m1, e.r1, a.rows_e));
         CK(ffn_fwd(c, w.l1, w.l2, e.x1_16, e.x1_32, a.rows_e, e.f, e.s2, e.site[2], e.site[3]));
         CK(ln_fwd(c, w.n2, e.s2, a.x32[l + 1], a.x16[l + 1], e.m2, e.r2, a.rows_e));
@@ -248,7 +251,8 @@ int forward_decoder(Ctx& c, bool project_kv, bool logits_f32, const DecoderGeom*
 //   cross: writes d xq (fp32) = gs32 + q-proj dgrad into gout and d K|V into gkv, this layer's columns of gkv_all (memory_kv_bwd takes them on)
 static int attn_block_bwd(Ctx& c, const Attn& at, const bf16* xq16, int rows_q, int Tq, int Tk, bool self, bool causal, const int* klens,
                           const bf16* qkv_or_q, const bf16* kv, const bf16* ao, const float* lse, const float* gs32, const bf16* gs16, bf16* gao,
-                          bf16* gqkv_or_q, bf16* gkv, float* delta, float* gout, uint32_t site_p, bool split, LnSumArgs* defer = nullptr) {
+                          bf16* gqkv_or_q, bf16* gkv, float* delta, float* gout, uint32_t site_p, bool split, LnSumArgs* defer = nullptr,
+                          bool chunk = false) {
     masr_model* m = c.m; const int E = m->E; float* G = m->G;
     CK(lin_wgrad(c, gs16, E, ao, E, rows_q, E, E, G + at.out.w, G + at.out.b, split));
     { GemmArgs g = lin_dgrad_args(gs16, E, at.out.t16, E, rows_q, E, E); g.C16 = gao; g.ldc16 = E; CK(gemm(c, g)); }
@@ -262,6 +266,7 @@ static int attn_block_bwd(Ctx& c, const Attn& at, const bf16* xq16, int rows_q, 
     }
     a.o = const_cast<bf16*>(ao); a.ldo = E; a.lse = const_cast<float*>(lse); a.dout = gao; a.lddo = E; a.delta = delta; a.klens = klens;
     a.B = m->acts.B; a.H = m->H; a.Tq = Tq; a.Tk = Tk; a.hd = m->hd; a.causal = causal; a.drop_p = c.p_drop; a.seed = c.seed; a.seed_ptr = c.seed_ptr; a.site = site_p;
+    if (chunk) { a.chunk = c.chunk; a.left = c.left; a.chunk_ptr = c.chunk_ptr; }      // the mask of the forward (attn_block_fwd)
     { Prof p(m, Tk == m->acts.Tp && Tq == Tk ? MASR_PROF_ATTN_ENC : MASR_PROF_ATTN_DEC, c.s); CK(mk_attn_bwd(a, c.s)); }
     if (self) {
         CK(lin_wgrad(c, gqkv_or_q, 3 * E, xq16, E, rows_q, 3 * E, E, G + at.in.w, G + at.in.b, split));
@@ -362,7 +367,7 @@ static int backward(Ctx& c, const float* xs) {
         CK(ffn_bwd(c, w.l1, w.l2, e.x1_16, e.f, gs, eg.g2, a.rows_e, eg.gf, gcur, true));
         CK(ln_bwd(c, w.n1, gcur, e.s1, e.m1, e.r1, gs, eg.g1, e.site[1], a.rows_e));
         CK(attn_block_bwd(c, w.sa, a.x16[l], a.rows_e, a.Tp, a.Tp, true, false, a.enc_lens, e.qkv, nullptr, e.ao, e.lse, gs, eg.g1, a.gao_e,
-                          eg.gqkv, nullptr, a.delta_e, gcur, e.site[0], true));
+                          eg.gqkv, nullptr, a.delta_e, gcur, e.site[0], true, nullptr, true));
     }
     // ---- vgg2enc (through the positional dropout)
     { Prof p(m, MASR_PROF_MISC, s); CK(mk_cast_dropout(gcur, a.ge16, (long)a.rows_e * E, c.p_pos, c.seed, a.site_v2e, s, c.seed_ptr)); }
@@ -476,7 +481,11 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
           train ? m->cfg.dropout : 0.f, train ? m->cfg.pos_dropout : 0.f};
     m->step++;
     const float inv_ntot = 1.0f / (float)ntot;
-    std::memcpy(h_len + B, &c.seed, 4); std::memcpy(h_len + B + 1, &inv_ntot, 4);     // Acts::meta
+    // the chunk mask of this step's encoder self-attention (masr_set_chunk): the policy's size, or a dynamic policy's draw for a training step
+    const bool chunk_dyn = train && m->chunk_on && m->chunk.dynamic;
+    c.chunk = chunk_dyn ? chunk_draw_of(c.seed, a.Tp) : m->chunk.size; c.left = m->chunk.left;
+    m->chunk_last = c.chunk;
+    std::memcpy(h_len + B, &c.seed, 4); std::memcpy(h_len + B + 1, &inv_ntot, 4); h_len[B + 2] = c.chunk;     // Acts::meta
     {   // the decoder-input positions grouped by token (counting sort, stable: ascending position inside a token) for the embedding backward.
         // Only the positions 0 .. olens[b] of an utterance: behind them the inputs are eos padding whose gradient is exactly zero (their
         // outputs carry no loss, and the causal mask keeps every valid output from reading them) -- hundreds of hits on ONE table row
@@ -538,6 +547,7 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
         }
         masr_model::StepGraph ng{B, T, L, key[3], m->ws, m->P, xs, nullptr, nullptr, 0};
         Ctx cc = c; cc.seed_ptr = a.meta; cc.inv_ptr = reinterpret_cast<const float*>(a.meta + 1);
+        if (chunk_dyn) cc.chunk_ptr = reinterpret_cast<const int*>(a.meta + 2);      // a drawn chunk changes from step to step: read at replay
         HIP_CHECK_RET(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         const int rc = run(cc);
         const hipError_t e = hipStreamEndCapture(s, &ng.g);

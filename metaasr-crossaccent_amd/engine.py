@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._cabi import MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists, nbest_lists_bias
+from ._cabi import MasrChunkPolicy, MasrConfig, MasrSpecaugPolicy, align_lists, align_outputs, check, check_target_lengths, check_beam_args, check_lm_args, check_nlm_args, lib, nbest_lists, nbest_lists_bias
 from .bias import check_bias_args
 
 MASR_TRAIN, MASR_EVAL = 1, 0
@@ -68,6 +68,49 @@ def _specaug_policy(policy, idim: int, what: str = "asr_model.specaug"):
 def specaug_of(model_para: dict):
     """asr_model.specaug (absent or null = off), validated: the policy dict that MasrEngine hands to masr_set_specaug, or None"""
     return _specaug_policy(model_para.get('specaug'), int(model_para["idim"]))
+
+
+CHUNK_KEYS = ("size", "left", "dynamic")
+
+
+def _chunk_policy(policy, what: str = "asr_model.chunk"):
+    """a chunk policy dict (None: off) -> the complete validated dict {size, left, dynamic}, or None when it masks nothing.  Absent keys: size 0,
+    left -1, dynamic 0.  The bounds are include/masr.h masr_chunk_policy's; a ValueError names the key."""
+    if policy is None:
+        return None
+    if not isinstance(policy, dict):
+        raise ValueError(f"{what} must be a mapping of {', '.join(CHUNK_KEYS)}, got {type(policy).__name__}")
+    unknown = sorted(set(policy) - set(CHUNK_KEYS))
+    if unknown:
+        raise ValueError(f"{what}: unknown key {unknown[0]} (known: {', '.join(CHUNK_KEYS)})")
+    out = {}
+    for k, default in zip(CHUNK_KEYS, (0, -1, 0)):
+        v = policy.get(k, default)
+        if isinstance(v, bool) and k == "dynamic":
+            v = int(v)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}.{k} must be an integer, got {v!r}")
+        out[k] = int(v)
+    if not 0 <= out["size"] < 2 ** 31:
+        raise ValueError(f"{what}.size must be >= 0 (encoder frames; 0 = full context), got {out['size']}")
+    if not -1 <= out["left"] < 2 ** 31:
+        raise ValueError(f"{what}.left must be >= -1 (-1 = every earlier chunk), got {out['left']}")
+    if out["dynamic"] not in (0, 1):
+        raise ValueError(f"{what}.dynamic must be 0 or 1, got {out['dynamic']}")
+    if out["size"] == 0 and out["dynamic"] == 0:
+        return None
+    return out
+
+
+def chunk_of(model_para: dict):
+    """asr_model.chunk (absent or null = off), validated: the policy dict that MasrEngine hands to masr_set_chunk, or None"""
+    return _chunk_policy(model_para.get('chunk'))
+
+
+def chunk_draw(seed: int, step: int, Tp: int) -> int:
+    """the chunk a dynamic policy's training step draws at the dropout position (seed, step) for a batch of Tp encoder frames
+    (include/masr.h masr_chunk_draw): 0 = full context, else 1..25"""
+    return int(lib().masr_chunk_draw(C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint64(step & (2 ** 64 - 1)), int(Tp)))
 
 
 def _policy_struct(policy):
@@ -148,6 +191,7 @@ class MasrEngine:
         self.odim = odim
         self.ctc_weight = ctc_weight_of(model_para)      # joint CTC/attention objective: loss = (1 - w) CE + w CTC (include/masr.h masr_create_ctc)
         policy = specaug_of(model_para)                  # SpecAugment inside the training step (include/masr.h masr_set_specaug; None = off)
+        chunk = chunk_of(model_para)                     # chunk mask of the encoder's self-attention (include/masr.h masr_set_chunk; None = off)
         self.cfg = MasrConfig(
             idim=model_para["idim"], odim=odim, d_model=model_para["d_model"], nheads=model_para["nheads"],
             d_inner=model_para["d_inner"], enc_layers=model_para["encoder"]["nlayers"],
@@ -175,6 +219,8 @@ class MasrEngine:
         self._ws_key = (0, 0, 0)
         self.specaug = None
         self.set_specaug(policy)                         # (before the first bind: the plan holds the augmented batch)
+        self.chunk = None
+        self.set_chunk(chunk)
         self._ensure_ws(1, 64, 8)
         self._dirty = True
 
@@ -267,6 +313,20 @@ class MasrEngine:
         check(self._l.masr_specaug_last(self.h, C.byref(xp), C.byref(B), C.byref(T), C.byref(D)), "masr_specaug_last")
         lo, n = xp.value - self.ws.data_ptr(), B.value * T.value * D.value
         return self.ws[lo:lo + n * 4].view(torch.float32).view(B.value, T.value, D.value)
+
+    def set_chunk(self, policy):
+        """chunk mask of the encoder's self-attention (include/masr.h masr_set_chunk): a dict of CHUNK_KEYS as asr_model.chunk, or None = off.
+        Evaluation and every recog* run under `size`; training steps under `size`, or with dynamic = 1 under the step's draw."""
+        pol = _chunk_policy(policy, "policy")
+        st = MasrChunkPolicy(*[pol[k] for k in CHUNK_KEYS]) if pol else None
+        check(self._l.masr_set_chunk(self.h, C.byref(st) if st else None), "masr_set_chunk")
+        self.chunk = pol
+
+    def chunk_last(self) -> int:
+        """the chunk (encoder frames; 0 = full context) the last run_batch or recog* ran its encoder with"""
+        c = C.c_int()
+        check(self._l.masr_chunk_last(self.h, C.byref(c)), "masr_chunk_last")
+        return int(c.value)
 
     def dropout_state(self):
         """(seed, batches run since set_seed): the position of the dropout mask stream (include/masr.h masr_dropout_state)"""

@@ -71,7 +71,10 @@ anything is decoded.  Tester.MODES is the table of them:
                  start and end (one past the last) in ENCODER frames -- one encoder frame is 4 input frames on both models.  An utterance
                  with too few frames for its transcript gets an empty middle field and -inf.  `--resume` counts the lines of ctc-ali.
                  Needs a CTC output layer (a transformer without one: ValueError).
-The LM modes build the LM once per Tester and (path, <s> id, </s> id)."""
+The LM modes build the LM once per Tester and (path, <s> id, </s> id).
+Every mode of a transformer runs one encoder forward, under the chunk mask of asr_model.chunk (DESIGN 5.15) where the config has one;
+`--decode_chunk SIZE` / `--decode_left N` put their values over its `size` / `left` for this run (SIZE 0: full context), so one checkpoint is
+scored at several latencies.  A BLSTM with either flag raises ValueError."""
 import math
 from pathlib import Path
 from shutil import rmtree
@@ -83,6 +86,29 @@ from .marcos import *  # noqa: F401,F403
 from .model import MyTransformer
 from .monitor import logger
 from .pretrain_interface import load_units
+
+
+def decode_chunk_policy(model_para, paras, model_name='transformer'):
+    """the chunk policy of a --test run: asr_model.chunk with --decode_chunk SIZE / --decode_left N over its size / left, so one checkpoint is
+    scored at several latencies (every --decode_mode runs one encoder forward, under `size`).  -> (policy dict or None, overridden?)"""
+    from .engine import _chunk_policy, chunk_of
+    size, left = getattr(paras, 'decode_chunk', None), getattr(paras, 'decode_left', None)
+    if size is None and left is None:
+        return (None if model_name == 'blstm' else chunk_of(model_para)), False
+    if model_name == 'blstm':
+        raise ValueError("--decode_chunk / --decode_left: transformer only")
+    if size is not None and size < 0:
+        raise ValueError(f"--decode_chunk must be >= 0 (encoder frames; 0 = full context), got {size}")
+    if left is not None and left < -1:
+        raise ValueError(f"--decode_left must be >= -1 (-1 = every earlier chunk), got {left}")
+    pol = dict(chunk_of(model_para) or {"size": 0, "left": -1, "dynamic": 0})
+    if size is not None:
+        pol["size"] = int(size)
+    if left is not None:
+        pol["left"] = int(left)
+    if pol["size"] == 0 and left is not None:
+        raise ValueError("--decode_left needs a chunk: pass --decode_chunk SIZE or set asr_model.chunk.size")
+    return _chunk_policy(pol, "--decode_chunk / --decode_left"), True
 
 
 class Tester:
@@ -100,6 +126,8 @@ class Tester:
         self.decode_dir = Path(self.log_dir, paras.decode_suffix)
         self.decode_mode = paras.decode_mode
         self.batch_size = paras.decode_batch_size
+        self.chunk_policy, self.chunk_override = decode_chunk_policy(config['asr_model'], paras, self.model_name)   # (argument errors before any I/O)
+        self.chunk_last = None                                     # the chunk the last batch's encoder ran with (engine.chunk_last)
         if not paras.resume:
             if self.decode_dir.exists():
                 assert paras.overwrite, f"Path exists ({self.decode_dir}). Use --overwrite or change decode suffix"
@@ -132,6 +160,10 @@ class Tester:
         self.asr_model.load_state_dict(torch.load(self.model_path, map_location='cpu'))
         self.asr_model.eval()
         self.sos_id, self.eos_id = self.asr_model.sos_id, self.asr_model.eos_id
+        if self.chunk_override:
+            self.asr_model.engine.set_chunk(self.chunk_policy)
+        if self.chunk_policy:
+            logger.notice(f"encoder self-attention under a chunk of {self.chunk_policy['size']} encoder frames, left {self.chunk_policy['left']}")
 
     def trim(self, hyp):
         """tester.py:189-207 (transformer): everything from the first </s> at position >= 1 is dropped; a
@@ -588,5 +620,7 @@ class Tester:
             else:
                 for hyp, y in zip(best_hyps(self, xs, ilens), ys):
                     self.write_hyp(y.tolist(), hyp)
+            if self.model_name != 'blstm':
+                self.chunk_last = self.asr_model.engine.chunk_last()
             seen += n
         self._skip_lines = 0
