@@ -432,6 +432,36 @@ int masr_recog_beam_ctc_nlm(masr_model* m, const masr_nlm* nlm, const float* xs,
 int64_t masr_ctc_beam_workspace_bytes(const masr_model* m, int B, int T, int K);
 int masr_recog_ctc_beam(masr_model* m, const float* xs, const int64_t* ilens, int B, int T, int K, int nbest, int32_t* tokens, int32_t* lens,
                         float* scores, void* stream);
+/* Streaming first pass on the CTC head (hybrid models under a chunk policy with size c > 0).  The batch's audio arrives in pieces;
+ * the encoder runs incrementally -- the front-end on input windows, every layer on a chunk's rows against a per-layer K|V cache -- and produces,
+ * chunk by chunk, the head logits that one chunk-masked full pass (masr_recog_ctc_beam's encoder and head GEMM) produces on the zero-padded
+ * batch, for every frame t < ilens[b] / 4 (equal in exact arithmetic; the summation order differs).  A greedy (best-path) CTC decode follows
+ * the chunks; after the last piece the full-utterance prefix beam runs on the accumulated logits.  Chunk n = encoder frames [n c, (n + 1) c)
+ * runs once the input frames up to 4 (n + 1) c + 8 are buffered, so what is emitted does not depend on how the audio was cut into pieces.
+ *   masr_stream_workspace_bytes  the workspace an open stream of B utterances of at most max_frames input frames needs under the model's
+ *                  current chunk size (bind one at least that large); -1: no CTC head, no chunk size, B < 1, max_frames outside [4, 12000].
+ *   masr_stream_begin   opens a stream (an open one is dropped).  -1 for the same reasons or an unbound model, -2 for a workspace that is too
+ *                  small.  The policy's `dynamic` is ignored; `size` and `left` are those of the moment of the call.
+ *   masr_stream_feed    the next n input frames of every utterance, xs device fp32 [B][n][idim].  valid (host int32 [B], null = all n):
+ *                  valid[b] < n ends utterance b behind its first valid[b] frames, and every later piece must give it 0 (otherwise -1); the
+ *                  engine zero-fills behind an utterance's end itself.  Runs every chunk whose window is complete; with last != 0 all that
+ *                  remain (a final partial chunk; the trailing T % 4 input frames make no encoder frame, as in the full pass).  *frames_out
+ *                  (may be null) = the encoder frames emitted so far.  -1: no open stream, a piece after the last, more than max_frames.
+ *   masr_stream_partial device views of the greedy result so far: tokens / frames int32 [B][*ld] (a token and the encoder frame that emitted
+ *                  it; -1 behind the list), lens int32 [B].
+ *   masr_stream_logits  the accumulated head logits in the layout masr_ctc_beam_search reads (row of utterance b, frame t at logits +
+ *                  (b * (max_frames / 4) + t) * *ld), enc_lens int32 [B] = (frames of b received) / 4, *frames = frames emitted so far.
+ *   masr_stream_ctc_beam  after the last piece: masr_ctc_beam_search on those logits and lengths with blank 0, eos = odim - 1; tokens int32
+ *                  [B][nbest][max_frames / 4], lens int32 [B][nbest], scores fp32 [B][nbest] (device).  Refuses what masr_recog_ctc_beam does.
+ * Any other call that plans the workspace (masr_run_batch, masr_recog*, masr_bind, masr_set_chunk) ends an open stream: the next feed returns
+ * -1 with "no open stream".  Every refusal sets masr_last_error and launches nothing. */
+int64_t masr_stream_workspace_bytes(const masr_model* m, int B, int max_frames);
+int masr_stream_begin(masr_model* m, int B, int max_frames, void* stream);
+int masr_stream_feed(masr_model* m, const float* xs, int n, const int32_t* valid, int last, int* frames_out, void* stream);
+int masr_stream_partial(masr_model* m, const int32_t** tokens, const int32_t** frames, const int32_t** lens, int* ld);
+int masr_stream_logits(masr_model* m, const float** logits, int64_t* ld, const int32_t** enc_lens, int* frames);
+int masr_stream_ctc_beam(masr_model* m, int K, int nbest, int32_t* tokens, int32_t* lens, float* scores, void* stream);
+
 /* masr_recog_ctc_beam with the n-gram LM fused into the search: the same encoder pass, head GEMM and workspace, then
  * masr_ctc_beam_search_lm (below) with blank 0 and eos = odim - 1.  scores fp32 [B][nbest] are the fused finals, am fp32 [B][nbest] the acoustic
  * totals.  -1 besides masr_recog_ctc_beam's refusals: a null LM, an LM whose C is not the model's odim, lm_w negative or not finite, len_bonus

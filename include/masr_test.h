@@ -172,6 +172,17 @@ int masr_test_attention_chunk(const uint16_t* q, const uint16_t* k, const uint16
 int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* o,
                         uint16_t* dq, uint16_t* dk, uint16_t* dv, float* lse, float* delta, const int32_t* klens,
                         int B, int H, int Tq, int Tk, int hd, int causal, void* stream);
+/* The chunk step's self-attention against a K|V cache, alone (csrc/stream.hip attn_stream_kernel): q / knew / vnew / o bf16
+ * [B][R][H * hd], the cache kc / vc bf16 [B][cap][H * hd] each.  Every query row attends the keys [lo, min(pos + R, klens[b])) (klens null:
+ * pos + R): cache rows in front of pos, knew / vnew from pos on; the launch also copies knew / vnew into the cache rows [pos, pos + R).  A row
+ * without a key gets o = 0.  -1 with a message, before any launch: R < 1, pos + R > cap, lo > pos, hd outside {16, 32, 64}. */
+int masr_test_attention_stream(const uint16_t* q, const uint16_t* knew, const uint16_t* vnew, uint16_t* kc, uint16_t* vc, uint16_t* o,
+                               const int32_t* klens, int B, int H, int hd, int R, int pos, int lo, int cap, void* stream);
+/* The streamed greedy CTC decode, alone (csrc/stream.hip ctc_greedy_stream_kernel): logits fp32 [B][R][ld] = the frames pos .. pos + R, C valid
+ * columns, blank 0; state int32 [2][B] (previous arg-max | len, all 0 at the start) is read and written; a frame < klens[b] (null: every frame)
+ * whose arg-max (ties to the lower index) is neither blank nor the previous frame's appends to tokens / frames int32 [B][ld_out]. */
+int masr_test_ctc_greedy_stream(const float* logits, int64_t ld, const int32_t* klens, int B, int R, int C, int pos, int32_t* state, int32_t* tokens,
+                                int32_t* frames, int ld_out, void* stream);
 /* where the last masr_recog_ctc_beam call with this B, T, K left the inputs of its masr_ctc_beam_search in the bound workspace: the CTC
  * head's fp32 logits (row of utterance b, frame t at logits + (b * (T / 4) + t) * ld, C = odim valid columns) and enc_lens int32 [B].
  * Valid until the next call that uses the workspace. */

@@ -218,6 +218,14 @@ _SIGS = {
     "masr_test_attention_dropout_bwd": (i32, [vp] * 10 + [i32] * 6 + [f32, C.c_uint32, C.c_uint32, vp]),
     "masr_test_attention_chunk": (i32, [vp] * 10 + [i32] * 6 + [f32, C.c_uint32, C.c_uint32, i32, i32, vp, vp]),
     "masr_test_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "masr_test_attention_stream": (i32, [vp] * 7 + [i32] * 7 + [vp]),
+    "masr_test_ctc_greedy_stream": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "masr_stream_workspace_bytes": (i64, [vp, i32, i32]),
+    "masr_stream_begin": (i32, [vp, i32, i32, vp]),
+    "masr_stream_feed": (i32, [vp, vp, i32, C.POINTER(C.c_int32), i32, C.POINTER(i32), vp]),
+    "masr_stream_partial": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]),
+    "masr_stream_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32)]),
+    "masr_stream_ctc_beam": (i32, [vp, i32, i32, vp, vp, vp, vp]),
     "masr_test_lstm_shadows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "masr_test_lstm_unperm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "masr_test_lstm_fwd": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -5,7 +5,7 @@ cd "$(dirname "$0")"
 OUT=../lib
 mkdir -p $OUT build
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-unused-value"
-SRCS="gemm conv attention rowops optim fold data ctc decode beam lm nlm bias ctc_beam ctc_align rescore fbank pitch lstm lstm_rec blstm comm engine train recog test_abi"
+SRCS="gemm conv attention rowops optim fold data ctc decode beam lm nlm bias ctc_beam ctc_align rescore fbank pitch lstm lstm_rec blstm comm stream engine train recog stream_engine test_abi"
 HDRS="kernels.h common.h folds.h search.h lm.h nlm.h bias.h host_util.h engine_internal.h ../../include/masr.h ../../include/masr_test.h"
 pids=()
 objs=()

@@ -2,7 +2,8 @@
 // src/model/transformer_pytorch/mono_transformer_torch.py) orchestrated as fixed sequences of hand-written gfx950
 // kernels on one HIP stream, behind the C ABI of include/masr.h.  This file: the model behind the handle, its parameter
 // table, the arena plans, bind / refresh, setters, stats, and the optimiser / utility wrappers.  The training step
-// is train.hip, the decoders recog.hip, the standalone kernel entry points test_abi.hip; engine_internal.h is what they share.
+// is train.hip, the decoders recog.hip, the streaming first pass stream_engine.hip, the standalone kernel entry points test_abi.hip;
+// engine_internal.h is what they share.
 //
 // Memory model (sized for 288 GB HBM3E): ONE flat fp32 parameter buffer and ONE flat gradient buffer
 // (caller-owned; every optimiser / clip / all-reduce is a single streaming pass), bf16 operand shadows
@@ -282,6 +283,7 @@ int masr_bind(masr_model* m, float* params, float* grads, const float* pe, void*
     if (!params || !grads || !pe || !workspace || ws_bytes < m->persist_bytes) { mk_set_error("masr_bind", "null pointer or workspace too small"); return -1; }
     if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 15) || ((uintptr_t)grads & 15)) { mk_set_error("masr_bind", "misaligned buffers"); return -1; }
     m->P = params; m->G = grads; m->pe = pe; m->ws = (char*)workspace; m->ws_bytes = ws_bytes;
+    stream_close(m);
     Arena ar{m->ws, ws_bytes, 0};
     plan_persistent(m, ar);
     if (!m->h_stage) {
@@ -376,6 +378,7 @@ int masr_set_chunk(masr_model* m, const masr_chunk_policy* p) {
     if (!on) q = masr_chunk_policy{0, -1, 0};
     if (on != m->chunk_on || memcmp(&q, &m->chunk, sizeof q)) drop_step_graphs(m);            // (chunk and left are kernel arguments of the captured launches)
     m->chunk = q; m->chunk_on = on;
+    stream_close(m);                                                                          // (an open stream was planned for the old chunk)
     return 0;
 }
 int masr_chunk_last(masr_model* m, int* size) {

@@ -137,6 +137,14 @@ struct masr_model {
     //   G_CTC_NLM      CTC beam + LSTM LM, a frame  words {B, T/4, K, NLM serial, the offsets of enc_lens and of the head's logits in ws, in
     //                  (ctc_first_pass)             4-byte units}, pointers {ws, P, the search's work buffer}
     DecodeGraph decode_graphs[G_COUNT];
+    // the streaming first pass (stream_engine.hip): the open stream's geometry and host bookkeeping; its buffers are the plan of
+    // (B, max_frames, c) behind the persistent region.  Every other call that plans the workspace closes it (stream_close)
+    struct Stream {
+        bool open = false, last = false;
+        int B = 0, max_frames = 0, c = 0, left = -1;
+        int recv = 0, emitted = 0;                         // input frames buffered, encoder frames emitted
+        std::vector<int> len; std::vector<char> ended;     // per utterance: valid frames received, ended
+    } stream;
     struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
     bool prof = false;
@@ -207,6 +215,9 @@ inline int ln_fwd(Ctx& c, const Norm& n, const float* x, float* y32, bf16* y16, 
     if (sum && sum->n > 0) return mk_layernorm_fwd_sum(*sum, m->P + n.w, m->P + n.b, y32, y16, mean, rstd, rows, m->E, c.s);
     return mk_layernorm_fwd(x, m->P + n.w, m->P + n.b, y32, y16, mean, rstd, rows, m->E, c.s);
 }
+
+// what every call that plans the workspace does to an open stream: its buffers are about to be overwritten
+inline void stream_close(masr_model* m) { m->stream.open = false; }
 
 // engine.hip.  ctc: the branches of masr_run_batch alone, which the decoders do not plan -- the joint objective's (hybrid models) and
 // SpecAugment's batch

@@ -119,6 +119,34 @@ struct AttnArgs {
 int mk_attn_fwd(const AttnArgs& a, hipStream_t s);
 int mk_attn_bwd(const AttnArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- streaming first pass (stream.hip)
+// One chunk step of an encoder layer's self-attention: R new rows per utterance (row b*R + i of q / knew / vnew / o, head h at column h*hd)
+// against the layer's cache.  Every row attends the keys [lo, min(pos + R, klens[b])): cache rows in front of pos, the step's own rows from
+// pos on (read from knew / vnew).  The same launch appends the new rows to the cache at [pos, pos + R).  A row without a key: o = 0.
+struct AttnStreamArgs {
+    const bf16* q; long ldq;
+    const bf16 *knew, *vnew; long ldnew;
+    bf16 *kc, *vc; long ldc, batch_stride;     // cache row j of utterance b: kc + b*batch_stride + j*ldc + h*hd
+    const int* klens;                          // [B] valid keys per utterance (device) or null (pos + R)
+    bf16* o; long ldo;
+    int B, H, hd, R, pos, lo, cap;             // cap: rows of the cache per utterance
+};
+int mk_attn_stream(const AttnStreamArgs& a, hipStream_t s);
+// Greedy (best-path) CTC over the step's R logit rows of every utterance (row (b, i) at logits + b*batch_stride + i*ld, absolute frame pos + i):
+// arg-max over the C valid columns, ties to the lower index; a frame < klens[b] whose arg-max is neither blank (0) nor the previous frame's
+// appends (token, frame) at tokens / frames [b][len].  state [2][B] = previous arg-max | len, carried across steps (start: all 0)
+struct CtcGreedyStreamArgs {
+    const float* logits; long ld, batch_stride;
+    const int* klens;                          // [B] or null (every frame of the step counts)
+    int B, R, C, pos;
+    int* state; int *tokens, *frames; int ld_out;
+};
+int mk_ctc_greedy_stream(const CtcGreedyStreamArgs& a, hipStream_t s);
+// win [B][W][D] = rows w0 .. w0 + W of xbuf [B][cap_frames][D], zero at and behind lens[b]
+int mk_stream_window(const float* xbuf, const int* lens, float* win, int B, int W, int D, int w0, long cap_frames, hipStream_t s);
+// x32 / x16 [B*R][E] = rows off .. off + R of each utterance of v [B*Wp][E] + pe[s0 + i] (fp32 add, then the bf16 rounding)
+int mk_stream_centre_pe(const float* v, const float* pe, float* x32, bf16* x16, int B, int R, int E, int Wp, int off, int s0, hipStream_t s);
+
 // ---------------------------------------------------------------- incremental greedy decode (decode.hip)
 // C[m][n] = epi(sum_k A[m][k] W[n][k]) for a handful of rows (one per utterance): bias, ReLU, fp32 residual
 struct SkinnyArgs {

@@ -338,6 +338,7 @@ static int recog_prepare(masr_model* m, const float* xs, const int64_t* ilens, i
     int Ldec = 0;
     CK(check_ilens("masr_recog", ilens, B, T, [&](int, int enc) { Ldec = std::max(Ldec, enc); }));
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    stream_close(m);
     const DecodeBufs planned = plan_decode(m, ar, m->acts, B, T, Ldec, d);
     if (bufs) *bufs = planned;
     if (ar.off > m->ws_bytes) { mk_set_error("masr_recog", d.too_small().c_str()); return -2; }

@@ -726,6 +726,25 @@ int masr_test_attention(const uint16_t* q, const uint16_t* k, const uint16_t* v,
     return 0;
 }
 
+// ---- the streaming first pass's two kernels alone (tests/test_hip_stream_kernels.py)
+int masr_test_attention_stream(const uint16_t* q, const uint16_t* knew, const uint16_t* vnew, uint16_t* kc, uint16_t* vc, uint16_t* o,
+                               const int32_t* klens, int B, int H, int hd, int R, int pos, int lo, int cap, void* stream) {
+    const long E = (long)H * hd;
+    AttnStreamArgs a{};
+    a.q = (const bf16*)q; a.ldq = E; a.knew = (const bf16*)knew; a.vnew = (const bf16*)vnew; a.ldnew = E;
+    a.kc = (bf16*)kc; a.vc = (bf16*)vc; a.ldc = E; a.batch_stride = (long)cap * E; a.klens = klens; a.o = (bf16*)o; a.ldo = E;
+    a.B = B; a.H = H; a.hd = hd; a.R = R; a.pos = pos; a.lo = lo; a.cap = cap;
+    return mk_attn_stream(a, (hipStream_t)stream);
+}
+int masr_test_ctc_greedy_stream(const float* logits, int64_t ld, const int32_t* klens, int B, int R, int C, int pos, int32_t* state, int32_t* tokens,
+                                int32_t* frames, int ld_out, void* stream) {
+    CtcGreedyStreamArgs a{};
+    a.logits = logits; a.ld = (long)ld; a.batch_stride = (long)R * ld; a.klens = klens; a.B = B; a.R = R; a.C = C; a.pos = pos;
+    a.state = state; a.tokens = tokens; a.frames = frames; a.ld_out = ld_out;
+    if (C > ld) { mk_set_error("masr_test_ctc_greedy_stream", "need C <= ld"); return -1; }
+    return mk_ctc_greedy_stream(a, (hipStream_t)stream);
+}
+
 // ---- the BLSTM path's LSTM kernels alone (tests/test_hip_lstm_kernels.py)
 static inline bool test_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int test_kp(int H) { return (H + 31) / 32 * 32; }

@@ -438,6 +438,7 @@ extern "C" int masr_run_batch(masr_model* m, const float* xs, const int64_t* ile
     for (int b = 0; b < B; ++b) { if (olens[b] > maxo) maxo = (int)olens[b]; ntot += olens[b] + 1; }
     const int L = maxo + 1;
     Arena ar{m->ws, m->ws_bytes, m->persist_bytes};
+    stream_close(m);
     plan_acts(m, ar, m->acts, B, T, L, train, true);
     if (ar.off > m->ws_bytes) { mk_set_error("masr_run_batch", "workspace too small (see masr_workspace_bytes)"); return -2; }
     Acts& a = m->acts; m->have_acts = true;

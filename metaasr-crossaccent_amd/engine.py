@@ -755,6 +755,68 @@ class MasrEngine:
         logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
         return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)
 
+    # ------------------------------------------------------------------ streaming first pass (include/masr.h masr_stream_*)
+    def _ws_view(self, ptr, count, dtype):
+        off = ptr - self.ws.data_ptr()
+        return self.ws[off:off + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def stream_begin(self, B: int, max_frames: int):
+        """open a stream of B utterances of at most max_frames input frames under the engine's chunk policy (size > 0; needs a hybrid model)"""
+        self._decode_ws("masr_stream_workspace_bytes", int(B), int(max_frames))
+        check(self._l.masr_stream_begin(self.h, int(B), int(max_frames), self.stream()), "masr_stream_begin")
+        self._stream_shape = (int(B), int(max_frames))
+
+    def stream_feed(self, xs: torch.Tensor, valid=None, last: bool = False) -> int:
+        """the next piece xs [B, n, idim] of every utterance; valid[b] < n ends utterance b (later pieces must give it 0).  Returns the number
+        of encoder frames emitted so far."""
+        if xs.device != self.device:
+            xs = xs.to(self.device, non_blocking=True)
+        xs = xs.contiguous().float()
+        n = int(xs.shape[1])
+        v = None if valid is None else (C.c_int32 * xs.shape[0])(*[int(x) for x in valid])
+        out = C.c_int(0)
+        check(self._l.masr_stream_feed(self.h, _ptr(xs) if n else None, n, v, int(bool(last)), C.byref(out), self.stream()), "masr_stream_feed")
+        self._last_x = xs
+        return out.value
+
+    def stream_partial(self):
+        """the greedy result so far as views into the workspace: (tokens int32 [B, ld], frames int32 [B, ld], lens int32 [B])"""
+        tp, fp, lp, ld = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
+        check(self._l.masr_stream_partial(self.h, C.byref(tp), C.byref(fp), C.byref(lp), C.byref(ld)), "masr_stream_partial")
+        B = self._stream_shape[0]
+        return (self._ws_view(tp.value, B * ld.value, torch.int32).view(B, ld.value),
+                self._ws_view(fp.value, B * ld.value, torch.int32).view(B, ld.value), self._ws_view(lp.value, B, torch.int32))
+
+    def stream_logits(self):
+        """the accumulated head logits as views into the workspace: (logits fp32 [B, max_frames // 4, ld], enc_lens int32 [B], frames emitted)"""
+        gp, ep, ld, fr = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int()
+        check(self._l.masr_stream_logits(self.h, C.byref(gp), C.byref(ld), C.byref(ep), C.byref(fr)), "masr_stream_logits")
+        B, cap = self._stream_shape[0], self._stream_shape[1] // 4
+        return self._ws_view(gp.value, B * cap * ld.value, torch.float32).view(B, cap, ld.value), self._ws_view(ep.value, B, torch.int32), fr.value
+
+    def stream_ctc_beam(self, beam_size: int, nbest: int = 1, raw: bool = False):
+        """after the last piece: the CTC prefix beam of recog_ctc_beam on the logits the stream left behind"""
+        K, N = check_beam_args(beam_size, nbest)
+        B, cap = self._stream_shape[0], self._stream_shape[1] // 4
+        out = self._outputs(B, N, ld=cap)
+        check(self._l.masr_stream_ctc_beam(self.h, K, N, *map(_ptr, out), self.stream()), "masr_stream_ctc_beam")
+        return out if raw else nbest_lists(*out)
+
+    def recog_stream(self, xs: torch.Tensor, ilens, piece: int, beam_size=None, nbest: int = 1):
+        """the padded batch xs [B, T, idim] streamed in pieces of `piece` input frames, `valid` derived from ilens.  Returns per utterance
+        (greedy token list, the encoder frame of each token); with beam_size the final beam's lists as recog_ctc_beam returns them."""
+        if int(piece) < 1:
+            raise ValueError("recog_stream: piece must be >= 1")
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        self.stream_begin(B, T)
+        for t0 in range(0, T, int(piece)):
+            t1 = min(T, t0 + int(piece))
+            self.stream_feed(xs[:, t0:t1], [max(0, min(int(l), t1) - t0) for l in il.tolist()], last=t1 == T)
+        if beam_size is not None:
+            return self.stream_ctc_beam(beam_size, nbest)
+        tok, frm, lens = (t.cpu() for t in self.stream_partial())
+        return [(tok[b, :int(lens[b])].tolist(), frm[b, :int(lens[b])].tolist()) for b in range(B)]
+
     def read_stats(self):
         out = (C.c_float * 4)()
         check(self._l.masr_read_stats(self.h, out, self.stream()), "masr_read_stats")

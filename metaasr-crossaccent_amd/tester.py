@@ -71,6 +71,11 @@ anything is decoded.  Tester.MODES is the table of them:
                  start and end (one past the last) in ENCODER frames -- one encoder frame is 4 input frames on both models.  An utterance
                  with too few frames for its transcript gets an empty middle field and -inf.  `--resume` counts the lines of ctc-ali.
                  Needs a CTC output layer (a transformer without one: ValueError).
+  stream_ctc_greedy  masr_stream_*, the streaming first pass of DESIGN 5.16: every batch is fed to the incremental chunk-cached encoder in pieces
+                 of `--stream_piece N` input frames (default 4 * the chunk size) and the greedy (best-path) CTC decode that follows the chunks
+                 is written.  Needs a chunk size (asr_model.chunk.size or `--decode_chunk`; without one: ValueError) and a CTC output layer (a
+                 transformer without one: ValueError); a BLSTM raises NotImplementedError.  No solver.beam_decode block is read.
+  stream_ctc_beam    the same stream, then `ctc_beam`'s search (beam_size) on the logits it left behind.  Refuses what `stream_ctc_greedy` does.
 The LM modes build the LM once per Tester and (path, <s> id, </s> id).
 Every mode of a transformer runs one encoder forward, under the chunk mask of asr_model.chunk (DESIGN 5.15) where the config has one;
 `--decode_chunk SIZE` / `--decode_left N` put their values over its `size` / `left` for this run (SIZE 0: full context), so one checkpoint is
@@ -111,6 +116,30 @@ def decode_chunk_policy(model_para, paras, model_name='transformer'):
     return _chunk_policy(pol, "--decode_chunk / --decode_left"), True
 
 
+STREAM_MODES = ('stream_ctc_greedy', 'stream_ctc_beam')
+
+
+def _no_ctc_head_error(mode, instead):
+    return ValueError(f"decode_mode '{mode}' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
+                      f"use --decode_mode {instead}")
+
+
+def stream_decode_args(model_para, paras, mode, chunk_policy, model_name='transformer'):
+    """the argument errors of the streaming modes (before any I/O) -> the input frames per feed, --stream_piece or 4 * the chunk size"""
+    from .engine import ctc_weight_of
+    if model_name == 'blstm':
+        raise NotImplementedError(f"{mode}: the streaming first pass runs the transformer's chunk-masked encoder, the BLSTM has none; "
+                                  "use --decode_mode ctc_beam or greedy")
+    if not chunk_policy or chunk_policy['size'] <= 0:
+        raise ValueError(f"{mode}: no chunk size; pass --decode_chunk SIZE or set asr_model.chunk.size")
+    if not ctc_weight_of(model_para) > 0.0:
+        raise _no_ctc_head_error(mode, "beam or greedy")
+    piece = getattr(paras, 'stream_piece', None)
+    if piece is not None and piece < 1:
+        raise ValueError(f"--stream_piece must be >= 1 (input frames per feed), got {piece}")
+    return int(piece) if piece is not None else 4 * chunk_policy['size']
+
+
 class Tester:
     def __init__(self, config, paras, id2accent):
         self.config, self.paras = config, paras
@@ -128,6 +157,8 @@ class Tester:
         self.batch_size = paras.decode_batch_size
         self.chunk_policy, self.chunk_override = decode_chunk_policy(config['asr_model'], paras, self.model_name)   # (argument errors before any I/O)
         self.chunk_last = None                                     # the chunk the last batch's encoder ran with (engine.chunk_last)
+        if self.decode_mode in STREAM_MODES:
+            self.stream_piece = stream_decode_args(config['asr_model'], paras, self.decode_mode, self.chunk_policy, self.model_name)
         if not paras.resume:
             if self.decode_dir.exists():
                 assert paras.overwrite, f"Path exists ({self.decode_dir}). Use --overwrite or change decode suffix"
@@ -236,8 +267,7 @@ class Tester:
 
     def _need_ctc_head(self, mode, instead):
         if not self.asr_model.engine.ctc_weight > 0.0:
-            raise ValueError(f"decode_mode '{mode}' needs a CTC output layer: this transformer has none (asr_model.ctc_weight is 0 or absent); "
-                             f"use --decode_mode {instead}")
+            raise _no_ctc_head_error(mode, instead)
 
     def _step_ratios(self, bd):
         self.min_step_ratio = float(bd.get('min_step_ratio', 0.0))
@@ -333,6 +363,12 @@ class Tester:
         self._beam_size()
         if self.model_name != 'blstm':
             self._need_ctc_head('ctc_beam', "beam or greedy")
+
+    def _stream_settings(self):
+        """stream_ctc_greedy and stream_ctc_beam (their argument errors: stream_decode_args, in the constructor)"""
+        if self.decode_mode == 'stream_ctc_beam':
+            self._beam_size()
+        self._need_ctc_head(self.decode_mode, "beam or greedy")
 
     def _ctc_align_settings(self):
         if self.model_name != 'blstm':
@@ -583,6 +619,12 @@ class Tester:
                                 t.att_weight, t.ctc_weight)],
                             lambda t: f"phrase-biased joint CTC/attention beam decoding (bias_joint_beam, beam {t.beam_size}, {t.bias.phrases} phrases)"),
         'ctc_align': (_ctc_align_settings, None, lambda t: "CTC forced alignment of the reference transcripts"),
+        'stream_ctc_greedy': (_stream_settings,
+                              lambda t, xs, il: [tok for tok, _ in t.asr_model.engine.recog_stream(xs, il, t.stream_piece)],
+                              lambda t: f"streaming greedy CTC decoding (chunk {t.chunk_policy['size']}, pieces of {t.stream_piece} frames)"),
+        'stream_ctc_beam': (_stream_settings,
+                            lambda t, xs, il: t._ctc_best(t.asr_model.engine.recog_stream(xs, il, t.stream_piece, t.beam_size)),
+                            lambda t: f"streaming encoder, CTC prefix beam on its logits (chunk {t.chunk_policy['size']}, beam {t.beam_size})"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
                               xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],
