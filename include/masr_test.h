@@ -136,6 +136,10 @@ int masr_test_conv1_wgrad_fused(const uint16_t* dy, const uint16_t* dy_pooled, c
 int masr_test_conv3x3_wgrad(const uint16_t* in, const uint16_t* dy, float* dw, float* slab, int64_t slab_floats,
                             int B, int H, int W, int CIN, int COUT, void* stream);
 int64_t masr_test_conv3x3_wgrad_slab_floats(int B, int H, int W, int CIN, int COUT);
+/* n > 0: every persistent conv grid of this process (the 3x3 forward / dgrad kernels, the two weight-gradient kernels, conv1 forward) is capped
+ * at n workgroups, whatever the launch's `shared` hint says; 0 restores the normal rule (capped only beside other task slots).  Process-wide.
+ * No result depends on it: it lets tiny shapes reach the capped paths (tests/test_hip_conv_grid_cap.py). */
+void masr_test_set_conv_grid_cap(int n);
 /* Linear weight gradients as a grouped launch (mk_gemm_wgrad_grouped: one grid of 256 x 256 tiles): dW[N][K] = dy[rows][N]^T x[rows][K], db[N] =
  * column sums of dy (or null); a second member with the same operands when dW2 is given.
  * _n: `members` members over the same operands (member i writes dW + i * member_stride); first_members > 0: the two-segment tile list of the

@@ -10,6 +10,7 @@
 // The same kernel computes dgrad (input = dY, weights = 180-degree-rotated/transposed shadow).
 // wgrad is the reduction-major product dW[co][tap,ci] = sum_p dY[p][co] * in[p+off][ci]
 // (transposing LDS reads), split over pixel ranges with a deterministic slab reduce.
+#include <atomic>
 #include "common.h"
 #include "kernels.h"
 #include "folds.h"
@@ -1064,8 +1065,18 @@ __global__ __launch_bounds__(320) void conv3x3_resw_kernel(ConvArgs a, int ntile
 // UNPOOL: the input map (the gradient behind the first max-pool) is never materialised -- FOUR producer waves (4 .. 7, one per SIMD;
 // wave 4 keeps the tap image and the neighbourhood DMA) build each patch from the pooled gradient a.in_pooled + the pool codes
 // a.in_idx (unpool_expand), 512 threads.
+// VIRTUAL WORKGROUPS: the rows of 640 partial sums -- nvirt of them, row v = the sum over tiles v, v + nvirt, ... in that order -- are part of
+// the result's bits, the number of launched workgroups is not: workgroup r of gridDim.x runs the ids r, r + gridDim.x, ... one after the
+// other as ONE flattened tile sequence (w1x_next_tile: every role derives it on its own), so the patch pipeline never notices an id
+// boundary; the MFMA waves write row v and zero their partial behind v's last tile.  With gridDim.x == nvirt: the walk it always was.
+__device__ __forceinline__ int w1x_next_tile(int t, int nvirt, int G, int ntiles) {
+    if (t < 0) return -1;
+    if (t + nvirt < ntiles) return t + nvirt;               // the id's next tile
+    const int v = t % nvirt + G;                            // behind its last one: the first tile (= the id) of this workgroup's next id
+    return v < nvirt ? v : -1;
+}
 template <bool UNPOOL = false>
-__global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(ConvArgs a, int ntiles, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(ConvArgs a, int nvirt, int ntiles, int tiles_x, int tiles_y) {
     constexpr int MASK_TAP = 0;
     constexpr int CIN = 64, COUT = 64, TH = 16, TW = 16;
     constexpr int PW = TW + 2, PH = TH + 2, RPT = 16 / TW;
@@ -1116,7 +1127,7 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
     if constexpr (UNPOOL) {
     if (wave >= 4) {
         // ---------------- patch producers (see the streaming kernel's UNPOOL flavour: item = pooled cell x 16-byte channel chunk); wave 4
-        // also keeps the tap image, the neighbourhood DMA and tileq.  Tiles are dealt by a static stride, so every producer knows them.
+        // also keeps the tap image, the neighbourhood DMA and tileq.  Tiles are dealt by a static walk (w1x_next_tile), so every producer knows them.
         constexpr int NPROD = 4, NPR = PH / 2 + 1, NPC = PW / 2 + 1, NITEM = NPR * NPC * 8, NIT = (NITEM + 64 * NPROD - 1) / (64 * NPROD);
         const int pw = wave - 4, H2 = H / 2, W2 = W / 2;
         int rel[NIT], offA[NIT], offB[NIT], rcf[NIT];      // rcf = R << 16 | Cc << 8 | flags (1 item, 2 upper row, 4 lower row, 8 left, 16 right column in the patch)
@@ -1190,25 +1201,26 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
             }
         };
         const int G = (int)gridDim.x;
-        int cur = (int)blockIdx.x;                          // (the grid never exceeds the tile count)
+        auto next_tile = [&](int t) { return w1x_next_tile(t, nvirt, G, ntiles); };
+        int cur = (int)blockIdx.x;                          // (the grid never exceeds the id count, and the id count never the tile count)
         issue_loads(cur);
         if (pw == 0) {
             issue_x1(cur);
-            if (lane == 0) { tileq[0] = cur; tileq[1] = cur + G < ntiles ? cur + G : -1; }
+            if (lane == 0) { tileq[0] = cur; tileq[1] = next_tile(cur); }
         }
 #pragma unroll
         for (int it = 0; it < NIT; ++it) expand_store(it, pbuf);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");           // opening barrier: weights (every wave's share), patch 0, tileq[0..1]
         for (int k = 0; cur >= 0; ++k) {
-            const int nxt = cur + G < ntiles ? cur + G : -1;
+            const int nxt = next_tile(cur);
             if (nxt >= 0) issue_loads(nxt);
             if (pw == 0) {
                 // tile k is being computed: its tap image first (frees sxp), then tile k+1's neighbourhood
                 build_tap_image();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (nxt >= 0) issue_x1(nxt);
-                if (lane == 0) tileq[(k + 2) & 3] = (nxt >= 0 && nxt + G < ntiles) ? nxt + G : -1;
+                if (lane == 0) tileq[(k + 2) & 3] = next_tile(nxt);
             }
             if (nxt >= 0) {
                 char* const dst = pbuf + ((k + 1) & 1) * PBYTES;       // (patch k-1's buffer: free since E3 of tile k-1)
@@ -1288,11 +1300,11 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
             }
         };
         bool dry = false;
-        // Tiles are dealt by a STATIC stride (workgroup w: tiles w, w + G, ...), not by the tile counter: the wave-level partial sums
-        // run over all tiles of a workgroup, so the assignment fixes the summation order -- the gradient is bit-reproducible.
-        unsigned own = blockIdx.x;
+        // Tiles are dealt by a STATIC walk (virtual workgroup v: tiles v, v + nvirt, ...; w1x_next_tile), not by the tile counter: the
+        // wave-level partial sums run over all tiles of an id, so the assignment fixes the summation order -- the gradient is bit-reproducible.
+        int own = (int)blockIdx.x;
         const unsigned lim = (unsigned)ntiles;
-        auto issue_fetch = [&]() -> unsigned { const unsigned t = own; own += gridDim.x; return t; };
+        auto issue_fetch = [&]() -> unsigned { const int t = own; own = w1x_next_tile(own, nvirt, (int)gridDim.x, ntiles); return (unsigned)t; };   // (-1 = past the end: >= lim)
         int cur, nxt;
         {
             const unsigned t0f = issue_fetch(), t1f = issue_fetch();
@@ -1377,6 +1389,7 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
         const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
         const int d0 = tx * TW, t0 = ty * TH;
         const int tl = t0 + prow0, dl = d0 + pcol0;
+        const int id_done = tile + nvirt >= ntiles ? tile % nvirt : -1;       // the virtual workgroup whose last tile this is
         // ReLU mask of conv1's output as one 64-bit word per pixel (bit c = channel c passed; written by conv1's forward
         // launch, mk_conv1_fwd): this lane's pixel of row i, requested at the first tap -- four 8-byte loads per wave
         // and tile where the bf16 map itself cost eight 16-byte loads, in a launch that is bound by vector-memory instructions at the
@@ -1442,11 +1455,14 @@ __global__ __launch_bounds__(UNPOOL ? 512 : 320) void conv3x3_resw_w1x_kernel(Co
             cw = mma16(af, wtap < 9 ? xb : cfrag, cw);
         }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // E3
-    }
-    if ((lane & 15) < 10) {                                // one row of 640 partial sums per workgroup (mk_conv1_wgrad_fused_reduce)
+        if (id_done >= 0) {                                // one row of 640 partial sums per virtual workgroup (mk_conv1_wgrad_fused_reduce)
+            if ((lane & 15) < 10) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) a.w1_slab[(long)blockIdx.x * 640 + (wave * 16 + 4 * (lane >> 4) + r) * 10 + (lane & 15)] = cw[r];
+                for (int r = 0; r < 4; ++r) a.w1_slab[(long)id_done * 640 + (wave * 16 + 4 * (lane >> 4) + r) * 10 + (lane & 15)] = cw[r];
+            }
+            cw = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // E3
     }
 }
 
@@ -1537,7 +1553,8 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     const int pprel = (pp_r * W2p + pp_c) * COUT + (tid & 7) * 8;
     // the tiles of a workgroup are fetched in walk order (first, first + nwg, ...): their (x, y, image) coordinates advance by a fixed
     // step with two carries instead of three integer divisions per tile (~90 instructions of the staging waves' ~370 per tile)
-    int wt = blockIdx.x, wx = wt % tiles_x, wy = (wt / tiles_x) % tiles_y, wb = wt / (tiles_x * tiles_y);
+    int wt = 0, wx = 0, wy = 0, wb = 0;
+    auto begin_walk = [&](int first) { wt = first; wx = wt % tiles_x; wy = (wt / tiles_x) % tiles_y; wb = wt / (tiles_x * tiles_y); };
     const int sx = nwg % tiles_x, sy = (nwg / tiles_x) % tiles_y, sb = nwg / (tiles_x * tiles_y);
     const int lx = (ntiles - 1) % tiles_x, ly = ((ntiles - 1) / tiles_x) % tiles_y, lb = (ntiles - 1) / (tiles_x * tiles_y);
     auto bld8 = [](__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); };
@@ -1627,7 +1644,6 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     typedef __attribute__((address_space(3))) bf16x4 lds_b4;
     const int g = lane >> 4, q = (lane & 15) >> 2, p4 = (lane & 3) * 4;
     const float dbm1 = do_db ? 1.f : 0.f;
-    float* red = reinterpret_cast<float*>(patch_);                        // bias-gradient partials [256][8] floats = 8 KB (after the last tile)
 
     auto read_a = [&](const bf16* dyt, int kc, bf16x8 (&af)[4]) {
 #pragma unroll
@@ -1650,61 +1666,82 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
     // The partial slab is written in REGISTER order -- element ((tap * 4 + fm) * 256 + thread) * 4 + r of this (64-ci, 64-co) block's 36 864 --
     // 36 sixteen-byte stores per lane, a kilobyte per wave-instruction (in [co][tap][ci] order the same 147 KB left as 144 dword stores per
     // lane in 64-byte pieces, at the end of the launch with every CU storing at once); conv3x3_wgrad_reduce_body un-permutes (folds.h)
-    auto write_slab = [&](f32x4 (&acc)[9][4]) {
-        float* out = a.slab + (long)blockIdx.x * COUT * KTOT + (long)blockIdx.y * (64 * 9 * 64) + tid * 4;
+    auto write_slab = [&](f32x4 (&acc)[9][4], int v) {
+        float* out = a.slab + (long)v * COUT * KTOT + (long)blockIdx.y * (64 * 9 * 64) + tid * 4;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
             for (int fm = 0; fm < 4; ++fm) *reinterpret_cast<f32x4*>(out + (tap * 4 + fm) * 1024) = acc[tap][fm];
     };
-    auto fold_db = [&]() {                                       // threads with equal tid % 8 own the same 8 output channels
+    auto fold_db = [&](const float* red, int v) {                // threads with equal tid % 8 own the same 8 output channels
         const int rc = tid / 8, j = tid % 8;
         float sum = 0.f;
         for (int t = rc; t < 256; t += 8) sum += red[t * 8 + j];
-        a.slab[(long)nwg * COUT * KTOT + (long)blockIdx.x * COUT + ch * 64 + tid] = sum;
+        a.slab[(long)nwg * COUT * KTOT + (long)v * COUT + ch * 64 + tid] = sum;
     };
 
     {
-        // The two roles are two separate loops with the SAME sequence of barriers (one in front of the first tile, one behind every tile,
-        // one behind the bias partials): the accumulators live only in the consumers' branch and the staging registers only in the
-        // producers', so one register budget (256 per thread at two waves per SIMD) holds either.
-        const int first = blockIdx.x, niter = first < ntiles ? (ntiles - first + nwg - 1) / nwg : 0;
+        // The two roles are two separate loops with the SAME sequence of barriers (per virtual workgroup: one in front of its first tile, one
+        // behind every tile, one behind the bias partials): the accumulators live only in the consumers' branch and the staging registers
+        // only in the producers', so one register budget (256 per thread at two waves per SIMD) holds either.
+        // VIRTUAL WORKGROUPS: the partition of the tiles into nwg partial slabs (id v walks v, v + nwg, ...) is part of the result's bits, the
+        // number of launched workgroups is not: workgroup r of gridDim.x runs the ids r, r + gridDim.x, ... one after the other -- v's tiles in
+        // v's order, v's slab and bias partial written, accumulators zeroed.  With gridDim.x == nwg this is the one pass it always was.  Across
+        // an id boundary the loads stay in flight (the next id's first two tiles are requested before the bias partials are folded); the LDS
+        // side restarts, on the OTHER buffer (pb): the bias partials of the finished id sit in the buffer its first tile had, and are read
+        // while the next id's first tile is staged.
+        const int G = (int)gridDim.x;
+        auto tiles_of = [&](int v) { return (ntiles - v + nwg - 1) / nwg; };        // (v < nwg <= ntiles: at least one)
         if (producer) {
             // TWO tiles in flight: a tile's loads are requested two tile periods before they are staged (with one, the producers alone ran
             // at a memory round trip per tile, ~2 us, and set the pace of the launch).  Stage A carries the odd tiles of the walk, B the
             // even ones; behind the last tile the registers hold clamped re-reads, staged into the buffer nobody reads any more, not counted.
             Stage A, B;
             A.pcode = B.pcode = uint2{0u, 0u};
-            if (niter) { load_tile(B, first); load_tile(A, first + nwg); store_tile(B, patch_, dyt_, dbm1); load_tile(B, first + 2 * nwg); }
-            __syncthreads();
-            for (int it = 0; it < niter; it += 2) {
-                // consumers read buffer it & 1 = 0: tile it + 1 (A) goes into buffer 1, then A requests tile it + 3
-                const int tile = first + it * nwg;
-                store_tile(A, patch_ + PATCH_EL, dyt_ + DYT_EL, tile + nwg < ntiles ? dbm1 : 0.f);
-                load_tile(A, tile + 3 * nwg);
+            int v = blockIdx.x;
+            begin_walk(v); load_tile(B, v); load_tile(A, v + nwg);
+            for (int pb = 0; v < nwg; pb ^= 1) {
+                const int first = v, niter = tiles_of(v);
+                bf16* const p0 = patch_ + pb * PATCH_EL; bf16* const p1 = patch_ + (pb ^ 1) * PATCH_EL;
+                bf16* const d0 = dyt_ + pb * DYT_EL; bf16* const d1 = dyt_ + (pb ^ 1) * DYT_EL;
+                store_tile(B, p0, d0, dbm1); load_tile(B, first + 2 * nwg);
                 __syncthreads();
-                if (it + 1 < niter) {
-                    // consumers read buffer 1: tile it + 2 (B) goes into buffer 0, then B requests tile it + 4
-                    store_tile(B, patch_, dyt_, tile + 2 * nwg < ntiles ? dbm1 : 0.f);
-                    load_tile(B, tile + 4 * nwg);
+                for (int it = 0; it < niter; it += 2) {
+                    // consumers read the id's buffer 0 (p0): tile it + 1 (A) goes into buffer 1, then A requests tile it + 3
+                    const int tile = first + it * nwg;
+                    store_tile(A, p1, d1, tile + nwg < ntiles ? dbm1 : 0.f);
+                    load_tile(A, tile + 3 * nwg);
                     __syncthreads();
+                    if (it + 1 < niter) {
+                        // consumers read buffer 1: tile it + 2 (B) goes into buffer 0, then B requests tile it + 4
+                        store_tile(B, p0, d0, tile + 2 * nwg < ntiles ? dbm1 : 0.f);
+                        load_tile(B, tile + 4 * nwg);
+                        __syncthreads();
+                    }
                 }
-            }
-            if (do_db) {
+                v += G;
+                if (v < nwg) { begin_walk(v); load_tile(B, v); load_tile(A, v + nwg); }
+                if (do_db) {
+                    float* red = reinterpret_cast<float*>(p0);               // bias-gradient partials [256][8] floats = 8 KB (after the id's last tile)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) red[tid * 8 + j] = csum[j];
+                    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = csum[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) csum[j] = 0.f;
+                __syncthreads();
             }
-            __syncthreads();
         } else {
             f32x4 acc[9][4];
+            for (int v = blockIdx.x, pb = 0; v < nwg; v += G, pb ^= 1) {
+            const int niter = tiles_of(v);
 #pragma unroll
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
             __syncthreads();
             for (int it = 0; it < niter; ++it) {
-                const bf16* patch = patch_ + (it & 1) * PATCH_EL + hb;
-                const bf16* dyt = dyt_ + (it & 1) * DYT_EL;
+                const bf16* patch = patch_ + ((it + pb) & 1) * PATCH_EL + hb;
+                const bf16* dyt = dyt_ + ((it + pb) & 1) * DYT_EL;
                 // 36 steps (4 pixel slabs x 9 taps) of one x fragment x four dy fragments.  One wave per SIMD multiplies, so nobody else
                 // covers the LDS latency: the x halves arrive THREE steps ahead of the first step that multiplies them (one step = 4 MFMAs =
                 // 64 cycles; at one step ahead every tap waited ~a step for its fragment) and stay in registers until the last one has (hw:
@@ -1741,9 +1778,10 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad2_kernel(ConvWgradArgs a, in
 #undef CW_STEP
                 __syncthreads();
             }
-            write_slab(acc);
+            write_slab(acc, v);
             __syncthreads();
-            if (do_db && tid < 64) fold_db();
+            if (do_db && tid < 64) fold_db(reinterpret_cast<const float*>(patch_ + pb * PATCH_EL), v);
+            }
         }
     }
 }
@@ -1853,7 +1891,34 @@ __global__ void maxpool_idx_kernel(const bf16* __restrict__ in, uint8_t* __restr
 }  // namespace
 
 static int conv_ncu();
+// THE place that decides how many workgroups a persistent conv grid gets.  `resident`: what the launch takes when it has the GPU to itself
+// (one or two workgroups per CU).  A conv workgroup holds 98-154 KB of its CU's LDS for the whole launch (50-180 us), so beside it no
+// 48-72 KB GEMM workgroup of another task stream becomes resident.  `shared` (ConvArgs::shared) = the task slots that share the GPU, as the
+// training step reports them (masr_set_concurrency); every other caller leaves it 0.  THE RULE, measured on an MI355X:
+//   * one or two slots: never capped (a lone task loses 8-21 % under any cap; two slots lose 2.4 % at half the CUs and gain nothing at 5/8);
+//   * three slots or more: the kernels that take tiles from the atomic counter (`counter_fed`) get 5/8 of the CUs in workgroups (160 of 256),
+//     the static-walk kernels (wgrad2, fused conv1 wgrad) half of them (128: the cap has to spread their 256 virtual workgroups evenly,
+//     conv_static_grid) -- +1.5 % with four slots, +2.4 % with three; 3/8 of the CUs (96) gains nothing with four and loses with fewer.
+// The cap never changes a bit: the counter-fed kernels hand tiles to whoever asks, the static-walk kernels keep their partition and run it
+// as virtual workgroups (see there).
+static std::atomic<int> g_conv_grid_cap{0};                      // masr_test_set_conv_grid_cap: > 0 forces that cap on every launch
+void mk_conv_force_grid_cap(int n) { g_conv_grid_cap.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+static int conv_grid_limit(int resident, int shared, bool counter_fed) {
+    const int forced = g_conv_grid_cap.load(std::memory_order_relaxed);
+    const int cap = forced > 0 ? forced : shared >= 3 ? (counter_fed ? conv_ncu() * 5 / 8 : conv_ncu() / 2) : 0;
+    return cap > 0 && cap < resident ? cap : resident;
+}
+// The x dimension of the grid of a kernel that walks a FIXED share per virtual workgroup (V ids in x, `blocks` workgroups per id in y): the
+// launch lasts as long as its most loaded workgroup, so the cap is lowered to the grid that spreads the ids evenly over the rounds it needs
+// (256 ids under a cap of 128: 128; 200 ids: 100, not 128 with 72 of them running two ids and 56 one)
+static int conv_static_grid(int V, int blocks, int shared) {
+    int limit = conv_grid_limit(V * blocks, shared, false) / blocks;
+    if (limit < 1) limit = 1;
+    const int rounds = (V + limit - 1) / limit;
+    return (V + rounds - 1) / rounds;
+}
 // conv1 forward: exactly the workgroups that are resident together, every wave taking one contiguous run of the 16-pixel row segments
+// (a static split without sums: grid-independent bits.  A few KB of LDS per workgroup: it blocks nobody and takes no `shared` hint)
 static long conv1_mfma_grid(int B, int H, int W) {
     static const int resident = [] {
         int per_cu = 0;
@@ -1861,7 +1926,8 @@ static long conv1_mfma_grid(int B, int H, int W) {
         return conv_ncu() * (per_cu > 0 ? per_cu : 4);
     }();
     const long blocks = ((long)B * H * ((W + 15) / 16) + 3) / 4;
-    return blocks < resident ? blocks : resident;
+    const int limit = conv_grid_limit(resident, 0, true);
+    return blocks < limit ? blocks : limit;
 }
 int mk_conv1_fwd(const float* x, const float* w, const float* bias, bf16* out, int B, int H, int W, hipStream_t s, unsigned long long* relu_bits) {
     const long P = (long)B * H * W;
@@ -1899,7 +1965,7 @@ static int conv_ncu() {                                         // (task-slot th
     }();
     return ncu;
 }
-// workgroups (= rows of 640 partial sums) of the fused conv1-wgrad dgrad: one persistent workgroup per CU
+// virtual workgroups (= rows of 640 partial sums) of the fused conv1-wgrad dgrad: one per CU, whatever the launched grid
 static int resw_w1_rows(int B, int H, int W) {
     const long ntiles = (long)B * ((H + 15) / 16) * ((W + 15) / 16);
     return (int)(ntiles < conv_ncu() ? ntiles : conv_ncu());
@@ -1919,14 +1985,15 @@ static unsigned* sched_or_fallback(unsigned* sched) {
 static int launch_resw_w1(const ConvArgs& a, hipStream_t s) {
     const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 15) / 16, ntiles = tiles_x * tiles_y * a.B;
     if (!a.mask_bits) { mk_set_error("mk_conv3x3", "fused conv1 wgrad needs ConvArgs::mask_bits"); return -1; }
-    const dim3 g((unsigned)resw_w1_rows(a.B, a.H, a.W));
-    if (a.in_pooled) hipLaunchKernelGGL((conv3x3_resw_w1x_kernel<true>), g, dim3(512), 0, s, a, ntiles, tiles_x, tiles_y);
-    else hipLaunchKernelGGL((conv3x3_resw_w1x_kernel<false>), g, dim3(320), 0, s, a, ntiles, tiles_x, tiles_y);
+    const int nvirt = resw_w1_rows(a.B, a.H, a.W);        // rows of the slab = virtual workgroups, whatever the grid (see the kernel)
+    const dim3 g((unsigned)conv_static_grid(nvirt, 1, a.shared));
+    if (a.in_pooled) hipLaunchKernelGGL((conv3x3_resw_w1x_kernel<true>), g, dim3(512), 0, s, a, nvirt, ntiles, tiles_x, tiles_y);
+    else hipLaunchKernelGGL((conv3x3_resw_w1x_kernel<false>), g, dim3(320), 0, s, a, nvirt, ntiles, tiles_x, tiles_y);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // persistent grids: one workgroup per CU for the resident-weight kernel, as many as fit (1 or 2 per CU) for the streaming kernels
 static void launch_resw(const ConvArgs& a, hipStream_t s) {
-    const int resident = conv_ncu();
+    const int resident = conv_grid_limit(conv_ncu(), a.shared, true);
     ConvArgs b = a;
     b.sched = sched_or_fallback(a.sched);
     // 16 x 16 tiles at every width.  Round 6, measured and not kept: (i) 32 x 8 tiles where the width pads better to 8 -- the shipped idim 83:
@@ -1940,12 +2007,15 @@ static void launch_resw(const ConvArgs& a, hipStream_t s) {
 template <int CI, int CO, int TWV, int MASK, int THV = 16, bool UNPOOL = false>
 static void launch_stream_t(const ConvArgs& a, int tiles_x, int tiles_y, hipStream_t s) {
     constexpr int NT = UNPOOL ? 512 : 384;
-    static const int resident = [] {                             // (task-slot threads launch concurrently: thread-safe one-time initialisation)
+    static const int fit = [] {                                  // (task-slot threads launch concurrently: thread-safe one-time initialisation)
         int per_cu = 0;
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv3x3_stream_kernel<CI, CO, THV, TWV, MASK, UNPOOL>, NT, 0);
         if (per_cu <= 0) per_cu = 1;
         return conv_ncu() * (per_cu < 2 ? per_cu : 2);
     }();
+    // (any grid up to the tile count computes the same bits: tiles come from the counter -- UNPOOL: the first one is the workgroup's index,
+    // the later ones gridDim.x + counter -- and the last workgroup to run dry, counted against gridDim.x, re-arms it)
+    const int resident = conv_grid_limit(fit, a.shared, true);
     const int ntiles = tiles_x * tiles_y * a.B;
     ConvArgs b = a;
     b.sched = sched_or_fallback(a.sched);
@@ -2072,7 +2142,8 @@ int mk_conv3x3_wgrad(const ConvWgradArgs& a, hipStream_t s, int phase) {
     // phase 0: both launches; 1: the partial-slab kernel only; 2: the slab reduce only (the engine times them in separate slots)
     const Wgrad2Grid wg = wgrad2_grid(a);
     const int tw = wg.tw, tiles_x = wg.tiles_x, tiles_y = wg.tiles_y, ntiles = wg.ntiles, nwg = wg.nwg;
-    const dim3 grid(nwg, (a.CIN / 64) * (a.COUT / 64));
+    const int blocks = (a.CIN / 64) * (a.COUT / 64);
+    const dim3 grid(conv_static_grid(nwg, blocks, a.shared), blocks);    // (nwg virtual workgroups per channel block, see the kernel)
     // the staging fetches through 4 GB buffer descriptors (one per tensor); a larger tensor takes the instance with plain loads and zero selects
     const long px = (long)a.B * a.H * a.W;
     const bool buf = px * (a.CIN > a.COUT ? a.CIN : a.COUT) * 2 < (1L << 32) - 65536;

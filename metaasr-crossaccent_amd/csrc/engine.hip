@@ -343,7 +343,9 @@ static void drop_step_graphs(masr_model* m) {
 }
 // (no RESULT depends on the number of task slots -- "K task slots == the sequential run, bit for bit" is a guarantee of --tasks_per_gpu, and
 // every partition into partial sums is fixed per shape and per masr_set_ksplit; what follows the hint is the LDS footprint of a few launches:
-// GemmArgs::lean)
+// GemmArgs::lean -- and the size of the training step's persistent conv grids: ConvArgs::shared / ConvWgradArgs::shared cap them at 5/8 (tile-counter
+// kernels) and 1/2 (static-walk weight-gradient kernels) of the CUs from THREE slots on; one and two slots are never capped; conv_grid_limit in
+// conv.hip)
 void masr_set_concurrency(masr_model* m, int slots) { slots = slots < 1 ? 1 : slots; if (slots != m->slots) drop_step_graphs(m); m->slots = slots; }
 void masr_dropout_state(masr_model* m, uint64_t state[2], int set) {
     if (set) { m->seed = state[0]; m->step = state[1]; } else { state[0] = m->seed; state[1] = m->step; }

@@ -65,7 +65,7 @@ struct ConvArgs {
     unsigned long long* out_sign_bits;
     bf16* out; int B, H, W, CIN, COUT;
     // 64->64 dgrad of the second conv only: fuse the weight gradient of conv1 (x1 = fp32 network input [B][H][W]) into the
-    // epilogue; `out` is then never written, w1_slab receives 640 partial sums per workgroup (mk_conv1_wgrad_fused_reduce)
+    // epilogue; `out` is then never written, w1_slab receives 640 partial sums per virtual workgroup (mk_conv1_wgrad_fused_reduce)
     const float* x1; float* w1_slab;
     unsigned* sched;              // streaming kernel: 2 zero-initialised counters owned by the calling stream (null: a process-wide pair)
     bf16* pool_out;               // optional: MaxPool2d(2,2) (floor) of the ReLU'd output, [B][H/2][W/2][COUT], written by the same launch
@@ -77,6 +77,16 @@ struct ConvArgs {
     // out_coff .. out_coff + COUT of it (wk / bias already offset by the caller); 0 = a plain [..][COUT] map.  How mk_conv3x3 runs the
     // 256-channel convs of the BLSTM front-end: two passes of 128 output channels over the same patches.
     int out_cstride, out_coff;
+    // the task slots that share the GPU (masr_set_concurrency; the training step sets it, as GemmArgs::lean): from three on the persistent
+    // grid is capped below one workgroup per CU (conv_grid_limit in conv.hip states the rule), so that workgroups of the
+    // other streams find CUs whose LDS no conv workgroup holds for the whole launch.  Never part of the result's bits: the kernels that take
+    // tiles from the atomic counter do not care who computes a tile, and the two whose partition into partial sums IS part of the bits (the
+    // weight gradient, the fused conv1 weight gradient) keep that partition as VIRTUAL workgroups -- a launched workgroup runs the ids r,
+    // r + grid, ... one after the other, each with its own tile walk, slab row and zeroed accumulators.  0 = the grid of a launch that has
+    // the GPU to itself.  Which family a launcher belongs to is said in two places of conv.hip that go together: the static walks size
+    // their grid through conv_static_grid (which asks conv_grid_limit with counter_fed = false and spreads the ids evenly), every other
+    // launcher asks conv_grid_limit with counter_fed = true.
+    int shared;
 };
 int mk_conv3x3(const ConvArgs& a, hipStream_t s);
 long mk_conv1_wgrad_fused_slab_floats(int B, int H, int W);
@@ -87,7 +97,10 @@ struct ConvWgradArgs {
     // optional: dy = the 2x2 max-pool (+ ReLU) backward of dy_pooled [B][H/2][W/2][COUT] under the codes of ConvArgs::pool_idx -- the kernel
     // expands it while staging (a quarter of the gradient bytes + one code byte per pooled element instead of the full-resolution map)
     const bf16* dy_pooled; const uint8_t* pool_idx;
+    int shared;                   // as ConvArgs::shared
 };
+// test hook (masr_test_set_conv_grid_cap): n > 0 caps every persistent conv grid at n workgroups whatever `shared` says; 0 = the normal rule
+void mk_conv_force_grid_cap(int n);
 int mk_conv3x3_wgrad(const ConvWgradArgs& a, hipStream_t s, int phase = 0);     // phase 1 / 2: the partial-slab kernel / the slab reduce alone
 long mk_conv3x3_wgrad_slab_floats(int B, int H, int W, int CIN, int COUT);
 int mk_maxpool_fwd(const bf16* in, bf16* out, int B, int H, int W, int C, hipStream_t s, int ceil_mode = 0);
@@ -336,7 +349,7 @@ struct LnReduceGroup { int n; LnReduceDesc p[LN_GROUP_MAX]; };
 int mk_layernorm_bwd_reduce_grouped(const LnReduceGroup& grp, int E, hipStream_t s);
 // every fold pass that closes a transformer step's backward as ONE launch (fold.hip): conv[k] = slab reduce of a 3x3-conv weight gradient
 // (mk_conv3x3_wgrad phase 2; nsplit = the partial slabs its phase 1 wrote), conv1 = the 640-sum rows of the fused conv1 weight gradient
-// (nblocks rows: one per workgroup of that launch), ln = mk_layernorm_bwd_reduce_grouped's list, unperm = mk_vgg2enc_grad_unpermute,
+// (nblocks rows: one per VIRTUAL workgroup of that launch -- a function of the shape, not of the launched grid), ln = mk_layernorm_bwd_reduce_grouped's list, unperm = mk_vgg2enc_grad_unpermute,
 // embed = mk_embed_bwd.  A null output pointer (dw / dtable) leaves the job out.
 struct FoldJobs {
     int nconv, E;
@@ -347,7 +360,7 @@ struct FoldJobs {
     LnReduceGroup ln;
 };
 int mk_backward_folds(const FoldJobs& j, hipStream_t s);
-int mk_conv3x3_wgrad_nsplit(const ConvWgradArgs& a);                     // the partial slabs mk_conv3x3_wgrad's phase 1 writes for this launch
+int mk_conv3x3_wgrad_nsplit(const ConvWgradArgs& a);                     // the partial slabs mk_conv3x3_wgrad's phase 1 writes for this launch (virtual workgroups: whatever grid runs them)
 int mk_conv1_wgrad_fused_rows(int B, int H, int W);                      // the 640-sum rows the fused conv1 weight gradient writes
 int mk_embed_fwd(const int* tok, const float* table, const float* pe, float* y32, bf16* y16,
                    int B, int L, int E, float drop_p, uint32_t seed, uint32_t site, hipStream_t s, const uint32_t* seed_ptr = nullptr);

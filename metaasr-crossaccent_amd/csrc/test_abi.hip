@@ -631,6 +631,7 @@ int masr_test_conv3x3_wgrad(const uint16_t* in, const uint16_t* dy, float* dw, f
     ConvWgradArgs a{}; a.in = (const bf16*)in; a.dy = (const bf16*)dy; a.dw = dw; a.slab = slab; a.B = B; a.H = H; a.W = W; a.CIN = CIN; a.COUT = COUT;
     return mk_conv3x3_wgrad(a, (hipStream_t)stream);
 }
+void masr_test_set_conv_grid_cap(int n) { mk_conv_force_grid_cap(n); }
 int64_t masr_test_layernorm_slab_floats(int rows, int E) { return mk_layernorm_bwd_slab_floats(rows, E); }
 int masr_test_layernorm(const float* x, const float* gamma, const float* beta, const float* dy, float* y, uint16_t* y16, float* mean,
                         float* rstd, float* dx, uint16_t* dx16, float* dgamma, float* dbeta, float* slab, int rows, int E, float drop_p,

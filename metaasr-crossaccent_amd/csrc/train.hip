@@ -171,7 +171,7 @@ int forward_encoder(Ctx& c, const float* xs) {
     // element (which window position won, or that none passed the ReLU): the pooling convs store those and drop the map
     auto conv = [&](const bf16* in, const Conv& cv, bf16* out, int H, int W, bf16* pooled, uint8_t* idx) -> int {
         Prof p(m, MASR_PROF_CONV2_FWD + (int)(&cv - &m->conv[1]), s);
-        ConvArgs ca{}; ca.sched = m->conv_sched; ca.in = in; ca.wk = cv.k16; ca.bias = P + cv.b; ca.relu = 1; ca.mask = nullptr; ca.out = out;
+        ConvArgs ca{}; ca.sched = m->conv_sched; ca.in = in; ca.wk = cv.k16; ca.bias = P + cv.b; ca.relu = 1; ca.mask = nullptr; ca.out = out; ca.shared = c.train ? m->slots : 0;
         ca.B = B; ca.H = H; ca.W = W; ca.CIN = cv.CI; ca.COUT = cv.CO; ca.pool_out = pooled;      // MaxPool2d written by the producing conv's epilogue
         if (ca.pool_out) { ca.pool_idx = c.train ? idx : nullptr; ca.out_optional = 1; }
         if (&cv == &m->conv[2] && c.train) ca.out_sign_bits = a.a3_bits;      // conv3's ReLU mask as sign bits for conv4's masked dgrad
@@ -382,7 +382,7 @@ static int backward(Ctx& c, const float* xs) {
     auto wgrad = [&](const bf16* in, const bf16* dy, const Conv& cv, int H, int W, const bf16* dy_pooled = nullptr, const uint8_t* idx = nullptr) -> int {
         const int k = (int)(&cv - &m->conv[1]);
         ConvWgradArgs wa{}; wa.in = in; wa.dy = dy; wa.dw = G + cv.w; wa.db = G + cv.b; wa.slab = a.cw_slab[k]; wa.B = B; wa.H = H; wa.W = W; wa.CIN = cv.CI; wa.COUT = cv.CO;
-        wa.dy_pooled = dy_pooled; wa.pool_idx = idx;
+        wa.dy_pooled = dy_pooled; wa.pool_idx = idx; wa.shared = m->slots;
         { Prof p(m, MASR_PROF_CONV2_WGRAD + k, s); CK(mk_conv3x3_wgrad(wa, s, 1)); }     // the partial slabs; their reduce rides in the fold launch below
         folds.conv[folds.nconv++] = {a.cw_slab[k], mk_conv3x3_wgrad_nsplit(wa), G + cv.w, G + cv.b, cv.CI, cv.CO};
         return 0;
@@ -390,7 +390,7 @@ static int backward(Ctx& c, const float* xs) {
     auto dgrad = [&](const bf16* dy, const Conv& cv, bf16* out, int H, int W, const bf16* dy_pooled = nullptr, const uint8_t* idx = nullptr) -> int {
         Prof p(m, MASR_PROF_CONV2_DGRAD + (int)(&cv - &m->conv[1]), s);
         ConvArgs ca{}; ca.sched = m->conv_sched; ca.in = dy; ca.in_pooled = dy_pooled; ca.in_idx = idx; ca.wk = cv.d16; ca.out = out; ca.B = B; ca.H = H; ca.W = W;
-        ca.CIN = cv.CO; ca.COUT = cv.CI;
+        ca.CIN = cv.CO; ca.COUT = cv.CI; ca.shared = m->slots;       // (also the fused conv1 weight gradient's w1_slab launch)
         if (&cv == &m->conv[3]) { ca.mask = a.a3; ca.mask_bits = a.a3_bits; }      // conv3's ReLU mask: the sign words its forward launch wrote
         if (&cv == &m->conv[1]) {
             // d(conv1 output) is consumed only by conv1's weight gradient: contracted inside the dgrad epilogue, never stored
