@@ -369,6 +369,22 @@ int masr_test_transpose_cast_bf16(const float* x, uint16_t* y, int R, int C, int
 int masr_test_cast_bf16(const float* x, uint16_t* y, int64_t n, void* stream);
 int masr_test_conv_weight_shadows(const float* w, uint16_t* wk, uint16_t* wd, int CO, int CI, void* stream);
 
+/* ---- the CTC loss kernels alone (ctc.hip: ctc_lse_kernel, ctc_sweep_kernel, ctc_grad_kernel, ctc_mean_kernel, ctc_mix_kernel;
+ * tests/test_hip_ctc_loss_kernels.py against tests/ctc_loss_ref.py).  All arrays on the device.
+ * include/masr.h's CTC loss entry with its arguments, refusals and status word (masr_ctc_status on the same work buffer), and the launcher's
+ * batch_first flag exposed: set, logits and grad are [B][T][C] (what the BLSTM engine passes), else [T][B][C].  Does not synchronise. */
+int masr_test_ctc_loss_layout(const float* logits, const int32_t* targets, const int32_t* tgt_off, const int32_t* in_len, const int32_t* tgt_len, int T,
+                              int B, int C, int blank, float* nll, float* loss, float* grad, float* work, int maxS, void* stream, int batch_first);
+/* the transformer's joint form (mk_ctc_loss_joint as train.hip ctc_forward calls it): logits fp32 [B][T][ld] with C <= ld valid columns, blank 0;
+ * nll fp32 [B]; stats[0] (the decoder's CE on entry) becomes (1 - w) stats[0] + w mean_b(nll_b / max(tgt_len_b, 1)); grad16 bf16 [B][T][ld] =
+ * w * d CTC / d logits with the pad columns C .. ld zero on every row, or null: forward only.  work: as many floats as masr_ctc_work_floats gives for T, B, maxS.
+ * This path has no device-side status word, so the entry reads in_len, tgt_len, tgt_off and the targets back and refuses, before any launch:
+ * in_len outside [0, T], a negative tgt_len or tgt_off, 2 tgt_len + 1 > maxS, a target id outside [1, C); and with the launcher: maxS > 2048,
+ * C > 4096, ld < C, ld % 8 != 0 with a gradient.  Synchronises the stream. */
+int masr_test_ctc_loss_joint(const float* logits, int64_t ld, const int32_t* targets, const int32_t* tgt_off, const int32_t* in_len,
+                             const int32_t* tgt_len, int T, int B, int C, float* nll, uint16_t* grad16, float w, float* stats, float* work, int maxS,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

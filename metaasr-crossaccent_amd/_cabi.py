@@ -247,6 +247,8 @@ _SIGS = {
     "masr_test_transpose_cast_bf16": (i32, [vp, vp, i32, i32, i64, vp]),
     "masr_test_cast_bf16": (i32, [vp, vp, i64, vp]),
     "masr_test_conv_weight_shadows": (i32, [vp, vp, vp, i32, i32, vp]),
+    "masr_test_ctc_loss_layout": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32]),
+    "masr_test_ctc_loss_joint": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, f32, vp, vp, i32, vp]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_NAMES = ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "conv2_dgrad", "conv3_dgrad", "conv4_dgrad", "conv2_wgrad",

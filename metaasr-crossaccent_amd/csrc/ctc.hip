@@ -1,5 +1,6 @@
-// CTC forward-backward lattice (config 1 / BLSTM path only; reference call site src/blstm_trainer.py:22,62-70:
-// nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) on log_softmax(pred)).
+// CTC forward-backward lattice: the whole objective of config 1 / the BLSTM path (mk_ctc_loss; reference call site
+// src/blstm_trainer.py:22,62-70: nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) on log_softmax(pred)) and the CTC half of the
+// transformer's joint CTC/attention objective (mk_ctc_loss_joint, train.hip ctc_forward: bf16 gradient times the CTC weight, padded rows).
 // The alpha and the beta recursion of an utterance are wavefront scans over the S = 2L+1 lattice: rows double-buffered in LDS, one
 // barrier per frame, run side by side by two workgroups; their rows are parked in HBM scratch and a chip-filling grid (one workgroup
 // per frame) forms the posteriors and d loss / d logits = (softmax - posterior) / (L * B).

@@ -1062,5 +1062,36 @@ int masr_test_conv_weight_shadows(const float* w, uint16_t* wk, uint16_t* wd, in
     HIP_CHECK_RET(hipStreamSynchronize(s));
     return 0;
 }
+// ---- the CTC loss kernels alone (ctc.hip; tests/test_hip_ctc_loss_kernels.py)
+int masr_test_ctc_loss_layout(const float* logits, const int32_t* targets, const int32_t* tgt_off, const int32_t* in_len, const int32_t* tgt_len, int T,
+                              int B, int C, int blank, float* nll, float* loss, float* grad, float* work, int maxS, void* stream, int batch_first) {
+    return mk_ctc_loss(logits, targets, tgt_off, in_len, tgt_len, T, B, C, blank, nll, loss, grad, work, maxS, (hipStream_t)stream, batch_first != 0);
+}
+int masr_test_ctc_loss_joint(const float* logits, int64_t ld, const int32_t* targets, const int32_t* tgt_off, const int32_t* in_len,
+                             const int32_t* tgt_len, int T, int B, int C, float* nll, uint16_t* grad16, float w, float* stats, float* work, int maxS,
+                             void* stream) {
+    const char* fn = "masr_test_ctc_loss_joint";
+    if (!logits || !targets || !tgt_off || !in_len || !tgt_len || !nll || !stats || !work) { mk_set_error(fn, "null pointer"); return -1; }
+    if (T < 1 || B < 1 || C < 1 || maxS < 1) { mk_set_error(fn, "need T, B, C, maxS >= 1"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    // this path has no device-side status word (the engine vets its batch on the host): what the kernels would index with is vetted here
+    std::vector<int> il, tl, off, tg;
+    CK(test_read_ints(in_len, (size_t)B, il, s));
+    CK(test_read_ints(tgt_len, (size_t)B, tl, s));
+    CK(test_read_ints(tgt_off, (size_t)B, off, s));
+    for (int b = 0; b < B; ++b) {
+        if (il[b] < 0 || il[b] > T || tl[b] < 0) { mk_set_error(fn, "in_len outside [0, T] or a negative tgt_len"); return -1; }
+        if (tl[b] > (maxS - 1) / 2) { mk_set_error(fn, "target longer than the lattice the work buffer holds (2 tgt_len + 1 > maxS)"); return -1; }
+        if (off[b] < 0) { mk_set_error(fn, "negative target offset"); return -1; }
+    }
+    for (int b = 0; b < B; ++b) {
+        if (tl[b] == 0) continue;
+        CK(test_read_ints(targets + off[b], (size_t)tl[b], tg, s));
+        for (int v : tg) if (v < 1 || v >= C) { mk_set_error(fn, "target id outside [1, C)"); return -1; }
+    }
+    CK(mk_ctc_loss_joint(logits, (long)ld, targets, tgt_off, in_len, tgt_len, T, B, C, nll, (bf16*)grad16, w, stats, work, maxS, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    return 0;
+}
 
 }  // extern "C"
