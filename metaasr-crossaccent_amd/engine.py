@@ -180,6 +180,51 @@ class PendingStats:
         return self._result
 
 
+def _best_lists(tok, lens, scores, *nbias):
+    """a step beam's best hypotheses -> (B token lists, scores on the host[, credited tokens on the host])"""
+    tok, lens = tok.cpu(), lens.cpu()
+    return ([tok[b, :int(lens[b])].tolist() for b in range(lens.size(0))], scores.cpu(), *[n.cpu() for n in nbias])
+
+
+def _nbest_lists_nbias(tok, lens, scores, nbias):
+    """the biased joint beam's lists -> per utterance [(token list, score, credited tokens), ...]"""
+    return [[(t, sc, int(n)) for t, sc, n in u] for u in nbest_lists(tok, lens, scores, nbias)]
+
+
+def _rescore_lists(*out):
+    tok, lens, scores, att, ctc, order = (t.cpu() for t in out)
+    return [[(tok[b, j, :int(lens[b, j])].tolist(), float(scores[b, j]), float(att[b, j]), float(ctc[b, j]), int(order[b, j]))
+             for j in range(lens.size(1)) if int(lens[b, j]) >= 0] for b in range(lens.size(0))]
+
+
+# What MasrEngine._decode runs, per entry point of include/masr.h: (its workspace query, that query's arguments behind the model; the entry
+# point's own arguments between the model and the outputs, in its order; the outputs behind tokens, lens, scores as _outputs' `extra`; what
+# turns the outputs into the lists of raw=False).  The names are _decode's: lm and bias are handles (lm an n-gram or an LSTM LM, as the entry
+# point takes), xs and il the inputs' pointers, r0 / r1 the min / max step ratio, bonus the length bonus, L the token stride of the outputs.
+# An entry point with r0 r1 is a step beam: L is the longest utterance's step limit, everywhere else T // 4.  One with N returns lists:
+# the outputs are [B, N, ...], else [B, ...].  tests/test_engine_decode_calls_cpu.py pins every call this table leads to.
+_DECODES = {
+    "masr_recog_beam": ("masr_beam_workspace_bytes", "B T K L", "xs il B T K r0 r1", "", _best_lists),
+    "masr_recog_beam_ctc": ("masr_beam_ctc_workspace_bytes", "B T K L", "xs il B T K r0 r1 att_w ctc_w", "", _best_lists),
+    "masr_recog_beam_lm": ("masr_beam_lm_workspace_bytes", "B T K L", "lm xs il B T K r0 r1 lm_w", "", _best_lists),
+    "masr_recog_beam_nlm": ("masr_beam_nlm_workspace_bytes", "lm B T K L", "lm xs il B T K r0 r1 lm_w", "", _best_lists),
+    "masr_recog_beam_bias": ("masr_beam_bias_workspace_bytes", "B T K L", "lm bias xs il B T K r0 r1 lm_w bias_w", "i", _best_lists),
+    "masr_recog_beam_ctc_lm": ("masr_beam_ctc_lm_workspace_bytes", "B T K N L", "lm xs il B T K N r0 r1 att_w ctc_w lm_w bonus", "", nbest_lists),
+    "masr_recog_beam_ctc_nlm": ("masr_beam_ctc_nlm_workspace_bytes", "lm B T K N L", "lm xs il B T K N r0 r1 att_w ctc_w lm_w bonus", "", nbest_lists),
+    "masr_recog_beam_ctc_bias": ("masr_beam_ctc_bias_workspace_bytes", "B T K N L", "lm bias xs il B T K N r0 r1 att_w ctc_w lm_w bonus bias_w", "i",
+                                 _nbest_lists_nbias),
+    "masr_recog_ctc_beam": ("masr_ctc_beam_workspace_bytes", "B T K", "xs il B T K N", "", nbest_lists),
+    "masr_recog_ctc_beam_lm": ("masr_ctc_beam_workspace_bytes", "B T K", "lm xs il B T K N lm_w bonus", "f", nbest_lists),
+    "masr_recog_ctc_beam_nlm": ("masr_ctc_beam_nlm_workspace_bytes", "lm B T K", "lm xs il B T K N lm_w bonus", "f", nbest_lists),
+    "masr_recog_ctc_beam_bias": ("masr_ctc_beam_workspace_bytes", "B T K", "lm bias xs il B T K N lm_w bonus bias_w", "fi", nbest_lists_bias),
+    "masr_recog_rescore": ("masr_rescore_workspace_bytes", "B T K N L", "xs il B T K N att_w ctc_w", "ffi", _rescore_lists),
+    "masr_recog_rescore_lm": ("masr_rescore_workspace_bytes", "B T K N L", "lm xs il B T K N lm_w bonus att_w ctc_w", "ffi", _rescore_lists),
+    "masr_recog_rescore_nlm": ("masr_rescore_nlm_workspace_bytes", "lm B T K N L", "lm xs il B T K N lm_w bonus att_w ctc_w", "ffi", _rescore_lists),
+    "masr_recog_rescore_bias": ("masr_rescore_workspace_bytes", "B T K N L", "lm bias xs il B T K N lm_w bonus bias_w att_w ctc_w", "ffi", _rescore_lists),
+}
+_DECODE_FLOATS = frozenset("r0 r1 att_w ctc_w lm_w bonus bias_w".split())
+
+
 class MasrEngine:
     """One model instance on one GPU: flat fp32 params / grads + activation workspace."""
 
@@ -365,7 +410,7 @@ class MasrEngine:
               "masr_run_batch")
         self._last_x = xs          # keep the input alive until the stream has consumed it
 
-    # ------------------------------------------------------------------ decoding: what the wrappers below share
+    # ------------------------------------------------------------------ decoding: every recog_* below vets its arguments and calls _decode
     def _decode_inputs(self, xs, ilens):
         """xs on this device as contiguous fp32 and ilens as a host int64 tensor -> (xs, il, B, T)"""
         if xs.device != self.device:
@@ -391,10 +436,19 @@ class MasrEngine:
     def _beam_lmax(self, il, min_step_ratio, max_step_ratio):
         return max(ml for ml, _ in self.beam_lengths(il.tolist(), min_step_ratio, max_step_ratio))
 
-    @staticmethod
-    def _best_lists(tok, lens, scores):
-        tok, lens = tok.cpu(), lens.cpu()
-        return [tok[b, :int(lens[b])].tolist() for b in range(lens.size(0))], scores.cpu()
+    def _decode(self, fn, xs, ilens, raw=False, **v):
+        """one decode call: the entry point `fn` as its row of _DECODES describes it, on the arguments `v` that its method has vetted, under
+        the row's names.  Inputs, token stride, workspace, outputs, the call, then the device outputs (raw) or the row's lists."""
+        ws_fn, ws_args, order, extra, lists = _DECODES[fn]
+        order = order.split()
+        xs, il, B, T = self._decode_inputs(xs, ilens)
+        v.update(xs=_ptr(xs), il=_ptr(il), B=B, T=T)
+        v["L"] = self._beam_lmax(il, v["r0"], v["r1"]) if "r0" in order else T // 4
+        self._decode_ws(ws_fn, *[v[k] for k in ws_args.split()])
+        out = self._outputs(*[v[k] for k in ("B", "N") if k in order], ld=v["L"], extra=extra)
+        check(getattr(self._l, fn)(self.h, *[float(v[k]) if k in _DECODE_FLOATS else v[k] for k in order], *map(_ptr, out), self.stream()), fn)
+        self._last_x = xs
+        return out if raw else lists(*out)
 
     def recog(self, xs: torch.Tensor, ilens, full: bool = False):
         """greedy decode (MyTransformer.recog): returns int64 [Ldec, B] on the device, Ldec = max(ilens // 4).
@@ -426,16 +480,8 @@ class MasrEngine:
         CTC/attention search (masr_recog_beam_ctc: needs a hybrid model, ctc_weight > 0, att_weight >= 0); with ctc_weight == 0 the
         attention decoder alone decides and att_weight is not used."""
         K, _ = check_beam_args(beam_size)
-        joint = float(ctc_weight) != 0.0
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_ctc_workspace_bytes" if joint else "masr_beam_workspace_bytes", B, T, K, Lmax)
-        out = self._outputs(B, ld=Lmax)
-        fn, wts = ("masr_recog_beam_ctc", (float(att_weight), float(ctc_weight))) if joint else ("masr_recog_beam", ())
-        check(getattr(self._l, fn)(self.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), *wts, *map(_ptr, out),
-                                   self.stream()), fn)
-        self._last_x = xs
-        return self._best_lists(*out)
+        return self._decode("masr_recog_beam_ctc" if float(ctc_weight) != 0.0 else "masr_recog_beam", xs, ilens, K=K, r0=min_step_ratio,
+                            r1=max_step_ratio, att_w=att_weight, ctc_w=ctc_weight)
 
     def recog_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
         """beam search with an n-gram LM fused in (masr_recog_beam_lm): recog_beam's attention-only search with the per-step
@@ -443,14 +489,7 @@ class MasrEngine:
         Returns what recog_beam returns: (B token lists without sos / eos, fp32 scores [B] on the host)."""
         K, _ = check_beam_args(beam_size)
         lm_w, _ = check_lm_args(lm, lm_w, 0.0)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_lm_workspace_bytes", B, T, K, Lmax)
-        out = self._outputs(B, ld=Lmax)
-        check(self._l.masr_recog_beam_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), lm_w,
-                                         *map(_ptr, out), self.stream()), "masr_recog_beam_lm")
-        self._last_x = xs
-        return self._best_lists(*out)
+        return self._decode("masr_recog_beam_lm", xs, ilens, K=K, lm=lm.h, lm_w=lm_w, r0=min_step_ratio, r1=max_step_ratio)
 
     def recog_beam_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0):
         """beam search with an LSTM LM fused in (masr_recog_beam_nlm): recog_beam's attention-only search with the per-step
@@ -458,14 +497,7 @@ class MasrEngine:
         model's odim classes; lm_w finite and >= 0.  Returns what recog_beam returns."""
         K, _ = check_beam_args(beam_size)
         lm_w = check_nlm_args(nlm, lm_w)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_nlm_workspace_bytes", nlm.h, B, T, K, Lmax)
-        out = self._outputs(B, ld=Lmax)
-        check(self._l.masr_recog_beam_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio), float(max_step_ratio), lm_w,
-                                          *map(_ptr, out), self.stream()), "masr_recog_beam_nlm")
-        self._last_x = xs
-        return self._best_lists(*out)
+        return self._decode("masr_recog_beam_nlm", xs, ilens, K=K, lm=nlm.h, lm_w=lm_w, r0=min_step_ratio, r1=max_step_ratio)
 
     def recog_beam_ctc_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                           min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, att_weight: float = 0.7, ctc_weight: float = 0.3,
@@ -476,15 +508,8 @@ class MasrEngine:
         nbest (token list, score), best first (raw: the device tensors tokens [B, nbest, Lmax], lens, scores instead)."""
         K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_ctc_lm_workspace_bytes", B, T, K, N, Lmax)
-        out = self._outputs(B, N, ld=Lmax)
-        check(self._l.masr_recog_beam_ctc_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio), float(max_step_ratio),
-                                             float(att_weight), float(ctc_weight), lm_w, len_bonus, *map(_ptr, out), self.stream()),
-              "masr_recog_beam_ctc_lm")
-        self._last_x = xs
-        return out if raw else nbest_lists(*out)
+        return self._decode("masr_recog_beam_ctc_lm", xs, ilens, raw, K=K, N=N, lm=lm.h, lm_w=lm_w, bonus=len_bonus, r0=min_step_ratio,
+                            r1=max_step_ratio, att_w=att_weight, ctc_w=ctc_weight)
 
     def recog_beam_ctc_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                            min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, att_weight: float = 0.7, ctc_weight: float = 0.3,
@@ -495,27 +520,15 @@ class MasrEngine:
         recog_beam_ctc_lm returns: per utterance a list of at most nbest (token list, score), best first (raw: the device tensors)."""
         K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_ctc_nlm_workspace_bytes", nlm.h, B, T, K, N, Lmax)
-        out = self._outputs(B, N, ld=Lmax)
-        check(self._l.masr_recog_beam_ctc_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio), float(max_step_ratio),
-                                              float(att_weight), float(ctc_weight), lm_w, len_bonus, *map(_ptr, out), self.stream()),
-              "masr_recog_beam_ctc_nlm")
-        self._last_x = xs
-        return out if raw else nbest_lists(*out)
+        return self._decode("masr_recog_beam_ctc_nlm", xs, ilens, raw, K=K, N=N, lm=nlm.h, lm_w=lm_w, bonus=len_bonus, r0=min_step_ratio,
+                            r1=max_step_ratio, att_w=att_weight, ctc_w=ctc_weight)
 
     def recog_ctc_beam(self, xs: torch.Tensor, ilens, beam_size: int, nbest: int = 1, raw: bool = False):
         """CTC prefix beam search on the CTC head alone (masr_recog_ctc_beam; needs a hybrid model): one encoder pass, the
         head GEMM, one sweep over the T/4 frames.  Returns per utterance a list of at most nbest (token list, score), best first
         (raw: the device tensors tokens [B, nbest, T // 4], lens, scores instead)."""
         K, N = check_beam_args(beam_size, nbest)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
-        out = self._outputs(B, N, ld=T // 4)
-        check(self._l.masr_recog_ctc_beam(self.h, _ptr(xs), _ptr(il), B, T, K, N, *map(_ptr, out), self.stream()), "masr_recog_ctc_beam")
-        self._last_x = xs
-        return out if raw else nbest_lists(*out)
+        return self._decode("masr_recog_ctc_beam", xs, ilens, raw, K=K, N=N)
 
     def recog_ctc_beam_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                           raw: bool = False):
@@ -524,13 +537,7 @@ class MasrEngine:
         nbest (token list, fused score, acoustic score), best first (raw: the device tensors tokens, lens, scores, am instead)."""
         K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
-        out = self._outputs(B, N, ld=T // 4, extra="f")
-        check(self._l.masr_recog_ctc_beam_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, *map(_ptr, out), self.stream()),
-              "masr_recog_ctc_beam_lm")
-        self._last_x = xs
-        return out if raw else nbest_lists(*out)
+        return self._decode("masr_recog_ctc_beam_lm", xs, ilens, raw, K=K, N=N, lm=lm.h, lm_w=lm_w, bonus=len_bonus)
 
     def recog_ctc_beam_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
                             len_bonus: float = 0.0, nbest: int = 1, raw: bool = False):
@@ -541,13 +548,8 @@ class MasrEngine:
         K, N = check_beam_args(beam_size, nbest)
         bias_w = check_bias_args(bias, bias_w)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus) if lm is not None else (0.0, 0.0)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_ctc_beam_workspace_bytes", B, T, K)
-        out = self._outputs(B, N, ld=T // 4, extra="fi")
-        check(self._l.masr_recog_ctc_beam_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus,
-                                               bias_w, *map(_ptr, out), self.stream()), "masr_recog_ctc_beam_bias")
-        self._last_x = xs
-        return out if raw else nbest_lists_bias(*out)
+        return self._decode("masr_recog_ctc_beam_bias", xs, ilens, raw, K=K, N=N, lm=getattr(lm, "h", None), bias=bias.h, lm_w=lm_w, bonus=len_bonus,
+                            bias_w=bias_w)
 
     def recog_beam_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
                         min_step_ratio: float = 0.0, max_step_ratio: float = 1.0, raw: bool = False):
@@ -558,14 +560,8 @@ class MasrEngine:
         K, _ = check_beam_args(beam_size)
         bias_w = check_bias_args(bias, bias_w)
         lm_w, _ = check_lm_args(lm, lm_w, 0.0) if lm is not None else (0.0, 0.0)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_bias_workspace_bytes", B, T, K, Lmax)
-        out = self._outputs(B, ld=Lmax, extra="i")
-        check(self._l.masr_recog_beam_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, float(min_step_ratio),
-                                           float(max_step_ratio), lm_w, bias_w, *map(_ptr, out), self.stream()), "masr_recog_beam_bias")
-        self._last_x = xs
-        return out if raw else (*self._best_lists(*out[:3]), out[3].cpu())
+        return self._decode("masr_recog_beam_bias", xs, ilens, raw, K=K, lm=getattr(lm, "h", None), bias=bias.h, lm_w=lm_w, bias_w=bias_w,
+                            r0=min_step_ratio, r1=max_step_ratio)
 
     def recog_beam_ctc_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
                             len_bonus: float = 0.0, nbest: int = 1, min_step_ratio: float = 0.0, max_step_ratio: float = 1.0,
@@ -582,15 +578,8 @@ class MasrEngine:
             lm_w, len_bonus = 0.0, float(len_bonus)
             if not math.isfinite(len_bonus):
                 raise ValueError(f"len_bonus must be finite, got {len_bonus}")
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        Lmax = self._beam_lmax(il, min_step_ratio, max_step_ratio)
-        self._decode_ws("masr_beam_ctc_bias_workspace_bytes", B, T, K, N, Lmax)
-        out = self._outputs(B, N, ld=Lmax, extra="i")
-        check(self._l.masr_recog_beam_ctc_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, float(min_step_ratio),
-                                               float(max_step_ratio), float(att_weight), float(ctc_weight), lm_w, len_bonus, bias_w,
-                                               *map(_ptr, out), self.stream()), "masr_recog_beam_ctc_bias")
-        self._last_x = xs
-        return out if raw else [[(t, sc, int(n)) for t, sc, n in u] for u in nbest_lists(*out)]
+        return self._decode("masr_recog_beam_ctc_bias", xs, ilens, raw, K=K, N=N, lm=getattr(lm, "h", None), bias=bias.h, lm_w=lm_w, bonus=len_bonus,
+                            bias_w=bias_w, r0=min_step_ratio, r1=max_step_ratio, att_w=att_weight, ctc_w=ctc_weight)
 
     def recog_rescore_bias(self, xs: torch.Tensor, ilens, beam_size: int, bias, bias_w: float = 3.0, lm=None, lm_w: float = 0.3,
                            len_bonus: float = 0.0, nbest=None, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
@@ -600,13 +589,8 @@ class MasrEngine:
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
         bias_w = check_bias_args(bias, bias_w)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus) if lm is not None else (0.0, 0.0)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
-        out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore_bias(self.h, lm.h if lm is not None else None, bias.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus,
-                                              bias_w, att_w, ctc_w, *map(_ptr, out), self.stream()), "masr_recog_rescore_bias")
-        self._last_x = xs
-        return out if raw else self._rescore_lists(out)
+        return self._decode("masr_recog_rescore_bias", xs, ilens, raw, K=K, N=N, lm=getattr(lm, "h", None), bias=bias.h, lm_w=lm_w, bonus=len_bonus,
+                            bias_w=bias_w, att_w=att_w, ctc_w=ctc_w)
 
     def recog_ctc_beam_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest: int = 1,
                            raw: bool = False):
@@ -616,13 +600,7 @@ class MasrEngine:
         (token list, fused score, acoustic score), best first (raw: the device tensors tokens, lens, scores, am instead)."""
         K, N = check_beam_args(beam_size, nbest)
         lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_ctc_beam_nlm_workspace_bytes", nlm.h, B, T, K)
-        out = self._outputs(B, N, ld=T // 4, extra="f")
-        check(self._l.masr_recog_ctc_beam_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, *map(_ptr, out), self.stream()),
-              "masr_recog_ctc_beam_nlm")
-        self._last_x = xs
-        return out if raw else nbest_lists(*out)
+        return self._decode("masr_recog_ctc_beam_nlm", xs, ilens, raw, K=K, N=N, lm=nlm.h, lm_w=lm_w, bonus=len_bonus)
 
     def ctc_align(self, xs: torch.Tensor, ilens, ys, olens, raw: bool = False):
         """CTC forced alignment of each utterance's transcript on the CTC head (masr_recog_ctc_align; needs a hybrid model): one
@@ -658,12 +636,6 @@ class MasrEngine:
         """tokens, lens, scores, att, ctc, order"""
         return self._outputs(B, N, ld=ld, extra="ffi")
 
-    @staticmethod
-    def _rescore_lists(out):
-        tok, lens, scores, att, ctc, order = (t.cpu() for t in out)
-        return [[(tok[b, j, :int(lens[b, j])].tolist(), float(scores[b, j]), float(att[b, j]), float(ctc[b, j]), int(order[b, j]))
-                 for j in range(lens.size(1)) if int(lens[b, j]) >= 0] for b in range(lens.size(0))]
-
     def recog_rescore(self, xs: torch.Tensor, ilens, beam_size: int, nbest=None, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
         """attention rescoring of the CTC beam's N-best (masr_recog_rescore; needs a hybrid model): the CTC prefix beam of
         recog_ctc_beam(beam_size, nbest), then ONE teacher-forced decoder pass over all B * nbest hypotheses, and the list re-ranked by
@@ -671,12 +643,7 @@ class MasrEngine:
         (raw: the device tensors tokens, lens, scores, att, ctc, order instead).  The call waits for the stream once, between the passes."""
         K, N = check_beam_args(beam_size, nbest)
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
-        out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore(self.h, _ptr(xs), _ptr(il), B, T, K, N, att_w, ctc_w, *map(_ptr, out), self.stream()), "masr_recog_rescore")
-        self._last_x = xs
-        return out if raw else self._rescore_lists(out)
+        return self._decode("masr_recog_rescore", xs, ilens, raw, K=K, N=N, att_w=att_w, ctc_w=ctc_w)
 
     def recog_rescore_lm(self, xs: torch.Tensor, ilens, beam_size: int, lm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest=None,
                          att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
@@ -685,13 +652,7 @@ class MasrEngine:
         K, N = check_beam_args(beam_size, nbest)
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
         lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_rescore_workspace_bytes", B, T, K, N, T // 4)
-        out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore_lm(self.h, lm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, att_w, ctc_w, *map(_ptr, out),
-                                            self.stream()), "masr_recog_rescore_lm")
-        self._last_x = xs
-        return out if raw else self._rescore_lists(out)
+        return self._decode("masr_recog_rescore_lm", xs, ilens, raw, K=K, N=N, lm=lm.h, lm_w=lm_w, bonus=len_bonus, att_w=att_w, ctc_w=ctc_w)
 
     def recog_rescore_nlm(self, xs: torch.Tensor, ilens, beam_size: int, nlm, lm_w: float = 0.3, len_bonus: float = 0.0, nbest=None,
                           att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
@@ -700,13 +661,7 @@ class MasrEngine:
         K, N = check_beam_args(beam_size, nbest)
         att_w, ctc_w = self._rescore_weights(att_w, ctc_w)
         lm_w, len_bonus = check_nlm_args(nlm, lm_w, len_bonus)
-        xs, il, B, T = self._decode_inputs(xs, ilens)
-        self._decode_ws("masr_rescore_nlm_workspace_bytes", nlm.h, B, T, K, N, T // 4)
-        out = self._rescore_outputs(B, N, T // 4)
-        check(self._l.masr_recog_rescore_nlm(self.h, nlm.h, _ptr(xs), _ptr(il), B, T, K, N, lm_w, len_bonus, att_w, ctc_w, *map(_ptr, out),
-                                             self.stream()), "masr_recog_rescore_nlm")
-        self._last_x = xs
-        return out if raw else self._rescore_lists(out)
+        return self._decode("masr_recog_rescore_nlm", xs, ilens, raw, K=K, N=N, lm=nlm.h, lm_w=lm_w, bonus=len_bonus, att_w=att_w, ctc_w=ctc_w)
 
     def rescore_nbest(self, xs: torch.Tensor, ilens, tokens, lens, ctc, att_w: float = 0.5, ctc_w: float = 0.5, raw: bool = False):
         """attention rescoring of a caller's N-best lists (masr_rescore_nbest): tokens int32 [B, N, ld], lens int32 [B, N] (-1 = no entry),
@@ -726,40 +681,40 @@ class MasrEngine:
         check(self._l.masr_rescore_nbest(self.h, _ptr(xs), _ptr(il), B, T, N, _ptr(tokens), ld, _ptr(lens), _ptr(ctc), att_w, ctc_w,
                                          *map(_ptr, out), self.stream()), "masr_rescore_nbest")
         self._last_x = xs
-        return out if raw else self._rescore_lists(out)
+        return out if raw else _rescore_lists(*out)
+
+    def _ws_view(self, ptr, count, dtype):
+        """`count` elements of `dtype` at the device address `ptr`, as a view into the workspace"""
+        off = ptr - self.ws.data_ptr()
+        return self.ws[off:off + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def _head_logits_view(self, B, T, lp, ld, ep):
+        """(head logits fp32 [B, T // 4, ld], enc_lens int32 [B]) at the addresses a masr_test_*_logits hook answered"""
+        return self._ws_view(lp.value, B * (T // 4) * ld.value, torch.float32).view(B, T // 4, ld.value), self._ws_view(ep.value, B, torch.int32)
 
     def last_rescore_logits(self):
         """test hook (include/masr_test.h masr_test_rescore_logits): what the last rescoring call's score kernel read, as views into the
         workspace: (decoder logits fp32 [R, L, ld], gold int32 [R, L]); row r = b * N + first-pass rank"""
         lp, gp, ld, R, L = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int(), C.c_int()
         check(self._l.masr_test_rescore_logits(self.h, C.byref(lp), C.byref(ld), C.byref(gp), C.byref(R), C.byref(L)), "masr_test_rescore_logits")
-        base, n = self.ws.data_ptr(), R.value * L.value
-        logits = self.ws[lp.value - base:lp.value - base + n * ld.value * 4].view(torch.float32).view(R.value, L.value, ld.value)
-        return logits, self.ws[gp.value - base:gp.value - base + n * 4].view(torch.int32).view(R.value, L.value)
+        R, L = R.value, L.value
+        return self._ws_view(lp.value, R * L * ld.value, torch.float32).view(R, L, ld.value), self._ws_view(gp.value, R * L, torch.int32).view(R, L)
 
     def last_ctc_beam_logits(self, B, T, K):
         """test hook (include/masr_test.h masr_test_ctc_beam_logits): what the last recog_ctc_beam of this (B, T, K) searched, as views
         into the workspace: (head logits fp32 [B, T // 4, ld], enc_lens int32 [B])"""
         lp, ep, ld = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(self._l.masr_test_ctc_beam_logits(self.h, B, T, K, C.byref(lp), C.byref(ld), C.byref(ep)), "masr_test_ctc_beam_logits")
-        base, n = self.ws.data_ptr(), B * (T // 4) * ld.value * 4
-        logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
-        return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)
+        return self._head_logits_view(B, T, lp, ld, ep)
 
     def last_ctc_align_logits(self, B, T, maxL):
         """test hook (include/masr_test.h masr_test_ctc_align_logits): what the last ctc_align of this (B, T, maxL) aligned to, as views into
         the workspace: (head logits fp32 [B, T // 4, ld], enc_lens int32 [B])"""
         lp, ep, ld = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(self._l.masr_test_ctc_align_logits(self.h, B, T, maxL, C.byref(lp), C.byref(ld), C.byref(ep)), "masr_test_ctc_align_logits")
-        base, n = self.ws.data_ptr(), B * (T // 4) * ld.value * 4
-        logits = self.ws[lp.value - base:lp.value - base + n].view(torch.float32).view(B, T // 4, ld.value)
-        return logits, self.ws[ep.value - base:ep.value - base + B * 4].view(torch.int32)
+        return self._head_logits_view(B, T, lp, ld, ep)
 
     # ------------------------------------------------------------------ streaming first pass (include/masr.h masr_stream_*, DESIGN 5.16)
-    def _ws_view(self, ptr, count, dtype):
-        off = ptr - self.ws.data_ptr()
-        return self.ws[off:off + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
-
     def stream_begin(self, B: int, max_frames: int):
         """open a stream of B utterances of at most max_frames input frames under the engine's chunk policy (size > 0; needs a hybrid model)"""
         self._decode_ws("masr_stream_workspace_bytes", int(B), int(max_frames))

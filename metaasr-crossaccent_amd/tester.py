@@ -330,12 +330,22 @@ class Tester:
             logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
         logger.notice(f"LM shallow fusion: {self._load_lm(lm_path, self.sos_id, self.eos_id)}, lm_w = {self.lm_weight}")
 
-    def _load_nlm(self, path, start_id):
-        """self.nlm = the checkpoint as an LstmLM started with start_id, built once per Tester and (path, start_id)"""
-        key = (path, start_id)
+    @staticmethod
+    def _lm_start(bd):
+        start = bd.get('lm_start', 'sos')
+        if start not in ('sos', 'eos'):
+            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
+        return start
+
+    def _load_nlm(self, path, start, mode):
+        """self.nlm = the checkpoint as an LstmLM started with the token `start` (sos | eos), built once per Tester and (path, start id); one
+        over another number of classes than the model's is refused under `mode`'s name -> what the modes' log lines say about it"""
+        key = (path, self.sos_id if start == 'sos' else self.eos_id)
         if getattr(self, 'nlm', None) is None or getattr(self, '_nlm_key', None) != key:
             from .nlm import LstmLM
-            self.nlm, self._nlm_key = LstmLM.load(path, start_id=start_id), key
+            self.nlm, self._nlm_key = LstmLM.load(path, start_id=key[1]), key
+        if self.nlm.C != len(self.id2ch):
+            raise ValueError(f"{mode}: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
         return f"{path}, {self.nlm.L} x {self.nlm.H} LSTM on {self.nlm.E}-dim embeddings"
 
     def _nlm_beam_settings(self):
@@ -346,17 +356,13 @@ class Tester:
         bd = self._beam_size()
         self._step_ratios(bd)
         self.lm_weight = self._weight(bd, 'lm_w', 0.3)
-        start = bd.get('lm_start', 'sos')
-        if start not in ('sos', 'eos'):
-            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
+        start = self._lm_start(bd)
         if self._weight(bd, 'ctc_w', 0.0) > 0.0:
             if self.asr_model.engine.ctc_weight > 0.0:
                 raise ValueError(f"nlm_beam: the LSTM LM is not fused into the joint CTC/attention beam (beam_decode.ctc_w = {bd['ctc_w']}); "
                                  "set beam_decode.ctc_w: 0 to fuse it into the attention beam, or use --decode_mode beam without an LM")
             logger.notice(f"beam_decode.ctc_w = {bd['ctc_w']} ignored: this model has no CTC head")
-        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
-        if self.nlm.C != len(self.id2ch):
-            raise ValueError(f"nlm_beam: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        lm = self._load_nlm(lm_path, start, 'nlm_beam')
         logger.notice(f"LSTM LM shallow fusion: {lm}, start token {start}, lm_w = {self.lm_weight}")
 
     def _ctc_beam_settings(self):
@@ -419,12 +425,8 @@ class Tester:
         bd = self.config['solver']['beam_decode']
         self.lm_weight = self._weight(bd, 'lm_w', 0.3)
         self._len_bonus(bd)
-        start = bd.get('lm_start', 'sos')
-        if start not in ('sos', 'eos'):
-            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
-        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
-        if self.nlm.C != len(self.id2ch):
-            raise ValueError(f"{mode}: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        start = self._lm_start(bd)
+        lm = self._load_nlm(lm_path, start, mode)
         logger.notice(f"LSTM-LM-fused CTC beam: {lm}, start token {start}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}")
 
     def _lm_joint_settings(self):
@@ -464,12 +466,8 @@ class Tester:
         self.lm_weight = self._weight(bd, 'lm_w', 0.3)
         self._len_bonus(bd)
         self._nbest(bd, 1)
-        start = bd.get('lm_start', 'sos')
-        if start not in ('sos', 'eos'):
-            raise ValueError(f"solver.beam_decode.lm_start must be sos or eos, got {start!r}")
-        lm = self._load_nlm(lm_path, self.sos_id if start == 'sos' else self.eos_id)
-        if self.nlm.C != len(self.id2ch):
-            raise ValueError(f"nlm_joint_beam: the LSTM LM has {self.nlm.C} classes, the model {len(self.id2ch)} output units")
+        start = self._lm_start(bd)
+        lm = self._load_nlm(lm_path, start, 'nlm_joint_beam')
         logger.notice(f"Joint CTC/attention beam with LSTM LM: {lm}, start token {start}, att_w = {self.att_weight}, ctc_w = {self.ctc_weight}, "
                       f"lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}, nbest = {self.nbest}")
 
@@ -552,25 +550,16 @@ class Tester:
         applied to keep the Tester's contract)"""
         return [self.trim(n[0][0]) if self.model_name == 'blstm' else n[0][0] for n in lists]
 
-    def _lm_ctc_beam_lists(self, xs, ilens):
+    def _fused_ctc_beam_lists(self, mode, lm, xs, ilens, **bias):
+        """the N-best lists of lm_ctc_beam, nlm_ctc_beam and bias_ctc_beam (`bias`: its bias and bias_weight): a BLSTM runs them all through
+        ctc_beam_decode, per utterance; a transformer through the mode's own <mode>_decode, which takes the phrase list in front of the LM"""
         if self.model_name == 'blstm':
-            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus)
-        return self.asr_model.lm_ctc_beam_decode(xs, ilens, self.beam_size, self.lm, self.lm_weight, self.len_bonus)
-
-    def _nlm_ctc_beam_lists(self, xs, ilens):
-        if self.model_name == 'blstm':
-            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.nlm, self.lm_weight, self.len_bonus)
-        return self.asr_model.nlm_ctc_beam_decode(xs, ilens, self.beam_size, self.nlm, self.lm_weight, self.len_bonus)
-
-    def _bias_ctc_beam_lists(self, xs, ilens):
-        if self.model_name == 'blstm':
-            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, self.lm, self.lm_weight, self.len_bonus, bias=self.bias,
-                                                  bias_weight=self.bias_weight)
-        return self.asr_model.bias_ctc_beam_decode(xs, ilens, self.beam_size, self.bias, self.bias_weight, self.lm, self.lm_weight, self.len_bonus)
+            return self.asr_model.ctc_beam_decode(xs, ilens, self.beam_size, 1, lm, self.lm_weight, self.len_bonus, **bias)
+        return getattr(self.asr_model, mode + '_decode')(xs, ilens, self.beam_size, *bias.values(), lm, self.lm_weight, self.len_bonus)
 
     # mode -> (its settings function, (Tester, xs, ilens) -> the best hypothesis of each utterance, Tester -> what the start-up line names);
     # greedy has neither settings nor such a function: batch_greedy_decode writes its lines itself; nor has ctc_align, which reads the
-    # references too and writes ctc-ali (batch_ctc_align)
+    # references too and writes ctc-ali (batch_ctc_align).  _fused_ctc_beam_lists is reached through the class: `t` need only carry what it reads
     MODES = {
         'greedy': (None, None, lambda t: "greedy decoding"),
         'beam': (_beam_settings,
@@ -589,21 +578,22 @@ class Tester:
                     lambda t, xs, il: [n[0][0] for n in t.asr_model.rescore_decode(xs, il, t.beam_size, t.nbest, t.att_weight, t.ctc_weight)],
                     lambda t: f"attention rescoring (CTC beam {t.beam_size}, {t.nbest}-best, att_w = {t.att_weight}, ctc_w = {t.ctc_weight})"),
         'lm_ctc_beam': (_lm_ctc_settings,
-                        lambda t, xs, il: t._ctc_best(t._lm_ctc_beam_lists(xs, il)),
+                        lambda t, xs, il: t._ctc_best(Tester._fused_ctc_beam_lists(t, 'lm_ctc_beam', t.lm, xs, il)),
                         lambda t: f"LM-fused CTC prefix beam decoding (beam {t.beam_size})"),
         'lm_rescore': (_lm_ctc_settings,
                        lambda t, xs, il: [n[0][0] for n in t.asr_model.lm_rescore_decode(xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest,
                                                                                          t.att_weight, t.ctc_weight)],
                        lambda t: f"attention rescoring of the LM-fused CTC beam (beam {t.beam_size})"),
         'nlm_ctc_beam': (_nlm_ctc_settings,
-                         lambda t, xs, il: t._ctc_best(t._nlm_ctc_beam_lists(xs, il)),
+                         lambda t, xs, il: t._ctc_best(Tester._fused_ctc_beam_lists(t, 'nlm_ctc_beam', t.nlm, xs, il)),
                          lambda t: f"LSTM-LM-fused CTC prefix beam decoding (beam {t.beam_size})"),
         'nlm_rescore': (_nlm_ctc_settings,
                         lambda t, xs, il: [n[0][0] for n in t.asr_model.nlm_rescore_decode(xs, il, t.beam_size, t.nlm, t.lm_weight, t.len_bonus, t.nbest,
                                                                                            t.att_weight, t.ctc_weight)],
                         lambda t: f"attention rescoring of the LSTM-LM-fused CTC beam (beam {t.beam_size})"),
         'bias_ctc_beam': (_bias_ctc_settings,
-                          lambda t, xs, il: t._ctc_best(t._bias_ctc_beam_lists(xs, il)),
+                          lambda t, xs, il: t._ctc_best(Tester._fused_ctc_beam_lists(t, 'bias_ctc_beam', t.lm, xs, il, bias=t.bias,
+                                                                                     bias_weight=t.bias_weight)),
                           lambda t: f"phrase-biased CTC prefix beam decoding (bias_ctc_beam, beam {t.beam_size}, {t.bias.phrases} phrases)"),
         'bias_rescore': (_bias_ctc_settings,
                          lambda t, xs, il: [n[0][0] for n in t.asr_model.bias_rescore_decode(xs, il, t.beam_size, t.bias, t.bias_weight, t.lm, t.lm_weight,
