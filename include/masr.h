@@ -748,6 +748,55 @@ int masr_recog_rescore_bias(masr_model* m, const masr_lm* lm, const masr_bias* b
                             float lm_w, float len_bonus, float bias_w, float att_w, float ctc_w, int32_t* tokens, int32_t* lens, float* scores,
                             float* att, float* ctc, int32_t* order, void* stream);
 
+/* The resumable CTC prefix beam.  Model-free.  masr_ctc_beam_search (lm and bias null), masr_ctc_beam_search_lm (lm given) or
+ * masr_ctc_beam_search_bias (bias given, lm or not) run over frame ranges: the beam is kept in a state block of the work buffer between calls,
+ * so the search can follow logits that arrive piece by piece, and a result can be read at any point.  The run object is host memory only; it
+ * owns no GPU memory and holds the pointers it was opened with (logits, enc_lens, the LM's and the phrase list's tables, the work buffer),
+ * which must stay valid until masr_ctc_beam_run_close.  The LSTM LM search has no resumable form.
+ *   masr_ctc_beam_run_work_bytes  masr_ctc_beam_work_bytes(B, Tp, C, K) + the state block (per entry p_b, p_nb, last, len, hash, parent hash,
+ *                  lmacc, the packed LM context, the automaton's node and credit; per utterance the live count and the frame cursor).
+ *   masr_ctc_beam_run_open     checks the arguments, launches the initial state (the empty prefix, cursor 0).  NULL on a refusal.
+ *   masr_ctc_beam_run_advance  runs the frames [t_done, t_end) of every utterance, t_done the largest t_end so far (0 after open): the frame
+ *                  statistics of those rows, then for utterance b the frames [cursor_b, min(t_end, clamp(enc_lens[b]))).  Two launches; none
+ *                  when t_end == t_done.
+ *   masr_ctc_beam_run_result   the tail on the beam as it stands: outputs as the matching one-shot search writes them (am may be null without
+ *                  an LM and a phrase list, nbias without a phrase list).  Stores nothing into the state: the search continues afterwards.
+ *   masr_ctc_beam_run_close    frees the run object (null is allowed).
+ * Final result: after advance(Tp) the result equals the matching one-shot search on the same arguments bit for bit, however [0, Tp) was cut
+ * into calls.  Partial result: after advance(t) the result equals what the matching one-shot search returns with enc_lens[b] replaced by
+ * min(enc_lens[b], t), bit for bit -- the search is causal, so this is the definition of a partial result.  Causality: advance(t_end) reads no
+ * logits row at t >= t_end.  enc_lens is read on the device at every call; the caller may change enc_lens[b] between calls only among values
+ * >= the largest t_end passed so far (a stream's lengths: frames received / 4 until the utterance ends).  Otherwise results are unspecified,
+ * but every access stays inside the planned buffers: an utterance that stopped in front of a call's t_end, because its length said so then,
+ * stays stopped there whatever its length says later (a call runs an utterance only from the frame where the call's own rows begin), and
+ * one whose length fell below its cursor runs nothing.
+ * Refusals return -1 (open: NULL) with their text in masr_last_error() before any launch and leave the state unwritten: what the matching
+ * one-shot search refuses of these arguments, a work buffer below masr_ctc_beam_run_work_bytes or not 8-byte aligned, t_end < t_done or
+ * t_end > Tp, nbest outside [1, K], a null output that the search writes, a null run. */
+typedef struct masr_ctc_beam_run masr_ctc_beam_run;
+int64_t masr_ctc_beam_run_work_bytes(int B, int Tp, int C, int K);
+masr_ctc_beam_run* masr_ctc_beam_run_open(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int blank, int eos,
+                                          const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work,
+                                          int64_t work_bytes, void* stream);
+int masr_ctc_beam_run_advance(masr_ctc_beam_run* run, int t_end, void* stream);
+int masr_ctc_beam_run_result(const masr_ctc_beam_run* run, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias,
+                             void* stream);
+void masr_ctc_beam_run_close(masr_ctc_beam_run* run);
+/* The resumable beam inside a stream: the prefix beam follows the chunks, with the n-gram LM and the phrase list if given.
+ *   masr_stream_beam_open    on an open stream at any time (an open beam is replaced): a masr_ctc_beam_run on the stream's logits and
+ *                  lengths with blank 0, eos = odim - 1, in a work buffer and state block of its own behind the stream's other buffers
+ *                  (masr_stream_workspace_bytes includes them: masr_ctc_beam_run_work_bytes(B, max_frames / 4, odim, 64) more than before).
+ *                  Opened after some chunks have run, it runs the frames emitted so far at once (also after the last piece, when its result
+ *                  is then the final one).  Refuses what masr_recog_ctc_beam, _lm and _bias do.
+ *   masr_stream_feed         with a beam open, advances it once to the frames emitted, after the feed's chunk steps: two launches per feed.
+ *   masr_stream_beam_result  at any time: the partial result as defined above (before the first chunk: the empty prefix); after the last
+ *                  piece the final one, which without an LM and a phrase list equals masr_stream_ctc_beam(K, nbest) bit for bit.
+ *                  tokens int32 [B][nbest][max_frames / 4], lens, scores, am, nbias [B][nbest] (device).
+ * Whatever ends the stream ends its beam.  A stream without an open beam runs exactly the launches it ran before; masr_stream_ctc_beam is
+ * unchanged and may be called beside an open beam. */
+int masr_stream_beam_open(masr_model* m, int K, const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* stream);
+int masr_stream_beam_result(masr_model* m, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias, void* stream);
+
 /* Contextual phrase biasing of the attention beam and the joint beam.  A hypothesis of these searches is one token sequence on one
  * path (prefixes are never merged), so each live row carries the state (u, n) of its hypothesis, starting at (root, 0).  For a hypothesis h of
  * st - 1 tokens in state (u, n) and a class c at step st:

@@ -155,6 +155,11 @@ _SIGS = {
     "masr_ctc_beam_bias_work_bytes": (i64, [i32, i32, i32, i32]),
     "masr_ctc_beam_search_bias": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, f32, vp, i64, vp, vp, vp, vp, vp, vp]),
     "masr_ctc_beam_search_lm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
+    "masr_ctc_beam_run_work_bytes": (i64, [i32, i32, i32, i32]),
+    "masr_ctc_beam_run_open": (vp, [vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, f32, vp, i64, vp]),
+    "masr_ctc_beam_run_advance": (i32, [vp, i32, vp]),
+    "masr_ctc_beam_run_result": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+    "masr_ctc_beam_run_close": (None, [vp]),
     "masr_ctc_beam_nlm_work_bytes": (i64, [vp, i32, i32, i32, i32]),
     "masr_ctc_beam_search_nlm": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, f32, vp, i64, vp, vp, vp, vp, vp]),
     "masr_ctc_align_work_bytes": (i64, [i32, i32, i32]),
@@ -227,6 +232,8 @@ _SIGS = {
     "masr_stream_partial": (i32, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]),
     "masr_stream_logits": (i32, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i32)]),
     "masr_stream_ctc_beam": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "masr_stream_beam_open": (i32, [vp, i32, vp, f32, f32, vp, f32, vp]),
+    "masr_stream_beam_result": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
     "masr_test_lstm_shadows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "masr_test_lstm_unperm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "masr_test_lstm_fwd": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -337,6 +344,20 @@ def nbest_lists_bias(tok, lens, scores, am, nbias):
 
 
 nbest_lists_lm = nbest_lists                                   # (the name the LM-fused searches' callers know)
+
+
+def stable_prefix(nbest_lists):
+    """the longest common prefix of the token lists of all live entries of one utterance's partial K-best (stream_beam_result with
+    nbest = beam_size): [(token list, ...), ...] -> token list.  Every entry of a later beam extends an entry of this one, so the prefix
+    only grows from feed to feed and is a prefix of the final best hypothesis: the text a streaming front end can commit.  No live entry:
+    the empty list."""
+    toks = [list(e[0]) for e in nbest_lists]
+    if not toks:
+        return []
+    n = 0
+    while n < min(map(len, toks)) and all(t[n] == toks[0][n] for t in toks):
+        n += 1
+    return toks[0][:n]
 
 
 def check_beam_args(beam_size, nbest=1):

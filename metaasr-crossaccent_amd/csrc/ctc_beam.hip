@@ -34,6 +34,11 @@
 // runs of it: ctc_beam_sweep<LM, BIAS> = <LM, BIAS, PH_SWEEP> starts from the empty prefix and runs every frame and the tail; ctc_beam_frame
 // = <2, false, PH_FRAME> loads the beam from the work buffer, runs one frame and stores it; ctc_beam_tail = <2, false, PH_TAIL> loads and
 // runs the tail.  The modes differ in lm(c | h) alone (one switch in the frame, one in the tail) and in what an entry carries.
+//
+// The resumable search (masr_ctc_beam_run_*) is two more phases of the plain, n-gram and biased searches: <0|1, BIAS, PH_RANGE>
+// loads an utterance's beam and frame cursor from a state block in the work buffer, runs the frames [cursor, min(t_end, enc_len)) and stores
+// both back; <0|1, BIAS, PH_TAIL> loads them and runs the tail from the cursor without storing anything, so a result can be read at any
+// point and the search goes on.  ctc_beam_frames_kernel takes the frame range its launch covers.
 #include <cmath>
 #include <type_traits>
 
@@ -116,13 +121,14 @@ __device__ __forceinline__ float lm_score_packed(const LmDev& lm, unsigned long 
     return add_rn(acc, uni);
 }
 
-// grid ceil(B*Tp / 4), 256 threads: one wave per frame row b*Tp + t
-__global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
+// grid ceil(B*nt / 4), 256 threads: one wave per frame row b*Tp + t of the frames t_from <= t < t_from + nt <= Tp (the whole batch: 0, Tp)
+__global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a, int t_from, int nt) {
     const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (long)a.B * a.Tp) return;
-    const int b = (int)(row / a.Tp), t = (int)(row % a.Tp);
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= (long)a.B * nt) return;
+    const int b = (int)(r / nt), t = t_from + (int)(r % nt);
     if (t >= clamp_len(a.enc_lens[b], a.Tp)) return;
+    const long row = (long)b * a.Tp + t;
     const float* z = a.logits + row * a.ld;
     const RowLse l = row_lse(z, a.C, lane);
     const float lse = l.mx + l.log_s;
@@ -152,13 +158,31 @@ __global__ __launch_bounds__(256) void ctc_beam_frames_kernel(CtcBeamArgs a) {
 // re-ranks with or without an LM; without one la carries only am.
 struct CtcBiasArgs { BiasDev bias; float bias_w; int* nbias; };        // nbias [B][nbest]: n_final, -1 = no entry
 
-enum { PH_SWEEP, PH_FRAME, PH_TAIL };
-template <int M> using CtcLmSide = std::conditional_t<M == 2, CtcNlmArgs, CtcLmArgs>;
+// The resumable search (M = 0, 1) keeps its beam in a state block of the work buffer between launches --
+//   PH_RANGE  the beam and the frame cursor of the utterance from the state block, the frames [cursor, min(t_end, Tb)), both back.  One
+//             parity: the whole beam is in LDS before anything is stored.  The launch's frame statistics cover the rows [t_from, t_end), so
+//             an utterance whose cursor is behind t_from (it stopped at a shorter enc_len in an earlier call) runs nothing, whatever its
+//             enc_len says now: it stays stopped, and no row is read that no launch wrote
+//   PH_TAIL   the beam and the cursor, the tail with its record walk from cursor - 1 down; nothing is stored
+// -- and la is then a CtcLmRunArgs: the LM side, the state block and the call's frame range.
+// (plain ints, not an unnamed enum: PH == PH_SWEEP below is part of the kernel's mangled name, and an unnamed type is numbered differently in
+// the host and the device pass, so the host would look up a symbol the code object does not have)
+constexpr int PH_SWEEP = 0, PH_FRAME = 1, PH_TAIL = 2, PH_RANGE = 3;
+// the state block, [B][K] each but for the live count and the cursor [B]; lmacc and ctx are read with an LM only, bnode and bn with BIAS only
+struct CtcBeamState {
+    float *pb, *pnb, *lmacc;
+    int *last, *len, *bnode, *bn, *nlive, *cursor;
+    unsigned long long *hash, *phash, *ctx;
+};
+struct CtcLmRunArgs : CtcLmArgs { CtcBeamState st; int t_from, t_end; };
+template <int M, int PH> using CtcLmSide = std::conditional_t<M == 2, CtcNlmArgs, std::conditional_t<PH == PH_SWEEP, CtcLmArgs, CtcLmRunArgs>>;
 
 template <int M, bool BIAS, int PH>
-__global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, CtcLmSide<M> la, CtcBiasArgs ba, int nbest, int* __restrict__ tokens,
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, CtcLmSide<M, PH> la, CtcBiasArgs ba, int nbest, int* __restrict__ tokens,
                                                               int* __restrict__ lens, float* __restrict__ scores) {
-    static_assert((M == 2) == (PH != PH_SWEEP), "the LSTM LM's search runs frame by frame, the others in one sweep");
+    static_assert(M == 2 ? PH == PH_FRAME || PH == PH_TAIL : PH == PH_SWEEP || PH == PH_RANGE || PH == PH_TAIL,
+                  "the LSTM LM's search runs frame by frame, the others in one sweep or over frame ranges from the state block");
+    constexpr bool RUN = M != 2 && PH != PH_SWEEP;                   // the resumable search: the beam comes from la.st
     static_assert(!(M == 2 && BIAS), "biasing the LSTM LM search needs the automaton's state per entry in the work buffer (DESIGN 5.13): not built");
     constexpr bool LM = M != 0;
     __shared__ float s_pb[2][KMAX], s_pnb[2][KMAX];
@@ -197,6 +221,17 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, Ctc
             s_hash[0][tid] = la.hash[o]; s_phash[0][tid] = la.phash[o]; s_lmacc[0][tid] = la.lmacc[o];
         }
         t0 = st - 2; t1 = PH == PH_FRAME && t0 >= 0 && t0 < Tb ? t0 + 1 : t0;
+    } else if constexpr (RUN) {
+        const long o = (long)b * K + tid;
+        n = clamp_live(la.st.nlive[b], K);
+        if (tid < n) {
+            s_pb[0][tid] = la.st.pb[o]; s_pnb[0][tid] = la.st.pnb[o]; s_last[0][tid] = la.st.last[o]; s_len[0][tid] = la.st.len[o];
+            s_hash[0][tid] = la.st.hash[o]; s_phash[0][tid] = la.st.phash[o];
+            if constexpr (LM) { s_lmacc[0][tid] = la.st.lmacc[o]; s_ctx[0][tid] = la.st.ctx[o]; }
+            if constexpr (BIAS) { s_bnode[0][tid] = la.st.bnode[o]; s_bn[0][tid] = la.st.bn[o]; }
+        }
+        // (an utterance whose length fell below its cursor, or whose cursor is not where this call's rows begin, runs nothing and keeps it)
+        t0 = clamp_len(la.st.cursor[b], Tp); t1 = PH == PH_RANGE && t0 == la.t_from ? max(t0, min(la.t_end, Tb)) : t0;
     } else if (tid == 0) {
         s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_hash[0][0] = HASH_EMPTY; s_phash[0][0] = 0;
         if constexpr (LM) { s_lmacc[0][0] = 0.f; s_ctx[0][0] = 1; }          // the context [sos]: sos = 0 as id + 1
@@ -360,8 +395,20 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, Ctc
         if (tid == 0) la.nlive[(st & 1) * a.B + b] = n;
         return;
     }
-    // N-best list of the final beam: each live slot walks its records backwards (a prefix of len tokens meets exactly len emitting
-    // records on the way); everything behind a list's length is -1
+    if constexpr (RUN && PH == PH_RANGE) {
+        // the beam behind the range's last frame and the new cursor
+        const long o = (long)b * K + tid;
+        if (tid < n) {
+            la.st.pb[o] = s_pb[cur][tid]; la.st.pnb[o] = s_pnb[cur][tid]; la.st.last[o] = s_last[cur][tid]; la.st.len[o] = s_len[cur][tid];
+            la.st.hash[o] = s_hash[cur][tid]; la.st.phash[o] = s_phash[cur][tid];
+            if constexpr (LM) { la.st.lmacc[o] = s_lmacc[cur][tid]; la.st.ctx[o] = s_ctx[cur][tid]; }
+            if constexpr (BIAS) { la.st.bnode[o] = s_bnode[cur][tid]; la.st.bn[o] = s_bn[cur][tid]; }
+        }
+        if (tid == 0) { la.st.nlive[b] = n; la.st.cursor[b] = t1; }
+        return;
+    }
+    // N-best list of the final beam (the resumable search's tail: of the beam in front of the cursor): each live slot walks its records
+    // backwards (a prefix of len tokens meets exactly len emitting records on the way); everything behind a list's length is -1
     // LM: final(h) = fl(fl(am + lmacc) + fl(lm_w * lm(eos | h))), and list position i is the entry of rank i by (final descending, beam rank
     // ascending) -- ranked on the ordered bits, so the ranks are a permutation whatever the values
     // BIAS: final(h) = fl(y + fl(bias_w * n_final(h))), y the LM's final or, without one, am; s_bn becomes n_final
@@ -410,7 +457,7 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_kernel(CtcBeamArgs a, Ctc
         } else {
             scores[b * nbest + tid] = live ? log_add(s_pb[cur][tid], s_pnb[cur][tid]) : NEG_INF;
         }
-        for (int t = Tb - 1; t >= 0 && pos > 0; --t) {
+        for (int t = (RUN ? t0 : Tb) - 1; t >= 0 && pos > 0; --t) {
             const int rec = a.rec[((long)b * Tp + t) * K + slot];
             if (rec >> 8) out[(long)tid * Tp + --pos] = (rec >> 8) - 1;
             slot = rec & 0xff;
@@ -436,6 +483,18 @@ __global__ __launch_bounds__(SW_THREADS) void ctc_beam_nlm_prepare_kernel(CtcNlm
     for (long i = (long)b * SW_THREADS + threadIdx.x; i < htop_n; i += (long)gridDim.x * SW_THREADS) htop[i] = (bf16)0.f;
 }
 
+// grid B, 256 threads: the resumable search's initial state, the empty prefix in slot 0 of every utterance and the cursor at frame 0
+__global__ __launch_bounds__(SW_THREADS) void ctc_beam_run_init_kernel(CtcBeamState q, int K) {
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const long o = (long)b * K;
+        q.pb[o] = 0.f; q.pnb[o] = NEG_INF; q.last[o] = -1; q.len[o] = 0; q.hash[o] = HASH_EMPTY; q.phash[o] = 0;
+        q.lmacc[o] = 0.f; q.ctx[o] = 1;                              // the context [sos]: sos = 0 as id + 1
+        q.bnode[o] = 0; q.bn[o] = 0;
+        q.nlive[b] = 1; q.cursor[b] = 0;
+    }
+}
+
 long align256(long v) { return (v + 255) & ~255l; }
 int beam_width(int C, int K, int eos) { const int e = C - 1 - (eos >= 0 ? 1 : 0); return K < e ? K : e; }
 
@@ -447,14 +506,13 @@ int64_t mk_ctc_beam_work_bytes(int B, int Tp, int C, int K) {
     return 2 * align256(4 * rows) + 2 * align256(4 * rows * P) + align256(4 * rows * K);
 }
 
-// the argument checks of the three entry points; with_lm: an LM is fused (either kind), whose classes are lm_C
-static int ctc_beam_check(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
-                          const void* work, const int* tokens, const int* lens, const float* scores, bool with_lm, int lm_C, int lm_order, float lm_w,
-                          float len_bonus, const float* am) {
-    if (!logits || !enc_lens || !work || !tokens || !lens || !scores) { mk_set_error(fn, "null pointer"); return -1; }
+// the argument checks of the entry points, in two parts: what a search is run on (the resumable search has only this when it opens), and
+// where a result goes.  with_lm: an LM is fused (either kind), whose classes are lm_C
+static int ctc_beam_check_search(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int blank, int eos,
+                                 const void* work, bool with_lm, int lm_C, int lm_order, float lm_w, float len_bonus) {
+    if (!logits || !enc_lens || !work) { mk_set_error(fn, "null pointer"); return -1; }
     if (B < 1 || Tp < 1) { mk_set_error(fn, "need B >= 1 and Tp >= 1"); return -1; }
     if (K < 1 || K > 64) { mk_set_error(fn, "beam size K must be in [1, 64]"); return -1; }
-    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
     if (C < 2 || C > 4096 || ld < C) { mk_set_error(fn, "need 2 <= C <= 4096 and ld >= C"); return -1; }
     if (blank < 0 || blank >= C) { mk_set_error(fn, "blank must be in [0, C)"); return -1; }
     if (eos < -1 || eos >= C || eos == blank) { mk_set_error(fn, "eos must be -1 or a class in [0, C) other than blank"); return -1; }
@@ -466,9 +524,21 @@ static int ctc_beam_check(const char* fn, const float* logits, long ld, const in
         if (lm_order < 1 || lm_order > LM_MAX_ORDER) { mk_set_error(fn, "the language model's order must be in [1, 4]"); return -1; }
         if (!(lm_w >= 0.f) || !std::isfinite(lm_w)) { mk_set_error(fn, "lm_w must be finite and >= 0"); return -1; }
         if (!std::isfinite(len_bonus)) { mk_set_error(fn, "len_bonus must be finite"); return -1; }
-        if (!am) { mk_set_error(fn, "null pointer"); return -1; }
     }
     return 0;
+}
+// am: the search writes acoustic totals (an LM or a phrase list is fused); nbias: it writes the credited tokens (a phrase list)
+static int ctc_beam_check_result(const char* fn, int K, int nbest, const int* tokens, const int* lens, const float* scores, bool with_am, const float* am,
+                                 bool with_nbias, const int* nbias) {
+    if (!tokens || !lens || !scores || (with_am && !am) || (with_nbias && !nbias)) { mk_set_error(fn, "null pointer"); return -1; }
+    if (nbest < 1 || nbest > K) { mk_set_error(fn, "nbest must be in [1, K]"); return -1; }
+    return 0;
+}
+static int ctc_beam_check(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
+                          const void* work, const int* tokens, const int* lens, const float* scores, bool with_lm, int lm_C, int lm_order, float lm_w,
+                          float len_bonus, const float* am) {
+    CK(ctc_beam_check_search(fn, logits, ld, enc_lens, B, Tp, C, K, blank, eos, work, with_lm, lm_C, lm_order, lm_w, len_bonus));
+    return ctc_beam_check_result(fn, K, nbest, tokens, lens, scores, with_lm, am, false, nullptr);
 }
 // the plain search's arrays, carved from the front of the work buffer
 static CtcBeamArgs ctc_beam_carve(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int blank, int eos, void* work) {
@@ -484,14 +554,27 @@ static CtcBeamArgs ctc_beam_carve(const float* logits, long ld, const int* enc_l
     a.rec = (int*)w;
     return a;
 }
-static int ctc_beam_frames(const CtcBeamArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)(((long)a.B * a.Tp + 3) / 4)), dim3(256), 0, s, a);
+// the frame statistics of the rows (b, t_from <= t < t_end) with t < enc_len; rows outside the range are left as they are
+static int ctc_beam_frames(const CtcBeamArgs& a, int t_from, int t_end, hipStream_t s) {
+    const int nt = t_end - t_from;
+    hipLaunchKernelGGL(ctc_beam_frames_kernel, dim3((unsigned)(((long)a.B * nt + 3) / 4)), dim3(256), 0, s, a, t_from, nt);
     return LAUNCH_OK();
 }
+static int ctc_beam_frames(const CtcBeamArgs& a, hipStream_t s) { return ctc_beam_frames(a, 0, a.Tp, s); }
 
 template <bool LM, bool BIAS>
 static void ctc_beam_sweep(const CtcBeamArgs& a, const CtcLmArgs& la, const CtcBiasArgs& ba, int nbest, int* tokens, int* lens, float* scores, hipStream_t s) {
     hipLaunchKernelGGL((ctc_beam_kernel<LM ? 1 : 0, BIAS, PH_SWEEP>), dim3(a.B), dim3(SW_THREADS), 0, s, a, la, ba, nbest, tokens, lens, scores);
+}
+
+// the checks of a fused phrase list
+static int ctc_bias_check(const char* fn, int C, int blank, int eos, const CtcBiasArgs& ba) {
+    // the phrase tokens are the model's classes 1 .. C - 2 whether an LM is fused or not
+    if (blank != 0) { mk_set_error(fn, "blank must be 0 with a phrase list (class 0 is no phrase token)"); return -1; }
+    if (eos != C - 1) { mk_set_error(fn, "eos must be C - 1 with a phrase list (the last class is no phrase token)"); return -1; }
+    if (ba.bias.C != C) { mk_set_error(fn, "the phrase list's classes differ from C"); return -1; }
+    if (!(ba.bias_w >= 0.f) || !std::isfinite(ba.bias_w)) { mk_set_error(fn, "bias_w must be finite and >= 0"); return -1; }
+    return 0;
 }
 
 // the checks and the two launches of the sweep's entry points.  lm / bias: an n-gram LM / a phrase list is fused; without one its struct is
@@ -502,11 +585,7 @@ static int ctc_beam_run(const char* fn, const float* logits, long ld, const int*
     CK(ctc_beam_check(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, tokens, lens, scores, lm, la.lm.C, la.lm.order, la.lm_w,
                       la.len_bonus, la.am));
     if (bias) {
-        // the phrase tokens are the model's classes 1 .. C - 2 whether an LM is fused or not
-        if (blank != 0) { mk_set_error(fn, "blank must be 0 with a phrase list (class 0 is no phrase token)"); return -1; }
-        if (eos != C - 1) { mk_set_error(fn, "eos must be C - 1 with a phrase list (the last class is no phrase token)"); return -1; }
-        if (ba.bias.C != C) { mk_set_error(fn, "the phrase list's classes differ from C"); return -1; }
-        if (!(ba.bias_w >= 0.f) || !std::isfinite(ba.bias_w)) { mk_set_error(fn, "bias_w must be finite and >= 0"); return -1; }
+        CK(ctc_bias_check(fn, C, blank, eos, ba));
         if (!la.am || !ba.nbias) { mk_set_error(fn, "null pointer"); return -1; }
     }
     if (work_bytes < mk_ctc_beam_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 3)) {
@@ -552,6 +631,91 @@ int mk_ctc_beam_search_bias(const float* logits, long ld, const int* enc_lens, i
     return ctc_beam_run(fn, logits, ld, enc_lens, B, Tp, C, K, nbest, blank, eos, work, work_bytes, tokens, lens, scores, lm != nullptr,
                         lm ? CtcLmArgs{lm->dev, lm_w, len_bonus, am} : CtcLmArgs{LmDev{}, 0.f, 0.f, am}, true, CtcBiasArgs{bias->dev, bias_w, nbias}, s);
 }
+
+// ---------------------------------------------------------------- the resumable search
+// A host-only run object over a caller's work buffer: the plain search's arrays, then the state block (CtcBeamState: every array rounded up
+// to 256 bytes, planned with or without an LM or a phrase list).  It owns no GPU memory.
+struct masr_ctc_beam_run {
+    CtcBeamArgs a; CtcLmArgs la; CtcBiasArgs ba; CtcBeamState st;
+    bool lm, bias;
+    int t_done;                                                     // the frames [0, t_done) have run
+};
+namespace {
+int64_t ctc_beam_state_carve(char* w, int B, int K, CtcBeamState* st) {
+    const int64_t R = (int64_t)B * K;
+    int64_t off = 0;
+    auto take = [&](auto*& p, int64_t n) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>((uintptr_t)w + (uintptr_t)off);
+        off += align256((long)(sizeof(*p) * n));
+    };
+    CtcBeamState q{};
+    take(q.hash, R); take(q.phash, R); take(q.ctx, R);
+    take(q.pb, R); take(q.pnb, R); take(q.lmacc, R); take(q.last, R); take(q.len, R); take(q.bnode, R); take(q.bn, R);
+    take(q.nlive, B); take(q.cursor, B);
+    if (st) *st = q;
+    return off;
+}
+template <int M, bool BIAS, int PH>
+void ctc_beam_run_launch(const masr_ctc_beam_run& r, const CtcLmArgs& la, const CtcBiasArgs& ba, int t_end, int nbest, int* tokens, int* lens,
+                         float* scores, hipStream_t s) {
+    hipLaunchKernelGGL((ctc_beam_kernel<M, BIAS, PH>), dim3(r.a.B), dim3(SW_THREADS), 0, s, r.a, CtcLmRunArgs{la, r.st, r.t_done, t_end}, ba, nbest,
+                       tokens, lens, scores);
+}
+using CtcRunLaunch = decltype(&ctc_beam_run_launch<0, false, PH_RANGE>);
+}  // namespace
+
+int64_t mk_ctc_beam_run_work_bytes(int B, int Tp, int C, int K) {
+    const int64_t base = mk_ctc_beam_work_bytes(B, Tp, C, K);
+    return base < 0 ? -1 : base + ctc_beam_state_carve(nullptr, B, K, nullptr);
+}
+
+masr_ctc_beam_run* mk_ctc_beam_run_open(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int blank, int eos,
+                                        const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work,
+                                        int64_t work_bytes, hipStream_t s) {
+    const CtcLmArgs la = lm ? CtcLmArgs{lm->dev, lm_w, len_bonus, nullptr} : CtcLmArgs{};
+    const CtcBiasArgs ba = bias ? CtcBiasArgs{bias->dev, bias_w, nullptr} : CtcBiasArgs{};
+    if (ctc_beam_check_search(fn, logits, ld, enc_lens, B, Tp, C, K, blank, eos, work, lm != nullptr, la.lm.C, la.lm.order, lm_w, len_bonus) != 0)
+        return nullptr;
+    if (bias && ctc_bias_check(fn, C, blank, eos, ba) != 0) return nullptr;
+    if (work_bytes < mk_ctc_beam_run_work_bytes(B, Tp, C, K) || ((uintptr_t)work & 7)) {
+        mk_set_error(fn, "work buffer too small (masr_ctc_beam_run_work_bytes(B, Tp, C, K)) or misaligned");
+        return nullptr;
+    }
+    masr_ctc_beam_run* r = new masr_ctc_beam_run{};
+    r->a = ctc_beam_carve(logits, ld, enc_lens, B, Tp, C, K, blank, eos, work);
+    r->la = la; r->ba = ba; r->lm = lm != nullptr; r->bias = bias != nullptr; r->t_done = 0;
+    ctc_beam_state_carve((char*)work + mk_ctc_beam_work_bytes(B, Tp, C, K), B, K, &r->st);
+    hipLaunchKernelGGL(ctc_beam_run_init_kernel, dim3(B), dim3(SW_THREADS), 0, s, r->st, K);
+    if (LAUNCH_OK() != 0) { delete r; return nullptr; }
+    return r;
+}
+
+int mk_ctc_beam_run_advance(const char* fn, masr_ctc_beam_run* r, int t_end, hipStream_t s) {
+    if (!r) { mk_set_error(fn, "null run"); return -1; }
+    if (t_end < r->t_done || t_end > r->a.Tp) { mk_set_error(fn, "t_end must lie in [the frames already run, Tp]"); return -1; }
+    if (t_end == r->t_done) return 0;
+    CK(ctc_beam_frames(r->a, r->t_done, t_end, s));
+    static constexpr CtcRunLaunch range[2][2] = {{ctc_beam_run_launch<0, false, PH_RANGE>, ctc_beam_run_launch<0, true, PH_RANGE>},
+                                                 {ctc_beam_run_launch<1, false, PH_RANGE>, ctc_beam_run_launch<1, true, PH_RANGE>}};
+    range[r->lm][r->bias](*r, r->la, r->ba, t_end, 0, nullptr, nullptr, nullptr, s);
+    CK(LAUNCH_OK());
+    r->t_done = t_end;
+    return 0;
+}
+
+int mk_ctc_beam_run_result(const char* fn, const masr_ctc_beam_run* r, int nbest, int* tokens, int* lens, float* scores, float* am, int* nbias,
+                           hipStream_t s) {
+    if (!r) { mk_set_error(fn, "null run"); return -1; }
+    CK(ctc_beam_check_result(fn, r->a.K, nbest, tokens, lens, scores, r->lm || r->bias, am, r->bias, nbias));
+    CtcLmArgs la = r->la; la.am = am;
+    CtcBiasArgs ba = r->ba; ba.nbias = nbias;
+    static constexpr CtcRunLaunch tail[2][2] = {{ctc_beam_run_launch<0, false, PH_TAIL>, ctc_beam_run_launch<0, true, PH_TAIL>},
+                                                {ctc_beam_run_launch<1, false, PH_TAIL>, ctc_beam_run_launch<1, true, PH_TAIL>}};
+    tail[r->lm][r->bias](*r, la, ba, 0, nbest, tokens, lens, scores, s);
+    return LAUNCH_OK();
+}
+
+void mk_ctc_beam_run_close(masr_ctc_beam_run* r) { delete r; }
 
 // ---------------------------------------------------------------- the LSTM LM search
 // the work buffer: the plain search's arrays | step [2] | the two weights | the beam by parity [2][B][K]: p_b, p_nb, lmacc, last, len, hash,

@@ -250,6 +250,7 @@ masr_model* masr_create_ctc(const masr_config* cfg, float ctc_weight) {
 
 void masr_destroy(masr_model* m) {
     if (!m) return;
+    stream_close(m);
     if (m->h_stage) hipHostFree(m->h_stage);
     if (m->h_stats) hipHostFree(m->h_stats);
     for (int i = 0; i < masr_model::RING; ++i) if (m->ring_ev[i]) { if (m->ring_used[i]) hipEventSynchronize(m->ring_ev[i]); hipEventDestroy(m->ring_ev[i]); }
@@ -567,6 +568,21 @@ int masr_ctc_beam_search_bias(const float* logits, int64_t ld, const int32_t* en
     return mk_ctc_beam_search_bias(logits, (long)ld, enc_lens, B, Tp, C, K, nbest, blank, eos, lm, lm_w, len_bonus, bias, bias_w, work, work_bytes, tokens,
                                    lens, scores, am, nbias, (hipStream_t)stream);
 }
+int64_t masr_ctc_beam_run_work_bytes(int B, int Tp, int C, int K) { return mk_ctc_beam_run_work_bytes(B, Tp, C, K); }
+masr_ctc_beam_run* masr_ctc_beam_run_open(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int blank, int eos,
+                                          const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work,
+                                          int64_t work_bytes, void* stream) {
+    return mk_ctc_beam_run_open("masr_ctc_beam_run_open", logits, (long)ld, enc_lens, B, Tp, C, K, blank, eos, lm, lm_w, len_bonus, bias, bias_w, work,
+                                work_bytes, (hipStream_t)stream);
+}
+int masr_ctc_beam_run_advance(masr_ctc_beam_run* run, int t_end, void* stream) {
+    return mk_ctc_beam_run_advance("masr_ctc_beam_run_advance", run, t_end, (hipStream_t)stream);
+}
+int masr_ctc_beam_run_result(const masr_ctc_beam_run* run, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias,
+                             void* stream) {
+    return mk_ctc_beam_run_result("masr_ctc_beam_run_result", run, nbest, tokens, lens, scores, am, nbias, (hipStream_t)stream);
+}
+void masr_ctc_beam_run_close(masr_ctc_beam_run* run) { mk_ctc_beam_run_close(run); }
 int64_t masr_ctc_beam_nlm_work_bytes(const masr_nlm* nlm, int B, int Tp, int C, int K) { return mk_ctc_beam_nlm_work_bytes(nlm, B, Tp, C, K); }
 int masr_ctc_beam_search_nlm(const float* logits, int64_t ld, const int32_t* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                              const masr_nlm* nlm, float lm_w, float len_bonus, void* work, int64_t work_bytes, int32_t* tokens, int32_t* lens,

@@ -144,6 +144,7 @@ struct masr_model {
         int B = 0, max_frames = 0, c = 0, left = -1;
         int recv = 0, emitted = 0;                         // input frames buffered, encoder frames emitted
         std::vector<int> len; std::vector<char> ended;     // per utterance: valid frames received, ended
+        masr_ctc_beam_run* beam = nullptr;                 // the resumable prefix beam that follows the chunks, if one is open
     } stream;
     struct { float* logits; int* gold; int R, L; } last_rescore{};   // where the last rescoring call's decoder pass left its logits / gold (masr_test_rescore_logits)
     // profiling
@@ -217,7 +218,11 @@ inline int ln_fwd(Ctx& c, const Norm& n, const float* x, float* y32, bf16* y16, 
 }
 
 // what every call that plans the workspace does to an open stream: its buffers are about to be overwritten
-inline void stream_close(masr_model* m) { m->stream.open = false; }
+inline void stream_close(masr_model* m) {
+    m->stream.open = false;
+    mk_ctc_beam_run_close(m->stream.beam);                  // (host memory only; null is allowed)
+    m->stream.beam = nullptr;
+}
 
 // engine.hip.  ctc: the branches of masr_run_batch alone, which the decoders do not plan -- the joint objective's (hybrid models) and
 // SpecAugment's batch

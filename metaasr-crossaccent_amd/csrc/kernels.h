@@ -300,6 +300,19 @@ int64_t mk_ctc_beam_bias_work_bytes(int B, int Tp, int C, int K);
 int mk_ctc_beam_search_bias(const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int nbest, int blank, int eos,
                             const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work, int64_t work_bytes,
                             int* tokens, int* lens, float* scores, float* am, int* nbias, hipStream_t s);
+// the resumable form of the three searches above (include/masr.h masr_ctc_beam_run_* has the contract): a host-only run object
+// over the caller's work buffer of mk_ctc_beam_run_work_bytes = mk_ctc_beam_work_bytes + the state block.  open checks, launches the initial
+// state and returns null on a refusal; advance runs the frames [done, t_end) (two launches, none with nothing to do); result runs the tail on
+// the beam as it stands and stores nothing into the state.  fn: the entry point named in a refusal
+struct masr_ctc_beam_run;
+int64_t mk_ctc_beam_run_work_bytes(int B, int Tp, int C, int K);
+masr_ctc_beam_run* mk_ctc_beam_run_open(const char* fn, const float* logits, long ld, const int* enc_lens, int B, int Tp, int C, int K, int blank, int eos,
+                                        const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* work,
+                                        int64_t work_bytes, hipStream_t s);
+int mk_ctc_beam_run_advance(const char* fn, masr_ctc_beam_run* r, int t_end, hipStream_t s);
+int mk_ctc_beam_run_result(const char* fn, const masr_ctc_beam_run* r, int nbest, int* tokens, int* lens, float* scores, float* am, int* nbias,
+                           hipStream_t s);
+void mk_ctc_beam_run_close(masr_ctc_beam_run* r);
 // (nodes_out, n_out)[i] = bias_step((nodes_in, n_in)[i], tokens[i]) for count independent states (device arrays)
 int mk_bias_step(const BiasDev& d, const int* nodes_in, const int* n_in, const int* tokens, int count, int* nodes_out, int* n_out, hipStream_t s);
 

@@ -1,6 +1,7 @@
 // libmasr engine, the streaming first pass: the chunk-masked encoder of masr_set_chunk run incrementally -- the front-end on
 // input windows, every encoder layer on the chunk's rows against a per-layer K|V cache (stream.hip) --, a greedy CTC decode that carries its
-// state across chunks, and the full-utterance CTC prefix beam (ctc_beam.hip, unchanged) on the logits the stream left behind.
+// state across chunks, the full-utterance CTC prefix beam (ctc_beam.hip, unchanged) on the logits the stream left behind, and the resumable
+// prefix beam (ctc_beam.hip's run object) that follows the chunks feed by feed once masr_stream_beam_open has opened one.
 //
 // Chunk n covers the encoder frames [s, e) = [n c, min((n + 1) c, T / 4)).  Encoder frame t reads the input frames 4t - 6 .. 4t + 9, so the
 // four convs and vgg2enc on the input window [max(0, 4s - 8), min(T, 4e + 8)) give the chunk's rows exactly: the window starts at a multiple
@@ -26,6 +27,7 @@ struct StreamBufs {
     bf16 *a1, *p1, *a3, *p2, *qkv, *ao, *x1_16, *f, *mem16;
     std::vector<float*> x32; std::vector<bf16*> x16; std::vector<StreamLayer> layer;
     void* work; int64_t work_bytes;
+    void* beam_work; int64_t beam_work_bytes;             // the resumable beam's own work buffer and state block
 };
 
 void plan_stream(const masr_model* m, Arena& ar, StreamBufs& sb, int B, int max_frames, int c) {
@@ -48,6 +50,9 @@ void plan_stream(const masr_model* m, Arena& ar, StreamBufs& sb, int B, int max_
     sb.logits = ar.get<float>((int64_t)B * sb.cap * m->Cp);
     sb.work_bytes = mk_ctc_beam_work_bytes(B, sb.cap, m->C, STREAM_BEAM_K);
     sb.work = ar.get<char>(sb.work_bytes);
+    // behind everything else, so that no other offset moves: masr_stream_ctc_beam may run beside an open beam
+    sb.beam_work_bytes = mk_ctc_beam_run_work_bytes(B, sb.cap, m->C, STREAM_BEAM_K);
+    sb.beam_work = ar.get<char>(sb.beam_work_bytes);
 }
 
 int sfail(const char* fn, const char* msg) { mk_set_error(fn, msg); return -1; }
@@ -163,7 +168,7 @@ int masr_stream_begin(masr_model* m, int B, int max_frames, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     m->have_acts = false;                                   // (the activation plan of the last batch is overwritten)
     masr_model::Stream& st = m->stream;
-    st.open = false;
+    stream_close(m);
     HIP_CHECK_RET(hipMemsetAsync(sb.lens, 0, sizeof(int) * 2 * (size_t)B, s));
     HIP_CHECK_RET(hipMemsetAsync(sb.state, 0, sizeof(int) * 2 * (size_t)B, s));
     HIP_CHECK_RET(hipMemsetAsync(sb.tokens, 0xFF, sizeof(int) * (size_t)B * sb.cap, s));
@@ -219,6 +224,7 @@ int masr_stream_feed(masr_model* m, const float* xs, int n, const int32_t* valid
         CK(stream_step(m, sb, s0, e, s));
         st.emitted = e;
     }
+    if (st.beam) CK(mk_ctc_beam_run_advance(fn, st.beam, st.emitted, s));      // once per feed, whatever the cut
     if (frames_out) *frames_out = st.emitted;
     return 0;
 }
@@ -253,6 +259,29 @@ int masr_stream_ctc_beam(masr_model* m, int K, int nbest, int32_t* tokens, int32
     if (!m->stream.last) return sfail(fn, "the stream has not had its last piece");
     return mk_ctc_beam_search(sb.logits, m->Cp, sb.lens + m->stream.B, m->stream.B, sb.cap, m->C, K, nbest, 0, m->C - 1, sb.work, sb.work_bytes, tokens,
                               lens, scores, (hipStream_t)stream);
+}
+
+int masr_stream_beam_open(masr_model* m, int K, const masr_lm* lm, float lm_w, float len_bonus, const masr_bias* bias, float bias_w, void* stream) {
+    const char* fn = "masr_stream_beam_open";
+    StreamBufs sb;
+    CK(open_stream(fn, m, sb));
+    masr_model::Stream& st = m->stream;
+    masr_ctc_beam_run* run = mk_ctc_beam_run_open(fn, sb.logits, m->Cp, sb.lens + st.B, st.B, sb.cap, m->C, K, 0, m->C - 1, lm, lm_w, len_bonus, bias,
+                                                  bias_w, sb.beam_work, sb.beam_work_bytes, (hipStream_t)stream);
+    if (!run) return -1;
+    // the frames emitted so far at once: after the last piece no feed would come to catch up with
+    if (mk_ctc_beam_run_advance(fn, run, st.emitted, (hipStream_t)stream) != 0) { mk_ctc_beam_run_close(run); return -1; }
+    mk_ctc_beam_run_close(st.beam);
+    st.beam = run;
+    return 0;
+}
+
+int masr_stream_beam_result(masr_model* m, int nbest, int32_t* tokens, int32_t* lens, float* scores, float* am, int32_t* nbias, void* stream) {
+    const char* fn = "masr_stream_beam_result";
+    StreamBufs sb;
+    CK(open_stream(fn, m, sb));
+    if (!m->stream.beam) return sfail(fn, "no open beam (masr_stream_beam_open)");
+    return mk_ctc_beam_run_result(fn, m->stream.beam, nbest, tokens, lens, scores, am, nbias, (hipStream_t)stream);
 }
 
 }  // extern "C"

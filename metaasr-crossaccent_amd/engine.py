@@ -720,6 +720,7 @@ class MasrEngine:
         self._decode_ws("masr_stream_workspace_bytes", int(B), int(max_frames))
         check(self._l.masr_stream_begin(self.h, int(B), int(max_frames), self.stream()), "masr_stream_begin")
         self._stream_shape = (int(B), int(max_frames))
+        self._stream_beam = None
 
     def stream_feed(self, xs: torch.Tensor, valid=None, last: bool = False) -> int:
         """the next piece xs [B, n, idim] of every utterance; valid[b] < n ends utterance b (later pieces must give it 0).  Returns the number
@@ -757,16 +758,50 @@ class MasrEngine:
         check(self._l.masr_stream_ctc_beam(self.h, K, N, *map(_ptr, out), self.stream()), "masr_stream_ctc_beam")
         return out if raw else nbest_lists(*out)
 
-    def recog_stream(self, xs: torch.Tensor, ilens, piece: int, beam_size=None, nbest: int = 1):
+    def stream_beam_open(self, beam_size: int, lm=None, lm_w: float = 0.3, len_bonus: float = 0.0, bias=None, bias_w: float = 3.0):
+        """open the resumable CTC prefix beam on the open stream (masr_stream_beam_open): it runs the frames emitted so far at once
+        and from the next feed on follows the chunks, with the n-gram LM `lm` and the phrase list `bias` fused in if given (as recog_ctc_beam_lm / recog_ctc_beam_bias do)."""
+        K, _ = check_beam_args(beam_size)
+        bias_w = check_bias_args(bias, bias_w) if bias is not None else 0.0
+        lm_w, len_bonus = check_lm_args(lm, lm_w, len_bonus) if lm is not None else (0.0, 0.0)
+        check(self._l.masr_stream_beam_open(self.h, K, getattr(lm, "h", None), lm_w, len_bonus, getattr(bias, "h", None), bias_w, self.stream()),
+              "masr_stream_beam_open")
+        self._stream_beam = (K, lm is not None, bias is not None, lm, bias)       # (the LM and the list stay alive with the beam)
+
+    def stream_beam_result(self, nbest: int = 1, raw: bool = False):
+        """the open beam's result after the frames emitted so far (masr_stream_beam_result): the partial N-best, after the last piece the
+        final one.  Lists as recog_ctc_beam / _lm / _bias return them (raw: the device tensors tokens, lens, scores[, am[, nbias]])."""
+        beam = getattr(self, "_stream_beam", None)
+        K, with_lm, with_bias = beam[:3] if beam else (64, False, False)       # (without a beam the call below says so)
+        K, N = check_beam_args(K, nbest)
+        B, cap = self._stream_shape[0], self._stream_shape[1] // 4
+        out = self._outputs(B, N, ld=cap, extra="fi" if with_bias else "f" if with_lm else "")
+        ptrs = list(map(_ptr, out)) + [None] * (6 - len(out))
+        check(self._l.masr_stream_beam_result(self.h, N, *ptrs[:5], self.stream()), "masr_stream_beam_result")
+        return out if raw else (nbest_lists_bias if with_bias else nbest_lists)(*out)
+
+    def recog_stream(self, xs: torch.Tensor, ilens, piece: int, beam_size=None, nbest: int = 1, sync_beam: bool = False, lm=None,
+                     lm_w: float = 0.3, len_bonus: float = 0.0, bias=None, bias_w: float = 3.0):
         """the padded batch xs [B, T, idim] streamed in pieces of `piece` input frames, `valid` derived from ilens.  Returns per utterance
-        (greedy token list, the encoder frame of each token); with beam_size the final beam's lists as recog_ctc_beam returns them."""
+        (greedy token list, the encoder frame of each token); with beam_size the final beam's lists as recog_ctc_beam returns them.
+        sync_beam (needs beam_size): the resumable beam follows the feeds (stream_beam_open with lm / bias); returns (the final lists, per
+        feed the partial top-1 token list of every utterance)."""
         if int(piece) < 1:
             raise ValueError("recog_stream: piece must be >= 1")
+        if sync_beam and beam_size is None:
+            raise ValueError("recog_stream: sync_beam needs a beam_size")
         xs, il, B, T = self._decode_inputs(xs, ilens)
         self.stream_begin(B, T)
+        if sync_beam:
+            self.stream_beam_open(beam_size, lm, lm_w, len_bonus, bias, bias_w)
+        partials = []
         for t0 in range(0, T, int(piece)):
             t1 = min(T, t0 + int(piece))
             self.stream_feed(xs[:, t0:t1], [max(0, min(int(l), t1) - t0) for l in il.tolist()], last=t1 == T)
+            if sync_beam:
+                partials.append([u[0][0] if u else [] for u in self.stream_beam_result(1)])
+        if sync_beam:
+            return self.stream_beam_result(nbest), partials
         if beam_size is not None:
             return self.stream_ctc_beam(beam_size, nbest)
         tok, frm, lens = (t.cpu() for t in self.stream_partial())

@@ -76,6 +76,10 @@ anything is decoded.  Tester.MODES is the table of them:
                  is written.  Needs a chunk size (asr_model.chunk.size or `--decode_chunk`; without one: ValueError) and a CTC output layer (a
                  transformer without one: ValueError); a BLSTM raises NotImplementedError.  No solver.beam_decode block is read.
   stream_ctc_beam    the same stream, then `ctc_beam`'s search (beam_size) on the logits it left behind.  Refuses what `stream_ctc_greedy` does.
+  stream_sync_ctc_beam  the same stream with the resumable prefix beam of DESIGN 5.17 following the feeds (masr_stream_beam_open; beam_size): the
+                 final result is written, which without an LM and a phrase list is `stream_ctc_beam`'s bit for bit.  `--lm_model_path` (an
+                 ARPA file, fused with lm_w 0.3 / len_bonus 0 as in `lm_ctc_beam`) and `--context_path` (phrases boosted by bias_w 3.0 as in
+                 `bias_ctc_beam`) are optional, separately or together.  Refuses what `stream_ctc_greedy` does.
 The LM modes build the LM once per Tester and (path, <s> id, </s> id).
 Every mode of a transformer runs one encoder forward, under the chunk mask of asr_model.chunk (DESIGN 5.15) where the config has one;
 `--decode_chunk SIZE` / `--decode_left N` put their values over its `size` / `left` for this run (SIZE 0: full context), so one checkpoint is
@@ -116,7 +120,7 @@ def decode_chunk_policy(model_para, paras, model_name='transformer'):
     return _chunk_policy(pol, "--decode_chunk / --decode_left"), True
 
 
-STREAM_MODES = ('stream_ctc_greedy', 'stream_ctc_beam')
+STREAM_MODES = ('stream_ctc_greedy', 'stream_ctc_beam', 'stream_sync_ctc_beam')
 
 
 def _no_ctc_head_error(mode, instead):
@@ -371,10 +375,29 @@ class Tester:
             self._need_ctc_head('ctc_beam', "beam or greedy")
 
     def _stream_settings(self):
-        """stream_ctc_greedy and stream_ctc_beam (their argument errors: stream_decode_args, in the constructor)"""
-        if self.decode_mode == 'stream_ctc_beam':
+        """stream_ctc_greedy, stream_ctc_beam and stream_sync_ctc_beam (their argument errors: stream_decode_args, in the constructor)"""
+        if self.decode_mode != 'stream_ctc_greedy':
             self._beam_size()
         self._need_ctc_head(self.decode_mode, "beam or greedy")
+        if self.decode_mode != 'stream_sync_ctc_beam':
+            return
+        # the resumable beam's optional LM and phrase list, as bias_ctc_beam reads them
+        bd = self.config['solver']['beam_decode']
+        lm_path, ctx_path = getattr(self.paras, 'lm_model_path', None), getattr(self.paras, 'context_path', None)
+        self.lm_weight, self.len_bonus, self.bias_weight = 0.0, 0.0, 0.0
+        lm, bias = "no LM", "no phrase list"
+        if lm_path is not None:
+            self.lm_weight = self._weight(bd, 'lm_w', 0.3)
+            self._len_bonus(bd)
+            lm = f"{self._load_lm(lm_path, 0, len(self.id2ch) - 1)}, lm_w = {self.lm_weight}, len_bonus = {self.len_bonus}"
+        else:
+            self.lm = None
+        if ctx_path is not None:
+            self.bias_weight = self._weight(bd, 'bias_w', 3.0)
+            bias = f"phrase list {self._load_bias(ctx_path)}, bias_w = {self.bias_weight}"
+        else:
+            self.bias = None
+        logger.notice(f"stream_sync_ctc_beam: {lm}; {bias}")
 
     def _ctc_align_settings(self):
         if self.model_name != 'blstm':
@@ -615,6 +638,12 @@ class Tester:
         'stream_ctc_beam': (_stream_settings,
                             lambda t, xs, il: t._ctc_best(t.asr_model.engine.recog_stream(xs, il, t.stream_piece, t.beam_size)),
                             lambda t: f"streaming encoder, CTC prefix beam on its logits (chunk {t.chunk_policy['size']}, beam {t.beam_size})"),
+        'stream_sync_ctc_beam': (_stream_settings,
+                                 lambda t, xs, il: t._ctc_best(t.asr_model.engine.recog_stream(
+                                     xs, il, t.stream_piece, t.beam_size, sync_beam=True, lm=t.lm, lm_w=t.lm_weight, len_bonus=t.len_bonus, bias=t.bias,
+                                     bias_w=t.bias_weight)[0]),
+                                 lambda t: f"streaming encoder, resumable CTC prefix beam following the feeds (chunk {t.chunk_policy['size']}, "
+                                           f"beam {t.beam_size})"),
         'lm_joint_beam': (_lm_joint_settings,
                           lambda t, xs, il: [n[0][0] if n else [] for n in t.asr_model.lm_joint_beam_decode(
                               xs, il, t.beam_size, t.lm, t.lm_weight, t.len_bonus, t.nbest, t.min_step_ratio, t.max_step_ratio, t.att_weight, t.ctc_weight)],

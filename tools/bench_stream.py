@@ -5,7 +5,10 @@
      8 heads of 64, B = 1 and 16.  Device events around WINDOW back-to-back calls, the legs alternating, REPS windows behind a warm-up round;
   2. the chunk step: a T = 1000 stream fed in pieces of 4 c frames, B = 1 and 16 -- GPU ms per chunk step (device events around the whole
      stream / its 16 chunks), the host's enqueue time for the same calls, the real-time factor at 640 ms per chunk, the step's launches;
-  3. the whole stream + the final K = 1 beam against masr_recog_ctc_beam (K = 1) = one full chunk-masked encoder pass + head + the same sweep.
+  3. the whole stream + the final K = 1 beam against masr_recog_ctc_beam (K = 1) = one full chunk-masked encoder pass + head + the same sweep;
+  4. the resumable prefix beam, left = -1: the chunk step with the beam open at K in {1, 4, 10, 20} beside the step without it
+     (the legs alternating), and on the logits the stream left behind the sum of the resumed calls over the utterance (masr_ctc_beam_run_*:
+     one advance per 16 frames, then the result) beside the one-shot masr_ctc_beam_search.
 python tools/bench_stream.py      prints one JSON line at the end (run it in three processes and take the medians)"""
 import ctypes as C
 import json
@@ -112,4 +115,69 @@ for B in (1, 16):
              "rtf": statistics.median(gpu) / chunks / 640.0, "stream_plus_beam_ms": statistics.median(with_beam), "full_pass_plus_beam_ms": statistics.median(full)}
         res["step"][f"B{B}_left{left}"] = r
         print(f"B {B:2d} left {left:2d}: " + ", ".join(f"{k} {v:.4g}" for k, v in r.items()))
+
+# ---- 4. the resumable beam inside the stream and alone
+KS = (1, 4, 10, 20)
+res["beam"] = {}
+for B in (1, 16):
+    gc = torch.Generator().manual_seed(B)
+    lens = torch.randint(600, T + 1, (B,), generator=gc)
+    lens[0] = T
+    xs = torch.zeros(B, T, D)
+    for b in range(B):
+        xs[b, :int(lens[b])] = torch.randn(int(lens[b]), D, generator=gc)
+    xs = xs.cuda()
+    eng = MasrEngine(dict(HK, chunk=dict(size=CH, left=-1)), 367)
+    eng.load_state_dict(sd)
+    pieces = [(xs[:, t0:t0 + 4 * CH].contiguous(), [max(0, min(int(l), t0 + 4 * CH) - t0) for l in lens.tolist()], t0 + 4 * CH >= T)
+              for t0 in range(0, T, 4 * CH)]
+    chunks = (T // 4 + CH - 1) // CH
+
+    def run_stream(K):
+        eng.stream_begin(B, T)
+        if K:
+            eng.stream_beam_open(K)
+        for x, v, last in pieces:
+            eng.stream_feed(x, v, last)
+
+    step = {K: [] for K in (0,) + KS}
+    for rep_ in range(4):                                        # (the first round warms up and is dropped)
+        for K in step:
+            t = timed(lambda: run_stream(K), 1) / chunks
+            if rep_:
+                step[K].append(t)
+    # the search alone, on the logits of the last stream
+    z, klen, _ = eng.stream_logits()
+    z, klen = z.clone(), klen.clone()
+    cap, ld = z.shape[1], z.shape[2]
+    alone = {}
+    for K in KS:
+        nb = int(L.masr_ctc_beam_run_work_bytes(B, cap, 367, K))
+        work = torch.empty(nb, dtype=torch.uint8, device="cuda")
+        tok = torch.empty(B, 1, cap, dtype=torch.int32, device="cuda")
+        ln, sc = torch.empty(B, 1, dtype=torch.int32, device="cuda"), torch.empty(B, 1, device="cuda")
+
+        def one_shot():
+            check(L.masr_ctc_beam_search(vp(z), ld, vp(klen), B, cap, 367, K, 1, 0, 366, vp(work), nb, vp(tok), vp(ln), vp(sc), stream()))
+
+        def resumed():
+            run = L.masr_ctc_beam_run_open(vp(z), ld, vp(klen), B, cap, 367, K, 0, 366, None, 0.0, 0.0, None, 0.0, vp(work), nb, stream())
+            assert run, L.masr_last_error()
+            for t in list(range(CH, cap, CH)) + [cap]:
+                check(L.masr_ctc_beam_run_advance(run, t, stream()))
+            check(L.masr_ctc_beam_run_result(run, 1, vp(tok), vp(ln), vp(sc), None, None, stream()))
+            L.masr_ctc_beam_run_close(run)                       # (host memory only: the launches hold their own arguments)
+
+        ms = {"one_shot": [], "resumed": []}
+        for rep_ in range(REPS + 1):
+            for name, fn in (("one_shot", one_shot), ("resumed", resumed)):
+                t = timed(fn, 1)
+                if rep_:
+                    ms[name].append(t)
+        alone[K] = {n: statistics.median(x) for n, x in ms.items()}
+    r = {"gpu_ms_per_chunk": {f"K{K}" if K else "no_beam": statistics.median(x) for K, x in step.items()},
+         "search_ms": {f"K{K}": v for K, v in alone.items()}}
+    res["beam"][f"B{B}"] = r
+    print(f"B {B:2d} chunk step, GPU ms: " + ", ".join(f"{k} {v:.4f}" for k, v in r["gpu_ms_per_chunk"].items()))
+    print(f"B {B:2d} search over {cap} frames, ms: " + ", ".join(f"{k} one-shot {v['one_shot']:.3f} resumed {v['resumed']:.3f}" for k, v in r["search_ms"].items()))
 print(json.dumps(res))

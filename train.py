@@ -44,7 +44,7 @@ def build_parser():
     p.add_argument('--test', action='store_true')
     p.add_argument('--test_model', type=str, default='model.wer.best')
     p.add_argument('--decode_batch_size', type=int, default=1)
-    p.add_argument('--decode_mode', choices=['greedy', 'beam', 'lm_beam', 'nlm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore', 'lm_joint_beam', 'nlm_joint_beam', 'nlm_ctc_beam', 'nlm_rescore', 'ctc_align', 'bias_ctc_beam', 'bias_rescore', 'bias_beam', 'bias_joint_beam', 'stream_ctc_greedy', 'stream_ctc_beam'], default='greedy')
+    p.add_argument('--decode_mode', choices=['greedy', 'beam', 'lm_beam', 'nlm_beam', 'ctc_beam', 'rescore', 'lm_ctc_beam', 'lm_rescore', 'lm_joint_beam', 'nlm_joint_beam', 'nlm_ctc_beam', 'nlm_rescore', 'ctc_align', 'bias_ctc_beam', 'bias_rescore', 'bias_beam', 'bias_joint_beam', 'stream_ctc_greedy', 'stream_ctc_beam', 'stream_sync_ctc_beam'], default='greedy')
     p.add_argument('--decode_suffix', default=None, type=str)
     p.add_argument('--decode_chunk', default=None, type=int, help='--test: decode under a chunk mask of SIZE encoder frames (0 = full context), over asr_model.chunk.size')
     p.add_argument('--decode_left', default=None, type=int, help='--test: earlier chunks a frame may see (-1 = all), over asr_model.chunk.left')
